@@ -1,17 +1,20 @@
 """Headline benchmark (BASELINE.json): train images/s of DeepLabV2-ResNet101 + ASPP at 769x769, bf16 operands,
 B = 8 per GPU, on N MI355X of one node (weak scaling), synthetic data resident in HBM, formula weights.
 
-  python bench.py --gpus 1 --steps K --warmup W
+  python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 One step = reference core/trainers/aspp_trainer.py:77-95 (poly LR, zero_grad, forward, CE loss, backward, both SGD
 steps) through host/trainer.py:ASPPTrainer.train_step on the HIP engine; N > 1 adds the RCCL gradient average.
-Prints ONE JSON line on rank 0.  `roofline` is for the dominant kernel (the one with the largest total launch time in
-the instrumented steps): algorithmic FLOPs / its launch time measured with HIP events on the launch stream inside the
-timed region; `kernels` lists every timed kernel, `kernel_families` the north-star groups (dilated 3x3 family, ASPP head:
+Prints ONE JSON line on rank 0.  A plain run sets up, runs W warm-up and K timed steps, and reports the timed steps only
+(`value`, `ms_per_step`).  `--dump-outputs DIR` then writes what the last timed step computed (dump_outputs below) as .npy
+files; the inputs are seeded, so two builds can be compared output for output.
+`--full` adds what takes runs of its own (off by default).  `roofline` is for the dominant kernel (the one with the largest
+total launch time in the instrumented steps): algorithmic FLOPs / its launch time measured with HIP events on the launch
+stream; `kernels` lists every timed kernel, `kernel_families` the north-star groups (dilated 3x3 family, ASPP head:
 fraction of the MFMA peak; the K = 256 <-> N = 1024 pointwise class: fraction of the HBM peak).  `cpu_baseline` times the
-oracle's torch-CPU port of the same step on all granted host cores (rank 0, N = 1).  MI_GRAPH=1 replays the step as a HIP
-graph (no per-launch events then).
+oracle's torch-CPU port of the same step on all granted host cores (rank 0, N = 1); `eager` (--workload pranet) times the
+step without its HIP graph.  MI_GRAPH=1 replays the step as a HIP graph (no per-launch events then).
 """
 import argparse
 import json
@@ -44,6 +47,30 @@ def synthetic_batch(batch, size, rank, device):
     lab[:, :, -band:] = 255
     lab[torch.rand((batch, size, size), generator=g) < 0.02] = 255
     return x.to(device), lab.to(device)
+
+
+DUMP_SAMPLE = 1 << 20          # elements per dumped array at most (4 MB of float32)
+
+
+def dump_outputs(path, loss, modules):
+    """--dump-outputs: what the last timed step computed, as DIR/<name>.npy - `loss.npy` (float64, the loss the step returned) and, per
+    (tag, module), `<tag>_params.npy` / `<tag>_grads.npy` (float32): the parameters the optimizer step left and the gradients of that step,
+    concatenated in module.parameters() order.  An array longer than DUMP_SAMPLE is a fixed seeded sample of its elements (same indices in
+    every run of the same workload), which keeps the deeplab dump at 16 MB and every workload's under 64 MB."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = {"loss": np.asarray([float(loss)], np.float64)}
+    for tag, m in modules:
+        ps = list(m.parameters())
+        for kind, ts in (("params", ps), ("grads", [p.grad if p.grad is not None else torch.zeros_like(p) for p in ps])):
+            flat = torch.cat([t.detach().reshape(-1).float() for t in ts])
+            if flat.numel() > DUMP_SAMPLE:
+                idx = torch.randint(0, flat.numel(), (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(4321)).sort().values
+                flat = flat[idx.to(flat.device)]
+            arrays["%s_%s" % (tag, kind)] = flat.cpu().numpy()
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    note("outputs of the last timed step -> %s (%d arrays, %.1f MB)" % (path, len(arrays), sum(a.nbytes for a in arrays.values()) / 1e6))
 
 
 def head_commit():
@@ -156,6 +183,7 @@ def aux_workload(args, device):
         if pranet.graph_mode_default():                   # PraNetTrainer's default: the whole optimizer step as one HIP graph (bit-equal to eager: tests/test_gpu_pranet.py); MI_GRAPH=0: eager
             graphed = pranet.GraphedStep(net, opt, x, gt)
         runner = (lambda: graphed()[3]) if graphed else step
+        dump_mods = (("pranet", net),)
         metric = "train images/sec at %dx%d bf16 (PraNet Res2Net-50, BASELINE config[3]; one step = ONE of the three passes of a reference iteration)" % (H, W)
         workload = ("configs/pranet_src_polyp.yaml: PraNet, one optimizer step = forward, four structure losses, backward, clamped Adam on B=%d %dx%d - the "
                     "reference's iteration (pranet_trainer.py:44-61) runs three such steps per batch (its three 'scales' all resize to trainsize)" % (B, H, W))
@@ -188,6 +216,7 @@ def aux_workload(args, device):
         def step():
             return combo.train_step(xs, ys, xt, 10000)["loss_seg"]          # max_iter 10 000: the poly learning rate stays near its base value
         graphed, runner = None, step
+        dump_mods = (("feature_extractor", combo.aspp.feature_extractor), ("classifier", combo.aspp.classifier), ("discriminator", combo.fada.model_D))
         metric = "train images/sec at %dx%d bf16 (FADA adversarial iteration, source + target images; BASELINE config[4] on one GPU)" % (W, H)
         workload = ("train_adv.py configs/deeplabv2_r101_adv.yaml: one AsppFada iteration = %d source + %d target %dx%d crops, DeepLabV2-R101 + ASPP + "
                     "PixelDiscriminator, 2 x SGD + Adam" % (hb, hb, W, H))
@@ -210,6 +239,7 @@ def aux_workload(args, device):
             od.step()
             return loss
         graphed, runner = None, step
+        dump_mods = (("encoder", enc), ("decoder", dec))
         metric = "train images/sec at %dx%d bf16 (GALD: HarDNet-68 + GCPA decoder)" % (W, H)
         workload = "configs/gald_src.yaml: GALD, one training step, B=%d %dx%d" % (B, W, H)
     note("warm-up")
@@ -225,7 +255,9 @@ def aux_workload(args, device):
     out = {"metric": metric, "value": round(B / dt, 2), "unit": "images/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
            "ms_per_step": round(dt * 1e3, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "bf16",
            "data": "synthetic, random-init weights", "config": {"workload": workload, "hip_graph": bool(graphed)}, "loss": round(float(loss), 4)}
-    if graphed:                                           # the same step eagerly (what MI_GRAPH=0 runs): both numbers in one line
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, loss, dump_mods)
+    if graphed and args.full:                             # the same step eagerly (what MI_GRAPH=0 runs): both numbers in one line
         for _ in range(2):
             step()
         torch.cuda.synchronize()
@@ -235,7 +267,7 @@ def aux_workload(args, device):
         torch.cuda.synchronize()
         de = (time.perf_counter() - t0) / max(3, args.steps // 2)
         out["eager"] = {"value": round(B / de, 2), "ms_per_step": round(de * 1e3, 3)}
-    if not args.no_kernel_events:
+    if args.full and not args.no_kernel_events:
         note("instrumented steps (eager, HIP events per launch)")
         events = []
         kernels.PROFILE = events
@@ -300,7 +332,7 @@ def aux_workload(args, device):
         out["kernels"] = {k: {"ms_per_step": round(1e3 * v[0] / INST, 3), "launches_per_step": v[2] // INST, "share": round(v[0] / tot, 3),
                               "tflops": round(v[1] / v[0] / 1e12, 1) if v[1] else None} for k, v in sorted(by.items(), key=lambda kv: -kv[1][0])[:14]}
         out["launches_per_step"] = sum(v[2] for v in by.values()) // INST
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         note("CPU baseline (oracle port)")
         out["cpu_baseline"] = aux_cpu_baseline(args.workload, H, W)
     print(json.dumps(out), flush=True)
@@ -387,8 +419,12 @@ def main():
     ap.add_argument("--workload", choices=("deeplab", "deeplab_bn", "pranet", "gald", "fada"), default="deeplab",
                     help="deeplab = BASELINE config[1] (the headline, default); deeplab_bn = the same step with MODEL.FREEZE_BN False (trainable "
                          "BatchNorm2d on batch statistics); pranet = config[3]; gald = the third model of train_src.py; fada = config[4] on one GPU: train_adv.py's adversarial iteration, 4 source + 4 target crops")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-kernel-events", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (loss, parameters, gradients) to DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also the measurements beyond the headline: instrumented steps (roofline, per-kernel table), CPU baseline, eager timing of a graphed step")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-kernel-events", action="store_true", help="with --full: skip the instrumented steps")
     args = ap.parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -475,7 +511,9 @@ def main():
     exposed = red.exposed_ms() if red is not None else None
     if red is not None:
         red.measure = False
-    events = [] if not args.no_kernel_events else None
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, loss, (("feature_extractor", trainer.feature_extractor), ("classifier", trainer.classifier)))
+    events = [] if args.full and not args.no_kernel_events else None
     if events is not None:
         if graph:
             os.environ["MI_GRAPH"] = "0"          # events cannot be taken inside a graph replay
@@ -599,7 +637,7 @@ def main():
             # data-parallel diagnostics of THIS rank (rank 0): how many ranks the process group really has, what travels, and how long the
             # compute stream waited for the exchange at the join before the optimizer (the part of the all-reduce that backward did not hide)
             out["ddp"] = dict(red.diag, exchange_ms_exposed=None if exposed is None else round(exposed, 4), backend=dist.get_backend() if dist.is_initialized() else None)
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args.size)
         print(json.dumps(out), flush=True)
     if dist.is_initialized():

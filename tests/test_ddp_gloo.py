@@ -35,6 +35,11 @@ def _batch(rank):
     return torch.from_numpy(x), torch.from_numpy(lab)
 
 
+def _cpu_only():
+    """The trainers move to cuda whenever a GPU is visible (host/plugin.py); the ranks of this module test the CPU data-parallel path, on any host."""
+    torch.cuda.is_available = lambda: False
+
+
 def test_bucket_ranges_cover_the_store_from_the_end():
     params = [("p%d" % i, torch.nn.Parameter(torch.zeros(n))) for i, n in enumerate((1000, 64, 5000, 300, 7000, 10))]
     st = engine.FlatStore(params, torch.device("cpu"))
@@ -51,6 +56,7 @@ def _worker(rank, world, port, tmpdir):
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
     dist.init_process_group("gloo", rank=rank, world_size=world)
     torch.set_num_threads(2)
+    _cpu_only()
     try:
         # (2) raw reducer
         fe, cls = _models()
@@ -140,6 +146,7 @@ def _fada_worker(rank, world, port, tmpdir):
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
     dist.init_process_group("gloo", rank=rank, world_size=world)
     torch.set_num_threads(2)
+    _cpu_only()
     try:
         import logging
         from rnd_semantic_segmentation_amd.host import fada

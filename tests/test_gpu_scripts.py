@@ -94,10 +94,10 @@ def test_bench_under_torchrun_nccl_single_rank_exercises_the_reducer():
 @pytest.mark.parametrize("workload,extra", [("pranet", ["--batch", "2", "--size", "96"]), ("gald", ["--batch", "1"]), ("deeplab_bn", ["--batch", "2", "--size", "161"]),
                                             ("fada", ["--batch", "2", "--size", "129"])])
 def test_bench_other_workloads_print_the_contract_line(workload, extra):
-    """bench.py --workload pranet | gald | deeplab_bn | fada (BASELINE config[3], the GALD step, the trainable-BatchNorm DeepLab step, config[4] on one GPU): one JSON line with the
-    contract's keys, a roofline object for the dominant kernel of the instrumented steps, finite loss."""
+    """bench.py --full --workload pranet | gald | deeplab_bn | fada (BASELINE config[3], the GALD step, the trainable-BatchNorm DeepLab step, config[4] on one GPU): one JSON
+    line with the contract's keys, a roofline object for the dominant kernel of the instrumented steps, finite loss."""
     import math
-    r = run(["bench.py", "--workload", workload, "--steps", "2", "--warmup", "1", "--no-cpu-baseline"] + extra, {})
+    r = run(["bench.py", "--full", "--workload", workload, "--steps", "2", "--warmup", "1", "--no-cpu-baseline"] + extra, {})
     assert r.returncode == 0, r.stderr[-3000:]
     out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config", "roofline"):
@@ -106,6 +106,30 @@ def test_bench_other_workloads_print_the_contract_line(workload, extra):
     assert out["roofline"]["bound"] in ("mfma", "hbm") and out["roofline"]["kernel"]
     loss = out.get("loss", out["config"].get("final_loss"))
     assert loss is not None and math.isfinite(loss)
+
+
+def test_bench_plain_run_reports_the_timed_steps_and_dumps_the_last_one(tmp_path):
+    """A plain bench.py run measures the timed steps only (no instrumented steps, no CPU baseline: those are --full), and `--dump-outputs DIR`
+    writes what the last timed step computed - its loss, a seeded sample of the parameters and gradients it left - as float32 / float64 .npy
+    files of 64 MB at most, the same in two runs (seeded inputs, formula weights)."""
+    import numpy as np
+    dumps = []
+    for i in range(2):
+        d = tmp_path / ("dump%d" % i)
+        r = run(["bench.py", "--steps", "3", "--warmup", "1", "--size", "161", "--batch", "2", "--dump-outputs", str(d)], {})
+        assert r.returncode == 0, r.stderr[-3000:]
+        out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+        assert out["steps"] == 3 and out["value"] > 0 and abs(out["ms_per_step"] * out["value"] - 2000) < 1
+        assert not {"roofline", "kernels", "kernel_families", "cpu_baseline"} & set(out), sorted(out)
+        arrs = {f: np.load(d / f) for f in os.listdir(d)}
+        assert {"loss.npy", "feature_extractor_params.npy", "feature_extractor_grads.npy", "classifier_params.npy", "classifier_grads.npy"} <= set(arrs)
+        assert all(a.dtype in (np.float32, np.float64) and np.isfinite(a).all() for a in arrs.values())
+        assert sum(os.path.getsize(d / f) for f in arrs) <= 64 << 20
+        assert abs(float(arrs["loss.npy"][0]) - out["config"]["final_loss"]) < 1e-4
+        assert np.abs(arrs["feature_extractor_grads.npy"]).max() > 0 and np.abs(arrs["classifier_grads.npy"]).max() > 0
+        dumps.append(arrs)
+    for f, a in dumps[0].items():
+        assert np.abs(a - dumps[1][f]).max() <= 1e-4 * np.abs(a).max(), f
 
 
 def test_opt_in_kernel_variants_and_single_stream_schedule_stay_correct():

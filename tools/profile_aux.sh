@@ -32,7 +32,7 @@ if [ "${PMC:-1}" = "1" ]; then
     pmc deeplab_bn sgd_kernel 2 --workload deeplab_bn --steps 3 --warmup 2 --no-cpu-baseline --no-kernel-events
     pmc fada adam 1 --workload fada --steps 3 --warmup 2 --no-cpu-baseline --no-kernel-events
 fi
-run pranet $root/bench.py --workload pranet --no-cpu-baseline --no-kernel-events
+run pranet $root/bench.py --full --workload pranet --no-cpu-baseline --no-kernel-events     # --full: the eager timing beside the graph replay
 run gald $root/bench.py --workload gald --steps 10 --warmup 3 --no-cpu-baseline --no-kernel-events
 run deeplab_bn $root/bench.py --workload deeplab_bn --steps 10 --warmup 4 --no-cpu-baseline --no-kernel-events
 run fada $root/bench.py --workload fada --steps 10 --warmup 3 --no-cpu-baseline --no-kernel-events
