@@ -387,7 +387,8 @@ int mi_gbn_finalize(const float* partials, int tiles, int C, long count, const f
 /* eval(): scale = gamma * rsqrt(running_var + eps), shift = beta - running_mean * scale */
 int mi_gbn_fold(const float* gamma, const float* beta, const float* running_mean, const float* running_var, float eps, float* scale, float* shift, int C,
                 void* stream);
-/* out = act(y * scale[c] + shift[c] (+ add)); relu: 0 none, 1 ReLU, 2 ReLU6 (hardnet_68.py:78); out bf16, or fp32 when out_f32 */
+/* out = act(y * scale[c] + shift[c] (+ add)); relu: 0 none, 1 ReLU, 2 ReLU6 (hardnet_68.py:78), any other code is refused; out bf16, or fp32 when
+ * out_f32 */
 int mi_gbn_apply(const void* y, long ldy, const float* scale, const float* shift, const void* add, long ldadd, void* out, long ldo, int out_f32, long M, int C,
                  int relu, void* stream);
 /* mi_gbn_apply (bf16 output) with up to 4 extra destinations (round 5): channels [c0[k], c1[k]) of the result AS STORED (rounded to bf16), plus add2[k] when

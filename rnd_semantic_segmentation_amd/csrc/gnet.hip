@@ -1056,6 +1056,7 @@ int mi_gbn_apply(const void* y, long ldy, const float* scale, const float* shift
                  int relu, void* stream) {
     MI_REQUIRE(y && scale && shift && out, "mi_gbn_apply: null operand");
     MI_REQUIRE(M > 0 && C > 0 && ldy >= C && ldo >= C && (!add || ldadd >= C), "mi_gbn_apply: bad shape");
+    MI_REQUIRE(relu >= 0 && relu <= 2, "mi_gbn_apply: activation code %d (0 none, 1 ReLU, 2 ReLU6)", relu);
     hipStream_t s = (hipStream_t)stream;
     const __bf16* yy = (const __bf16*)y;
     const __bf16* aa = (const __bf16*)add;
@@ -1073,6 +1074,7 @@ int mi_gbn_apply_multi(const void* y, long ldy, const float* scale, const float*
                        int n_extra, const int* c0, const int* c1, void* const* dst, const long* ldd, const void* const* add2, const long* lda2, void* stream) {
     MI_REQUIRE(y && scale && shift, "mi_gbn_apply_multi: null operand");
     MI_REQUIRE(M > 0 && C > 0 && ldy >= C && (!out || ldo >= C) && (!add || ldadd >= C), "mi_gbn_apply_multi: bad shape");
+    MI_REQUIRE(relu >= 0 && relu <= 2, "mi_gbn_apply_multi: activation code %d (0 none, 1 ReLU, 2 ReLU6)", relu);
     MI_REQUIRE(n_extra >= 0 && n_extra <= APPLY_MAX_EXTRA && (n_extra == 0 || (c0 && c1 && dst && ldd && add2 && lda2)), "mi_gbn_apply_multi: 0 .. %d extra destinations", APPLY_MAX_EXTRA);
     MI_REQUIRE(out || n_extra > 0, "mi_gbn_apply_multi: nothing to write");
     GApplyExtras ex;

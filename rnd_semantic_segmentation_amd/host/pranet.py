@@ -269,6 +269,9 @@ class _Run:
         return gk.gbn_apply_multi(y, sc, sh, act, [(c0, c1, d, None if a2 is None else a2.t) for c0, c1, d, a2 in extras], add=add, out=out)
 
     def conv_bn(self, x, u, relu, add=None, out=None, out_f32=False, extras=None):
+        if relu == 6 and add is not None:
+            # the residual's backward masks with OP_RELU_MASK (out > 0), which would keep the gradient where ReLU6 clamped to 6; no layer needs the pair
+            raise _lib.MiError("conv_bn: ReLU6 together with a residual add is not supported")
         net, bn = self.net, u.bn
         act = 2 if relu == 6 else int(bool(relu))
         bias = None if u.bias is None else u.bias.detach()

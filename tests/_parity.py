@@ -1,5 +1,5 @@
-"""Shared helpers of the network-level GPU parity tests (PraNet, GALD): error measures, oracle / engine runners, and the TEACHER-FORCED
-comparison.
+"""Shared helpers of the GPU parity tests: the kernel-level bf16 operand / tolerance helpers, and for the network-level tests (PraNet, GALD) error
+measures, oracle / engine runners and the TEACHER-FORCED comparison.
 
 Why teacher forcing.  Both networks normalise with BatchNorm2d on batch statistics and are 50-80 convolutions deep; run freely in the bf16 regime,
 rounding accumulates from block to block - the reference's OWN modules under torch.autocast(bfloat16) end 0.15-0.25 away from their fp32 outputs and
@@ -12,6 +12,32 @@ the block that makes it.
 """
 import numpy as np
 import torch
+
+
+# ---- kernel-level parity (tests/test_gpu_gops.py, tests/test_gpu_gald_kernels.py): bf16 operands, float64 torch on the same rounded values
+def _rand(shape, seed, scale=1.0):
+    g = torch.Generator().manual_seed(seed)
+    return (torch.randn(shape, generator=g) * scale).to(torch.bfloat16)
+
+
+def _nhwc(x_nchw):
+    return x_nchw.permute(0, 2, 3, 1).contiguous()
+
+
+def _embed(x_nhwc, ld, off):
+    """x as the channel slice [off, off + C) of a wider NHWC tensor filled with a sentinel."""
+    B, H, W, C = x_nhwc.shape
+    big = torch.full((B, H, W, ld), 7.0, dtype=x_nhwc.dtype, device=x_nhwc.device)
+    big[..., off:off + C] = x_nhwc
+    return big, big[..., off:off + C]
+
+
+def _close_bf16(got, ref, what, ulps=1.0, floor=2e-5):
+    got = got.double().cpu()
+    ref = ref.double()
+    tol = ulps * 2.0 ** -8 * ref.abs() + floor * ref.abs().max()
+    bad = (got - ref).abs() > tol
+    assert not bad.any(), "%s: %d of %d outside tolerance, worst %.3e (ref max %.3e)" % (what, int(bad.sum()), bad.numel(), float((got - ref).abs().max()), float(ref.abs().max()))
 
 
 def rel(a, b):

@@ -7,6 +7,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from _parity import _close_bf16, _embed, _nhwc, _rand
+
 pytestmark = pytest.mark.gpu
 
 
@@ -16,31 +18,6 @@ def gk():
     entry.build()
     from rnd_semantic_segmentation_amd import gk as g
     return g
-
-
-def _rand(shape, seed, scale=1.0):
-    g = torch.Generator().manual_seed(seed)
-    return (torch.randn(shape, generator=g) * scale).to(torch.bfloat16)
-
-
-def _nhwc(x_nchw):
-    return x_nchw.permute(0, 2, 3, 1).contiguous()
-
-
-def _embed(x_nhwc, ld, off):
-    """x as the channel slice [off, off + C) of a wider NHWC tensor filled with a sentinel."""
-    B, H, W, C = x_nhwc.shape
-    big = torch.full((B, H, W, ld), 7.0, dtype=x_nhwc.dtype, device=x_nhwc.device)
-    big[..., off:off + C] = x_nhwc
-    return big, big[..., off:off + C]
-
-
-def _close_bf16(got, ref, what, ulps=1.0, floor=2e-5):
-    got = got.double().cpu()
-    ref = ref.double()
-    tol = ulps * 2.0 ** -8 * ref.abs() + floor * ref.abs().max()
-    bad = (got - ref).abs() > tol
-    assert not bad.any(), "%s: %d of %d outside tolerance, worst %.3e (ref max %.3e)" % (what, int(bad.sum()), bad.numel(), float((got - ref).abs().max()), float(ref.abs().max()))
 
 
 CONV_CASES = [
@@ -264,9 +241,13 @@ def test_gconv_weight_gradient_is_bit_reproducible_and_splits_k(gk):
 
 
 @pytest.mark.parametrize("C,relu,with_add,f32", [(26, True, False, False), (104, True, True, False), (32, False, False, False), (1, False, False, True),
-                                                 (256, True, False, False)])
+                                                 (256, True, False, False), (104, 6, False, False), (26, 6, False, False), (32, 6, False, True)])
 def test_batchnorm_train_forward_backward(gk, C, relu, with_add, f32):
-    """conv statistics -> mi_gbn_finalize -> mi_gbn_apply, and the two backward kernels, against nn.BatchNorm2d in train() (float64)."""
+    """conv statistics -> mi_gbn_finalize -> mi_gbn_apply, and the two backward kernels, against nn.BatchNorm2d in train() (float64).  relu: False,
+    True or 6 (ReLU6 = F.hardtanh(., 0, 6), activation code 2 as conv_bn passes it; gamma / beta put over a third of the outputs above 6 and some
+    within one bf16 ulp of it; bf16 g on VEC 8 / VEC 2 channel counts and an fp32 g).  The kernels mask the gradient by the STORED output; that
+    mask may differ from torch's only where the float64 pre-activation lies within one bf16 ulp of 0 or 6 - asserted, and inside that band the
+    reference takes the kernel's mask."""
     B, H, W = 3, 13, 9
     x = _rand((B, max(C, 8), H, W), 40 + C)
     w = _rand((C, max(C, 8), 1, 1), 41 + C, 0.3).float()
@@ -274,26 +255,24 @@ def test_batchnorm_train_forward_backward(gk, C, relu, with_add, f32):
     y, st = gk.gconv(_nhwc(x).cuda(), wp, C, (1, 1, 1, 1, 0, 0, 1, 1), stats=True)          # y: bf16 conv output + tile statistics
     bn = torch.nn.BatchNorm2d(C).double()
     with torch.no_grad():
-        bn.weight.copy_(torch.linspace(0.5, 1.5, C))
-        bn.bias.copy_(torch.linspace(-0.3, 0.4, C))
+        bn.weight.copy_(torch.linspace(2, 4, C) if relu == 6 else torch.linspace(0.5, 1.5, C))
+        bn.bias.copy_(torch.linspace(4.5, 5.5, C) if relu == 6 else torch.linspace(-0.3, 0.4, C))
         bn.running_mean.copy_(torch.linspace(-1, 1, C))
         bn.running_var.copy_(torch.linspace(0.5, 2, C))
     rm, rv = bn.running_mean.float().cuda(), bn.running_var.float().cuda()
     yd = y.permute(0, 3, 1, 2).double().cpu().requires_grad_(True)
     add = _rand((B, C, H, W), 43) if with_add else None
-    ref = bn(yd)
+    pre = bn(yd)
     if add is not None:
-        ref = ref + add.double()
-    if relu:
-        ref = F.relu(ref)
+        pre = pre + add.double()
+    ref = F.hardtanh(pre, 0.0, 6.0) if relu == 6 else (F.relu(pre) if relu else pre)
     g = _rand((B, C, H, W), 44)
     if f32:
         g = g.float() * 1.37
-    ref.backward(g.double())
     fin = gk.gbn_finalize(st, C, B * H * W, bn.weight.float().cuda(), bn.bias.float().cuda(), rm, rv, 0.1, 1e-5)
     mean, invstd, scale, shift = fin[0], fin[1], fin[2], fin[3]
     addv = _embed(_nhwc(add).cuda(), C + 6, 4)[1] if add is not None else None
-    out = gk.gbn_apply(y, scale, shift, relu, add=addv, out_f32=f32)
+    out = gk.gbn_apply(y, scale, shift, 2 if relu == 6 else int(bool(relu)), add=addv, out_f32=f32)
     torch.cuda.synchronize()
     if f32:
         assert float((out.permute(0, 3, 1, 2).double().cpu() - ref.detach()).abs().max()) < 2e-5 * float(ref.abs().max()) + 1e-5
@@ -301,18 +280,47 @@ def test_batchnorm_train_forward_backward(gk, C, relu, with_add, f32):
         _close_bf16(out.permute(0, 3, 1, 2), ref.detach(), "bn apply C=%d" % C, floor=1e-4)
     assert torch.allclose(rm.double().cpu(), bn.running_mean, rtol=1e-5, atol=1e-6)
     assert torch.allclose(rv.double().cpu(), bn.running_var, rtol=1e-4, atol=1e-6)
-    # backward: the ReLU mask comes from the stored output
+    if relu:
+        # mask agreement: near 0 the band is one bf16 ulp of the magnitudes that cancel (|gamma xhat| + |beta| + |add|), at 6 one ulp of 6 (2^-5)
+        o, p = out.permute(0, 3, 1, 2).double().cpu(), pre.detach()
+        hi = 6.0 if relu == 6 else float("inf")
+        beta = bn.bias.detach().view(1, C, 1, 1)
+        a64 = add.double() if add is not None else torch.zeros_like(p)
+        mag = (p - beta - a64).abs() + beta.abs() + a64.abs()
+        band = (p.abs() <= 2.0 ** -8 * mag) | ((p - 6.0).abs() <= 2.0 ** -5 if relu == 6 else torch.zeros_like(p, dtype=torch.bool))
+        mk, mt = (o > 0) & (o < hi), (p > 0) & (p < hi)
+        flip = mk != mt
+        print("bn C=%d relu=%s: %d of %d above the clamp, %d in the one-ulp band, %d masks differ (bar: none outside the band)"
+              % (C, relu, int((p >= 6).sum()) if relu == 6 else 0, p.numel(), int(band.sum()), int(flip.sum())))
+        assert not bool((flip & ~band).any()), "the kernels' gradient mask differs from torch's outside the one-ulp band"
+        pre.backward(g.double() * torch.where(band, mk, mt))
+    else:
+        pre.backward(g.double())
+    # backward: the ReLU / ReLU6 mask comes from the stored output
     gv = _nhwc(g).cuda()
     dbeta, dgamma = torch.empty(C, device="cuda"), torch.empty(C, device="cuda")
     mask = out if relu else None
-    gk.gbn_bwd_sums(gv, y, mask, mean, invstd, dbeta, dgamma)
-    dy = gk.gbn_bwd_apply(gv, y, mask, mean, invstd, bn.weight.float().cuda(), dbeta, dgamma, B * H * W)
+    gk.gbn_bwd_sums(gv, y, mask, mean, invstd, dbeta, dgamma, relu6=relu == 6)
+    dy = gk.gbn_bwd_apply(gv, y, mask, mean, invstd, bn.weight.float().cuda(), dbeta, dgamma, B * H * W, relu6=relu == 6)
     torch.cuda.synchronize()
-    # the reference masks by its own (float64) output; a bf16-rounded output that became exactly 0 differs only where |ref| < 1 ulp
     assert torch.allclose(dbeta.double().cpu(), bn.bias.grad, rtol=2e-3, atol=2e-3 * float(bn.bias.grad.abs().max()))
     assert torch.allclose(dgamma.double().cpu(), bn.weight.grad, rtol=2e-3, atol=2e-3 * float(bn.weight.grad.abs().max()))
     e = float((dy.permute(0, 3, 1, 2).double().cpu() - yd.grad).abs().max()) / float(yd.grad.abs().max())
     assert e < 1.5e-2, e                # bf16 dy (2^-8) on top of the mask agreement
+
+
+def test_batchnorm_apply_refuses_unknown_activation_codes(gk):
+    """The applies take an activation CODE (0 none, 1 ReLU, 2 ReLU6); 6 - what gconv_f32's relu=6 means - or any other value is refused instead of
+    running as a plain ReLU."""
+    from rnd_semantic_segmentation_amd._lib import MiError
+    y = _nhwc(_rand((1, 16, 3, 3), 7)).cuda()
+    sc, sh = torch.ones(16, device="cuda"), torch.zeros(16, device="cuda")
+    for code in (6, 3, -1):
+        with pytest.raises(MiError, match="activation code"):
+            gk.gbn_apply(y, sc, sh, code)
+        with pytest.raises(MiError, match="activation code"):
+            gk.gbn_apply_multi(y, sc, sh, code, [])
+    assert torch.equal(gk.gbn_apply(y, sc, sh, 2), y.clamp(0, 6))
 
 
 def test_bias_gradient_is_a_column_sum(gk):
@@ -379,6 +387,12 @@ def test_elementwise_and_reverse_attention(gk):
     _close_bf16(gk.gbinary(gk.OP_MUL, av, bv).permute(0, 3, 1, 2), a.double() * b.double(), "mul")
     _close_bf16(gk.gbinary(gk.OP_RELU_MASK, av, bv).permute(0, 3, 1, 2), torch.where(b > 0, a, torch.zeros_like(a)).double(), "mask")
     assert torch.equal(gk.gbinary(gk.OP_COPY, av).cpu(), _nhwc(a))
+    # OP_MULRELU (FAM's relu(a * b)): on the 2-byte-offset view above (VEC 2), a 64-channel pair (VEC 8) and an odd channel offset (VEC 1)
+    _close_bf16(gk.gbinary(gk.OP_MULRELU, av, bv).permute(0, 3, 1, 2), F.relu(a.double() * b.double()), "mulrelu VEC 2")
+    a8, b8 = _rand((2, 64, 7, 9), 84), _rand((2, 64, 7, 9), 85)
+    _close_bf16(gk.gbinary(gk.OP_MULRELU, _nhwc(a8).cuda(), _nhwc(b8).cuda()).permute(0, 3, 1, 2), F.relu(a8.double() * b8.double()), "mulrelu VEC 8")
+    _, a1 = _embed(_nhwc(a).cuda(), 104, 27)
+    _close_bf16(gk.gbinary(gk.OP_MULRELU, a1, bv).permute(0, 3, 1, 2), F.relu(a.double() * b.double()), "mulrelu VEC 1")
     f = torch.randn(2, 7, 9, 1, device="cuda")
     assert torch.equal(gk.gbinary(gk.OP_COPY, f, out_dtype=torch.bfloat16), f.to(torch.bfloat16))
     # reverse attention

@@ -329,3 +329,13 @@ def test_tile_route_of_the_tape_engines_is_consistent_with_the_padded_gathers():
     u = layers[15]
     ok = lambda c: pranet._mfma_tile_ok(u, torch.empty((6, 90, 160, c), dtype=torch.bfloat16, device="meta"))
     assert ok(480) and not ok(466) and not ok(512)
+
+
+def test_conv_bn_refuses_relu6_with_a_residual_before_any_launch():
+    """_Run.conv_bn's residual backward masks with OP_RELU_MASK (out > 0), which would keep the gradient where ReLU6 clamped to 6 (torch's hardtanh
+    backward drops it there).  No layer combines the two, so the pair is refused at entry - before any operand is touched or any kernel launched."""
+    from rnd_semantic_segmentation_amd import _lib
+    from rnd_semantic_segmentation_amd.host import pranet
+    run = pranet._Run(object(), True, True)
+    with pytest.raises(_lib.MiError, match="ReLU6"):
+        run.conv_bn(None, None, 6, add=object())
