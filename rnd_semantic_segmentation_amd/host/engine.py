@@ -99,51 +99,59 @@ def grad_slot(p):
 
 
 # ------------------------------------------------------------------------------------------------ weight-gradient stream
-class _SideStream:
-    """Weight gradients are off the backward critical path (nothing consumes them before the optimizer / all-reduce), so they
-    run on a second HIP stream: their workgroups fill the CUs that the data-gradient kernels leave idle in their last partial
-    round (tile quantisation costs 10-25 % of a launch at M = 75 272), and the small slab reducers hide entirely.
-    MI_WGRAD_STREAM=0 puts everything back on one stream."""
-    _by_device = {}
+class WgradScheduler:
+    """Where the weight gradients of one backward pass run.  They are off the critical path (nothing consumes them before the
+    optimizer / all-reduce), so they run on a second HIP stream: their workgroups fill the CUs that the data-gradient kernels leave
+    idle in their last partial round (tile quantisation costs 10-25 % of a launch at M = 75 272), and the small slab reducers hide
+    entirely.  One side stream per device; none (everything inline) with MI_WGRAD_STREAM=0, off CUDA, or under per-launch timing."""
+    _streams = {}
 
-    def __init__(self, device):
-        self.stream = torch.cuda.Stream(device=device)          # (high priority for it measured 288.4 vs 290.7 images/s: profiles/r05_wgrad_sched_ab.txt)
+    def __init__(self, side):
+        self.side = side                  # a torch.cuda.Stream, or None: jobs run inline on the current stream
         self.dirty = False
 
     @classmethod
-    def get(cls, device):
+    def on(cls, device):
+        """The scheduler of a backward pass on `device`, with the device's side stream when there is one."""
         if os.environ.get("MI_WGRAD_STREAM", "1") == "0" or device.type != "cuda":
-            return None
+            return cls(None)
         if K.PROFILE is not None:      # per-launch timing requested (bench.py's instrumented steps): one stream, so that a
-            return None                # launch's event-to-event time is that kernel's alone
+            return cls(None)           # launch's event-to-event time is that kernel's alone
         key = device.index if device.index is not None else torch.cuda.current_device()
-        if key not in cls._by_device:
-            cls._by_device[key] = cls(torch.device("cuda", key))
-        return cls._by_device[key]
+        if key not in cls._streams:    # (high priority for it measured 288.4 vs 290.7 images/s: profiles/r05_wgrad_sched_ab.txt)
+            cls._streams[key] = torch.cuda.Stream(device=torch.device("cuda", key))
+        return cls(cls._streams[key])
 
-    def run(self, fn, *inputs):
-        """fn() on the side stream after everything enqueued so far on the current stream; `inputs` are the tensors it reads
-        (their memory must not be recycled by the allocator before the side stream is done with them)."""
-        ev = torch.cuda.Event()
-        ev.record(torch.cuda.current_stream())
-        self.stream.wait_event(ev)
-        with torch.cuda.stream(self.stream):
+    def run(self, fn, *keep):
+        """fn() off the critical path: on the side stream after everything enqueued so far on the current stream, else inline.
+        `keep`: the tensors it reads or writes that this backward pass may free (the allocator must not recycle them before the side
+        stream is done); scratch it needs beyond those it allocates itself, on the stream that runs it."""
+        if self.side is None:
             fn()
-        for t in inputs:
-            t.record_stream(self.stream)
+            return
+        self.side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(self.side):
+            fn()
+        for t in keep:
+            t.record_stream(self.side)
         self.dirty = True
 
+    def end_block(self, batch, store, params):
+        """A block's weight gradients are all enqueued: its deferred slab reducers (`batch`, a K.WgradBatch, or None) as one launch on
+        the stream their partials ran on, then the store's grad hooks for the span of `params`, ordered after them on that stream."""
+        if batch is not None:
+            self.run(batch.flush)
+        if store is not None and store.grad_hooks:
+            lo, hi = store.span(params)
+            with torch.cuda.stream(self.side) if self.side is not None else contextlib.nullcontext():
+                for hook in store.grad_hooks:         # the all-reduce of this range is ordered after its weight gradients
+                    hook(store, lo, hi)
+
     def join(self):
+        """The current stream waits for the side stream: the optimizer / caller sees complete gradients on its own stream."""
         if self.dirty:
-            torch.cuda.current_stream().wait_stream(self.stream)
+            torch.cuda.current_stream().wait_stream(self.side)
             self.dirty = False
-
-
-def _off_path(side, fn, *inputs):
-    if side is None:
-        fn()
-    else:
-        side.run(fn, *inputs)
 
 
 class _Lanes:
@@ -413,25 +421,11 @@ class StageEngine:
         """dfeat: d loss / d feat (bf16 NHWC); fbits: sign bits of feat.  Returns d loss / d x of the first block."""
         g = K.relu_mask(dfeat, fbits)                     # through the last block's ReLU
         store = getattr(self.convs[0].weight, "_mi_store", None)
-        side = _SideStream.get(dfeat.device)
-        # MI_BWD_PAIR=1 (experiment, section 8 of DESIGN.md): pair the launches of the two streams by the resource that bounds them.  In stream order a
-        # block is D3 D2 D1 on the main stream (data gradients: MFMA-, MFMA-, HBM-bound) and W3 W2 W1 behind them on the side stream (weight gradients:
-        # HBM-, MFMA-, HBM-bound), i.e. W2 beside D2 (both MFMA-bound) and W1 beside D1 (both HBM-bound).  Deferring W1 to the next block's start puts
-        # W3 + W1' beside D3 D2 and W2 beside D1.
-        bwd_pair = side is not None and os.environ.get("MI_BWD_PAIR", "0") == "1"
-        deferred = None
+        sched = WgradScheduler.on(dfeat.device)
         chain = self.chain_mode() in ("all", "bwd") and self._chain_fits(dfeat)
         ga2_ahead = None
-
-        def hooks(rts_):
-            if store is not None and store.grad_hooks:
-                lo, hi = store.span([rt.weight for rt in rts_])
-                with torch.cuda.stream(side.stream) if side is not None else contextlib.nullcontext():
-                    for hook in store.grad_hooks:         # the all-reduce of this range is ordered after its weight gradients
-                        hook(store, lo, hi)
-        # MI_WGRAD_REDUCE_BATCH=1 (default): the slab reducers of a block's weight gradients run as ONE launch at the end of the block (K.WgradBatch)
-        # instead of one 10-us launch behind each weight gradient - on the side stream each of those waited ~35 us for its turn beside the data-gradient chain
-        batching = os.environ.get("MI_WGRAD_REDUCE_BATCH", "1") != "0" and not bwd_pair and K.PROFILE is None
+        # The slab reducers of a block's weight gradients run as ONE launch at the end of the block (K.WgradBatch) instead of one 10-us launch behind each
+        # weight gradient - on the side stream each of those waited ~35 us for its turn beside the data-gradient chain (rounds 1-4: 295.4 vs 300.0 images/s).
         # (Tried, profiles/r05_wgrad_sched_ab.txt: the block's three weight gradients on two / three streams - 281 / 280 images/s against 297 on one, the
         #  streams' workgroups evict each other's L2 lines; reducers batched over two blocks - 298.4 against 297.5, inside the noise.  Neither is kept.)
         for bi in range(len(self.blocks) - 1, -1, -1):
@@ -440,27 +434,18 @@ class StageEngine:
             first = bi == 0
             hw_in = (x.shape[1], x.shape[2])
             hw_mid = (a1.shape[1], a1.shape[2])
-            wb = K.WgradBatch() if batching else None
-            _off_path(side, lambda: self._wgrad(g, a2, rts[2], wb), g, a2)
-            if deferred is not None:                      # the previous block's W1 (and its hooks) ride beside this block's D3 / D2
-                dga1, dx_, drts = deferred
-                _off_path(side, lambda: self._wgrad(dga1, dx_, drts[0]), dga1, dx_)
-                hooks(drts)
-                deferred = None
+            wb = K.WgradBatch() if K.PROFILE is None else None
+            sched.run(lambda: self._wgrad(g, a2, rts[2], wb), g, a2)
             if ga2_ahead is not None:                     # written by the chained launch of the block above (its conv1's data gradient)
                 ga2, ga2_ahead = ga2_ahead, None
             else:
                 ga2 = self._dgrad(g, rts[2], (a2.shape[1], a2.shape[2]), bits=b2)
-            _off_path(side, lambda: self._wgrad(ga2, a1, rts[1], wb), ga2, a1)
+            sched.run(lambda: self._wgrad(ga2, a1, rts[1], wb), ga2, a1)
             ga1 = self._dgrad(ga2, rts[1], hw_mid, bits=b1)
             if blk.down:
-                _off_path(side, lambda: self._wgrad(g, x, rts[3], wb), g, x)
-            if bwd_pair and not first:
-                deferred = (ga1, x, rts)
-            else:
-                _off_path(side, lambda: self._wgrad(ga1, x, rts[0], wb), ga1, x)
-            if wb is not None:
-                _off_path(side, wb.flush)
+                sched.run(lambda: self._wgrad(g, x, rts[3], wb), g, x)
+            sched.run(lambda: self._wgrad(ga1, x, rts[0], wb), ga1, x)
+            sched.end_block(wb, store, [rt.weight for rt in rts])
             pair = self._chain_pair(bi - 1) if chain and not first and not blk.down else None
             if first and not need_dx:
                 g = None
@@ -471,10 +456,7 @@ class StageEngine:
                 skip = self._dgrad(g, rts[3], hw_in) if blk.down else g
                 g = self._dgrad(ga1, rts[0], hw_in, res=skip, bits=None if first else xb)
             saved[bi] = None                              # release activations as we go
-            if deferred is None:
-                hooks(rts)
-        if side is not None:
-            side.join()                                   # the optimizer / caller sees complete gradients on its own stream
+        sched.join()
         return g
 
 
@@ -515,52 +497,42 @@ class StageEngine:
         mask (no separate add or mask pass); weight gradients on the side stream."""
         g = K.relu_mask(dfeat, fbits)
         store = getattr(self.convs[0].weight, "_mi_store", None)
-        side = _SideStream.get(dfeat.device)
+        sched = WgradScheduler.on(dfeat.device)
 
-        batching = os.environ.get("MI_WGRAD_REDUCE_BATCH", "1") != "0" and K.PROFILE is None
-        wb = [None]                                   # the block's slab reducers as one launch (K.WgradBatch), as in backward()
-
-        def wgrad(dy, xin, rt):
+        def wgrad(dy, xin, rt, wb):
             c = rt.spec
 
             def go():
                 dw, acc = grad_slot(rt.weight)
-                K.conv_wgrad(dy, xin, dw, c.k, c.stride, c.pad, c.dil, accumulate=acc, batch=wb[0])
-            _off_path(side, go, dy, xin)
+                K.conv_wgrad(dy, xin, dw, c.k, c.stride, c.pad, c.dil, accumulate=acc, batch=wb)
+            sched.run(go, dy, xin)
 
         for bi in range(len(self.blocks) - 1, -1, -1):
             blk, rts = self.blocks[bi]
             x, xb, (u1, u2, u3, ud) = saved[bi]
             first = bi == 0
             hw_in = (x.shape[1], x.shape[2])
-            wb[0] = K.WgradBatch() if batching else None
+            wb = K.WgradBatch() if K.PROFILE is None else None      # the block's slab reducers as one launch, as in backward()
             dy3 = bn_backward(g, u3[1], u3[2], u3[3], rts[2].bn)
-            wgrad(dy3, u2[0], rts[2])
+            wgrad(dy3, u2[0], rts[2], wb)
             ga2 = self._dgrad(dy3, rts[2], (u2[0].shape[1], u2[0].shape[2]))
             dy2 = bn_backward(ga2, u2[1], u2[2], u2[3], rts[1].bn, bits=u2[4])
-            wgrad(dy2, u1[0], rts[1])
+            wgrad(dy2, u1[0], rts[1], wb)
             ga1 = self._dgrad(dy2, rts[1], (u1[0].shape[1], u1[0].shape[2]))
             dy1 = bn_backward(ga1, u1[1], u1[2], u1[3], rts[0].bn, bits=u1[4])
-            wgrad(dy1, x, rts[0])
+            wgrad(dy1, x, rts[0], wb)
             dyd = None
             if blk.down:
                 dyd = bn_backward(g, ud[1], ud[2], ud[3], rts[3].bn)
-                wgrad(dyd, x, rts[3])
+                wgrad(dyd, x, rts[3], wb)
             if first and not need_dx:
                 g = None
             else:
                 skip = self._dgrad(dyd, rts[3], hw_in) if blk.down else g
                 g = self._dgrad(dy1, rts[0], hw_in, res=skip, bits=None if first else xb)
             saved[bi] = None
-            if wb[0] is not None:
-                _off_path(side, wb[0].flush)
-            if store is not None and store.grad_hooks:
-                lo, hi = store.span([p for rt in rts for p in (rt.weight, rt.bn.weight, rt.bn.bias)])
-                with torch.cuda.stream(side.stream) if side is not None else contextlib.nullcontext():
-                    for hook in store.grad_hooks:
-                        hook(store, lo, hi)
-        if side is not None:
-            side.join()
+            sched.end_block(wb, store, [p for rt in rts for p in (rt.weight, rt.bn.weight, rt.bn.bias)])
+        sched.join()
         return g
 
 
@@ -850,7 +822,7 @@ class AsppEngine:
         g = K.aspp_im2col(dlow, self.rates)
         w4, ws = self._w4()
         b4, bs = self._b4()
-        side = _SideStream.get(x.device)
+        sched = WgradScheduler.on(x.device)
 
         def weight_and_bias_grads():
             slots = [grad_slot(p) for p in ws]
@@ -876,10 +848,9 @@ class AsppEngine:
                     slot.add_(db4[i]) if acc else slot.copy_(db4[i])
 
         # off the critical path: runs beside the data-gradient GEMM below; joined right after it is enqueued
-        _off_path(side, weight_and_bias_grads, g, x, dlow)
+        sched.run(weight_and_bias_grads, g, x, dlow)
         dx = K.conv_gemm(g, self.wallT, (h, w), msk=msk, flop_cols=36 * self.K) if need_dx else None
-        if side is not None:
-            side.join()
+        sched.join()
         store = getattr(ws[0], "_mi_store", None)
         if store is not None and store.grad_hooks:
             for hook in store.grad_hooks:

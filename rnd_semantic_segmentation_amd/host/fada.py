@@ -85,7 +85,7 @@ class _DiscEngine:
         hw = (x.shape[1], x.shape[2])
         g = ddlow.to(torch.bfloat16).contiguous()
         k = ps[4].shape[0]
-        side = engine._SideStream.get(x.device) if need_wgrad else None      # weight gradients beside the data-gradient chain
+        sched = engine.WgradScheduler.on(x.device)      # weight gradients beside the data-gradient chain
 
         def head_grads():
             dwc = torch.empty((NPAD,) + tuple(ps[4].shape[1:]), dtype=torch.float32, device=x.device)
@@ -103,16 +103,15 @@ class _DiscEngine:
             K.bias_grad_bf16(dy, slot, accumulate=acc)
 
         if need_wgrad:
-            engine._off_path(side, head_grads, g, a2)
+            sched.run(head_grads, g, a2)
         ga2 = K.conv_gemm(g, P["wct"], hw, 3, 1, 1, 1, K.GATHER_DGRAD, bits=m2, leaky=LEAK)
         if need_wgrad:
-            engine._off_path(side, lambda: conv_grads(ga2, a1, ps[2], ps[3]), ga2, a1)
+            sched.run(lambda: conv_grads(ga2, a1, ps[2], ps[3]), ga2, a1)
         ga1 = K.conv_gemm(ga2, P["w2t"], hw, 3, 1, 1, 1, K.GATHER_DGRAD, bits=m1, leaky=LEAK)
         if need_wgrad:
-            engine._off_path(side, lambda: conv_grads(ga1, x, ps[0], ps[1]), ga1, x)
+            sched.run(lambda: conv_grads(ga1, x, ps[0], ps[1]), ga1, x)
         dx = K.conv_gemm(ga1, P["w1t"], hw, 3, 1, 1, 1, K.GATHER_DGRAD) if need_dx else None
-        if side is not None:
-            side.join()
+        sched.join()
         return dx
 
 

@@ -26,7 +26,7 @@ from .. import _lib
 from .. import gk
 from .. import kernels as K
 from . import arch
-from .engine import FlatStore, _SideStream, _off_path
+from .engine import FlatStore, WgradScheduler
 from .plugin import BaseTrainer
 
 
@@ -109,10 +109,12 @@ def _basic(name, cin, cout, k, pad=0):
 
 
 _SIDE_MIN_WORK = 8e9          # weight gradients at least this large go to the side stream one by one (GALD: flat from 2 to 16 GFLOP; none: -3 %)
-_WQ_BUDGET = int(float(os.environ.get("MI_WGRAD_QUEUE_MB", "2048")) * (1 << 20))
+# the queue keeps every dy alive (and its flush sums a private split-K slab per job): bounded, so that backward's peak memory does not grow with the depth
+# of the net - 2048 MB of queued gradients (PraNet at 16 x 352 x 352 and GALD at 6 x 720 x 1280 never reach it; a flush costs one more pair of launches)
+_WQ_BUDGET = 2048 << 20
 # With a side stream (GALD) the queue is flushed every few convs, so that the table-driven launches run beside the data-gradient chain instead of alone at the end
 # of the tape: 4 jobs per launch 176.8 images/s, 8: 175.9, 2: 175.3, 16: 174.0, only at the end: 172.1 (one box, two rounds)
-_WQ_SIDE_JOBS = int(os.environ.get("MI_TAPE_WQ_JOBS", "4"))
+_WQ_SIDE_JOBS = 4
 
 
 # ------------------------------------------------------------------------------------------------ tape
@@ -205,16 +207,75 @@ def _grad_target(v):
     return v.want if (v.want is not None and v.g is None) else None
 
 
+class _WgradQueue:
+    """Where and when the tape's weight gradients run, on a WgradScheduler (with a side stream when the run class's WGRAD_STREAM asks for one).
+    General-kernel weight gradients below _SIDE_MIN_WORK, and the image's, are queued and run as one table-driven launch - alone each is a 25 - 60 us
+    latency chain of which 15 - 25 us are fixed; the rest are written directly, on the side stream or inline.  The accumulate flags come from tape
+    order, so two rules hold for every write to a gradient slot, whatever its route: a slot with a queued job is flushed before anything else writes
+    it, and an inline write to a slot that the side stream has written since the last join waits for the side stream first."""
+
+    def __init__(self, sched):
+        self.sched = sched
+        self.jobs, self.queued, self.beside, self.bytes = [], set(), set(), 0
+
+    def _claim(self, slot, on_side):
+        key = slot.data_ptr()
+        if key in self.queued:
+            self.flush()
+        if on_side:
+            self.beside.add(key)
+        elif key in self.beside:
+            self.sched.join()
+            self.beside.clear()
+
+    def direct(self, slot, fn, dy, x, side):
+        """fn() writes `slot` now: on the side stream (side: True) or inline."""
+        self._claim(slot, side)
+        self.sched.run(fn, dy, x) if side else fn()
+
+    def put(self, dy, x, slot, geom, acc, cin):
+        """Queue slot (+)= the weight gradient of (dy, x), keeping dy and x alive until the flush.  cin: x is the zero-padded image, whose gradient
+        for all its channels goes to scratch that the flush allocates on the stream that runs it, the real `cin` cut out after (else None)."""
+        self._claim(slot, self.sched.side is not None)
+        self.jobs.append((dy, x, slot, geom, acc, cin))
+        self.queued.add(slot.data_ptr())
+        self.bytes += dy.numel() * dy.element_size()
+        if self.bytes > _WQ_BUDGET or (self.sched.side is not None and len(self.jobs) >= _WQ_SIDE_JOBS):
+            self.flush()
+
+    def flush(self):
+        jobs = self.jobs
+        if not jobs:
+            return
+        if self.sched.side is not None:
+            self.beside |= self.queued
+        self.jobs, self.queued, self.bytes = [], set(), 0
+
+        def go():
+            table, fix = [], []
+            for dy, x, slot, geom, acc, cin in jobs:
+                if cin is None:
+                    table.append((dy, x, slot, geom, acc))
+                else:
+                    wide = torch.empty((slot.shape[0], x.shape[-1]) + tuple(geom[:2]), dtype=torch.float32, device=dy.device)
+                    table.append((dy, x, wide, geom, False))
+                    fix.append((slot, wide[:, :cin], acc))
+            gk.gconv_wgrad_multi(table)
+            for slot, real, acc in fix:
+                slot.add_(real) if acc else slot.copy_(real)
+        # with a side stream (GALD) the table-driven launch runs beside the data-gradient chain that is still being enqueued
+        self.sched.run(go, *[t for j in jobs for t in j[:2]])
+
+
 class _Run:
     """One forward pass.  train: BatchNorm2d on batch statistics (module.training); rec: record the backward tape."""
     WGRAD_STREAM = False          # the large weight gradients of backward() on the side stream (see _conv_backward)
 
     def __init__(self, net, train, rec):
-        self.net, self.train, self.rec, self.tape, self.side = net, train, rec, [], None
-        self.wq, self.wq_slots, self.wq_fix = None, None, []            # weight gradients queued during backward (see _conv_backward)
+        self.net, self.train, self.rec, self.tape = net, train, rec, []
+        self.wq = None                  # the weight-gradient queue of backward() (_WgradQueue)
         # MI_APPLY_MULTI=0: every gather copy / hierarchical add as its own launch again (the BatchNorm apply then has one destination; same bits)
         self.multi = os.environ.get("MI_APPLY_MULTI", "1") != "0"
-        self.wq_bytes = 0
         # fp32: the evaluation forward in the reference's precision (csrc/gf32.hip; _Engine.set_precision): every activation fp32, every conv with
         # its eval()-BatchNorm affine, residual and activation in one launch
         self.f32 = (not train) and getattr(net, "precision", "bf16") == "fp32"
@@ -334,65 +395,43 @@ class _Run:
         return ov
 
     def _conv_backward(self, x, u, dy):
-        """Weight gradient (off the critical path: nothing reads it before the optimizer, so it runs on the side stream beside the data-gradient
-        chain - the convs of these nets are far too small to fill 256 CUs alone) and data gradient."""
+        """Weight gradient (off the critical path, _WgradQueue: nothing reads it before the optimizer, and the convs of these nets are far too small to
+        fill 256 CUs alone) and data gradient."""
         slot, acc = self.net._grad_slot(u.weight)
-        # MI_TAPE_WGRAD_STREAM (default: the run class's WGRAD_STREAM - off for PraNet, on for GALD).  Measured: every weight gradient on the side stream costs
+        q = self.wq
+        # The run class's WGRAD_STREAM (off for PraNet, on for GALD) gives the queue its side stream.  Measured: every weight gradient on the side stream costs
         # PraNet 6 % as a graph and 18 % eager (hundreds of 20-60 us launches, each fork / join a dependency the GPU has to resolve); only the launches of
         # >= 8 GFLOP there: PraNet still -10 % as a graph (659 vs 734 images/s: a second stream in the capture changes how the whole graph is scheduled),
         # GALD (eager, its decoder's and padded gathers' weight gradients are 100 - 400 us launches) +1.5 % (175.6 vs 173.0 images/s, round 5)
         work = 2.0 * dy.shape[0] * dy.shape[1] * dy.shape[2] * u.cout * (1 if u.depthwise else u.cin) * u.geom[0] * u.geom[1]
-        side = self.side if work >= _SIDE_MIN_WORK else None
+        side = q.sched.side is not None and work >= _SIDE_MIN_WORK
         if _mfma_tile_ok(u, x.t) and dy.is_contiguous() and dy.shape[-1] == _rup32(u.cout):
             k, s, p, d = u.geom[0], u.geom[2], u.geom[4], u.geom[6]
             np_, cp = _rup32(u.cout), _rup32(u.cin)
             def wgrad(dw, accumulate):
                 # on the side stream the launch runs beside the data-gradient chain: the deferred-reducer form plans its split for that (mi_conv_wgrad_partial)
-                if side is not None:                     # (GALD: 176.6 vs 175.9 images/s)
+                if side:                                 # (GALD: 176.6 vs 175.9 images/s)
                     b = K.WgradBatch()
                     K.conv_wgrad(dy, x.t, dw, k, s, p, d, accumulate=accumulate, batch=b)
                     b.flush()
                 else:
                     K.conv_wgrad(dy, x.t, dw, k, s, p, d, accumulate=accumulate)
-            if np_ == u.cout and cp == u.cin:
-                _off_path(side, lambda: wgrad(slot, acc), dy, x.t)
-            else:           # padded operands: the gradient of the padded weight, its real corner into the parameter's slot
-                def padded_wgrad():
-                    wide = torch.empty((np_, cp, k, k), dtype=torch.float32, device=dy.device)
-                    wgrad(wide, False)
-                    slot.add_(wide[:u.cout, :u.cin]) if acc else slot.copy_(wide[:u.cout, :u.cin])
-                _off_path(side, padded_wgrad, dy, x.t)
+            def padded_wgrad():         # padded operands: the gradient of the padded weight, its real corner into the parameter's slot
+                wide = torch.empty((np_, cp, k, k), dtype=torch.float32, device=dy.device)
+                wgrad(wide, False)
+                slot.add_(wide[:u.cout, :u.cin]) if acc else slot.copy_(wide[:u.cout, :u.cin])
+            q.direct(slot, (lambda: wgrad(slot, acc)) if np_ == u.cout and cp == u.cin else padded_wgrad, dy, x.t, side)
             if x.needs:
                 tgt = _grad_target(x)
                 dx = K.conv_gemm(dy, u.wpt.view(k * k, cp, np_), (x.t.shape[1], x.t.shape[2]), k, s, p, d, K.GATHER_DGRAD,
                                  out=tgt if (tgt is not None and tgt.is_contiguous() and tgt.shape[-1] == cp) else None)
                 _acc(x, dx, True)
             return
-        if x.t.shape[-1] != u.cin and not u.depthwise:
-            # the zero-padded image (_nhwc_input): the gradient for its eight channels goes to a scratch tensor, the real channels are cut out after the flush
-            wide = torch.empty((u.cout, x.t.shape[-1]) + tuple(u.geom[:2]), dtype=torch.float32, device=dy.device)
-            if self.wq is not None and side is None:
-                self.wq.append((dy, x.t, wide, u.geom, False))
-                self.wq_fix.append((slot, wide, u.cin, acc))
-            else:
-                gk.gconv_wgrad(dy, x.t, wide, u.geom)
-                slot.add_(wide[:, :u.cin]) if acc else slot.copy_(wide[:, :u.cin])
-        elif self.wq is not None and side is None:
-            # queued: the whole backward's weight gradients run as one table-driven launch at the end of the tape (gk.gconv_wgrad_multi) - alone each
-            # is a 25 - 60 us latency chain of which 15 - 25 us are fixed.  The queue keeps dy and x alive until then; a slot that is already in the
-            # queue (a module applied twice) flushes first, so that the accumulation order stays the tape's.
-            if slot.data_ptr() in self.wq_slots:
-                self.flush_wgrads()
-            self.wq.append((dy, x.t, slot, u.geom, acc))
-            self.wq_slots.add(slot.data_ptr())
-            # the queue keeps every dy alive (and its flush sums a private split-K slab per job): bounded, so that backward's peak memory does not
-            # grow with the depth of the net - MI_WGRAD_QUEUE_MB of queued gradients (default 2048: PraNet at 16 x 352 x 352 and GALD at 6 x 720 x 1280
-            # never reach it; a flush costs one more pair of launches)
-            self.wq_bytes += dy.numel() * dy.element_size()
-            if self.wq_bytes > _WQ_BUDGET or (self.side is not None and len(self.wq) >= _WQ_SIDE_JOBS):
-                self.flush_wgrads()
+        padded = x.t.shape[-1] != u.cin and not u.depthwise              # the zero-padded image (_nhwc_input)
+        if side and not padded:
+            q.direct(slot, lambda: gk.gconv_wgrad(dy, x.t, slot, u.geom, accumulate=acc), dy, x.t, True)
         else:
-            _off_path(side, lambda: gk.gconv_wgrad(dy, x.t, slot, u.geom, accumulate=acc), dy, x.t)
+            q.put(dy, x.t, slot, u.geom, acc, u.cin if padded else None)
         if x.needs:
             dx, _ = gk.gconv(dy, u.wpt, u.cin, u.geom, out=_grad_target(x), mode=gk.GATHER_DGRAD, out_hw=(x.t.shape[1], x.t.shape[2]))
             _acc(x, dx, True)
@@ -579,31 +618,14 @@ class _Run:
         self.record(gather)
         return parts, slots
 
-    def flush_wgrads(self):
-        if self.wq:
-            jobs, fix = self.wq, self.wq_fix
-
-            def go():
-                gk.gconv_wgrad_multi(jobs)
-                for slot, wide, cin, acc in fix:
-                    slot.add_(wide[:, :cin]) if acc else slot.copy_(wide[:, :cin])
-            # with a side stream (GALD) the table-driven launch runs beside the data-gradient chain that is still being enqueued
-            _off_path(self.side, go, *[t for j in jobs for t in j[:2]])
-        if self.wq is not None:
-            self.wq, self.wq_slots, self.wq_fix = [], set(), []
-        self.wq_bytes = 0
-
     def backward(self):
-        self.side = _SideStream.get(self.net._store.data.device) if os.environ.get("MI_TAPE_WGRAD_STREAM", "1" if self.WGRAD_STREAM else "0") == "1" else None
-        self.wq, self.wq_slots = ([], set()) if os.environ.get("MI_WGRAD_BATCH", "1") != "0" else (None, None)
-        self.wq_fix = []
+        self.wq = _WgradQueue(WgradScheduler.on(self.net._store.data.device) if self.WGRAD_STREAM else WgradScheduler(None))
         for fn in reversed(self.tape):
             fn()
         self.tape = []
-        self.flush_wgrads()
+        self.wq.flush()
+        self.wq.sched.join()          # the caller (optimizer, gradient exchange) sees complete weight gradients on its own stream
         self.wq = None
-        if self.side is not None:
-            self.side.join()          # the caller (optimizer, gradient exchange) sees complete weight gradients on its own stream
 
 
 # ------------------------------------------------------------------------------------------------ graph pieces

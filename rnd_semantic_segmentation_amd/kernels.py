@@ -241,7 +241,8 @@ def conv_chain(a, w_first, res, w_second, scale1=None, shift1=None, scale2=None,
 class WgradBatch:
     """The slab reducers of up to eight weight gradients as ONE launch (mi_conv_wgrad_partial + mi_conv_wgrad_reduce): conv_wgrad(..., batch=b) runs the
     main kernel only and keeps its split-K slabs in a workspace of its own; b.flush() (same stream, after the last of them) sums them all.  Same bits as
-    the one-call form.  A full batch flushes itself."""
+    the one-call form, except where the fused-row 3x3 split applies: mi_conv_wgrad_partial plans it for 448 workgroup slots (a launch beside a
+    data-gradient chain), mi_conv_wgrad for 512, so the fp32 partial sums are partitioned differently.  A full batch flushes itself."""
     MAX = 8
 
     def __init__(self):
@@ -277,7 +278,6 @@ def conv_wgrad(dy, x, dw, ksize=1, stride=1, pad=0, dil=1, scale=None, accumulat
     _, Ha, Wa, I = x.shape
     L = _lib.lib()
     need = L.mi_conv_wgrad_workspace(B, Ho, Wo, O, I, ksize)
-    ws = _workspace(need, dy.device, "wgrad")
     if out_map == 1 and not 0 < 36 * ncls <= O:
         raise _lib.MiError("conv_wgrad(out_map=1) needs ncls with 36*ncls <= %d, got %r" % (O, ncls))
     o_real = 36 * ncls if out_map == 1 else O
@@ -294,6 +294,7 @@ def conv_wgrad(dy, x, dw, ksize=1, stride=1, pad=0, dil=1, scale=None, accumulat
             int(accumulate), out_map, int(ncls), dw.numel(), _p(ws), ws.numel(), job, _stream()), tag=("wgrad", ksize, I, O, B * Ho * Wo, out_map, dil)), "mi_conv_wgrad_partial")
         batch.added(ws, dw, scale)
         return dw
+    ws = _workspace(need, dy.device, "wgrad")
     check(_timed(kern, flops, lambda: L.mi_conv_wgrad(
         _p(dy), _p(x), _p(dw), B, Ha, Wa, I, Ho, Wo, O, ksize, stride, pad, dil, _p(scale),
         int(accumulate), out_map, int(ncls), dw.numel(), _p(ws), ws.numel(), _stream()), tag=("wgrad", ksize, I, O, B * Ho * Wo, out_map, dil)), "mi_conv_wgrad")

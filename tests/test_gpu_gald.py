@@ -424,3 +424,47 @@ def test_applies_with_extra_destinations_leave_every_bit_of_a_block_unchanged(wh
     assert ga.keys() == gb.keys() and len(ga) > 0
     for k in ga:
         assert torch.equal(ga[k], gb[k]), k
+
+
+def test_shared_unit_queued_then_beside_accumulates_both_applications():
+    """One conv + BatchNorm unit applied twice with shared parameters, under GALD's run class (weight gradients of >= _SIDE_MIN_WORK on the side stream,
+    the smaller ones queued): first at 2 x 320 x 320 (8.5 GFLOP of weight gradient: the side stream, at once), then at 2 x 64 x 64 (0.3 GFLOP: the queue).
+    Backward meets the queued application first and writes its slot (overwrite), the direct one accumulates: the queue must be flushed before it, or the
+    later flush overwrites the accumulated sum.  48 channels keep both on the general kernels.  Parameter gradients against float64 torch."""
+    from rnd_semantic_segmentation_amd.host import engine, gald, pranet
+
+    class Twice(pranet._Engine):
+        RUN = gald._GaldRun
+
+        def __init__(self):
+            super().__init__()
+            self._u = pranet._Unit("conv", "bn", 48, 48, 3, 1, 1)
+            self._register([self._u])
+
+        def _graph(self, run, big, small):
+            return [run.conv_bn(big, self._u, True), run.conv_bn(small, self._u, True)]
+
+    assert engine.WgradScheduler.on(torch.device("cuda")).side is not None
+    mod = Twice()
+    synth.load_formula_weights(mod, prefix="twice.", bn_bias=synth.COND_BN_BIAS)
+    mod.cuda().train()
+    work = lambda hw: 2.0 * 2 * hw * hw * 48 * 48 * 9
+    assert work(64) < pranet._SIDE_MIN_WORK <= work(320)
+    xs = [torch.from_numpy(np.maximum(_u("twice.x%d" % hw, (2, 48, hw, hw), 3), 0)).bfloat16() for hw in (320, 64)]
+    rs = [torch.from_numpy(_u("twice.r%d" % hw, (2, 48, hw, hw))) for hw in (320, 64)]
+    outs = mod(*[x.cuda() for x in xs])
+    sum((o.float() * r.cuda()).sum() for o, r in zip(outs, rs)).backward()
+    torch.cuda.synchronize()
+    got = {k: p.grad.detach().cpu().double() for k, p in mod.named_parameters()}
+    ps = {k: p.detach().cpu().double().cuda().requires_grad_(True) for k, p in mod.named_parameters()}
+    loss = 0
+    for x, r in zip(xs, rs):
+        y = F.conv2d(x.double().cuda(), ps["conv.weight"], padding=1)
+        y = F.batch_norm(y, None, None, ps["bn.weight"], ps["bn.bias"], training=True, eps=mod.bn.eps)
+        loss = loss + (F.relu(y) * r.double().cuda()).sum()
+    loss.backward()
+    for k, p in ps.items():
+        want = p.grad.cpu()
+        e_norm, e_cos = abs(float(got[k].norm() / want.norm()) - 1), 1 - _cos(got[k].numpy(), want.numpy())
+        print("\n[twice %s] |grad| %.2e  1-cos %.2e" % (k, e_norm, e_cos))
+        assert e_norm < _GALD_BARS["cca_twice"][2] and e_cos < _GALD_BARS["cca_twice"][3], (k, e_norm, e_cos)

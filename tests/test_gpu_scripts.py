@@ -153,7 +153,7 @@ def test_opt_in_kernel_variants_and_single_stream_schedule_stay_correct():
                      ({"MI_BN_TWO_PASS": "1"}, ["tests/test_gpu_bn.py", "-k", "tinynet_trainable"]),             # BatchNorm statistics as two passes
                      ({"MI_GWGRAD3": "2"}, ["tests/test_gpu_gops.py", "-k", "weight_gradient"]),                  # general family: fused-row weight gradient forced onto the small shapes
                      ({"MI_GWGRAD3": "0", "MI_INLAUNCH": "1", "MI_BN_INLAUNCH": "1"}, ["tests/test_gpu_gops.py", "tests/test_gpu_pranet.py", "-k", "weight_gradient or batch_statistics or graph_replay or running_statistics"]),   # per-tap kernel, in-launch reductions (opt-in since round 5)
-                     ({"MI_WGRAD_BATCH": "0", "MI_GCONV_REMAP": "0"}, ["tests/test_gpu_pranet.py", "-k", "building_blocks or graph_replay or stale"]),     # tape: every weight gradient its own launch (the queue off), plain tile order
+                     ({"MI_GCONV_REMAP": "0"}, ["tests/test_gpu_pranet.py", "-k", "building_blocks or graph_replay or stale"]),     # tape: plain tile order
                      ({"MI_GCONV3_WGS": "1"}, ["tests/test_gpu_gops.py", "-k", "gconv"]),                                          # kernel-row window conv on every eligible (tiny) shape
                      ({"MI_GCONV_BN_ANY": "0", "MI_GCONV_KS2_WGS": "0", "MI_GCONV3_WGS": "0"}, ["tests/test_gpu_gops.py", "-k", "gconv"]),   # 32 / 64-wide tiles, one wave group, no window kernel
                      ({"MI_GWM_STEPS": "4", "MI_GWM_FUSED3": "0"}, ["tests/test_gpu_gops.py", "-k", "many_convs"]),                # batched weight gradients: many K splits, the one-conv fusing rule

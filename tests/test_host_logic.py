@@ -1,5 +1,6 @@
 """CPU tests of the host-side mirror: config node, LR, metrics vs the reference's golden outputs, state_dict keys,
 drop-in import surface, trainer/tester plumbing (with the oracle's CPU model substituted), checkpoints."""
+import contextlib
 import json
 import logging
 import os
@@ -339,3 +340,114 @@ def test_conv_bn_refuses_relu6_with_a_residual_before_any_launch():
     run = pranet._Run(object(), True, True)
     with pytest.raises(_lib.MiError, match="ReLU6"):
         run.conv_bn(None, None, 6, add=object())
+
+
+class _TapeOnFakeStreams:
+    """The tape's weight-gradient scheduling (engine.WgradScheduler + pranet._WgradQueue, GALD's run class: side stream on) on CPU tensors: the side
+    stream is a recording fake, the general-kernel weight gradients are fakes that write slot (+)= sum(dy) * sum(x) at once, in enqueue order, and
+    log which stream they were enqueued on and which tensors they touched."""
+
+    class Stream:
+        def __init__(self, name, log):
+            self.name, self.log = name, log
+
+        def wait_stream(self, other):
+            self.log.append(("wait", self.name, other.name))
+
+    def __init__(self, monkeypatch):
+        from rnd_semantic_segmentation_amd import gk
+        from rnd_semantic_segmentation_amd.host import engine, pranet
+        self.pranet, self.log, self.touched, self.kept, self.born_on_side = pranet, [], [], [], []
+        self.main, self.side = self.Stream("main", self.log), self.Stream("side", self.log)
+        self.current = [self.main]
+
+        @contextlib.contextmanager
+        def stream(s):
+            self.current.append(s)
+            try:
+                yield
+            finally:
+                self.current.pop()
+        empty = torch.empty
+
+        def tracked_empty(*a, **k):
+            t = empty(*a, **k)
+            if self.current[-1] is self.side:
+                self.born_on_side.append(t)
+            return t
+
+        def wgrad(dy, x, dw, geom, accumulate=False):
+            self.log.append(("wgrad", self.current[-1].name, dw.data_ptr(), accumulate))
+            self.touched.append((self.current[-1].name, (dy, x, dw)))
+            v = dy.float().sum() * x.float().sum()
+            dw.add_(v) if accumulate else dw.fill_(v)
+        monkeypatch.setattr(torch.cuda, "current_stream", lambda: self.current[-1])
+        monkeypatch.setattr(torch.cuda, "stream", stream)
+        monkeypatch.setattr(torch, "empty", tracked_empty)
+        monkeypatch.setattr(torch.Tensor, "record_stream", lambda t, s: self.kept.append((t, s.name)))
+        monkeypatch.setattr(gk, "gconv_wgrad", wgrad)
+        monkeypatch.setattr(gk, "gconv_wgrad_multi", lambda jobs: [wgrad(dy, x, dw, geom, acc) for dy, x, dw, geom, acc in jobs])
+        monkeypatch.setattr(engine.WgradScheduler, "on", classmethod(lambda cls, device: cls(self.side)))
+
+        class Run(pranet._Run):
+            WGRAD_STREAM = True
+        self.net = type("Net", (), {"_grad_slot": pranet._Engine._grad_slot})()
+        self.Run = Run
+
+    def store(self, *params):
+        from rnd_semantic_segmentation_amd.host import engine
+        self.net._store = engine.FlatStore([("p%d" % i, p) for i, p in enumerate(params)], "cpu")
+        return self.net._store
+
+    def backward(self, applications):
+        """applications: (unit, x NHWC bf16, dy NHWC bf16) in FORWARD order; the tape replays them in reverse."""
+        run = self.Run(self.net, True, True)
+        for u, x, dy in applications:
+            run.record(lambda u=u, x=x, dy=dy: run._conv_backward(self.pranet._Var(x, needs=False), u, dy))
+        run.backward()
+
+
+def test_tape_scratch_of_a_deferred_weight_gradient_is_handed_over_or_allocated_in_the_job(monkeypatch):
+    """Every tensor a weight-gradient job on the side stream touches must outlive it there: handed to the scheduler (record_stream), allocated by the
+    job itself on the side stream, or the flat gradient buffer.  The image's weight gradient (the zero-padded 8-channel input of a 3-channel stem conv)
+    is queued and written into a scratch tensor for all eight channels first; that scratch once came from the main stream at tape time and was released
+    while the side stream still used it."""
+    f = _TapeOnFakeStreams(monkeypatch)
+    from rnd_semantic_segmentation_amd.host import pranet
+    stem, mid = pranet._Unit("stem", None, 3, 32, 3, 2, 1), pranet._Unit("mid", None, 32, 32, (1, 3), 1, (0, 1))
+    stem.weight, mid.weight = torch.nn.Parameter(torch.randn(32, 3, 3, 3)), torch.nn.Parameter(torch.randn(32, 32, 1, 3))
+    st = f.store(stem.weight, mid.weight)
+    img = torch.zeros(2, 16, 16, 8, dtype=torch.bfloat16)
+    img[..., :3] = torch.randn(2, 16, 16, 3).bfloat16()
+    a, dy_img = torch.randn(2, 8, 8, 32).bfloat16(), torch.randn(2, 8, 8, 32).bfloat16()
+    f.backward([(stem, img, dy_img), (mid, a, torch.randn(2, 8, 8, 32).bfloat16())])
+    on_side = [ts for s, ts in f.touched if s == "side"]
+    assert len(on_side) == 2 and ("wait", "main", "side") in f.log                  # both queued jobs ran on the side stream, then the join
+    safe = {t.untyped_storage().data_ptr() for t, s in f.kept if s == "side"} | {t.untyped_storage().data_ptr() for t in f.born_on_side}
+    safe.add(st.grad.untyped_storage().data_ptr())
+    for ts in on_side:
+        for t in ts:
+            ptr = t.untyped_storage().data_ptr()
+            assert ptr in safe, tuple(t.shape)
+    want = dy_img.float().sum() * img.float().sum()
+    assert torch.allclose(stem.weight.grad, want.expand(32, 3, 3, 3))              # the real channels were cut out of the scratch
+
+
+def test_tape_queued_overwrite_then_direct_accumulate_to_one_slot_flushes_first(monkeypatch):
+    """A module applied twice (GALD's criss-cross attention): the accumulate flag of its weight-gradient slot comes from tape order.  When backward meets
+    the application whose weight gradient is queued first (overwrite) and then one large enough to go to the side stream directly (accumulate), the
+    queue must be flushed before the direct write - otherwise the accumulate runs first and the later overwrite loses it."""
+    f = _TapeOnFakeStreams(monkeypatch)
+    from rnd_semantic_segmentation_amd.host import pranet
+    u = pranet._Unit("cc", None, 48, 48, 3, 1, 1)
+    u.weight = torch.nn.Parameter(torch.randn(48, 48, 3, 3))
+    f.store(u.weight)
+    big, small = torch.randn(1, 16, 16, 48).bfloat16(), torch.randn(1, 8, 8, 48).bfloat16()
+    dy_big, dy_small = torch.randn(1, 16, 16, 48).bfloat16(), torch.randn(1, 8, 8, 48).bfloat16()
+    work = lambda x: 2.0 * x.shape[1] * x.shape[2] * 48 * 48 * 9
+    monkeypatch.setattr(pranet, "_SIDE_MIN_WORK", (work(big) + work(small)) / 2)
+    f.backward([(u, big, dy_big), (u, small, dy_small)])                           # backward: the small (queued) application first
+    writes = [e for e in f.log if e[0] == "wgrad"]
+    assert [(s, acc) for _, s, _, acc in writes] == [("side", False), ("side", True)], writes
+    want = dy_small.float().sum() * small.float().sum() + dy_big.float().sum() * big.float().sum()
+    assert torch.allclose(u.weight.grad, want.expand_as(u.weight), rtol=1e-5)
