@@ -362,6 +362,14 @@ size_t mi_gconv_stats_elems(int B, int Ho, int Wo, int N);
 int mi_gconv(const void* a, long lda, const void* wp, void* out, long ldo, int B, int Ha, int Wa, int Ca, int Ho, int Wo, int N,
              int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw, int mode, const float* bias, float* stats, int out_f32,
              void* stream);
+/* The instance mi_gconv (bn_finalize = 0) or mi_gconv_bn (bn_finalize = 1) launches for these arguments, from the same planning function, on the host
+ * (no GPU, no launch; a and out count for their alignment only and are never dereferenced).  route: int[MI_GROUTE_LEN] =
+ * {kernel (MI_GROUTE_*), tile width BN, K chunk KC (0 for gconv3), AVEC, OVEC, OUTF32, GEN (general source map), KS (wave groups over K; 0 for gconv3), grid x, grid y}. */
+#define MI_GROUTE_GCONV 0     /* gconv_kernel<BN, KC, AVEC, OVEC, OUTF32, GEN, KS> */
+#define MI_GROUTE_GCONV3 1    /* gconv3_kernel<BN, AVEC, OVEC> (kernel-row window) */
+#define MI_GROUTE_LEN 10
+int mi_gconv_route(const void* a, long lda, const void* out, long ldo, int B, int Ha, int Wa, int Ca, int Ho, int Wo, int N, int kh, int kw, int sh, int sw,
+                   int ph, int pw, int dh, int dw, int mode, int out_f32, int bn_finalize, int* route);
 /* dw[o][i][ky][kx] (+)= sum_m dy[m][o] * x[src(m,ky,kx)][i], fp32 OIHW; split-K slabs summed in a fixed order. */
 size_t mi_gconv_wgrad_workspace(int B, int Ho, int Wo, int O, int I, int kh, int kw);
 int mi_gconv_wgrad(const void* dy, long ldy, const void* x, long ldx, float* dw, int B, int Ha, int Wa, int I, int Ho, int Wo, int O,
@@ -380,6 +388,12 @@ typedef struct MiWgradJob {
 size_t mi_gconv_wgrad_multi_table_bytes(int n);
 size_t mi_gconv_wgrad_multi_workspace(const MiWgradJob* jobs, int n);
 int mi_gconv_wgrad_multi(const MiWgradJob* jobs, int n, void* table_dev, size_t table_bytes, void* workspace, size_t workspace_bytes, void* stream);
+/* The weight-gradient instance mi_gconv_wgrad (multi = 0) or a job of mi_gconv_wgrad_multi (multi = 1) launches for these arguments, from the same planning
+ * function, on the host (dy and x count for their alignment only).  route: int[MI_GWROUTE_LEN] = {fused (1: gwgrad3 kernel-row kernel, 0: per tap), YVEC, XVEC,
+ * K splits S, output pixels per split, workgroups: of the main launch, or (multi) of this job within its class's launch}. */
+#define MI_GWROUTE_LEN 6
+int mi_gconv_wgrad_route(const void* dy, long ldy, const void* x, long ldx, int B, int Ha, int Wa, int I, int Ho, int Wo, int O, int kh, int kw, int sh, int sw,
+                         int ph, int pw, int dh, int dw_, int multi, int* route);
 /* nn.BatchNorm2d in train() from the conv's tile statistics: mean, invstd = rsqrt(biased var + eps), scale = gamma * invstd,
  * shift = beta - mean * scale, and the running-statistics update (momentum; unbiased variance), all per channel.  count = pixels. */
 int mi_gbn_finalize(const float* partials, int tiles, int C, long count, const float* gamma, const float* beta, float* running_mean, float* running_var,

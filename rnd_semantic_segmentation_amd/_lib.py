@@ -83,11 +83,13 @@ SIGNATURES = {
     "mi_gconv_pack_multi": (I, [P, P, P, P, I, I, P]),
     "mi_gconv_stats_elems": (Z, [I] * 4),
     "mi_gconv": (I, [P, L, P, P, L] + [I] * 16 + [P, P, I, P]),
+    "mi_gconv_route": (I, [P, L, P, L] + [I] * 18 + [P]),
     "mi_gconv_wgrad_workspace": (Z, [I] * 7),
     "mi_gconv_wgrad": (I, [P, L, P, L, P] + [I] * 16 + [P, Z, P, I, P]),
     "mi_gconv_wgrad_multi_table_bytes": (Z, [I]),
     "mi_gconv_wgrad_multi_workspace": (Z, [P, I]),
     "mi_gconv_wgrad_multi": (I, [P, I, P, Z, P, Z, P]),
+    "mi_gconv_wgrad_route": (I, [P, L, P, L] + [I] * 16 + [P]),
     "mi_gbn_finalize": (I, [P, I, I, L, P, P, P, P, F, F, P, P, P, P, P]),
     "mi_gbn_fold": (I, [P, P, P, P, F, P, P, I, P]),
     "mi_gbn_apply": (I, [P, L, P, P, P, L, P, L, I, L, I, I, P]),

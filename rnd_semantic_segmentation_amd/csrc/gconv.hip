@@ -690,16 +690,23 @@ __global__ __launch_bounds__(256) void gconv3_kernel(GConvP p) {
     gconv_epilogue<BN, OVEC, false>(p, smem, acc, tid, m0, n0, mt, nt, m_tiles);
 }
 
+// The instance a general-conv launch runs, as planned by gconv_plan (below): mi_gconv / mi_gconv_bn launch what it says, mi_gconv_route reports it.
+struct GRoute {
+    int kernel;               // MI_GROUTE_GCONV (gconv_kernel) | MI_GROUTE_GCONV3 (gconv3_kernel)
+    int bn, kc, avec, ovec;   // tile width, K chunk (gconv_kernel), operand vector widths
+    int f32, gen, ks;         // fp32 output, general source map (data gradient of a strided conv), wave groups over the K chunks
+    int grid_x, grid_y;       // row tiles, column tiles
+};
+
 template <int BN, int KC, int AVEC, int OVEC, bool OUTF32>
-void glaunch(const GConvP& p, hipStream_t s) {
-    dim3 grid((p.M + GBM - 1) / GBM, (p.N + BN - 1) / BN);
-    if (p.mode != MI_GATHER_FWD && (p.sh != 1 || p.sw != 1)) {                     // data gradient of a strided conv: the general source map
+void glaunch(const GConvP& p, const GRoute& r, hipStream_t s) {
+    dim3 grid(r.grid_x, r.grid_y);
+    if (r.gen) {                                                                     // data gradient of a strided conv: the general source map
         hipLaunchKernelGGL((gconv_kernel<BN, KC, AVEC, OVEC, OUTF32, true>), grid, dim3(256), 0, s, p);
         return;
     }
     if constexpr (!OUTF32 && (BN == 32 || BN == 64) && KC == 64 && AVEC >= 4 && OVEC >= 4) {       // two wave groups over the K chunks (see KS above)
-        const int ks2_wgs = mi_sw().gconv_ks2_wgs;
-        if ((int)(grid.x * grid.y) <= ks2_wgs && p.T * p.nchunks >= 8) {
+        if (r.ks == 2) {
             constexpr int bytes = 2 * GSmem<BN, KC, false>::AB;
             static_assert(bytes >= GSmem<BN, KC, false>::CS + GSmem<BN, KC, false>::RED && bytes >= 2 * (BN / 16) * 4 * 256 * 4, "LDS of the two-group launch");
             static std::atomic<uint64_t> attr;
@@ -712,26 +719,27 @@ void glaunch(const GConvP& p, hipStream_t s) {
 }
 
 template <int BN, int KC, int AVEC>
-void glaunch_o(const GConvP& p, int ovec, bool f32, hipStream_t s) {
-    if (f32) {
-        if constexpr (BN == 32) glaunch<32, KC, AVEC, 1, true>(p, s);
+void glaunch_o(const GConvP& p, const GRoute& r, hipStream_t s) {
+    if (r.f32) {
+        if constexpr (BN == 32) glaunch<32, KC, AVEC, 1, true>(p, r, s);
         return;
     }
-    if (ovec == 8) glaunch<BN, KC, AVEC, 8, false>(p, s);
-    else if (ovec == 4) glaunch<BN, KC, AVEC, 4, false>(p, s);
-    else glaunch<BN, KC, AVEC, 1, false>(p, s);
+    if (r.ovec == 8) glaunch<BN, KC, AVEC, 8, false>(p, r, s);
+    else if (r.ovec == 4) glaunch<BN, KC, AVEC, 4, false>(p, r, s);
+    else glaunch<BN, KC, AVEC, 1, false>(p, r, s);
 }
 
 template <int BN, int KC>
-void glaunch_a(const GConvP& p, int avec, int ovec, bool f32, hipStream_t s) {
-    if (avec == 8) glaunch_o<BN, KC, 8>(p, ovec, f32, s);
-    else if (avec == 4) glaunch_o<BN, KC, 4>(p, ovec, f32, s);
-    else glaunch_o<BN, KC, 1>(p, ovec, f32, s);
+void glaunch_a(const GConvP& p, const GRoute& r, hipStream_t s) {
+    if (r.avec == 8) glaunch_o<BN, KC, 8>(p, r, s);
+    else if (r.avec == 4) glaunch_o<BN, KC, 4>(p, r, s);
+    else glaunch_o<BN, KC, 1>(p, r, s);
 }
 
 template <int BN>
-void glaunch3(const GConvP& p, int avec, int ovec, hipStream_t s) {
-    dim3 grid((p.M + GBM - 1) / GBM, (p.N + BN - 1) / BN);
+void glaunch3(const GConvP& p, const GRoute& r, hipStream_t s) {
+    dim3 grid(r.grid_x, r.grid_y);
+    const int avec = r.avec, ovec = r.ovec;
 #define G3L(AV, OV) hipLaunchKernelGGL((gconv3_kernel<BN, AV, OV>), grid, dim3(256), 0, s, p)
     if (avec == 8 && ovec == 8) G3L(8, 8);
     else if (avec == 8 && ovec == 4) G3L(8, 4);
@@ -745,23 +753,18 @@ void glaunch3(const GConvP& p, int avec, int ovec, hipStream_t s) {
 #undef G3L
 }
 
-// BN = 128 keeps 32-channel chunks (its LDS image with 64 would pass the 64 KiB of static LDS)
+// (BN = 128 keeps 32-channel chunks: gconv_plan's gplan_kc)
 template <int BN>
-void glaunch_k(GConvP& p, int avec, int ovec, bool f32, hipStream_t s) {
-    if constexpr (2 * (GBM + BN) * (64 + 8) * 2 <= 64 * 1024) {          // (BN <= 80: the 64-channel image fits the 64 KiB of static LDS)
-        // 64-channel chunks halve the K steps; a conv on a large map (thousands of workgroups) gains more from the occupancy of
-        // the 32-channel tile (30 KB of LDS instead of 55: 104 -> 256 at 16 x 88 x 88 54.7 vs 63.7 us, 208 -> 512 at 44 x 44 33.5 vs 41.0)
-        const int kc32_wgs = mi_sw().gconv_kc32_wgs;
-        const long wgs = (long)((p.M + GBM - 1) / GBM) * ((p.N + BN - 1) / BN);
-        const bool small_k_big_m = wgs >= kc32_wgs && mi_sw().gconv_kc != 64;          // (3x3 convs on large maps too: GALD 38.4 -> 37.6 ms with 32-channel chunks)
-        if (p.Cpad >= 64 && p.T * ((p.Cpad + 63) / 64) >= 2 && mi_sw().gconv_kc != 32 && !small_k_big_m) {
+void glaunch_k(GConvP& p, const GRoute& r, hipStream_t s) {
+    if constexpr (2 * (GBM + BN) * (64 + 8) * 2 <= 64 * 1024) {
+        if (r.kc == 64) {
             p.nchunks = (p.Cpad + 63) / 64;
-            glaunch_a<BN, 64>(p, avec, ovec, f32, s);
+            glaunch_a<BN, 64>(p, r, s);
             return;
         }
     }
     p.nchunks = p.Cpad / 32;
-    glaunch_a<BN, 32>(p, avec, ovec, f32, s);
+    glaunch_a<BN, 32>(p, r, s);
 }
 
 int view_vec(const void* ptr, long ld, int C, bool load = true) {
@@ -772,6 +775,92 @@ int view_vec(const void* ptr, long ld, int C, bool load = true) {
 }
 
 inline int rup(int x, int m) { return (x + m - 1) / m * m; }
+
+// K chunk of a BN-wide gconv_kernel launch of wgs workgroups.  64-channel chunks halve the K steps; a conv on a large map (thousands of workgroups) gains
+// more from the occupancy of the 32-channel tile (30 KB of LDS instead of 55: 104 -> 256 at 16 x 88 x 88 54.7 vs 63.7 us, 208 -> 512 at 44 x 44 33.5 vs 41.0).
+// Only BN <= 80 has the 64-channel instances: their LDS image with BN = 112 / 128 would pass the 64 KiB of static LDS.
+int gplan_kc(int bn, long wgs, int Cpad, int T) {
+    if (2 * (GBM + bn) * (64 + 8) * 2 > 64 * 1024) return 32;
+    const bool small_k_big_m = wgs >= mi_sw().gconv_kc32_wgs && mi_sw().gconv_kc != 64;          // (3x3 convs on large maps too: GALD 38.4 -> 37.6 ms with 32-channel chunks)
+    return Cpad >= 64 && T * ((Cpad + 63) / 64) >= 2 && mi_sw().gconv_kc != 32 && !small_k_big_m ? 64 : 32;
+}
+
+// The one planning function of the general conv: which kernel, tile width, K chunk, operand vector widths and wave groups a launch takes.  mi_gconv /
+// mi_gconv_bn launch exactly this; mi_gconv_route reports it (host only: the operand pointers count for their alignment alone).
+GRoute gconv_plan(const void* a, long lda, const void* out, long ldo, int B, int Ha, int Wa, int Ca, int Ho, int Wo, int N, int kh, int kw, int sh, int sw,
+                  int ph, int pw, int dh, int dw, int mode, int out_f32, bool fin) {
+    GRoute r{};
+    r.f32 = out_f32 ? 1 : 0;
+    r.avec = view_vec(a, lda, Ca);
+    r.ovec = out_f32 ? 1 : view_vec(out, ldo, N, false);
+    const int M = B * Ho * Wo, Cpad = rup(Ca, 32), T = kh * kw;
+    const long mt = (M + GBM - 1) / GBM;
+    const int bn32_wgs = mi_sw().gconv_bn32_wgs;
+    const bool bn_any = mi_sw().gconv_bn_any != 0;      // MI_GCONV_BN_ANY=0: tile widths 32 / 64 (/ 128) only
+    r.grid_x = (int)mt;
+    // kernel-row window kernel (gconv3_kernel): three kernel columns, stride 1, output of the input's size, large maps (MI_GCONV3_WGS: from this many 64-wide
+    // workgroups; 0 = never)
+    const int g3_wgs = mi_sw().gconv3_wgs;       // (GALD 36.56 / 36.27 / 36.16 ms at 1024 / 512 / 256; PraNet indifferent)
+    if (!out_f32 && !fin && g3_wgs > 0 && kw == 3 && sh == 1 && sw == 1 && pw == dw && dw <= G3_MAXD && Wo == Wa && Ho == Ha && 2 * ph == dh * (kh - 1) &&
+        mt * ((N + 63) / 64) >= g3_wgs && (Cpad / 32 >= 4 || g3_wgs == 1)) {
+        // measured per shape (tools/gkshape.py gald, MI_GCONV3_WGS = 0 | 1024): the window kernel wins where a kernel row has >= 4 chunks (3x3 142 -> 68 at
+        // 6 x 180 x 320: 206 vs 247 us, 466 -> 168 at 90 x 160: 287 vs 391, 218 -> 78: 78 vs 114) and loses with fewer (data gradient 68 -> 142: 239 vs 222);
+        // it has the widths 32 / 64 / 80 only (LDS), so a launch whose cost model wants 112 or 16 columns stays on gconv_kernel
+        static const int widths3[] = {64, 80, 112, 32, 16};
+        int best = 64;
+        long best_cost = 1L << 60;
+        for (int wdt : widths3) {
+            const long cost = (long)((N + wdt - 1) / wdt) * (wdt + 64);
+            if (cost < best_cost) best = wdt, best_cost = cost;
+        }
+        if (g3_wgs == 1 && best != 80 && best != 32) best = 64;          // (tests: every eligible conv)
+        if (best == 80 || best == 64 || best == 32) {
+            r.kernel = MI_GROUTE_GCONV3;
+            r.bn = best;
+            r.grid_y = (N + best - 1) / best;
+            return r;
+        }
+    }
+    int bn;
+    if (out_f32) bn = 32;                                   // (the one-channel side maps, N <= 32: gconv_impl)
+    else if (fin || !bn_any) {                              // (the in-launch finalize lives in the 32- / 64-wide instances)
+        if (N <= 32) bn = 32;
+        else if (mt * ((N + 63) / 64) < bn32_wgs) bn = 32;      // few pixels (1/16, 1/32 resolution): narrower tiles, more workgroups
+        else if (N <= 64 || N % 128 == 64 || mt * ((N + 127) / 128) < 512 || !mi_sw().gconv_bn128 || fin) bn = 64;
+        else bn = 128;
+    } else if (N > 32 && mt * ((N + 63) / 64) < bn32_wgs) bn = 32;
+    else {
+        // Tile width by a cost model fitted on HarDNet's shapes (tools/dbg/bn_width.sh: every width forced on every shape): a column tile costs its width
+        // plus ~64 columns' worth of fixed work (the A rows it re-reads, prologue, epilogue), so cost = ceil(N / w) * (w + 64).  N = 68 -> one 80-wide tile
+        // (248 vs 347 us for two 64-wide), 334 -> three 112-wide (221 vs 318), 256 -> four 64-wide; the least-padding rule tried first chose 16-wide tiles
+        // for N = 168 (1 270 us against 393).  MI_GCONV_BN_FORCE: one width for everything (measurement).
+        static const int widths[] = {64, 80, 112, 32, 16};
+        const int force = mi_sw().gconv_bn_force;
+        const int fixed = mi_sw().gconv_bn_c;
+        int best = 64;
+        long best_cost = 1L << 60;
+        for (int wdt : widths) {
+            const long cost = (long)((N + wdt - 1) / wdt) * (wdt + fixed);
+            if (cost < best_cost) best = wdt, best_cost = cost;
+        }
+        // (only where the wider tiles still leave the chip full: on the 11 x 11 / 22 x 22 maps a 2048-channel data gradient took 26 us as 304 112-wide
+        //  workgroups against 20 us as 512 64-wide ones)
+        if (best > 64 && mt * ((N + best - 1) / best) < 384) best = 64;
+        if (force) best = force;
+        bn = best == 16 || best == 32 || best == 80 || best == 112 ? best : 64;
+    }
+    r.kernel = MI_GROUTE_GCONV;
+    r.bn = bn;
+    r.grid_y = (N + bn - 1) / bn;
+    const long wgs = mt * r.grid_y;
+    r.kc = gplan_kc(bn, wgs, Cpad, T);
+    const int nchunks = r.kc == 64 ? (Cpad + 63) / 64 : Cpad / 32;
+    r.gen = mode != MI_GATHER_FWD && (sh != 1 || sw != 1);
+    // two wave groups over the K chunks (gconv_kernel's KS): the 32- / 64-wide instances with 64-channel chunks and vector operands, on launches too small to
+    // fill the chip (MI_GCONV_KS2_WGS) with enough K steps to split
+    r.ks = !r.gen && !out_f32 && (bn == 32 || bn == 64) && r.kc == 64 && r.avec >= 4 && r.ovec >= 4 && wgs <= mi_sw().gconv_ks2_wgs && T * nchunks >= 8 ? 2 : 1;
+    return r;
+}
 
 // ------------------------------------------------------------------------------------------------ weight gradient
 constexpr int WTO = 64, WTI = 64, WKP = 64;     // output tile 64 (o) x 64 (i), 64 pixels (two MFMA k) per K step
@@ -1442,16 +1531,13 @@ int mi_gconv_bn(const void* a, long lda, const void* wp, void* out, long ldo, in
     return gconv_impl(a, lda, wp, out, ldo, B, Ha, Wa, Ca, Ho, Wo, N, kh, kw, sh, sw, ph, pw, dh, dw, MI_GATHER_FWD, bias, stats, 0, stream, &fin);
 }
 
-static int gconv_impl(const void* a, long lda, const void* wp, void* out, long ldo, int B, int Ha, int Wa, int Ca, int Ho, int Wo, int N,
-                      int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw, int mode, const float* bias, float* stats, int out_f32,
-                      void* stream, const GFin* fin) {
-    MI_REQUIRE(a && wp && out, "mi_gconv: null operand");
+// the argument checks of mi_gconv (and mi_gconv_route): nothing is dereferenced
+static int gconv_check(const void* a, long lda, const void* out, long ldo, int B, int Ha, int Wa, int Ca, int Ho, int Wo, int N, int kh, int kw, int sh, int sw,
+                       int ph, int pw, int dh, int dw, int mode, int out_f32) {
     MI_REQUIRE(B > 0 && Ha > 0 && Wa > 0 && Ho > 0 && Wo > 0 && Ca > 0 && N > 0, "mi_gconv: empty shape");
     MI_REQUIRE(kh > 0 && kw > 0 && sh > 0 && sw > 0 && dh > 0 && dw > 0 && ph >= 0 && pw >= 0, "mi_gconv: bad conv geometry");
     MI_REQUIRE(mode == MI_GATHER_FWD || mode == MI_GATHER_DGRAD, "mi_gconv: gather mode %d", mode);
     MI_REQUIRE(lda >= Ca && ldo >= N, "mi_gconv: a view's row stride is smaller than its channel count (lda %ld / Ca %d, ldo %ld / N %d)", lda, Ca, ldo, N);
-    MI_REQUIRE((reinterpret_cast<uintptr_t>(wp) & 15) == 0, "mi_gconv: the packed weights must be 16-byte aligned");
-    MI_REQUIRE(!(out_f32 && stats), "mi_gconv: batch statistics are taken from bf16 outputs");
     MI_REQUIRE((long)B * Ho * Wo < (1L << 31) && (long)B * Ha * Wa < (1L << 31), "mi_gconv: more than 2^31 pixels");
     if (mode == MI_GATHER_FWD) {
         MI_REQUIRE((Ha + 2 * ph - dh * (kh - 1) - 1) / sh + 1 == Ho && (Wa + 2 * pw - dw * (kw - 1) - 1) / sw + 1 == Wo,
@@ -1460,6 +1546,33 @@ static int gconv_impl(const void* a, long lda, const void* wp, void* out, long l
         MI_REQUIRE((Ho + 2 * ph - dh * (kh - 1) - 1) / sh + 1 == Ha && (Wo + 2 * pw - dw * (kw - 1) - 1) / sw + 1 == Wa,
                    "mi_gconv: gradient input %dx%d does not follow from the forward input %dx%d", Ha, Wa, Ho, Wo);
     }
+    if (out_f32) {
+        MI_REQUIRE((reinterpret_cast<uintptr_t>(out) & 3) == 0, "mi_gconv: fp32 output must be 4-byte aligned");
+        MI_REQUIRE(N <= 32, "mi_gconv: fp32 outputs are the one-channel side maps (N <= 32), got N = %d", N);
+    }
+    return MI_OK;
+}
+
+int mi_gconv_route(const void* a, long lda, const void* out, long ldo, int B, int Ha, int Wa, int Ca, int Ho, int Wo, int N, int kh, int kw, int sh, int sw,
+                   int ph, int pw, int dh, int dw, int mode, int out_f32, int bn_finalize, int* route) {
+    MI_REQUIRE(route, "mi_gconv_route: null route");
+    const int rc = gconv_check(a, lda, out, ldo, B, Ha, Wa, Ca, Ho, Wo, N, kh, kw, sh, sw, ph, pw, dh, dw, mode, out_f32);
+    if (rc != MI_OK) return rc;
+    MI_REQUIRE(!bn_finalize || (mode == MI_GATHER_FWD && !out_f32), "mi_gconv_route: the in-launch finalize is a forward with bf16 output");
+    const GRoute r = gconv_plan(a, lda, out, ldo, B, Ha, Wa, Ca, Ho, Wo, N, kh, kw, sh, sw, ph, pw, dh, dw, mode, out_f32, bn_finalize != 0);
+    const int v[MI_GROUTE_LEN] = {r.kernel, r.bn, r.kc, r.avec, r.ovec, r.f32, r.gen, r.ks, r.grid_x, r.grid_y};
+    for (int k = 0; k < MI_GROUTE_LEN; ++k) route[k] = v[k];
+    return MI_OK;
+}
+
+static int gconv_impl(const void* a, long lda, const void* wp, void* out, long ldo, int B, int Ha, int Wa, int Ca, int Ho, int Wo, int N,
+                      int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw, int mode, const float* bias, float* stats, int out_f32,
+                      void* stream, const GFin* fin) {
+    MI_REQUIRE(a && wp && out, "mi_gconv: null operand");
+    const int rc = gconv_check(a, lda, out, ldo, B, Ha, Wa, Ca, Ho, Wo, N, kh, kw, sh, sw, ph, pw, dh, dw, mode, out_f32);
+    if (rc != MI_OK) return rc;
+    MI_REQUIRE((reinterpret_cast<uintptr_t>(wp) & 15) == 0, "mi_gconv: the packed weights must be 16-byte aligned");
+    MI_REQUIRE(!(out_f32 && stats), "mi_gconv: batch statistics are taken from bf16 outputs");
     GConvP p;
     p.A = (const __bf16*)a;
     p.Wp = (const __bf16*)wp;
@@ -1489,72 +1602,22 @@ static int gconv_impl(const void* a, long lda, const void* wp, void* out, long l
     p.count = fin ? fin->count : 0.0;
     p.momentum = fin ? fin->momentum : 0.f;
     p.eps = fin ? fin->eps : 0.f;
-    const int avec = view_vec(a, lda, Ca);
-    int ovec = 1;
-    if (!out_f32) ovec = view_vec(out, ldo, N, false);
-    else MI_REQUIRE((reinterpret_cast<uintptr_t>(out) & 3) == 0, "mi_gconv: fp32 output must be 4-byte aligned");
     hipStream_t s = (hipStream_t)stream;
-    const long mt = (p.M + GBM - 1) / GBM;
-    const int bn32_wgs = mi_sw().gconv_bn32_wgs;
-    const bool bn_any = mi_sw().gconv_bn_any != 0;      // MI_GCONV_BN_ANY=0: tile widths 32 / 64 (/ 128) only
-    // kernel-row window kernel (gconv3_kernel): three kernel columns, stride 1, output of the input's size, large maps (MI_GCONV3_WGS: from this many 64-wide
-    // workgroups; 0 = never)
-    const int g3_wgs = mi_sw().gconv3_wgs;       // (GALD 36.56 / 36.27 / 36.16 ms at 1024 / 512 / 256; PraNet indifferent)
-    if (!out_f32 && !fin && g3_wgs > 0 && kw == 3 && sh == 1 && sw == 1 && pw == dw && dw <= G3_MAXD && Wo == Wa && Ho == Ha && 2 * ph == dh * (kh - 1) &&
-        mt * ((N + 63) / 64) >= g3_wgs && (p.Cpad / 32 >= 4 || g3_wgs == 1)) {
-        // measured per shape (tools/gkshape.py gald, MI_GCONV3_WGS = 0 | 1024): the window kernel wins where a kernel row has >= 4 chunks (3x3 142 -> 68 at
-        // 6 x 180 x 320: 206 vs 247 us, 466 -> 168 at 90 x 160: 287 vs 391, 218 -> 78: 78 vs 114) and loses with fewer (data gradient 68 -> 142: 239 vs 222);
-        // it has the widths 32 / 64 / 80 only (LDS), so a launch whose cost model wants 112 or 16 columns stays on gconv_kernel
-        static const int widths3[] = {64, 80, 112, 32, 16};
-        int best = 64;
-        long best_cost = 1L << 60;
-        for (int wdt : widths3) {
-            const long cost = (long)((N + wdt - 1) / wdt) * (wdt + 64);
-            if (cost < best_cost) best = wdt, best_cost = cost;
-        }
-        if (g3_wgs == 1 && best != 80 && best != 32) best = 64;          // (tests: every eligible conv)
-        if (best == 80 || best == 64 || best == 32) {
-            if (best == 80) glaunch3<80>(p, avec, ovec, s);
-            else if (best == 32) glaunch3<32>(p, avec, ovec, s);
-            else glaunch3<64>(p, avec, ovec, s);
-            MI_CHECK_LAUNCH("gconv3_kernel");
-            return MI_OK;
-        }
+    const GRoute r = gconv_plan(a, lda, out, ldo, B, Ha, Wa, Ca, Ho, Wo, N, kh, kw, sh, sw, ph, pw, dh, dw, mode, out_f32, fin != nullptr);
+    if (r.kernel == MI_GROUTE_GCONV3) {
+        if (r.bn == 80) glaunch3<80>(p, r, s);
+        else if (r.bn == 32) glaunch3<32>(p, r, s);
+        else glaunch3<64>(p, r, s);
+        MI_CHECK_LAUNCH("gconv3_kernel");
+        return MI_OK;
     }
-    if (out_f32) {
-        MI_REQUIRE(N <= 32, "mi_gconv: fp32 outputs are the one-channel side maps (N <= 32), got N = %d", N);
-        glaunch_k<32>(p, avec, 1, true, s);
-    } else if (fin || !bn_any) {                            // (the in-launch finalize lives in the 32- / 64-wide instances)
-        if (N <= 32) glaunch_k<32>(p, avec, ovec, false, s);
-        else if (mt * ((N + 63) / 64) < bn32_wgs) glaunch_k<32>(p, avec, ovec, false, s);      // few pixels (1/16, 1/32 resolution): narrower tiles, more workgroups
-        else if (N <= 64 || N % 128 == 64 || mt * ((N + 127) / 128) < 512 || !mi_sw().gconv_bn128 || fin) glaunch_k<64>(p, avec, ovec, false, s);
-        else glaunch_k<128>(p, avec, ovec, false, s);
-    } else if (N > 32 && mt * ((N + 63) / 64) < bn32_wgs) glaunch_k<32>(p, avec, ovec, false, s);
-    else {
-        // Tile width by a cost model fitted on HarDNet's shapes (tools/dbg/bn_width.sh: every width forced on every shape): a column tile costs its width
-        // plus ~64 columns' worth of fixed work (the A rows it re-reads, prologue, epilogue), so cost = ceil(N / w) * (w + 64).  N = 68 -> one 80-wide tile
-        // (248 vs 347 us for two 64-wide), 334 -> three 112-wide (221 vs 318), 256 -> four 64-wide; the least-padding rule tried first chose 16-wide tiles
-        // for N = 168 (1 270 us against 393).  MI_GCONV_BN_FORCE: one width for everything (measurement).
-        static const int widths[] = {64, 80, 112, 32, 16};
-        const int force = mi_sw().gconv_bn_force;
-        const int fixed = mi_sw().gconv_bn_c;
-        int best = 64;
-        long best_cost = 1L << 60;
-        for (int wdt : widths) {
-            const long cost = (long)((N + wdt - 1) / wdt) * (wdt + fixed);
-            if (cost < best_cost) best = wdt, best_cost = cost;
-        }
-        // (only where the wider tiles still leave the chip full: on the 11 x 11 / 22 x 22 maps a 2048-channel data gradient took 26 us as 304 112-wide
-        //  workgroups against 20 us as 512 64-wide ones)
-        if (best > 64 && mt * ((N + best - 1) / best) < 384) best = 64;
-        if (force) best = force;
-        switch (best) {
-            case 16: glaunch_k<16>(p, avec, ovec, false, s); break;
-            case 32: glaunch_k<32>(p, avec, ovec, false, s); break;
-            case 80: glaunch_k<80>(p, avec, ovec, false, s); break;
-            case 112: glaunch_k<112>(p, avec, ovec, false, s); break;
-            default: glaunch_k<64>(p, avec, ovec, false, s); break;
-        }
+    switch (r.bn) {
+        case 16: glaunch_k<16>(p, r, s); break;
+        case 32: glaunch_k<32>(p, r, s); break;
+        case 80: glaunch_k<80>(p, r, s); break;
+        case 112: glaunch_k<112>(p, r, s); break;
+        case 128: glaunch_k<128>(p, r, s); break;
+        default: glaunch_k<64>(p, r, s); break;
     }
     MI_CHECK_LAUNCH("gconv_kernel");
     return MI_OK;
@@ -1573,16 +1636,47 @@ size_t mi_gconv_wgrad_workspace(int B, int Ho, int Wo, int O, int I, int kh, int
     return (size_t)S * kh * kw * O * ((I + 3) & ~3) * sizeof(float);
 }
 
-int mi_gconv_wgrad(const void* dy, long ldy, const void* x, long ldx, float* dw, int B, int Ha, int Wa, int I, int Ho, int Wo, int O,
-                   int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw_, int accumulate, void* workspace, size_t workspace_bytes,
-                   unsigned* tickets, int n_tickets, void* stream) {
-    MI_REQUIRE(dy && x && dw && workspace, "mi_gconv_wgrad: null operand");
+// The instance a weight-gradient launch runs (mi_gconv_wgrad_route): kernel family, operand vector widths, K split
+struct GWRoute {
+    int fused;              // 1: gwgrad3 (one staged x window for a kernel row's three taps), 0: gwgrad (per tap)
+    int yvec, xvec;
+    int S, rows;            // K splits, output pixels per split
+    int grid;               // workgroups of the main launch (a _multi job: its share of its class's launch)
+};
+
+// the argument checks of mi_gconv_wgrad (and mi_gconv_wgrad_route): nothing is dereferenced
+static int gwgrad_check(long ldy, long ldx, int B, int Ha, int Wa, int I, int Ho, int Wo, int O, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw_) {
     MI_REQUIRE(B > 0 && Ha > 0 && Wa > 0 && Ho > 0 && Wo > 0 && I > 0 && O > 0, "mi_gconv_wgrad: empty shape");
     MI_REQUIRE(ldy >= O && ldx >= I, "mi_gconv_wgrad: a view's row stride is smaller than its channel count");
     MI_REQUIRE(kh > 0 && kw > 0 && sh > 0 && sw > 0 && dh > 0 && dw_ > 0 && ph >= 0 && pw >= 0, "mi_gconv_wgrad: bad conv geometry");
     MI_REQUIRE((long)B * Ho * Wo < (1L << 31) && (long)B * Ha * Wa < (1L << 31), "mi_gconv_wgrad: more than 2^31 pixels");
     MI_REQUIRE((Ha + 2 * ph - dh * (kh - 1) - 1) / sh + 1 == Ho && (Wa + 2 * pw - dw_ * (kw - 1) - 1) / sw + 1 == Wo,
                "mi_gconv_wgrad: output %dx%d does not follow from input %dx%d", Ho, Wo, Ha, Wa);
+    return MI_OK;
+}
+
+// The one planning function of mi_gconv_wgrad (mi_gconv_wgrad_route reports it).
+static GWRoute gwgrad_route(const void* dy, long ldy, const void* x, long ldx, int B, int Ha, int Wa, int I, int Ho, int Wo, int O, int kh, int kw, int sh, int sw,
+                            int pw, int dw_, int* o_tiles, int* i_tiles) {
+    GWRoute r{};
+    const int M = B * Ho * Wo;
+    // fused kernel row (gwgrad3_kernel): three-column kernels at stride 1 whose output has the input's height and width
+    // (measured, bench.py --workload gald / pranet: GALD's weight gradients 9.96 -> 8.90 ms per step with every eligible conv fused, PraNet's 5.02 -> 5.23:
+    //  on the small maps of the deep stages a third of the workgroups leaves the launch latency-bound on fewer CUs - fused from 65 536 pixels up, or when forced)
+    r.fused = kw == 3 && sh == 1 && sw == 1 && pw == dw_ && Ho == Ha && Wo == Wa && dw_ <= W3_MAXD && (mi_sw().gwgrad3 == 2 || (mi_sw().gwgrad3 == 1 && M >= 65536));
+    gwgrad_plan(M, O, I, r.fused ? kh : kh * kw, &r.S, &r.rows, o_tiles, i_tiles);
+    r.yvec = view_vec(dy, ldy, O);
+    r.xvec = view_vec(x, ldx, I);
+    r.grid = *o_tiles * *i_tiles * (r.fused ? kh : kh * kw) * r.S;
+    return r;
+}
+
+int mi_gconv_wgrad(const void* dy, long ldy, const void* x, long ldx, float* dw, int B, int Ha, int Wa, int I, int Ho, int Wo, int O,
+                   int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw_, int accumulate, void* workspace, size_t workspace_bytes,
+                   unsigned* tickets, int n_tickets, void* stream) {
+    MI_REQUIRE(dy && x && dw && workspace, "mi_gconv_wgrad: null operand");
+    const int rc = gwgrad_check(ldy, ldx, B, Ha, Wa, I, Ho, Wo, O, kh, kw, sh, sw, ph, pw, dh, dw_);
+    if (rc != MI_OK) return rc;
     MI_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 15) == 0, "mi_gconv_wgrad: workspace must be 16-byte aligned");
     GWgP p;
     p.remap = mi_sw().gconv_remap;
@@ -1596,21 +1690,18 @@ int mi_gconv_wgrad(const void* dy, long ldy, const void* x, long ldx, float* dw,
     p.O = O; p.I = I; p.T = kh * kw;
     p.Ho = Ho; p.Wo = Wo; p.Ha = Ha; p.Wa = Wa;
     p.kw = kw; p.sh = sh; p.sw = sw; p.ph = ph; p.pw = pw; p.dh = dh; p.dw = dw_;
-    // fused kernel row (gwgrad3_kernel): three-column kernels at stride 1 whose output has the input's height and width
-    // (measured, bench.py --workload gald / pranet: GALD's weight gradients 9.96 -> 8.90 ms per step with every eligible conv fused, PraNet's 5.02 -> 5.23:
-    //  on the small maps of the deep stages a third of the workgroups leaves the launch latency-bound on fewer CUs - fused from 65 536 pixels up, or when forced)
-    const bool fused = kw == 3 && sh == 1 && sw == 1 && pw == dw_ && Ho == Ha && Wo == Wa && dw_ <= W3_MAXD &&
-                       (mi_sw().gwgrad3 == 2 || (mi_sw().gwgrad3 == 1 && p.M >= 65536));
-    gwgrad_plan(p.M, O, I, fused ? kh : p.T, &p.S, &p.rows_per_split, &p.o_tiles, &p.i_tiles);
+    const GWRoute r = gwgrad_route(dy, ldy, x, ldx, B, Ha, Wa, I, Ho, Wo, O, kh, kw, sh, sw, pw, dw_, &p.o_tiles, &p.i_tiles);
+    p.S = r.S;
+    p.rows_per_split = r.rows;
     const size_t need = (size_t)p.S * p.T * O * ((I + 3) & ~3) * sizeof(float);
     if (workspace_bytes < need) return mi_set_error(MI_ENOMEM, "mi_gconv_wgrad: workspace %zu < %zu bytes", workspace_bytes, need);
     hipStream_t s = (hipStream_t)stream;
-    const int yv = view_vec(dy, ldy, O), xv = view_vec(x, ldx, I);
-    if (fused) {
+    const int yv = r.yvec, xv = r.xvec;
+    if (r.fused) {
         p.ticket = nullptr;
         p.dwout = dw;
         p.accumulate = accumulate;
-        const dim3 grid3(p.o_tiles * p.i_tiles * kh * p.S);
+        const dim3 grid3(r.grid);
 #define GW3(YV, XV) hipLaunchKernelGGL((gwgrad3_kernel<YV, XV>), grid3, dim3(256), 0, s, p)
         if (yv == 8 && xv == 8) GW3(8, 8);
         else if (yv == 8 && xv == 4) GW3(8, 4);
@@ -1634,7 +1725,7 @@ int mi_gconv_wgrad(const void* dy, long ldy, const void* x, long ldx, float* dw,
     p.ticket = inlaunch ? tickets : nullptr;
     p.dwout = dw;
     p.accumulate = accumulate;
-    const dim3 grid(p.o_tiles * p.i_tiles * p.T * p.S);
+    const dim3 grid(r.grid);
 #define GW(YV, XV) hipLaunchKernelGGL((gwgrad_kernel<YV, XV>), grid, dim3(256), 0, s, p)
     if (yv == 8 && xv == 8) GW(8, 8);
     else if (yv == 8 && xv == 4) GW(8, 4);
@@ -1692,9 +1783,36 @@ static void gwm_plan(const MiWgradJob& j, GWgD& d) {
     const long n4 = (long)j.O * ((j.I + 3) / 4) * p.T;                  // the reducer's threads: four consecutive i each
     d.n_rblk = (int)((n4 + 255) / 256 < 512 ? (n4 + 255) / 256 : 512);
 }
+// The planning function of the table-driven launch: the job's descriptor and its class (0 .. 8: per-tap kernel by (yv, xv); 9 .. 17: fused-row kernel)
+static int gwm_route(const MiWgradJob& j, GWgD& d) {
+    auto vidx = [](int v) { return v == 8 ? 0 : (v == 4 ? 1 : 2); };
+    gwm_plan(j, d);
+    return vidx(view_vec(j.dy, j.ldy, j.O)) * 3 + vidx(view_vec(j.x, j.ldx, j.I)) + (gwm_fused(j, d.p.M) ? 9 : 0);
+}
 static inline size_t gwm_slab_bytes(const GWgD& d) { return ((size_t)d.p.S * d.p.T * d.p.O * ((d.p.I + 3) & ~3) * sizeof(float) + 255) & ~(size_t)255; }
 
 size_t mi_gconv_wgrad_multi_table_bytes(int n) { return (size_t)(n > 0 ? n : 0) * sizeof(GWgD); }
+
+int mi_gconv_wgrad_route(const void* dy, long ldy, const void* x, long ldx, int B, int Ha, int Wa, int I, int Ho, int Wo, int O, int kh, int kw, int sh, int sw,
+                         int ph, int pw, int dh, int dw_, int multi, int* route) {
+    MI_REQUIRE(route, "mi_gconv_wgrad_route: null route");
+    const int rc = gwgrad_check(ldy, ldx, B, Ha, Wa, I, Ho, Wo, O, kh, kw, sh, sw, ph, pw, dh, dw_);
+    if (rc != MI_OK) return rc;
+    GWRoute r{};
+    if (multi) {
+        const MiWgradJob j{dy, ldy, x, ldx, nullptr, B, Ha, Wa, I, Ho, Wo, O, kh, kw, sh, sw, ph, pw, dh, dw_, 0};
+        GWgD d;
+        const int c = gwm_route(j, d);
+        static const int vv[3] = {8, 4, 1};
+        r = GWRoute{c >= 9, vv[(c % 9) / 3], vv[c % 3], d.p.S, d.p.rows_per_split, d.nblk};
+    } else {
+        int ot, it;
+        r = gwgrad_route(dy, ldy, x, ldx, B, Ha, Wa, I, Ho, Wo, O, kh, kw, sh, sw, pw, dw_, &ot, &it);
+    }
+    const int v[MI_GWROUTE_LEN] = {r.fused, r.yvec, r.xvec, r.S, r.rows, r.grid};
+    for (int k = 0; k < MI_GWROUTE_LEN; ++k) route[k] = v[k];
+    return MI_OK;
+}
 
 size_t mi_gconv_wgrad_multi_workspace(const MiWgradJob* jobs, int n) {
     size_t total = 0;
@@ -1714,8 +1832,7 @@ int mi_gconv_wgrad_multi(const MiWgradJob* jobs, int n, void* table_dev, size_t 
     MI_REQUIRE(table_bytes >= mi_gconv_wgrad_multi_table_bytes(n), "mi_gconv_wgrad_multi: table buffer %zu < %zu bytes", table_bytes, mi_gconv_wgrad_multi_table_bytes(n));
     MI_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 15) == 0 && (reinterpret_cast<uintptr_t>(table_dev) & 15) == 0, "mi_gconv_wgrad_multi: buffers must be 16-byte aligned");
     std::vector<GWgD> table((size_t)n);
-    std::vector<int> cls((size_t)n);                        // 0 .. 8: per-tap kernel by (yv, xv); 9 .. 17: fused-row kernel
-    auto vidx = [](int v) { return v == 8 ? 0 : (v == 4 ? 1 : 2); };
+    std::vector<int> cls((size_t)n);                        // gwm_route's class
     std::vector<int> order;
     size_t need = 0;
     for (int k = 0; k < n; ++k) {
@@ -1728,8 +1845,7 @@ int mi_gconv_wgrad_multi(const MiWgradJob* jobs, int n, void* table_dev, size_t 
         MI_REQUIRE((j.Ha + 2 * j.ph - j.dh * (j.kh - 1) - 1) / j.sh + 1 == j.Ho && (j.Wa + 2 * j.pw - j.dw_ * (j.kw - 1) - 1) / j.sw + 1 == j.Wo,
                    "mi_gconv_wgrad_multi: job %d: output %dx%d does not follow from input %dx%d", k, j.Ho, j.Wo, j.Ha, j.Wa);
         for (int q = 0; q < k; ++q) MI_REQUIRE(jobs[q].dw != j.dw, "mi_gconv_wgrad_multi: jobs %d and %d write the same gradient", q, k);
-        gwm_plan(j, table[k]);
-        cls[k] = vidx(view_vec(j.dy, j.ldy, j.O)) * 3 + vidx(view_vec(j.x, j.ldx, j.I)) + (gwm_fused(j, table[k].p.M) ? 9 : 0);
+        cls[k] = gwm_route(j, table[k]);
         need += gwm_slab_bytes(table[k]);
     }
     if (workspace_bytes < need) return mi_set_error(MI_ENOMEM, "mi_gconv_wgrad_multi: workspace %zu < %zu bytes", workspace_bytes, need);

@@ -3,6 +3,7 @@
 A tensor handed to these functions is an NHWC tensor [B,H,W,C] or a CHANNEL SLICE of one (`t[..., a:b]`): last-dim stride 1, pixel
 stride `ld` (elements per pixel row of the parent), no other gaps.  One-channel fp32 maps are [B,H,W,1] with ld 1.
 """
+import collections
 import ctypes
 
 import torch
@@ -64,6 +65,57 @@ def conv_out_hw(H, W, kh, kw, sh, sw, ph, pw, dh, dw):
     return (H + 2 * ph - dh * (kh - 1) - 1) // sh + 1, (W + 2 * pw - dw * (kw - 1) - 1) // sw + 1
 
 
+# Opt-in route recorder (tests): None, or a set to which gconv, gconv_bn, gconv_wgrad and gconv_wgrad_multi add the route of every launch (GRoute / GWRoute).
+ROUTES = None
+
+
+class GRoute(collections.namedtuple("GRoute", "kernel bn kc avec ovec f32 gen ks grid_x grid_y")):
+    """include/mi355seg.h mi_gconv_route's descriptor (MI_GROUTE_LEN fields, in its order); `name` is the kernel instance as profilers print it."""
+    __slots__ = ()
+
+    @property
+    def name(self):
+        if self.kernel == 1:
+            return "gconv3_kernel<%d, %d, %d>" % (self.bn, self.avec, self.ovec)
+        b = ("false", "true")
+        return "gconv_kernel<%d, %d, %d, %d, %s, %s, %d>" % (self.bn, self.kc, self.avec, self.ovec, b[self.f32], b[self.gen], self.ks)
+
+
+class GWRoute(collections.namedtuple("GWRoute", "multi fused yvec xvec S rows grid")):
+    """multi (a job of mi_gconv_wgrad_multi), then include/mi355seg.h mi_gconv_wgrad_route's descriptor (MI_GWROUTE_LEN fields, in its order)."""
+    __slots__ = ()
+
+    @property
+    def name(self):
+        return "gwgrad%s%s_kernel<%d, %d>" % ("3" if self.fused else "", "_multi" if self.multi else "", self.yvec, self.xvec)
+
+
+GROUTE_LEN, GWROUTE_LEN = len(GRoute._fields), len(GWRoute._fields) - 1        # MI_GROUTE_LEN, MI_GWROUTE_LEN (tests/test_host_gconv_routes.py)
+
+
+def gconv_route(a_addr, lda, out_addr, ldo, a_shape, N, geom, mode=GATHER_FWD, out_hw=None, out_f32=False, bn_finalize=False):
+    """The instance mi_gconv (mi_gconv_bn: bn_finalize) launches for a [B,Ha,Wa,Ca] view at address a_addr (row stride lda) into out_addr (ldo): host only,
+    the addresses count for their alignment alone.  out_hw as in gconv (DGRAD: the forward input's (H, W))."""
+    B, Ha, Wa, Ca = a_shape
+    Ho, Wo = conv_out_hw(Ha, Wa, *geom) if mode == GATHER_FWD else out_hw
+    kh, kw, sh, sw, ph, pw, dh, dw = geom
+    r = (ctypes.c_int * GROUTE_LEN)()
+    check(_lib.lib().mi_gconv_route(ctypes.c_void_p(a_addr), lda, ctypes.c_void_p(out_addr), ldo, B, Ha, Wa, Ca, Ho, Wo, N, kh, kw, sh, sw, ph, pw, dh, dw, mode,
+                                    int(out_f32), int(bn_finalize), r), "mi_gconv_route")
+    return GRoute(*r)
+
+
+def gconv_wgrad_route(dy_addr, ldy, x_addr, ldx, dy_shape, x_shape, geom, multi=False):
+    """The weight-gradient instance mi_gconv_wgrad (multi: a job of mi_gconv_wgrad_multi) launches for dy [B,Ho,Wo,O] and x [B,Ha,Wa,I] views: host only."""
+    B, Ho, Wo, O = dy_shape
+    _, Ha, Wa, I = x_shape
+    kh, kw, sh, sw, ph, pw, dh, dw_ = geom
+    r = (ctypes.c_int * GWROUTE_LEN)()
+    check(_lib.lib().mi_gconv_wgrad_route(ctypes.c_void_p(dy_addr), ldy, ctypes.c_void_p(x_addr), ldx, B, Ha, Wa, I, Ho, Wo, O, kh, kw, sh, sw, ph, pw, dh, dw_,
+                                          int(multi), r), "mi_gconv_wgrad_route")
+    return GWRoute(int(multi), *r)
+
+
 def gconv(a, wp, N, geom, out=None, mode=GATHER_FWD, out_hw=None, bias=None, stats=False, out_f32=False):
     """geom = (kh, kw, sh, sw, ph, pw, dh, dw).  FWD: a is the input, returns (out [B,Ho,Wo,N], stats or None).
     DGRAD: a is d loss / d conv output, out_hw the forward input's (H, W), wp the transposed pack, N the forward input channels."""
@@ -79,6 +131,8 @@ def gconv(a, wp, N, geom, out=None, mode=GATHER_FWD, out_hw=None, bias=None, sta
     po, ldo = view(out, torch.float32 if out_f32 else torch.bfloat16)
     if tuple(out.shape) != (B, Ho, Wo, N):
         raise _lib.MiError("gconv: out is %s, the conv writes %s" % (tuple(out.shape), (B, Ho, Wo, N)))
+    if ROUTES is not None:
+        ROUTES.add(gconv_route(a.data_ptr(), lda, out.data_ptr(), ldo, a.shape, N, geom, mode, (Ho, Wo), out_f32))
     L = _L()
     st = None
     if stats:
@@ -134,6 +188,8 @@ def gconv_bn(a, wp, N, geom, bn_weight, bn_bias, running_mean, running_var, mome
         out = new(B, Ho, Wo, N, a.device)
     pa, lda = view(a, torch.bfloat16)
     po, ldo = view(out, torch.bfloat16)
+    if ROUTES is not None:
+        ROUTES.add(gconv_route(a.data_ptr(), lda, out.data_ptr(), ldo, a.shape, N, geom, bn_finalize=True))
     L = _L()
     st = torch.empty(int(L.mi_gconv_stats_elems(B, Ho, Wo, N)), dtype=torch.float32, device=a.device)
     fin = torch.empty((4, N), dtype=torch.float32, device=a.device)
@@ -154,6 +210,8 @@ def gconv_wgrad(dy, x, dw, geom, accumulate=False):
         raise _lib.MiError("gconv_wgrad: dw must be contiguous fp32 [O,I,kh,kw]")
     py, ldy = view(dy, torch.bfloat16)
     px, ldx = view(x, torch.bfloat16)
+    if ROUTES is not None:
+        ROUTES.add(gconv_wgrad_route(dy.data_ptr(), ldy, x.data_ptr(), ldx, dy.shape, x.shape, geom))
     L = _L()
     ws = _workspace(L.mi_gconv_wgrad_workspace(B, Ho, Wo, O, I, kh, kw), dy.device, "gwgrad")
     if _K.PROFILE is not None:
@@ -189,6 +247,8 @@ def gconv_wgrad_multi(jobs):
         j.B, j.Ha, j.Wa, j.I, j.Ho, j.Wo, j.O = B, Ha, Wa, I, Ho, Wo, O
         j.kh, j.kw, j.sh, j.sw, j.ph, j.pw, j.dh, j.dw_, j.accumulate = kh, kw, sh, sw, ph, pw, dh, dw_, int(accumulate)
         flops += 2.0 * B * Ho * Wo * O * I * kh * kw
+        if ROUTES is not None:
+            ROUTES.add(gconv_wgrad_route(dy.data_ptr(), ldy, x.data_ptr(), ldx, dy.shape, x.shape, geom, multi=True))
     dev = jobs[0][0].device
     L = _L()
     pj = ctypes.cast(arr, ctypes.c_void_p)

@@ -140,7 +140,7 @@ def test_opt_in_kernel_variants_and_single_stream_schedule_stay_correct():
     instrumented steps use.  (The kernels that did not win - the 256-wide tile of the 128-wide kernel, the shared-window 3x3 main loop, the
     8-wave fused-row weight gradient - are compiled only into experiment builds, tools/experiments/build.sh, since round 3.)
     Environment switches are read once per process, so each runs the relevant parity tests in a child pytest."""
-    for env, sel in (({"MI_IGEMM_PP": "0"}, ["tests/test_gpu_ops.py", "-k", "full_size or identity"]),
+    for env, sel, *reached in (({"MI_IGEMM_PP": "0"}, ["tests/test_gpu_ops.py", "-k", "full_size or identity"]),
                      ({"MI_IGEMM_PP_KORDER": "0"}, ["tests/test_gpu_ops.py", "-k", "identity or wide_tile"]),     # tap-major: bit-equal to the 128-wide kernel
                      ({"MI_WGRAD_Q3": "2"}, ["tests/test_gpu_ops.py", "-k", "conv_fwd_dgrad or fused_epilogue or tiny_and_ragged or wgrad_full or full_size_vs"]),
                      ({"MI_WGRAD_Q3": "0"}, ["tests/test_gpu_ops.py", "-k", "wgrad_full or full_size_vs"]),
@@ -156,11 +156,21 @@ def test_opt_in_kernel_variants_and_single_stream_schedule_stay_correct():
                      ({"MI_GCONV_REMAP": "0"}, ["tests/test_gpu_pranet.py", "-k", "building_blocks or graph_replay or stale"]),     # tape: plain tile order
                      ({"MI_GCONV3_WGS": "1"}, ["tests/test_gpu_gops.py", "-k", "gconv"]),                                          # kernel-row window conv on every eligible (tiny) shape
                      ({"MI_GCONV_BN_ANY": "0", "MI_GCONV_KS2_WGS": "0", "MI_GCONV3_WGS": "0"}, ["tests/test_gpu_gops.py", "-k", "gconv"]),   # 32 / 64-wide tiles, one wave group, no window kernel
+                     ({"MI_GCONV_BN_ANY": "0", "MI_GCONV_BN128": "1"}, ["tests/test_gpu_gconv_routes.py", "-s", "-k", "KC32_WGS or 1x7"],   # 128-wide tiles (>= 512 of them),
+                      "gconv_kernel<128, 32, 8, 8, false, false, 1>", "gconv_kernel<128, 32, 8, 4, false, false, 1>"),                   # N = 256 and 334: they must be reached
+                     ({"MI_BN_INLAUNCH": "1"}, ["tests/test_gpu_pranet.py", "-k", "building_blocks"]),     # the tape's in-launch finalize (only host/pranet.py reads the switch;
+                                                                                                              # test_gpu_gops.py runs mi_gconv_bn itself, a 64-wide launch included)
+                     ({"MI_GCONV_BN32_WGS": "0", "MI_GCONV_BN_FORCE": "16"}, ["tests/test_gpu_gops.py", "-k", "forward_and_batch_statistics or data_and_weight_gradient"]),   # every width forced onto the small ragged shapes
+                     ({"MI_GCONV_BN32_WGS": "0", "MI_GCONV_BN_FORCE": "64"}, ["tests/test_gpu_gops.py", "-k", "forward_and_batch_statistics or data_and_weight_gradient"]),
+                     ({"MI_GCONV_BN32_WGS": "0", "MI_GCONV_BN_FORCE": "80"}, ["tests/test_gpu_gops.py", "-k", "forward_and_batch_statistics or data_and_weight_gradient"]),
+                     ({"MI_GCONV_BN32_WGS": "0", "MI_GCONV_BN_FORCE": "112"}, ["tests/test_gpu_gops.py", "-k", "forward_and_batch_statistics or data_and_weight_gradient"]),
                      ({"MI_GWM_STEPS": "4", "MI_GWM_FUSED3": "0"}, ["tests/test_gpu_gops.py", "-k", "many_convs"]),                # batched weight gradients: many K splits, the one-conv fusing rule
                      ({"MI_WGRAD_STREAM": "0", "MI_BATCH_LANES": "1"}, ["tests/test_gpu_model.py", "-k", "tinynet"])):
         r = run(["-m", "pytest", "-q", "-m", "gpu", "-x", "-p", "no:cacheprovider"] + sel, env)
         assert r.returncode == 0, (env, r.stdout[-3000:])
         assert " passed" in r.stdout and " failed" not in r.stdout
+        for route in reached:                                # (routes the child run must have launched, as tests/test_gpu_gconv_routes.py prints them)
+            assert route in r.stdout, (env, route)
 
 
 def test_rccl_entry_points_of_the_cabi_single_rank_communicator():
