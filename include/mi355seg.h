@@ -243,6 +243,15 @@ size_t mi_upsample_softce_workspace(int B, int h, int w, int K, int H, int W);
 int mi_upsample_softce(const float* seg_low, float inv_temperature, float clip, const float* d_low, int ldD, int domain,
                        float* loss_out, float* dd_low, int B, int h, int w, int K, int H, int W, float grad_scale,
                        void* workspace, size_t workspace_bytes, void* stream);
+/* The same loss with the two operands on their own grids and conventions (GaldFada; reference core/combos/gald_fada.py:96-121): seg_low
+ * [B][hs][ws][K] upsampled with seg_align_corners, d_low [B][hd][wd][ldD] with d_align_corners, both to H x W (H >= hs, hd; W >= ws, wd;
+ * any ratio, integer or not).  Computed per high-resolution pixel, no [B,C,H,W] tensor, fixed summation orders (bitwise reproducible); LDS
+ * per workgroup depends on K only.  K <= 32 (19: compile-time path), 2K <= ldD, domain 0 | 1; bad arguments return MI_EINVAL before any
+ * launch.  loss_out[2], dd_low (may be NULL; padding channels zeroed) as mi_upsample_softce. */
+size_t mi_upsample_softce_2grid_workspace(int B, int hd, int wd, int K, int H, int W);
+int mi_upsample_softce_2grid(const float* seg_low, int hs, int ws, int seg_align_corners, float inv_temperature, float clip,
+                             const float* d_low, int hd, int wd, int ldD, int d_align_corners, int domain, float grad_scale,
+                             float* loss_out, float* dd_low, int B, int K, int H, int W, void* workspace, size_t workspace_bytes, void* stream);
 /* torch.optim.Adam (no amsgrad, weight_decay 0; fada_adapter.py:24) on flat fp32 buffers; step >= 1 is this update's index */
 int mi_adam_step(float* p, const float* g, float* exp_avg, float* exp_avg_sq, size_t n, float lr, float beta1, float beta2,
                  float eps, int step, void* stream);

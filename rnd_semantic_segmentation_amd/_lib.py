@@ -53,6 +53,8 @@ SIGNATURES = {
     "mi_bias_grad_bf16": (I, [P, P, I, I, I, P, Z, P]),
     "mi_upsample_softce_workspace": (Z, [I] * 6),
     "mi_upsample_softce": (I, [P, F, F, P, I, I, P, P] + [I] * 6 + [F, P, Z, P]),
+    "mi_upsample_softce_2grid_workspace": (Z, [I] * 6),
+    "mi_upsample_softce_2grid": (I, [P, I, I, I, F, F, P, I, I, I, I, I, F, P, P, I, I, I, I, P, Z, P]),
     "mi_adam_step": (I, [P, P, P, P, Z, F, F, F, F, I, P]),
     "mi_adam_step_clamped": (I, [P, P, P, P, Z, F, F, F, F, I, F, P]),
     "mi_adam_step_dev": (I, [P, P, P, P, Z, P, P]),

@@ -9,11 +9,15 @@ namespace {
 constexpr int KMAX = 32;       // segmentation classes held in registers
 constexpr int JT = 32;         // low-res columns per workgroup (same tiling as upce_pass1)
 
-struct Axis {                  // align_corners source index as ATen computes it in fp32 (same as upsample_ce.hip)
-    float scale;
+struct Axis {                  // source index as ATen computes it in fp32 (same as upsample_ce.hip): align_corners (off = 0): scale * dst;
+    float scale, off;          // otherwise (off = 0.5): max(scale * (dst + 0.5) - 0.5, 0)  (+/- 0.0f is exact: the align_corners bits are unchanged)
     int n_in, n_out;
+    __device__ __forceinline__ float srcf(int dst) const {
+        const float f = scale * ((float)dst + off) - off;
+        return f < 0.f ? 0.f : f;
+    }
     __device__ __forceinline__ void src(int dst, int& i0, int& i1, float& lam) const {
-        const float f = scale * (float)dst;
+        const float f = srcf(dst);
         i0 = (int)f;
         if (i0 > n_in - 1) i0 = n_in - 1;
         i1 = (i0 < n_in - 1) ? i0 + 1 : i0;
@@ -27,7 +31,7 @@ struct Axis {                  // align_corners source index as ATen computes it
         if (d < 0) d = 0;
         if (d > n_out) d = n_out;
         while (d < n_out) {
-            int i0 = (int)(scale * (float)d);
+            int i0 = (int)srcf(d);
             if (i0 > n_in - 1) i0 = n_in - 1;
             if (i0 >= c) break;
             ++d;
@@ -36,11 +40,12 @@ struct Axis {                  // align_corners source index as ATen computes it
     }
 };
 
-inline Axis make_axis(int n_in, int n_out) {
+inline Axis make_axis(int n_in, int n_out, int align_corners = 1) {
     Axis a;
     a.n_in = n_in;
     a.n_out = n_out;
-    a.scale = (n_out > 1) ? (float)(n_in - 1) / (float)(n_out - 1) : 0.f;
+    a.off = align_corners ? 0.f : 0.5f;
+    a.scale = align_corners ? ((n_out > 1) ? (float)(n_in - 1) / (float)(n_out - 1) : 0.f) : (float)n_in / (float)n_out;      // (a size was given: in / out)
     return a;
 }
 
@@ -215,6 +220,157 @@ __global__ void softce_pass2_kernel(const float* __restrict__ tmp, float* __rest
     dd[(((long)b * h + i) * w + j) * ldD + k] = s * scale;
 }
 
+// Two-grid variant (GaldFada: the segmentation logits at 1/4 resolution, align_corners=False, the discriminator's at 1/32, align_corners=True;
+// gald_fada.py:96-121).  Workgroup = (b, y, tile of jt discriminator columns).  The tile's high-res pixels go through in batches of NB, one per
+// thread: soft labels straight from the four segmentation corners (global / L2: no LDS that grows with that grid's ratio), log-softmax of the
+// 2K discriminator logits from a y-interpolated row of the tile's columns, loss term, d = S*softmax(z) - placed(soft) into LDS; after each batch
+// every (column, channel) item of the tile adds the batch's pixels in pixel order (registers, fixed order: bitwise reproducible).  LDS is
+// NB * 2K + (jt + 2) * 2K floats whatever the upsample factors.
+constexpr int NB = 256;        // pixels per batch (= threads)
+constexpr int JT2 = 32;        // most discriminator columns per tile
+constexpr int ITEMS = 8;       // (column, channel) items per thread: jt * 2K <= NB * ITEMS
+
+template <int KT>
+__global__ __launch_bounds__(256) void softce2_pass1_kernel(const float* __restrict__ seg, Axis sy, Axis sx, float inv_t, float clip,
+                                                            const float* __restrict__ dl, int ldD, int domain, float* __restrict__ partial,
+                                                            float* __restrict__ tmp, int Krt, Axis ay, Axis ax, int jt_cols) {
+    extern __shared__ __attribute__((aligned(16))) float sh[];
+    const int K = KT > 0 ? KT : Krt;
+    constexpr int KR = KT > 0 ? KT : KMAX;
+    const int K2 = 2 * K;
+    float* dbuf = sh;                                   // [NB][K2]
+    float* lam = dbuf + NB * K2;                        // [NB]
+    float* red = lam + NB;                              // [256]
+    int* pstart = reinterpret_cast<int*>(red + 256);    // [JT2+3] first pixel (relative to xa) whose x0 >= j0 - 1 + q
+    float* drow = red + 256 + JT2 + 4;                  // [JT2+2][K2]  discriminator logits interpolated along y
+    const int H = ay.n_out, hd = ay.n_in, wd = ax.n_in, hs = sy.n_in, ws = sx.n_in;
+    const int jt = blockIdx.x, y = blockIdx.y, b = blockIdx.z;
+    const int j0 = jt * jt_cols, j1 = min(wd, j0 + jt_cols);
+    const int xa = ax.first_with_i0_ge(j0 - 1), xb = ax.first_with_i0_ge(j1);
+    const int npx = xb - xa;
+    int y0, y1, t0, t1;
+    float ly, lt;
+    ay.src(y, y0, y1, ly);
+    sy.src(y, t0, t1, lt);
+    const float* srow0 = seg + ((long)b * hs + t0) * ws * K;
+    const float* srow1 = seg + ((long)b * hs + t1) * ws * K;
+    const int cbase = max(j0 - 1, 0), ncol = min(j1, wd - 1) - cbase + 1;
+    if (threadIdx.x < j1 - j0 + 2) pstart[threadIdx.x] = ax.first_with_i0_ge(j0 - 1 + (int)threadIdx.x) - xa;
+    for (int e = threadIdx.x; e < ncol * K2; e += 256) {
+        const int c = e / K2, k = e - c * K2;
+        const long o0 = (((long)b * hd + y0) * wd + cbase + c) * ldD + k, o1 = (((long)b * hd + y1) * wd + cbase + c) * ldD + k;
+        drow[e] = (1.f - ly) * dl[o0] + ly * dl[o1];
+    }
+    __syncthreads();
+    const int nj = j1 - j0, nitems = nj * K2;
+    float acc[ITEMS];
+#pragma unroll
+    for (int r = 0; r < ITEMS; ++r) acc[r] = 0.f;
+    float loss = 0.f;
+    for (int pb = 0; pb < npx; pb += NB) {
+        const int px = pb + (int)threadIdx.x;
+        if (px < npx) {
+            const int x = xa + px;
+            int x0, x1, u0, u1;
+            float lx, lu;
+            ax.src(x, x0, x1, lx);
+            sx.src(x, u0, u1, lu);
+            lam[threadIdx.x] = lx;
+            const float* z0 = drow + (x0 - cbase) * K2;
+            const float* z1 = drow + (x1 - cbase) * K2;
+            // soft labels: softmax(up(seg) / T), clipped (gald_fada.py:96-103); y first, then x (the order of softce_pass1_kernel's rows)
+            float soft[KR];
+            float mx = -3.0e38f;
+#pragma unroll
+            for (int k = 0; k < KR; ++k)
+                if (k < K) {
+                    const float a = (1.f - lt) * srow0[u0 * K + k] + lt * srow1[u0 * K + k];
+                    const float c = (1.f - lt) * srow0[u1 * K + k] + lt * srow1[u1 * K + k];
+                    soft[k] = ((1.f - lu) * a + lu * c) * inv_t;
+                    mx = fmaxf(mx, soft[k]);
+                }
+            float se = 0.f;
+#pragma unroll
+            for (int k = 0; k < KR; ++k)
+                if (k < K) {
+                    soft[k] = __expf(soft[k] - mx);
+                    se += soft[k];
+                }
+            float S = 0.f;
+            const float rse = 1.f / se;
+#pragma unroll
+            for (int k = 0; k < KR; ++k)
+                if (k < K) {
+                    soft[k] = fminf(soft[k] * rse, clip);
+                    S += soft[k];
+                }
+            float zm = -3.0e38f;
+            for (int k = 0; k < K2; ++k) zm = fmaxf(zm, (1.f - lx) * z0[k] + lx * z1[k]);
+            float ze = 0.f;
+            for (int k = 0; k < K2; ++k) ze += __expf((1.f - lx) * z0[k] + lx * z1[k] - zm);
+            const float lse = zm + __logf(ze), rze = 1.f / ze;
+            float* d = dbuf + threadIdx.x * K2;
+            float l = 0.f;
+            if (KT > 0) {
+#pragma unroll
+                for (int half = 0; half < 2; ++half)
+#pragma unroll
+                    for (int q = 0; q < KR; ++q) {
+                        const int k = half * KR + q;
+                        const float z = (1.f - lx) * z0[k] + lx * z1[k];
+                        const float placed = (half == domain) ? soft[q] : 0.f;
+                        l -= placed * (z - lse);
+                        d[k] = S * __expf(z - zm) * rze - placed;
+                    }
+            } else {
+                for (int k = 0; k < K2; ++k) {
+                    const float z = (1.f - lx) * z0[k] + lx * z1[k];
+                    float placed = 0.f;
+                    const int c = k - domain * K;
+#pragma unroll
+                    for (int q = 0; q < KMAX; ++q)
+                        if (q == c) placed = soft[q];
+                    l -= placed * (z - lse);
+                    d[k] = S * __expf(z - zm) * rze - placed;
+                }
+            }
+            if (x0 >= j0) loss += l;      // the tile that owns x0 accounts for the pixel's loss
+        }
+        if (tmp) {
+            __syncthreads();
+            const int pe = min(npx, pb + NB);
+#pragma unroll
+            for (int r = 0; r < ITEMS; ++r) {
+                const int item = (int)threadIdx.x + r * NB;
+                if (item < nitems) {
+                    const int jj = item / K2, k = item - jj * K2;
+                    const bool edge = j0 + jj == wd - 1;
+                    // pixels with x0 == j-1 contribute lam (as x1), then pixels with x0 == j contribute 1-lam (+ lam at the clamped right edge)
+                    const int p0 = max(max(pstart[jj], 0), pb), p1 = min(max(max(pstart[jj + 1], 0), pb), pe);
+                    const int p2 = min(pstart[jj + 2], pe);
+                    float s = acc[r];
+                    for (int p = p0; p < p1; ++p) s += (0.f + lam[p - pb]) * dbuf[(p - pb) * K2 + k];
+                    for (int p = max(p1, pb); p < p2; ++p) s += ((1.f - lam[p - pb]) + (edge ? lam[p - pb] : 0.f)) * dbuf[(p - pb) * K2 + k];
+                    acc[r] = s;
+                }
+            }
+            __syncthreads();
+        }
+    }
+    if (tmp) {
+#pragma unroll
+        for (int r = 0; r < ITEMS; ++r) {
+            const int item = (int)threadIdx.x + r * NB;
+            if (item < nitems) {
+                const int jj = item / K2, k = item - jj * K2;
+                tmp[(((long)b * H + y) * wd + j0 + jj) * K2 + k] = acc[r];
+            }
+        }
+    }
+    block_sum(loss, red);
+    if (threadIdx.x == 0) partial[((long)b * H + y) * gridDim.x + jt] = loss;
+}
+
 // torch.optim.Adam single-tensor update; CLAMP: the gradient is first clamped to [-clamp, clamp] IN PLACE (core/utils/utils.py:6-16
 // clip_gradient, called before optimizer.step() at pranet_trainer.py:59)
 template <bool CLAMP>
@@ -310,6 +466,69 @@ extern "C" int mi_upsample_softce(const float* seg_low, float inv_temperature, f
         hipLaunchKernelGGL(softce_pass2_kernel, dim3(nblk((long)B * h * w * K2, 256)), dim3(256), 0, (hipStream_t)stream, (const float*)tmp, dd_low,
                            B, K2, ldD, ay, w, grad_scale / count);
         MI_CHECK_LAUNCH("mi_upsample_softce pass2");
+    }
+    return MI_OK;
+}
+
+// discriminator columns per tile of softce2_pass1_kernel: about NB high-res pixels per tile, within the item budget of a thread
+inline int softce2_cols(int wd, int W, int K2) {
+    int c = (int)((long)NB * wd / W);
+    c = c < 1 ? 1 : c;
+    c = c > JT2 ? JT2 : c;
+    return c > NB * ITEMS / K2 ? NB * ITEMS / K2 : c;
+}
+
+inline size_t softce2_partial_bytes(int B, int wd, int H) { return (((size_t)B * H * wd * sizeof(float)) + 255) & ~(size_t)255; }
+
+extern "C" size_t mi_upsample_softce_2grid_workspace(int B, int hd, int wd, int K, int H, int W) {
+    (void)hd;
+    (void)W;
+    return softce2_partial_bytes(B, wd, H) + (size_t)B * H * wd * 2 * K * sizeof(float);
+}
+
+extern "C" int mi_upsample_softce_2grid(const float* seg_low, int hs, int ws, int seg_align_corners, float inv_temperature, float clip,
+                                        const float* d_low, int hd, int wd, int ldD, int d_align_corners, int domain, float grad_scale,
+                                        float* loss_out, float* dd_low, int B, int K, int H, int W, void* workspace, size_t workspace_bytes,
+                                        void* stream) {
+    MI_REQUIRE(seg_low && d_low && loss_out && workspace, "mi_upsample_softce_2grid: null operand");
+    MI_REQUIRE(K > 0 && K <= KMAX, "mi_upsample_softce_2grid: K = %d, supported 1..%d", K, KMAX);
+    MI_REQUIRE(ldD >= 2 * K, "mi_upsample_softce_2grid: ldD = %d < 2K = %d", ldD, 2 * K);
+    MI_REQUIRE(domain == 0 || domain == 1, "mi_upsample_softce_2grid: domain is 0 (source half) or 1 (target half), got %d", domain);
+    MI_REQUIRE((seg_align_corners == 0 || seg_align_corners == 1) && (d_align_corners == 0 || d_align_corners == 1),
+               "mi_upsample_softce_2grid: align_corners flags are 0 or 1");
+    MI_REQUIRE(B > 0 && hs > 0 && ws > 0 && hd > 0 && wd > 0 && H >= hs && W >= ws && H >= hd && W >= wd,
+               "mi_upsample_softce_2grid: bad dimension (both grids upsample to H x W)");
+    MI_REQUIRE(H <= 65535 && B <= 65535, "mi_upsample_softce_2grid: grid dimension overflow");
+    MI_REQUIRE(inv_temperature > 0.f && clip > 0.f, "mi_upsample_softce_2grid: inv_temperature and clip must be positive");
+    if (workspace_bytes < mi_upsample_softce_2grid_workspace(B, hd, wd, K, H, W))
+        return mi_set_error(MI_ENOMEM, "mi_upsample_softce_2grid: workspace too small");
+    const Axis ay = make_axis(hd, H, d_align_corners), ax = make_axis(wd, W, d_align_corners);
+    const Axis sy = make_axis(hs, H, seg_align_corners), sx = make_axis(ws, W, seg_align_corners);
+    const int K2 = 2 * K, jt_cols = softce2_cols(wd, W, K2), tiles = (wd + jt_cols - 1) / jt_cols;
+    float* partial = (float*)workspace;
+    float* tmp = dd_low ? (float*)((char*)workspace + softce2_partial_bytes(B, wd, H)) : nullptr;
+    const size_t lds = ((size_t)NB * K2 + NB + 256 + (JT2 + 4) + (size_t)(JT2 + 2) * K2) * 4;
+    static std::atomic<uint64_t> lds_set[2];
+    mi_allow_dynamic_lds((const void*)softce2_pass1_kernel<19>, MI_LDS_MAX, lds_set[0]);
+    mi_allow_dynamic_lds((const void*)softce2_pass1_kernel<0>, MI_LDS_MAX, lds_set[1]);
+    if (K == 19)
+        hipLaunchKernelGGL(softce2_pass1_kernel<19>, dim3(tiles, H, B), dim3(256), lds, (hipStream_t)stream, seg_low, sy, sx, inv_temperature, clip,
+                           d_low, ldD, domain, partial, tmp, K, ay, ax, jt_cols);
+    else
+        hipLaunchKernelGGL(softce2_pass1_kernel<0>, dim3(tiles, H, B), dim3(256), lds, (hipStream_t)stream, seg_low, sy, sx, inv_temperature, clip,
+                           d_low, ldD, domain, partial, tmp, K, ay, ax, jt_cols);
+    MI_CHECK_LAUNCH("mi_upsample_softce_2grid pass1");
+    const float count = (float)B * (float)H * (float)W;
+    hipLaunchKernelGGL(softce_finalize_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const float*)partial, B * H * tiles, count, loss_out);
+    MI_CHECK_LAUNCH("mi_upsample_softce_2grid finalize");
+    if (dd_low) {
+        if (ldD > K2) {
+            hipError_t e = hipMemsetAsync(dd_low, 0, (size_t)B * hd * wd * ldD * sizeof(float), (hipStream_t)stream);
+            if (e != hipSuccess) return mi_set_error(MI_EHIP, "mi_upsample_softce_2grid: memset: %s", hipGetErrorString(e));
+        }
+        hipLaunchKernelGGL(softce_pass2_kernel, dim3(nblk((long)B * hd * wd * K2, 256)), dim3(256), 0, (hipStream_t)stream, (const float*)tmp, dd_low,
+                           B, K2, ldD, ay, wd, grad_scale / count);
+        MI_CHECK_LAUNCH("mi_upsample_softce_2grid pass2");
     }
     return MI_OK;
 }

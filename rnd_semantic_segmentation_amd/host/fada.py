@@ -153,6 +153,28 @@ class _DiscSoftLossFn(torch.autograd.Function):
         return (dx,) + (None,) * (len(ctx.needs_input_grad) - 1)
 
 
+class _DiscSoftLossGridsFn(_DiscSoftLossFn):
+    """_DiscSoftLossFn with the segmentation logits on their own grid and convention (mi_upsample_softce_2grid): gald_fada.py:96-121, where
+    the soft labels come from linear2 at 1/4 resolution (align_corners=False) and the discriminator sees HarDNet's 1/32-resolution features
+    (align_corners=True)."""
+
+    @staticmethod
+    def forward(ctx, x, seg_low, eng, domain, size, weight, temperature, aligns, *params):
+        train = any(ctx.needs_input_grad)
+        eng.prepare(train)
+        dlow, saved = eng.forward(x, save=train)
+        loss_out, dd = K.upsample_softce_2grid(seg_low, dlow, size, domain, temperature, 0.9, want_grad=train, grad_scale=weight,
+                                               seg_align_corners=aligns[0], d_align_corners=aligns[1])
+        ctx.eng, ctx.saved, ctx.dd = eng, saved, dd
+        return loss_out[0] * weight
+
+    @staticmethod
+    def backward(ctx, gout):
+        dx = ctx.eng.backward(ctx.saved, ctx.dd * gout, ctx.needs_input_grad[0], any(ctx.needs_input_grad[8:]))
+        ctx.saved = ctx.dd = None
+        return (dx,) + (None,) * (len(ctx.needs_input_grad) - 1)
+
+
 class PixelDiscriminator(nn.Module):
     """discriminator.py:31-50.  state_dict keys D.0.{weight,bias}, D.2.{weight,bias}, cls1.*, cls2.*"""
 
@@ -207,13 +229,27 @@ class PixelDiscriminator(nn.Module):
         return _DiscSoftLossFn.apply(self._nhwc(x), seg, self._engine, int(domain), tuple(int(s) for s in size), float(weight),
                                      float(temperature), *self._engine._params())
 
+    def soft_loss_grids(self, x, seg_low, domain, size, weight=1.0, temperature=1.8, seg_align_corners=False, align_corners=True):
+        """soft_loss with the segmentation logits on their own grid and convention: seg_low [B,K,hs,ws] (detached) upsampled with
+        seg_align_corners, this discriminator's logits on x's grid with align_corners (GaldFada, gald_fada.py:96-121: linear2 at 1/4 resolution
+        with align_corners=False, D on HarDNet's 1/32 features with align_corners=True), one fused kernel (mi_upsample_softce_2grid)."""
+        _require_gpu(x, "PixelDiscriminator")
+        self.ensure_flat()
+        seg = seg_low.detach().permute(0, 2, 3, 1).contiguous().float()
+        return _DiscSoftLossGridsFn.apply(self._nhwc(x), seg, self._engine, int(domain), tuple(int(s) for s in size), float(weight),
+                                          float(temperature), (bool(seg_align_corners), bool(align_corners)), *self._engine._params())
+
 
 def build_adversarial_discriminator(cfg, num_features=None, mid_nc=256):
-    """core/models/build.py:33-53 (resnet branch)."""
+    """core/models/build.py:33-53 (resnet branch: 2048 features; hardnet branch: 1024, HarDNet-68's 1/32-resolution output for GaldFada)."""
     _, backbone_name = cfg.MODEL.NAME.split("_")
-    if not backbone_name.startswith("resnet"):
-        raise NotImplementedError("backbone %r: only the resnet family is on the MI355X hot path" % backbone_name)
-    return PixelDiscriminator(2048 if num_features is None else num_features, mid_nc, num_classes=cfg.MODEL.NUM_CLASSES)
+    if backbone_name.startswith("resnet"):
+        nf = 2048
+    elif backbone_name.startswith("hardnet"):
+        nf = 1024
+    else:
+        raise NotImplementedError("backbone %r: only the resnet and hardnet families are on the MI355X hot path" % backbone_name)
+    return PixelDiscriminator(nf if num_features is None else num_features, mid_nc, num_classes=cfg.MODEL.NUM_CLASSES)
 
 
 class FusedAdam(torch.optim.Adam):

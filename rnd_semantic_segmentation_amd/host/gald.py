@@ -109,16 +109,18 @@ class _GaldRun(_Run):
         self.record(back)
         return ov
 
-    def ce_head(self, low, labels, ignore_index):
+    def ce_head(self, low, labels, ignore_index, inv_t=None):
         """criterion(F.interpolate(low, size=labels.shape[-2:], mode="bilinear"), labels) (gcpa_cc2.py:78-81 + gald_trainer.py:76-79) fused: the
-        full-resolution logits are never written; d loss / d low comes out of the same pass."""
-        loss_out, dlow = K.upsample_ce(low.t, labels, want_grad=self.rec, ignore_index=ignore_index, align_corners=False)
+        full-resolution logits are never written; d loss / d low comes out of the same pass.  inv_t: criterion(out.div(T), labels) of
+        gald_fada.py:85-88 as the same kernel on low * (1 / T) - bilinear upsampling is linear, so scaling before it is scaling after it."""
+        src = low.t if inv_t is None else low.t * inv_t
+        loss_out, dlow = K.upsample_ce(src, labels, want_grad=self.rec, ignore_index=ignore_index, align_corners=False)
         _count_bad_labels(self.net, loss_out)
         ov = self.var(loss_out[0].clone())
 
         def back():
             if ov.g is not None:
-                _acc(low, dlow * ov.g, True)
+                _acc(low, dlow * (ov.g if inv_t is None else ov.g * inv_t), True)
                 ov.g = None
         self.record(back)
         return ov
@@ -271,6 +273,7 @@ class GCPAEncoder(_Engine):
     defaults unless a checkpoint is loaded."""
     RUN = _GaldRun
     PAD_IMAGE = True
+    SPARSE_OUTPUT_GRADS = True    # GaldFada's target pass: a gradient on feats[3] alone (the discriminator's input), no zero planes for the other three
 
     def __init__(self):
         super().__init__()
@@ -358,8 +361,10 @@ def _cca_units(prefix, c):
 
 
 class GCPADecoder(_Engine):
-    """gcpa_cc2.py:25-83.  forward(x, feats) -> (out5, out4, out3, out2): class logits [B,19,H,W] fp32 (NCHW-shaped views of NHWC memory)."""
+    """gcpa_cc2.py:25-83.  forward(x, feats) -> (out5, out4, out3, out2): class logits [B,19,H,W] fp32 (NCHW-shaped views of NHWC memory).
+    GaldFada's entries: loss() (the source loss on out2 alone) and low2() (the target logits, no tape)."""
     RUN = _GaldRun
+    SPARSE_OUTPUT_GRADS = True    # outputs no loss reached give their heads no gradient (gald_fada.py: out5/4/3 carry none, their .grad stays None)
 
     def __init__(self, num_classes=19, c=256):
         super().__init__()
@@ -390,6 +395,13 @@ class GCPADecoder(_Engine):
         o4 = run.tap("fam45", _fam_block(run, self._fam["fam45"], c, f4, top, run.tap("lam4", _local_attention(run, ctx, self._lam[4]))))
         o3 = run.tap("fam34", _fam_block(run, self._fam["fam34"], c, f3, o4, run.tap("lam3", _local_attention(run, ctx, self._lam[3]))))
         o2 = run.tap("fam23", _fam_block(run, self._fam["fam23"], c, f2, o3, run.tap("lam2", _local_attention(run, ctx, self._lam[2]))))
+        out2 = self.__dict__.get("_out2")
+        if out2 is not None:            # GaldFada: linear2 alone - linear5/4/3 feed nothing there and hold no BatchNorm
+            low2 = run.tap("linear2", run.conv_bias(o2, self._lin[2]))
+            self.last_low = low2.t.detach().permute(0, 3, 1, 2)
+            if out2 == "low":
+                return [low2]
+            return [run.ce_head(low2, self._ce_labels, self._ce_ignore, inv_t=out2)]
         lows = [run.tap("linear%d" % i, run.conv_bias(v, self._lin[i])) for i, v in ((5, top), (4, o4), (3, o3), (2, o2))]
         labels = self.__dict__.get("_ce_labels")
         if labels is not None:                                                                 # the trainer's fused path: four scalar losses
@@ -408,6 +420,29 @@ class GCPADecoder(_Engine):
             return super().forward(x, *feats)
         finally:
             self._ce_labels = None
+
+    def loss(self, x, feats, label, ignore_index=255, temperature=1.0):
+        """criterion(self(x, feats)[-1].div(temperature), label) of gald_fada.py:80-88 fused: out2 alone (linear5/4/3 are not run and get no
+        gradient), upsampled with align_corners=False and cross-entropy in one pass on linear2 * (1 / temperature) - the same kernel as losses():
+        bilinear upsampling is linear, so dividing the low-resolution logits divides the upsampled ones.  Leaves the 1/4-resolution linear2 logits
+        [B,K,h,w] fp32 (detached, before the division) in `self.last_low`."""
+        self._ce_labels, self._ce_ignore = label.long().contiguous(), int(ignore_index)
+        self._out2 = 1.0 / float(temperature)
+        try:
+            return super().forward(x, *feats)
+        finally:
+            self._ce_labels = self._out2 = None
+
+    def low2(self, x, feats):
+        """The 1/4-resolution linear2 logits [B,K,h,w] fp32 (NCHW-shaped view of NHWC memory) without a tape, in the module's mode: in train() the
+        BatchNorm layers normalise with batch statistics and update their running statistics, as the reference's target forward does
+        (gald_fada.py:94-96; its out2 only feeds detached soft labels).  Also left in `self.last_low`."""
+        self._out2 = "low"
+        try:
+            with torch.no_grad():
+                return super().forward(x, *feats)
+        finally:
+            self._out2 = None
 
 
 # ------------------------------------------------------------------------------------------------ the building blocks as stand-alone modules

@@ -731,6 +731,7 @@ class _Engine(nn.Module):
     one flat fp32 buffer for them and one for their gradients (engine.FlatStore), every conv's bf16 operands packed by ONE table-driven
     launch when a weight changed, BatchNorm buffers as views of one buffer."""
     RUN = _Run          # the tape class a module's graph is written against (host/gald.py extends it)
+    SPARSE_OUTPUT_GRADS = False         # True: outputs without a gradient reach backward() as None instead of zero tensors (host/gald.py)
 
     def _register(self, order):
         """order: _Unit objects and (key, tensor) pairs (parameters that belong to no conv: an unused classifier head, a scalar gate), in the
@@ -941,6 +942,8 @@ class _EngineFn(torch.autograd.Function):
         rec = any(ctx.needs_input_grad[2:]) and getattr(net, "_grad_mode", True)
         run, ins, outs = net._run(xs, rec, in_needs)
         ctx.run, ctx.ins, ctx.outs, ctx.n_in, ctx.in_dtypes = run, ins, outs, n_in, [x.dtype for x in xs]
+        if net.SPARSE_OUTPUT_GRADS:
+            ctx.set_materialize_grads(False)          # an output no loss reached keeps no gradient (its producer's backward is skipped), not zeros
         return tuple(o.t.permute(0, 3, 1, 2) if o.t.dim() == 4 else o.t for o in outs)          # NCHW-shaped views of NHWC memory (or scalars: losses)
 
     @staticmethod
@@ -1070,14 +1073,22 @@ class FlatAdam(torch.optim.Adam):
     """torch.optim.Adam(lr) over the module's flat parameter buffer with `clip_gradient(optimizer, clip)` (core/utils/utils.py:6-16) fused in:
     ONE launch per step (mi_adam_step_clamped) instead of one per tensor.  torch's state_dict format (per-parameter exp_avg / exp_avg_sq are
     views of the flat moment buffers).  Parameters the backward pass never writes (Res2Net's unused fc) keep a zero gradient: their moments
-    stay zero and they do not move, like the reference's (whose fc.grad is None)."""
+    stay zero and they do not move, like the reference's (whose fc.grad is None).
 
-    def __init__(self, net, lr, grad_clamp=None):
+    `skip_unwritten` (opt-in, default False): a parameter that no backward pass wrote since zero_grad() is skipped entirely - its value,
+    exp_avg, exp_avg_sq and its own `step` stay as they are, what torch.optim.Adam does for `p.grad is None`.  That matters once such a
+    parameter has non-zero moments (GaldFada resumed from a GALD checkpoint: linear5/4/3 get no gradient there, and a zero-gradient update
+    would keep moving them).  Steps are then counted per parameter (state_dict carries them); the written ones are updated with one launch
+    per run of consecutive parameters that share a step count."""
+
+    def __init__(self, net, lr, grad_clamp=None, skip_unwritten=False):
         self.net = net
         super().__init__(net.parameters(), lr)
         self.grad_clamp = grad_clamp
+        self.skip_unwritten = skip_unwritten
         self._m = self._v = None
         self._steps = 0
+        self._psteps = None              # {id(p): step} when the parameters' counts may differ (skip_unwritten, or loaded that way)
         self.device_hyper = None         # 6-float device tensor (lr, beta1, beta2, eps, clamp, step): HIP-graph mode
 
     def set_device_hyper(self, enable=True):
@@ -1103,14 +1114,19 @@ class FlatAdam(torch.optim.Adam):
         st = self.net.ensure_flat()
         if self._m is None or self._m.numel() != st.data.numel() or self._m.device != st.data.device:
             self._m, self._v = torch.zeros_like(st.data), torch.zeros_like(st.data)
+            loaded = {}
             for p in st.params:
                 s = self.state[p]
                 if "exp_avg" in s:                                   # restored by load_state_dict: adopt
                     self._m[p._mi_off:p._mi_off + p.numel()].copy_(s["exp_avg"].reshape(-1))
                     self._v[p._mi_off:p._mi_off + p.numel()].copy_(s["exp_avg_sq"].reshape(-1))
-                    self._steps = int(s["step"])
+                    loaded[id(p)] = int(s["step"])
                 s["exp_avg"] = self._m[p._mi_off:p._mi_off + p.numel()].view_as(p)
                 s["exp_avg_sq"] = self._v[p._mi_off:p._mi_off + p.numel()].view_as(p)
+            if loaded:
+                self._steps = max(loaded.values())
+                if len(set(loaded.values())) > 1 or len(loaded) != len(st.params):
+                    self._psteps = {id(p): loaded.get(id(p), 0) for p in st.params}
         return st
 
     @torch.no_grad()
@@ -1119,7 +1135,10 @@ class FlatAdam(torch.optim.Adam):
         g = self.param_groups[0]
         if g.get("amsgrad") or g.get("weight_decay", 0) != 0 or g.get("maximize"):
             raise NotImplementedError("FlatAdam implements the reference's configuration (pranet_trainer.py:20)")
+        if self.skip_unwritten:
+            return self._step_written(st, g)
         self._steps += 1
+        self._psteps = None
         # a backward pass that never reached this module (detached features, a loss that bypasses it) ran no zero_stale(): the previous pass's gradients
         # would still sit in the flat buffer and be applied.  Cleared here: what torch's zero_grad(set_to_none=False) leaves (a no-op after a normal pass)
         st.zero_stale()
@@ -1132,7 +1151,38 @@ class FlatAdam(torch.optim.Adam):
             K.adam_step(st.data, st.grad, self._m, self._v, g["lr"], g["betas"][0], g["betas"][1], g["eps"], self._steps, grad_clamp=self.grad_clamp)
         st.generation += 1
 
+    def _step_written(self, st, g):
+        """skip_unwritten: Adam on the parameters the backward passes since zero_grad() wrote, each with its own step count."""
+        if self.device_hyper is not None:
+            raise NotImplementedError("FlatAdam: skip_unwritten has per-parameter step counts; the graph mode keeps one on the device")
+        if self._psteps is None:
+            self._psteps = {id(p): self._steps for p in st.params}
+        self._steps += 1
+        runs = []                                                       # [lo, hi, step]: consecutive written parameters, one step count
+        for p in st.params:
+            if id(p) not in st.written:
+                runs.append(None)
+                continue
+            n = self._psteps[id(p)] = self._psteps[id(p)] + 1
+            lo, hi = p._mi_off, p._mi_off + p.numel()
+            if runs and runs[-1] is not None and runs[-1][2] == n:
+                runs[-1][1] = hi                                        # (alignment gaps between them: zero gradient, zero moments, unchanged)
+            else:
+                runs.append([lo, hi, n])
+        for r in runs:
+            if r is not None:
+                lo, hi, n = r
+                K.adam_step(st.data[lo:hi], st.grad[lo:hi], self._m[lo:hi], self._v[lo:hi], g["lr"], g["betas"][0], g["betas"][1], g["eps"], n,
+                            grad_clamp=self.grad_clamp)
+        st.generation += 1
+
     def state_dict(self):
+        if self._psteps is not None:                                   # per-parameter counts
+            for p in self.net._store.params:
+                s = self.state[p]
+                if "exp_avg" in s:
+                    s["step"] = torch.tensor(float(self._psteps[id(p)]))
+            return super().state_dict()
         step_t = torch.tensor(float(self._steps))                      # (graph replays advance the count without running step())
         for p, s in self.state.items():
             if "exp_avg" in s:

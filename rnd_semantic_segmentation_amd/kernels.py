@@ -517,6 +517,28 @@ def upsample_softce(seg_low, d_low, size, domain, temperature=1.8, clip=0.9, wan
     return out, dd
 
 
+def upsample_softce_2grid(seg_low, d_low, size, domain, temperature=1.8, clip=0.9, want_grad=True, grad_scale=1.0, seg_align_corners=False,
+                          d_align_corners=True):
+    """upsample_softce with the two operands on their own grids: seg_low [B,hs,ws,K] fp32 (detached) upsampled with seg_align_corners,
+    d_low [B,hd,wd,ldD] fp32 (first 2K used) with d_align_corners, both to `size` (GaldFada: 1/4 and 1/32 resolution).
+    Returns (loss_out[2], dd_low or None)."""
+    _chk(seg_low, torch.float32, "seg_low")
+    _chk(d_low, torch.float32, "d_low")
+    B, hs, ws, Kc = seg_low.shape
+    Bd, hd, wd, ldD = d_low.shape
+    if Bd != B:
+        raise _lib.MiError("upsample_softce_2grid: seg_low holds %d images, d_low %d" % (B, Bd))
+    H, W = size
+    L = _lib.lib()
+    ws_buf = _workspace(L.mi_upsample_softce_2grid_workspace(B, hd, wd, Kc, H, W), seg_low.device, "softce2")
+    out = torch.empty(2, dtype=torch.float32, device=seg_low.device)
+    dd = torch.empty_like(d_low) if want_grad else None
+    check(L.mi_upsample_softce_2grid(_p(seg_low), hs, ws, int(bool(seg_align_corners)), 1.0 / float(temperature), float(clip), _p(d_low), hd, wd,
+                                     ldD, int(bool(d_align_corners)), int(domain), float(grad_scale), _p(out), _p(dd), B, Kc, H, W, _p(ws_buf),
+                                     ws_buf.numel(), _stream()), "mi_upsample_softce_2grid")
+    return out, dd
+
+
 def adam_step(p, g, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, step, grad_clamp=None):
     for t, n in ((p, "p"), (g, "g"), (exp_avg, "exp_avg"), (exp_avg_sq, "exp_avg_sq")):
         _chk(t, torch.float32, n)

@@ -1,6 +1,6 @@
 """Adversarial (FADA) training entry point: same flags as the reference's train_adv.py:62-105
 (`-cfg FILE [--local_rank N] KEY VAL ...`) plus `--model` (the reference hard-codes main("gald_fada", ...) at :105 although
-the DeepLab YAMLs need "aspp_fada").  Source and target loaders each carry BATCH_SIZE // 2 images (train_adv.py:29,39),
+the DeepLab YAMLs need "aspp_fada"; `--model gald_fada -cfg configs/gald_adv.yaml` is the reference's default run).  Source and target loaders each carry BATCH_SIZE // 2 images (train_adv.py:29,39),
 the target set is repeated 9x (:17).  Under torchrun (WORLD_SIZE > 1) it runs data-parallel over RCCL."""
 import argparse
 import os
@@ -25,9 +25,14 @@ def main(name, cfg, local_rank):
         return torch.utils.data.DataLoader(data, batch_size=per_rank, shuffle=sampler is None, num_workers=4, pin_memory=True,
                                            collate_fn=collate, sampler=sampler, drop_last=True)
 
-    if name != "aspp_fada":
-        raise NotImplementedError("combo %r: only 'aspp_fada' (DeepLabV2-ResNet + ASPP + FADA) is on the MI355X hot path" % name)
-    AsppFada(name, cfg, loader(src, build_collate_fn(cfg)), loader(tgt, None), local_rank).train()
+    if name == "aspp_fada":
+        combo = AsppFada
+    elif name == "gald_fada":                                # what the reference's train_adv.py:105 runs (HarDNet-68 + GCPA decoder + FADA)
+        from rnd_semantic_segmentation_amd.host.gald_fada import GaldFada
+        combo = GaldFada
+    else:
+        raise NotImplementedError("combo %r: 'aspp_fada' (DeepLabV2-ResNet + ASPP + FADA) and 'gald_fada' (GALD + FADA) are on the MI355X hot path" % name)
+    combo(name, cfg, loader(src, build_collate_fn(cfg)), loader(tgt, None), local_rank).train()
 
 
 if __name__ == "__main__":
