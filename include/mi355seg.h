@@ -209,6 +209,27 @@ int mi_upsample_ce_ex(const float* low, const int64_t* labels, float* loss_out /
  * probs [B][K][H][W] fp32; pred (optional, may be NULL) [B][H][W] uint8 argmax (first max wins). */
 int mi_upsample_softmax(const float* low, float* probs, uint8_t* pred, int B, int h, int w, int K, int H, int W, void* stream);
 
+/* ---- multi-scale, flip-averaged inference tail (multi_scale_inference, utility.py:193-209) in one kernel ---------
+ * probs [K][H][W] fp32 = ((p_0 + p_1 + ... + p_{n-1}) / div_a) / div_b, where p_i = softmax_k(bilinear_align_corners(low_i -> H x W)),
+ * read at column W-1-x when src[i].mirror is set (the reference's pred.flip(3)).  src is a HOST array of n sources, 1 <= n <= 16, copied by
+ * value into the kernel arguments (no device table, no extra copy); each low is one image's [h][w][K] fp32 NHWC logits; K <= 32.
+ * Arithmetic contract (the reference adds materialised fp32 tensors):
+ *  - every p_i[k] is a rounded fp32 product before it is added: no fused multiply-add between the softmax and the sum;
+ *  - the sum runs left to right in source order; the two divisions are true divisions in that order (output / len(scales) / 2);
+ *    div_b == 1 skips the second;
+ *  - a mirrored source is evaluated AT output column W-1-x with the same source-index arithmetic as an unmirrored one (not through an
+ *    algebraically mirrored coordinate, which rounds differently);
+ *  - the per-source interpolation + softmax is the device code of mi_upsample_softmax: n = 1, mirror = 0, div_a = div_b = 1 is bit-equal to it.
+ * The only mandatory traffic is the one write of K*H*W*4 bytes (two floats per lane when W is even and probs is 8-byte aligned). */
+typedef struct { const float* low; int h, w; int mirror; } MiProbSource;
+int mi_upsample_softmax_multi(const MiProbSource* src, int n, float* probs, int K, int H, int W, float div_a, float div_b, void* stream);
+
+/* ---- input side of multi-scale evaluation: F.interpolate(x, (Ho, Wo), mode='bilinear', align_corners=True) (utility.py:197) ----
+ * x [B][C][H][W] fp32 NCHW (the loader's layout, what mi_stem_f32 consumes) -> out [B*(1+with_mirror)][C][Ho][Wo].  with_mirror != 0:
+ * image b's horizontally mirrored copy (torch.flip(resized, [3]), utility.py:204: the mirror of the RESIZED image) is written as image B + b
+ * in the same launch, bit-equal to the mirror of image b.  Ho == H && Wo == W reproduces the input bit for bit. */
+int mi_image_resize_ac(const float* x, float* out, int B, int C, int H, int W, int Ho, int Wo, int with_mirror, void* stream);
+
 /* ---- optimiser: torch.optim.SGD(momentum, weight_decay) on flat fp32 buffers (aspp_trainer.py:25-26,94-95)
  * g' = g + wd*p; buf = mu*buf + g'; p -= lr*buf  (buf zero-initialised == torch's first-step buf = g'). */
 int mi_sgd_step(float* p, const float* g, float* buf, size_t n, float lr, float momentum, float weight_decay, void* stream);

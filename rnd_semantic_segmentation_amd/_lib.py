@@ -47,6 +47,8 @@ SIGNATURES = {
     "mi_upsample_ce": (I, [P, P, P, P] + [I] * 7 + [F, P, Z, P]),
     "mi_upsample_ce_ex": (I, [P, P, P, P] + [I] * 7 + [F, I, P, Z, P]),
     "mi_upsample_softmax": (I, [P, P, P] + [I] * 6 + [P]),
+    "mi_upsample_softmax_multi": (I, [P, I, P, I, I, I, F, F, P]),
+    "mi_image_resize_ac": (I, [P, P] + [I] * 7 + [P]),
     "mi_stem_pool_fwd": (I, [P, P, P, P, P] + [I] * 6 + [P]),
     "mi_stem_pool_bwd": (I, [P, P, P, P] + [I] * 6 + [P]),
     "mi_stem_im2col": (I, [P, P] + [I] * 6 + [P]),
@@ -123,6 +125,11 @@ SIGNATURES = {
     "mi_gcca_f32": (I, [P, L, P, L, P, L, P, L] + [I] * 5 + [P]),
     "mi_gpoint_f32": (I, [I, P, L, P, L, P, P, I, P, L, L, I, P]),
 }
+
+class MiProbSource(ctypes.Structure):
+    """One source of mi_upsample_softmax_multi (include/mi355seg.h): low [h][w][K] fp32 NHWC on the device, mirror flag."""
+    _fields_ = [("low", c_void_p), ("h", c_int), ("w", c_int), ("mirror", c_int)]
+
 
 _lib = None
 

@@ -24,7 +24,7 @@ from .. import _lib
 from .. import gk
 from .. import kernels as K
 from . import arch
-from .metrics import AverageMeter, adjust_learning_rate, confusion_matrix, dump_json, intersectionAndUnionGPU
+from .metrics import AverageMeter, adjust_learning_rate, confusion_matrix, dump_json, intersectionAndUnionGPU, require_single_scale
 from .plugin import BaseTrainer
 from .pranet import FlatAdam, _acc, _Engine, _grad_target, _Run, _rup32, _tile_route, _Unit
 
@@ -642,6 +642,7 @@ class GALDTester:
     [K, K] like aspp_tester.py:53 and `trainid2name` is an optional constructor argument (class indices as names when absent)."""
 
     def __init__(self, cfg, device, test_loader, logger, palette, saveres=False, trainid2name=None):
+        require_single_scale(cfg, "GALDTester")
         self.cfg, self.logger, self.test_loader, self.device = cfg, logger, test_loader, device
         self.palette, self.saveres, self.trainid2name = palette, saveres, trainid2name
         self.encoder = GCPAEncoder()

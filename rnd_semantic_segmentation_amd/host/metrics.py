@@ -9,6 +9,9 @@ Differences that are deliberate and documented:
  * strip_prefix_if_present works when the prefix is present (the reference forgets to import
    OrderedDict, utility.py:167).
  * inference() runs the upsample + softmax tail in one HIP kernel (mi_upsample_softmax).
+ * multi_scale_inference() on the engine runs one resize (+ mirror) launch and one backbone + head pass per scale, then ONE kernel
+   (mi_upsample_softmax_multi) that interpolates every low-resolution logit map, takes the softmax, sums in the reference's order and
+   divides: the result is written once instead of being accumulated through full-size tensors.
 """
 import json
 import logging
@@ -182,6 +185,63 @@ def inference(feature_extractor, classifier, image, label, flip=True):
     else:
         out = probs[0]
     return out.unsqueeze(dim=0)
+
+
+def multi_scale_plan(size, flip=True, scales=(0.7, 1.0, 1.3)):
+    """What multi_scale_inference (utility.py:193-209) computes for an input of `size` (H, W), as data:
+    (sizes, sources, divisors).  sizes[i] = (int(H * s_i), int(W * s_i)) with Python floats (:197); sources = [(i, mirrored)] in
+    the order the reference adds them (s0, s0 mirrored, s1, ...); divisors = (len(scales), 2 if flip else 1) applied in that order
+    (`output / len(scales) / 2`, :207-209)."""
+    scales = list(scales)
+    if not scales:
+        raise ValueError("multi_scale_inference needs at least one scale")
+    H, W = int(size[0]), int(size[1])
+    sizes = [(int(H * s), int(W * s)) for s in scales]
+    if any(h < 1 or w < 1 for h, w in sizes):
+        raise ValueError("scales %r leave no pixels of a %dx%d input" % (scales, H, W))
+    sources = [(i, m) for i in range(len(scales)) for m in ((False, True) if flip else (False,))]
+    return sizes, sources, (len(scales), 2 if flip else 1)
+
+
+def multi_scale_inference(feature_extractor, classifier, image, label, flip=True, scales=[0.7, 1.0, 1.3]):
+    """utility.py:193-209: inference(flip=False) of the image resized (bilinear, align_corners) to every scale and, with flip, of its
+    horizontal mirror (prediction mirrored back), averaged; [1,K,H,W] fp32 for image 0 at the LABEL's size."""
+    sizes, sources, (div_a, div_b) = multi_scale_plan(image.shape[-2:], flip, scales)
+    if hasattr(classifier, "predict_probs_multi") and image.is_cuda:
+        from .. import kernels
+        x0 = image[:1].float().contiguous()                 # inference() keeps image 0 only (utility.py:190)
+        with torch.no_grad():
+            feats = [feature_extractor(kernels.image_resize_ac(x0, hw, with_mirror=flip)) for hw in sizes]     # batch 1 or 2 per scale
+            mirrors = [(False, True) if flip else (False,)] * len(sizes)
+            return classifier.predict_probs_multi(feats, mirrors, tuple(label.shape[-2:]), (div_a, div_b))
+    # a substituted / foreign classifier or CPU tensors: the reference's literal composition
+    interpolate = torch.nn.functional.interpolate
+    resized, output = {}, None
+    for i, mirrored in sources:
+        if i not in resized:
+            resized[i] = interpolate(image, size=sizes[i], mode="bilinear", align_corners=True)
+        pred = inference(feature_extractor, classifier, torch.flip(resized[i], [3]) if mirrored else resized[i], label, flip=False)
+        if mirrored:
+            pred = pred.flip(3)
+        output = pred if output is None else output + pred
+    output = output / div_a
+    return output / div_b if flip else output
+
+
+def tta_settings(cfg):
+    """(scales, flip) of cfg.TEST (SCALES / FLIP are not reference keys; absent = the defaults (1.0,) / False = plain inference())."""
+    scales = tuple(cfg.TEST.SCALES) if "SCALES" in cfg.TEST else (1.0,)
+    flip = bool(cfg.TEST.FLIP) if "FLIP" in cfg.TEST else False
+    return scales, flip
+
+
+def require_single_scale(cfg, who):
+    """The reference defines multi-scale evaluation for a (feature extractor, classifier) pair only: other testers refuse the keys
+    rather than ignore them."""
+    scales, flip = tta_settings(cfg)
+    if scales != (1.0,) or flip:
+        raise NotImplementedError("%s: TEST.SCALES %r / TEST.FLIP %r - multi-scale, flip-averaged evaluation exists for the DeepLab "
+                                  "(feature extractor, classifier) pair only (ASPPTester); leave both at their defaults" % (who, scales, flip))
 
 
 # ----------------------------------------------------------------------------- io / logging

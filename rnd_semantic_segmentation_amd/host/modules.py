@@ -254,6 +254,27 @@ class ASPP_Classifier_V2(nn.Module):
             probs, _ = kernels.upsample_softmax(low, tuple(int(s) for s in size), want_pred=False)
         return probs
 
+    def predict_probs_multi(self, feats, mirrors, size, divisors):
+        """The tail of multi_scale_inference (utility.py:193-209) in one kernel.  feats: feature maps [b,C,h,w] (one per scale, any sizes);
+        mirrors[i][j]: whether image j of feats[i] saw the horizontally mirrored input; every image is one source, in that order.
+        Returns ((p_0 + p_1 + ...) / divisors[0]) / divisors[1] as [1,K,H,W] fp32, p = softmax(interpolate(logits, size)), mirrored
+        sources mirrored back."""
+        from .. import kernels
+        lows, flags = [], []
+        with torch.no_grad():
+            for feat, mm in zip(feats, mirrors):
+                _require_gpu(feat, "ASPP_Classifier_V2")
+                if feat.shape[0] != len(mm):
+                    raise ValueError("predict_probs_multi: %d images but %d mirror flags" % (feat.shape[0], len(mm)))
+                if self.precision == "fp32":
+                    low = self._low_fp32(feat)
+                else:
+                    self._engine.prepare(False)
+                    low = self._engine.forward(self._nhwc(feat))
+                lows += list(low.unbind(0))
+                flags += list(mm)
+            return kernels.upsample_softmax_multi(lows, flags, tuple(int(s) for s in size), float(divisors[0]), float(divisors[1]))
+
 
 class CrossEntropyLoss(nn.Module):
     """torch.nn.CrossEntropyLoss(ignore_index=...) on the HIP kernel (aspp_trainer.py:61)."""

@@ -1377,6 +1377,8 @@ class PranetTester:
     {background, polyp} by which of (1 - p, p) is larger -> intersection / union meters."""
 
     def __init__(self, cfg, device, test_loader, logger):
+        from .metrics import require_single_scale
+        require_single_scale(cfg, "PranetTester")
         self.cfg, self.logger, self.test_loader, self.device = cfg, logger, test_loader, device
         self.model = PraNet()
         self.model.to(device)

@@ -6,8 +6,8 @@ import os
 import numpy as np
 import torch
 
-from .metrics import (AverageMeter, confusion_matrix, dump_json, inference, intersectionAndUnionGPU,
-                      strip_prefix_if_present)
+from .metrics import (AverageMeter, confusion_matrix, dump_json, inference, intersectionAndUnionGPU, multi_scale_inference,
+                      strip_prefix_if_present, tta_settings)
 from .modules import build_classifier, build_feature_extractor
 
 
@@ -56,10 +56,15 @@ class ASPPTester:
         self.classifier.eval()
         self.meter = AverageMeter()
         cmt = torch.zeros(num_classes, num_classes, dtype=torch.int64)
+        scales, flip = tta_settings(self.cfg)
+        single = scales == (1.0,) and not flip
         for x, y, name in self.test_loader:
             x = x.to(self.device, non_blocking=True)
             y = y.to(self.device, non_blocking=True).long()
-            output = inference(self.feature_extractor, self.classifier, x, y, flip=False)     # [1,K,H,W]
+            if single:
+                output = inference(self.feature_extractor, self.classifier, x, y, flip=False)     # [1,K,H,W]
+            else:                                          # the call aspp_tester.py:61 keeps commented out
+                output = multi_scale_inference(self.feature_extractor, self.classifier, x, y, flip=flip, scales=list(scales))
             pred = output.max(1)[1]
             if self.saveres:
                 self.save_distill(output, name)

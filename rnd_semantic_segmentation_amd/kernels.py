@@ -430,6 +430,38 @@ def upsample_softmax(low, size, want_pred=True):
     return probs, pred
 
 
+def upsample_softmax_multi(lows, mirrors, size, div_a, div_b=1.0):
+    """Multi-scale, flip-averaged inference tail in one launch: lows = per-source [h,w,K] fp32 NHWC logits (one image each, any sizes),
+    mirrors = per-source flags.  Returns ((p_0 + ... + p_{n-1}) / div_a) / div_b as [1,K,H,W] fp32, p_i = softmax(bilinear(low_i -> size)),
+    mirrored sources read at column W-1-x (reference multi_scale_inference, utility.py:193-209)."""
+    n = len(lows)
+    if not 1 <= n <= 16 or len(mirrors) != n:
+        raise _lib.MiError("upsample_softmax_multi: 1..16 sources with one mirror flag each (got %d / %d)" % (n, len(mirrors)))
+    K = lows[0].shape[-1]
+    src = (_lib.MiProbSource * n)()
+    for i, (low, m) in enumerate(zip(lows, mirrors)):
+        _chk(low, torch.float32, "lows[%d]" % i)
+        if low.dim() != 3 or low.shape[-1] != K or low.device != lows[0].device:
+            raise _lib.MiError("lows[%d] must be [h,w,%d] on %s, got %s on %s" % (i, K, lows[0].device, tuple(low.shape), low.device))
+        src[i].low, src[i].h, src[i].w, src[i].mirror = low.data_ptr(), low.shape[0], low.shape[1], int(bool(m))
+    H, W = size
+    probs = torch.empty((1, K, H, W), dtype=torch.float32, device=lows[0].device)
+    check(_lib.lib().mi_upsample_softmax_multi(ctypes.cast(src, ctypes.c_void_p), n, _p(probs), K, H, W, float(div_a), float(div_b),
+                                               _stream()), "mi_upsample_softmax_multi")
+    return probs
+
+
+def image_resize_ac(x, size, with_mirror=False):
+    """F.interpolate(x, size, mode='bilinear', align_corners=True) on [B,C,H,W] fp32 NCHW; with_mirror appends torch.flip(resized, [3]) of
+    image b as image B + b (one launch)."""
+    _chk(x, torch.float32, "x")
+    B, C, H, W = x.shape
+    Ho, Wo = size
+    out = torch.empty((B * (2 if with_mirror else 1), C, Ho, Wo), dtype=torch.float32, device=x.device)
+    check(_lib.lib().mi_image_resize_ac(_p(x), _p(out), B, C, H, W, Ho, Wo, int(bool(with_mirror)), _stream()), "mi_image_resize_ac")
+    return out
+
+
 def stem_pool_fwd(y, scale, shift):
     """y [B,Hc,Wc,C] bf16 (conv1 output) -> (pool [B,Hp,Wp,C] bf16, idx uint8): FrozenBN + ReLU + maxpool 3x3/2/1."""
     _chk(y, torch.bfloat16, "y")

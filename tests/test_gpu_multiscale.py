@@ -1,0 +1,223 @@
+"""GPU side of multi-scale, flip-averaged evaluation: mi_image_resize_ac, mi_upsample_softmax_multi (csrc/upsample_ce.hip) and
+multi_scale_inference / ASPPTester on the engine against the reference's own output (tests/golden/g14_*, written by
+tools/make_multiscale_golden.py).  Parity is claimed in fp32 precision; the mask / metric rule is tests/_multiscale.py's."""
+import logging
+import os
+
+import numpy as np
+import pytest
+import torch
+import torch.nn.functional as F
+
+import _multiscale as ms
+from rnd_semantic_segmentation_amd.host import synth
+
+pytestmark = pytest.mark.gpu
+
+K = None
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _kern():
+    global K
+    assert torch.cuda.is_available(), "GPU tests need a GPU"
+    from rnd_semantic_segmentation_amd import kernels
+    K = kernels
+    yield
+
+
+# ------------------------------------------------------------------------------------------------ mi_image_resize_ac
+@pytest.mark.parametrize("shape,size", [((1, 3, 129, 129), (90, 90)), ((1, 3, 129, 129), (167, 167)), ((1, 3, 512, 1024), (358, 716)),
+                                        ((1, 3, 512, 1024), (665, 1331)), ((2, 3, 65, 97), (45, 67)), ((2, 3, 65, 97), (84, 126))])
+def test_image_resize_ac_vs_torch_cpu_and_mirrored_half(shape, size):
+    x = synth.synth_image(shape[0], shape[2], shape[3], seed=81)
+    xt = torch.from_numpy(x).cuda()
+    want = F.interpolate(torch.from_numpy(x), size=size, mode="bilinear", align_corners=True).numpy()
+    got = K.image_resize_ac(xt, size)
+    assert got.shape == want.shape
+    e = ms.rel(got.cpu().numpy(), want)
+    print("image_resize_ac %s -> %s: %.2e of max" % (shape, size, e))
+    assert e < 2.6e-7                                        # 3x the measured 8.7e-8 (largest of the six cases: 7.5e-8 .. 8.7e-8)
+    both = K.image_resize_ac(xt, size, with_mirror=True)
+    B = shape[0]
+    assert both.shape == (2 * B,) + want.shape[1:]
+    assert torch.equal(both[:B], got)
+    assert torch.equal(both[B:], torch.flip(got, [3]))       # same registers stored twice: bit-equal mirrors
+
+
+def test_image_resize_ac_identity_is_bit_equal():
+    x = synth.synth_image(2, 65, 97, seed=82)
+    x[0, 0, 0, :4] = [-0.0, 0.0, 1e-40, -1e30]              # signed zero, a denormal, a large value
+    xt = torch.from_numpy(x).cuda()
+    both = K.image_resize_ac(xt, (65, 97), with_mirror=True)
+    assert np.array_equal(both[:2].cpu().numpy().view(np.uint32), x.view(np.uint32))
+    assert np.array_equal(both[2:].cpu().numpy().view(np.uint32), x[..., ::-1].view(np.uint32))
+
+
+# ------------------------------------------------------------------------------------------------ mi_upsample_softmax_multi
+def _lows(Kc, sizes, tag):
+    return [torch.from_numpy((synth.uniform("msk.%s.%d" % (tag, i), (h, w, Kc)) * 6).astype(np.float32)).cuda() for i, (h, w) in enumerate(sizes)]
+
+
+@pytest.mark.parametrize("Kc,hw,size", [(19, (17, 17), (129, 129)), (19, (65, 129), (512, 1024)), (2, (9, 13), (77, 150)), (32, (9, 13), (33, 151))])
+def test_multi_single_source_is_bit_equal_to_upsample_softmax(Kc, hw, size):
+    low = _lows(Kc, [hw], "one")[0]
+    want, _ = K.upsample_softmax(low[None], size, want_pred=False)
+    got = K.upsample_softmax_multi([low], [False], size, 1.0, 1.0)
+    assert got.shape == want.shape and torch.equal(got, want)
+
+
+SIX = [(9, 13), (17, 22), (12, 19), (25, 31), (5, 7), (21, 40)]       # six different source sizes, two of them larger than a small output
+
+
+@pytest.mark.parametrize("size", [(77, 150), (77, 151), (33, 64), (15, 30)])
+@pytest.mark.parametrize("Kc", [2, 19, 32])
+def test_multi_six_sources_bit_equal_to_composition(Kc, size):
+    """The no-contraction and ordering rules: one launch == six mi_upsample_softmax launches, flips, adds in source order and two true
+    divisions in torch on the GPU (division by a one-element TENSOR: by a Python scalar torch multiplies by the reciprocal)."""
+    lows = _lows(Kc, SIX, "six%d" % Kc)
+    mirrors = [False, True, False, True, False, True]
+    out = None
+    for low, m in zip(lows, mirrors):
+        p, _ = K.upsample_softmax(low[None], size, want_pred=False)
+        p = p.flip(3) if m else p
+        out = p if out is None else out + p
+    want = out / torch.tensor([3.0], device="cuda") / torch.tensor([2.0], device="cuda")
+    got = K.upsample_softmax_multi(lows, mirrors, size, 3.0, 2.0)
+    nd = int((got != want).sum())
+    print("multi n=6 K=%d %s: %d of %d values differ from the composition (max |d| %.1e)" % (Kc, size, nd, want.numel(), (got - want).abs().max().item()))
+    assert torch.equal(got, want)
+    # div_b == 1: the second division is skipped
+    want1 = (out / torch.tensor([3.0], device="cuda"))
+    assert torch.equal(K.upsample_softmax_multi(lows, mirrors, size, 3.0, 1.0), want1)
+
+
+def _f64_probs(low, size, mirror):
+    """softmax(bilinear align_corners) in float64 on the CPU, mirrored back when asked."""
+    h, w, _ = low.shape
+    H, W = size
+    a = low.astype(np.float64)
+
+    def axis(n_in, n_out):
+        f = np.arange(n_out, dtype=np.float64) * ((n_in - 1) / (n_out - 1) if n_out > 1 else 0.0)
+        i0 = np.minimum(np.floor(f).astype(np.int64), n_in - 1)
+        return i0, np.minimum(i0 + 1, n_in - 1), f - i0
+
+    y0, y1, ly = axis(h, H)
+    x0, x1, lx = axis(w, W)
+    ly, lx = ly[:, None, None], lx[None, :, None]
+    v = (1 - ly) * ((1 - lx) * a[y0][:, x0] + lx * a[y0][:, x1]) + ly * ((1 - lx) * a[y1][:, x0] + lx * a[y1][:, x1])
+    e = np.exp(v - v.max(2, keepdims=True))
+    p = np.transpose(e / e.sum(2, keepdims=True), (2, 0, 1))
+    return p[:, :, ::-1] if mirror else p
+
+
+@pytest.mark.parametrize("Kc,size", [(19, (77, 150)), (32, (77, 151))])
+def test_multi_six_sources_vs_float64(Kc, size):
+    lows = _lows(Kc, SIX, "f64%d" % Kc)
+    mirrors = [False, True, False, True, False, True]
+    want = sum(_f64_probs(low.cpu().numpy(), size, m) for low, m in zip(lows, mirrors)) / 3 / 2
+    got = K.upsample_softmax_multi(lows, mirrors, size, 3.0, 2.0)[0].cpu().numpy()
+    e = ms.rel(got, want)
+    print("multi n=6 K=%d %s vs float64: %.2e of max" % (Kc, size, e))
+    assert e < 7.1e-6                                        # 3x the measured 2.37e-6 (K = 32; K = 19: 2.09e-6): __expf's own error
+    assert abs(got.sum(0) - 1).max() < 1e-5                  # an average of distributions is one
+
+
+def test_multi_refuses_bad_arguments():
+    from rnd_semantic_segmentation_amd._lib import MiError
+    lows = _lows(19, [(5, 7)] * 17, "bad")
+    with pytest.raises(MiError):
+        K.upsample_softmax_multi(lows, [False] * 17, (33, 33), 3.0)
+    with pytest.raises(MiError):
+        K.upsample_softmax_multi([], [], (33, 33), 3.0)
+    with pytest.raises(MiError, match="zero divisor"):
+        K.upsample_softmax_multi(lows[:2], [False, True], (33, 33), 0.0)
+
+
+# ------------------------------------------------------------------------------------------------ whole nets
+@pytest.fixture(scope="module")
+def r101():
+    from rnd_semantic_segmentation_amd.host import modules
+    fe = modules.resnet_feature_extractor("resnet101", freeze_bn=True, pretrained_backbone=False)
+    cls = modules.ASPP_Classifier_V2(2048, [6, 12, 18, 24], [6, 12, 18, 24], 19)
+    synth.load_formula_weights(fe)
+    synth.load_formula_weights(cls)
+    return fe.cuda().eval().set_precision("fp32"), cls.cuda().eval().set_precision("fp32")
+
+
+# measured max error of the probability crop (of the crop's max), per case; the bar is 3x that
+R101_MEASURED = {("129", False): 3.42e-7, ("129", True): 3.30e-7, ("161x225", False): 1.29e-6, ("161x225", True): 8.58e-7,
+                 ("512x1024", False): 8.52e-7, ("512x1024", True): 7.29e-7}
+
+
+@pytest.mark.parametrize("flip", [False, True])
+@pytest.mark.parametrize("name", sorted(ms.R101_CASES))
+def test_r101_multi_scale_fp32_probabilities_masks_and_miou_equal_reference(r101, name, flip):
+    from core.utils.utility import multi_scale_inference
+    fe, cls = r101
+    hw, seed = ms.R101_CASES[name]
+    g = ms.load("g14_r101_%s_%s" % (name, ms.flip_tag(flip)))
+    x, lab = ms.inputs(hw, seed)
+    probs = multi_scale_inference(fe, cls, torch.from_numpy(x).cuda(), torch.from_numpy(lab).cuda(), flip=flip, scales=[0.7, 1.0, 1.3])
+    assert probs.shape == (1, 19) + hw and probs.dtype == torch.float32
+    y0, y1, x0, x1 = [int(v) for v in g["crop"]]
+    e = ms.rel(probs[0, :, y0:y1, x0:x1].cpu().numpy(), g["probs_crop"])
+    what = "r101@%s multi-scale %s" % (name, ms.flip_tag(flip))
+    print("%s: probabilities %.2e of max" % (what, e))
+    assert e < 3 * R101_MEASURED[(name, flip)]
+    pred = probs.max(1)[1]
+    flips = ms.mask_parity(pred.cpu().numpy().astype(np.uint8), g, what)
+    ms.eval_parity(pred, lab, g, flips, what)
+
+
+def _tester(tmp_path, *opts):
+    from core.configs import cfg as global_cfg
+    from core.datasets.build import build_dataset
+    from core.testers.aspp_tester import ASPPTester
+    cfg = global_cfg.clone()
+    cfg.defrost()
+    cfg.merge_from_list(["MODEL.FREEZE_BN", True, "MODEL.NUM_CLASSES", 19, "OUTPUT_DIR", str(tmp_path), "INPUT.INPUT_SIZE_TEST", (161, 97)] + list(opts))
+    os.environ["MI_SYNTH_LEN"] = "2"
+    try:
+        data = build_dataset(cfg, mode="test", is_source=False)
+        loader = torch.utils.data.DataLoader(data, batch_size=1, shuffle=False)
+        tester = ASPPTester(cfg, torch.device("cuda"), loader, logging.getLogger("t"), [0] * 768, {i: str(i) for i in range(19)})
+    finally:
+        os.environ.pop("MI_SYNTH_LEN", None)
+    synth.load_formula_weights(tester.feature_extractor)
+    synth.load_formula_weights(tester.classifier)
+    return cfg, loader, tester
+
+
+def test_aspp_tester_multi_scale_end_to_end(tmp_path):
+    """ASPPTester with TEST.SCALES / TEST.FLIP: its confusion matrix is the one accumulated from direct multi_scale_inference calls, and differs
+    from the single-scale matrix (the keys are not ignored)."""
+    from core.utils.utility import inference, multi_scale_inference
+    from rnd_semantic_segmentation_amd.host import metrics
+    cfg, loader, tester = _tester(tmp_path, "TEST.SCALES", "(0.7, 1.0, 1.3)", "TEST.FLIP", "True")
+    assert tester.classifier.precision == "fp32"
+    cmt = tester.test()
+    want = torch.zeros(19, 19, dtype=torch.int64)
+    single = torch.zeros(19, 19, dtype=torch.int64)
+    for xb, yb, _ in loader:
+        xb, yb = xb.cuda(), yb.cuda().long()
+        p = multi_scale_inference(tester.feature_extractor, tester.classifier, xb, yb, flip=True, scales=[0.7, 1.0, 1.3])
+        want += metrics.confusion_matrix(cfg, p.max(1)[1].flatten(), yb[:1].flatten())
+        s = inference(tester.feature_extractor, tester.classifier, xb, yb, flip=False)
+        single += metrics.confusion_matrix(cfg, s.max(1)[1].flatten(), yb[:1].flatten())
+    assert torch.equal(cmt, want) and int(want.sum()) > 0
+    assert not torch.equal(cmt, single)
+
+
+def test_aspp_tester_multi_scale_bf16_runs(tmp_path):
+    """TEST.PRECISION bf16: the training engine under the same tail; finite, a distribution over classes (no parity claim)."""
+    from core.utils.utility import multi_scale_inference
+    cfg, loader, tester = _tester(tmp_path, "TEST.SCALES", "(0.7, 1.0, 1.3)", "TEST.FLIP", "True", "TEST.PRECISION", "bf16")
+    assert tester.classifier.precision == "bf16" and tester.feature_extractor.precision == "bf16"
+    cmt = tester.test()
+    assert int(cmt.sum()) > 0
+    xb, yb, _ = next(iter(loader))
+    p = multi_scale_inference(tester.feature_extractor.eval(), tester.classifier.eval(), xb.cuda(), yb.cuda().long(), flip=True, scales=[0.7, 1.0, 1.3])
+    assert p.shape == (1, 19) + tuple(yb.shape[-2:]) and bool(torch.isfinite(p).all())
+    assert (p.sum(1) - 1).abs().max().item() < 1e-5
