@@ -534,6 +534,47 @@ int mi_gcca_f32(const float* q, long ldq, const float* k, long ldk, const float*
 int mi_gpoint_f32(int op, const float* a, long lda, const float* b, long ldb, const float* scale, const float* shift, int act, float* out, long ldo, long M, int C,
                   void* stream);
 
+/* ---- the `aspp` input transform of a batch (csrc/augment.hip) ------------------------------------------------------------------------------
+ * Replaces the per-image CPU transform of core/components/augment.py:87-120 / core/datasets/transform.py (ColorJitter, Resize | RandomScale +
+ * RandomCrop(pad_if_needed), RandomHorizontalFlip, ToTensor, Normalize, through PIL) for decoded uint8 images; the results equal PIL's bit for
+ * bit.  Everything random or derived is decided by the host (host/augment.py) and arrives as one MiAugSample per image; images of a batch may
+ * differ in size.  A fixed number of launches per batch whatever B is.
+ *
+ * Byte buffers (img, jit, tmp): 4-byte aligned, readable / writable up to their size rounded up to a multiple of 16.
+ *   jit: H*W*3 bytes (only when n_ops > 0).  tmp: (ry1 - ry0) * tstride bytes, tstride = 12 * ceil((cx1 - cx0) / 4) (only when sw != W).
+ * Geometry: the image is resampled to sh x sw (PIL BICUBIC: horizontal pass, then vertical, each rounding to uint8; a pass whose size does not
+ * change is skipped and its table pointers are NULL); output pixel (y, x) shows resampled pixel (y + off_y, xm + off_x), xm = flip ? out_w-1-x : x,
+ * or the fill (image 0, label 255) outside - off_* = crop offset minus padding.  [cy0,cy1) x [cx0,cx1) is the part of the resampled image
+ * the output shows, [ry0,ry1) x [rx0,rx1) the source rows / columns those need.  Tables: hcoef [hk][sw], vcoef [vk][sh] fixed point with 22
+ * fraction bits, tap-major; hbound [sw][2], vbound [sh][2] = {first source index, taps}.  The label is gathered from the nearest source pixel
+ * (PIL NEAREST) of a lab_sh x lab_sw resample with the same off / flip and mapped through lab_table.
+ * ops: 1 brightness, 2 contrast, 3 saturation, 4 hue (torchvision ColorJitter on uint8 RGB), applied in order; factor[i] is the blend factor,
+ * for hue the amount already as int(f * 255) mod 256 in hue_shift.  grey_sum must be 0 on entry (the contrast op's exact integer sum). */
+typedef struct MiAugSample {
+    const uint8_t* img;       /* [H][W][3] decoded RGB */
+    const uint8_t* lab;       /* [H][W] label ids, NULL: no label */
+    uint8_t* jit;
+    uint8_t* tmp;
+    const int32_t* hcoef;
+    const int32_t* hbound;
+    const int32_t* vcoef;
+    const int32_t* vbound;
+    unsigned long long grey_sum;
+    int32_t H, W, sh, sw, hk, vk;
+    int32_t off_y, off_x, flip;
+    int32_t cy0, cy1, cx0, cx1, ry0, ry1, rx0, rx1, tstride;
+    int32_t lab_sh, lab_sw;
+    int32_t n_ops, op[4], hue_shift;
+    float factor[4];
+    int32_t to_bgr255;
+    float mean[3], std[3];
+    uint8_t lab_table[256];
+} MiAugSample;
+/* table_dev: the B records in device memory (written by the launches: grey_sum); table_host: the same records, read here to validate them and
+ * to size the launches.  out_img [B][3][out_h][out_w] fp32, out_lab [B][lab_h][lab_w] fp32 (NULL when no sample has a label). */
+int mi_augment_batch(void* table_dev, const void* table_host, int B, int out_h, int out_w, int lab_h, int lab_w, float* out_img, float* out_lab,
+                     void* stream);
+
 #ifdef __cplusplus
 }
 #endif

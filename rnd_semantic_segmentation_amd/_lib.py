@@ -124,11 +124,24 @@ SIGNATURES = {
     "mi_gdwconv_f32": (I, [P, L, P, P, P, P, I, P, L] + [I] * 8 + [P]),
     "mi_gcca_f32": (I, [P, L, P, L, P, L, P, L] + [I] * 5 + [P]),
     "mi_gpoint_f32": (I, [I, P, L, P, L, P, P, I, P, L, L, I, P]),
+    "mi_augment_batch": (I, [P, P, I, I, I, I, I, P, P, P]),
 }
 
 class MiProbSource(ctypes.Structure):
     """One source of mi_upsample_softmax_multi (include/mi355seg.h): low [h][w][K] fp32 NHWC on the device, mirror flag."""
     _fields_ = [("low", c_void_p), ("h", c_int), ("w", c_int), ("mirror", c_int)]
+
+
+class MiAugSample(ctypes.Structure):
+    """One image of mi_augment_batch (include/mi355seg.h): buffers, geometry, colour ops, normalisation, label table."""
+    _fields_ = [("img", c_void_p), ("lab", c_void_p), ("jit", c_void_p), ("tmp", c_void_p), ("hcoef", c_void_p), ("hbound", c_void_p),
+                ("vcoef", c_void_p), ("vbound", c_void_p), ("grey_sum", ctypes.c_uint64),
+                ("H", c_int), ("W", c_int), ("sh", c_int), ("sw", c_int), ("hk", c_int), ("vk", c_int),
+                ("off_y", c_int), ("off_x", c_int), ("flip", c_int),
+                ("cy0", c_int), ("cy1", c_int), ("cx0", c_int), ("cx1", c_int), ("ry0", c_int), ("ry1", c_int), ("rx0", c_int), ("rx1", c_int),
+                ("tstride", c_int), ("lab_sh", c_int), ("lab_sw", c_int),
+                ("n_ops", c_int), ("op", c_int * 4), ("hue_shift", c_int), ("factor", c_float * 4),
+                ("to_bgr255", c_int), ("mean", c_float * 3), ("std", c_float * 3), ("lab_table", ctypes.c_uint8 * 256)]
 
 
 _lib = None

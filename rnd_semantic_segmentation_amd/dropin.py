@@ -41,6 +41,9 @@ ALIASES = {
     "core.models.classifiers.gcpacc.contextagg.ccnet": _PKG + "gald",         # CrissCrossAttention (ccnet.py:37-127)
     "core.models.classifiers.gcpacc.contextagg.GALDNet": _PKG + "gald",       # LocalAttenModule (GALDNet.py:124-157)
     "core.datasets.build": _PKG + "data",                             # core/datasets/build.py:5-30
+    "core.datasets.dataset_path_catalog": _PKG + "datasets",          # core/datasets/dataset_path_catalog.py (DatasetCatalog)
+    "core.datasets.gta5": _PKG + "datasets",                          # GTA5FoldDataSet
+    "core.datasets.cityscapes": _PKG + "datasets",                    # cityscapesDataSet, cityscapesSelfDistillDataSet
     "base.base_trainer": _PKG + "plugin",                             # base/base_trainer.py
     "base.base_model": _PKG + "plugin",                               # base/base_model.py
 }

@@ -1,9 +1,10 @@
 """Dataset surface: `build_dataset(cfg, mode, is_source)` / `build_collate_fn(cfg)` with the reference's
-signatures (core/datasets/build.py:5-30), backed by a synthetic generator.
+signatures (core/datasets/build.py:5-30).
 
-The reference's loaders read GTA5 / Cityscapes from disk through PIL/cv2/albumentations
-(core/datasets/*.py, core/components/augment.py) - none of that data or those packages exist here, and
-BASELINE.json's configs are defined on synthetic crops.  What is kept is the TENSOR CONTRACT of the loader
+GTA5 / Cityscapes are read from disk when DATASETS.DATASET_DIR holds them (host/datasets.py decodes, csrc/augment.hip runs the `aspp`
+transform on the batch).  Everything else - a synthetic dataset name, the polyp / kvasir names (their transforms need albumentations),
+a dataset directory that does not exist - is backed by a synthetic generator, on which BASELINE.json's configs are defined.
+Both keep the TENSOR CONTRACT of the loader
 (core/datasets/transform.py:31-46, cityscapes.py:137-151, defaults.py:21-24):
     image  float32 [3,H,W], RGB/255 then (x-mean)/std   (here: unit-variance noise of that shape)
     label  float32 [H,W] with train-ids 0..K-1 and 255 = ignore
@@ -66,8 +67,19 @@ class SyntheticPolyp(Dataset):
 def build_collate_fn(cfg):
     """core/datasets/build.py:5-13.  The reference's collate functions (core/datasets/func.py: attn_collate_fn, the missing pranet_collate_fn)
     turn numpy HWC images from disk into tensors; the synthetic datasets here already yield the tensors of the loader contract, so the
-    default collation applies for every value of AUG.COLLATE ("attn" is the default of defaults.py and what the PraNet YAML inherits)."""
+    default collation applies for every value of AUG.COLLATE ("attn" is the default of defaults.py and what the PraNet YAML inherits).  The
+    datasets read from disk are batched by host/datasets.DeviceAugmentLoader, which brings its own collation."""
     return None
+
+
+def real_dataset_root(cfg, name):
+    """The directory a GTA5 / Cityscapes dataset name reads, when it exists; None for every name and configuration that gets the synthetic data."""
+    from .datasets import DatasetCatalog
+    name = str(name)
+    if "polyp" in name or "kvasir" in name or not ("gta5" in name or "cityscapes" in name) or not cfg.DATASETS.DATASET_DIR:
+        return None
+    root = DatasetCatalog.root(cfg, name)
+    return root if root is not None and os.path.isdir(root) else None
 
 
 def build_dataset(cfg, mode="train", is_source=True):
@@ -75,4 +87,13 @@ def build_dataset(cfg, mode="train", is_source=True):
     name = cfg.DATASETS.SOURCE_TRAIN if (mode == "train" and is_source) else (cfg.DATASETS.TARGET_TRAIN if mode == "train" else cfg.DATASETS.TEST)
     if "polyp" in str(name) or "kvasir" in str(name):           # dataset_path_catalog.py:36-51,99-106
         return SyntheticPolyp(cfg, mode)
-    return SyntheticSegmentation(cfg, mode, is_source)
+    if real_dataset_root(cfg, name) is None:
+        return SyntheticSegmentation(cfg, mode, is_source)
+    if cfg.AUG.NAME != "aspp":
+        raise ValueError("AUG.NAME %r: datasets read from disk are transformed by the 'aspp' transform only (the reference's other transforms need "
+                         "albumentations); set AUG.NAME to 'aspp' or point DATASETS.DATASET_DIR away from %s" % (cfg.AUG.NAME, real_dataset_root(cfg, name)))
+    from .augment import AugmentSpec
+    from .datasets import DatasetCatalog
+    split = mode if mode != "test" else str(cfg.DATASETS.TEST).split("_")[-1]          # build.py:28
+    return DatasetCatalog.get(cfg, name, split, num_classes=cfg.MODEL.NUM_CLASSES, transform=AugmentSpec.from_cfg(cfg, mode, is_source),
+                              cross_val=cfg.DATASETS.CROSS_VAL)

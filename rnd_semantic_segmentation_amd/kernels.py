@@ -797,3 +797,24 @@ def maxpool_f32(y):
     pool = torch.empty((B, (Hc - 1) // 2 + 1, (Wc - 1) // 2 + 1, C), dtype=torch.float32, device=y.device)
     check(_lib.lib().mi_maxpool_f32(_p(y), _p(pool), B, Hc, Wc, C, _stream()), "mi_maxpool_f32")
     return pool
+
+
+def augment_batch(table_dev, table_host, B, out_img, out_lab=None):
+    """The `aspp` input transform of a batch (include/mi355seg.h, mi_augment_batch): table_dev / table_host hold the same B MiAugSample
+    records at their start (device copy, pinned or pageable host copy; host/augment.py builds them), out_img [B,3,h,w] fp32 and
+    out_lab [B,lh,lw] fp32 receive the loader contract's tensors.  Enqueued on the current stream."""
+    _chk(out_img, torch.float32, "out_img")
+    if not table_dev.is_cuda or table_host.is_cuda or table_dev.dtype != torch.uint8 or table_host.dtype != torch.uint8:
+        raise _lib.MiError("augment_batch: table_dev is a uint8 device tensor and table_host its uint8 host copy")
+    need = B * ctypes.sizeof(_lib.MiAugSample)
+    if table_dev.numel() < need or table_host.numel() < need or out_img.dim() != 4 or out_img.shape[0] != B or out_img.shape[1] != 3:
+        raise _lib.MiError("augment_batch: %d records need %d bytes of table, out_img must be [%d,3,h,w]" % (B, need, B))
+    lh = lw = 0
+    if out_lab is not None:
+        _chk(out_lab, torch.float32, "out_lab")
+        if out_lab.dim() != 3 or out_lab.shape[0] != B:
+            raise _lib.MiError("augment_batch: out_lab must be [%d,lh,lw]" % B)
+        lh, lw = out_lab.shape[1], out_lab.shape[2]
+    check(_lib.lib().mi_augment_batch(_p(table_dev), _p(table_host), B, out_img.shape[2], out_img.shape[3], lh, lw, _p(out_img), _p(out_lab),
+                                      _stream()), "mi_augment_batch")
+    return out_img, out_lab

@@ -8,6 +8,7 @@ from core.configs import cfg
 from core.datasets.build import build_collate_fn, build_dataset
 from core.testers.aspp_tester import ASPPTester
 from core.utils.utility import load_json, setup_logger
+from rnd_semantic_segmentation_amd.host.datasets import has_device_transform, wrap_loader
 
 device = torch.device("cuda" if torch.cuda.is_available() else "cpu")
 
@@ -18,8 +19,8 @@ def test(cfg, config, args):
     logger.info("#" * 20 + " Start Testing " + "#" * 20)
     logger.info("INPUT_SIZE_TEST: {}".format(cfg.INPUT.INPUT_SIZE_TEST))
     data = build_dataset(cfg, mode="test", is_source=False)
-    loader = torch.utils.data.DataLoader(data, batch_size=cfg.TEST.BATCH_SIZE, shuffle=False, num_workers=2, pin_memory=True,
-                                         collate_fn=build_collate_fn(cfg), sampler=None)
+    loader = wrap_loader(data, batch_size=cfg.TEST.BATCH_SIZE, shuffle=False, num_workers=8 if has_device_transform(data) else 2, pin_memory=True,
+                         collate_fn=build_collate_fn(cfg), sampler=None)
     if name.startswith("pranet"):                            # reference test.py:35-36
         from core.testers.pranet_tester import PranetTester
         tester = PranetTester(cfg, device, loader, logger)

@@ -12,6 +12,7 @@ from torch.utils.data import ConcatDataset
 from core.combos.aspp_fada import AsppFada
 from core.configs import cfg
 from core.datasets.build import build_collate_fn, build_dataset
+from rnd_semantic_segmentation_amd.host.datasets import has_device_transform, run_trainer, wrap_loader
 
 
 def main(name, cfg, local_rank):
@@ -22,8 +23,9 @@ def main(name, cfg, local_rank):
 
     def loader(data, collate):
         sampler = torch.utils.data.distributed.DistributedSampler(data, shuffle=True, drop_last=True) if world > 1 else None
-        return torch.utils.data.DataLoader(data, batch_size=per_rank, shuffle=sampler is None, num_workers=4, pin_memory=True,
-                                           collate_fn=collate, sampler=sampler, drop_last=True)
+        # (datasets read from disk: 8 decode workers per loader, 16 per process; the transform runs on the GPU)
+        return wrap_loader(data, batch_size=per_rank, shuffle=sampler is None, num_workers=8 if has_device_transform(data) else 4, pin_memory=True,
+                           collate_fn=collate, sampler=sampler, drop_last=True)
 
     if name == "aspp_fada":
         combo = AsppFada
@@ -32,7 +34,8 @@ def main(name, cfg, local_rank):
         combo = GaldFada
     else:
         raise NotImplementedError("combo %r: 'aspp_fada' (DeepLabV2-ResNet + ASPP + FADA) and 'gald_fada' (GALD + FADA) are on the MI355X hot path" % name)
-    combo(name, cfg, loader(src, build_collate_fn(cfg)), loader(tgt, None), local_rank).train()
+    src_loader, tgt_loader = loader(src, build_collate_fn(cfg)), loader(tgt, None)
+    run_trainer(combo(name, cfg, src_loader, tgt_loader, local_rank), src_loader, tgt_loader)
 
 
 if __name__ == "__main__":

@@ -10,23 +10,25 @@ import torch.distributed as dist
 from core.configs import cfg
 from core.datasets.build import build_collate_fn, build_dataset
 from core.trainers.aspp_trainer import ASPPTrainer
+from rnd_semantic_segmentation_amd.host.datasets import has_device_transform, run_trainer, wrap_loader
 
 
 def main(name, cfg, local_rank):
     world = dist.get_world_size() if dist.is_initialized() else 1
     data = build_dataset(cfg, mode="train", is_source=True)
     sampler = torch.utils.data.distributed.DistributedSampler(data, shuffle=True, drop_last=True) if world > 1 else None
-    loader = torch.utils.data.DataLoader(
-        data, batch_size=max(1, cfg.SOLVER.BATCH_SIZE // world), shuffle=sampler is None, num_workers=4, pin_memory=True,
-        collate_fn=build_collate_fn(cfg), sampler=sampler, drop_last=True)
+    # a dataset read from disk (DATASETS.DATASET_DIR) is decoded by up to 16 workers and transformed on the GPU; the synthetic ones keep the plain loader
+    loader = wrap_loader(
+        data, batch_size=max(1, cfg.SOLVER.BATCH_SIZE // world), shuffle=sampler is None, num_workers=16 if has_device_transform(data) else 4,
+        pin_memory=True, collate_fn=build_collate_fn(cfg), sampler=sampler, drop_last=True)
     if name == "aspp":
-        ASPPTrainer(name, cfg, loader, local_rank).train()
+        run_trainer(ASPPTrainer(name, cfg, loader, local_rank), loader)
     elif name == "pranet":                                   # reference train_src.py:29-30
         from core.trainers.pranet_trainer import PraNetTrainer
-        PraNetTrainer(name, cfg, loader, local_rank).train()
+        run_trainer(PraNetTrainer(name, cfg, loader, local_rank), loader)
     elif name == "gald":                                     # reference train_src.py:33-34 (what run.sh launches)
         from core.trainers.gald_trainer import GALDTrainer
-        GALDTrainer(name, cfg, loader, local_rank).train()
+        run_trainer(GALDTrainer(name, cfg, loader, local_rank), loader)
     else:
         raise NotImplementedError("model %r: 'aspp' (DeepLabV2-ResNet + ASPP), 'pranet' and 'gald' are on the MI355X engine" % name)
 
