@@ -224,6 +224,25 @@ int mi_upsample_softmax(const float* low, float* probs, uint8_t* pred, int B, in
 typedef struct { const float* low; int h, w; int mirror; } MiProbSource;
 int mi_upsample_softmax_multi(const MiProbSource* src, int n, float* probs, int K, int H, int W, float div_a, float div_b, void* stream);
 
+/* ---- evaluation tail without the probability map: masks, pseudo-labels and scores in one kernel ---------
+ * Per output pixel the K fp32 values are exactly those mi_upsample_softmax_multi writes (one shared device function; same sources, divisors
+ * and arithmetic contract; n = 1, div_a = div_b = 1 is the single-scale tail).  Instead of storing them the kernel writes
+ *   pred   [H][W] uint8: the LOWEST class index among their maxima (torch.max(dim) / numpy.argmax of the probability map - not the argmax of
+ *          the logits: exp and the products can round two different logits to one probability);
+ *   pseudo [H][W] uint8 or NULL: max >= threshold ? pred : 255;
+ * and, when labels [H][W] int64 is given, ADDS to counts (int64, K*K + 3K cells, zeroed by the caller; two launches into one buffer add up)
+ * the integers host/metrics.py derives from pred:
+ *   counts[gt*K + pd]          confusion matrix, label gt != 255 and 0 <= gt < K            (confusion_matrix)
+ *   counts[K*K + k]            area_intersection: pred == label == k, label != ignore_index (intersectionAndUnionGPU)
+ *   counts[K*K + K + k]        area_output: pred == k where label != ignore_index
+ *   counts[K*K + 2K + k]       area_target: label == k
+ * The counts never depend on threshold.  Counting runs in a per-workgroup LDS table of 32-bit counters (a workgroup sees at most 512 pixels),
+ * flushed with one 64-bit global atomic add per non-zero cell: integer sums, bit-reproducible.
+ * Refused before launch: n outside 1..16, K outside 1..32, NULL pred, labels without counts or counts without labels, ignore_index inside
+ * [0, K), threshold outside [0, 1], a zero divisor. */
+int mi_upsample_predict_score(const MiProbSource* src, int n, int K, int H, int W, float div_a, float div_b, const int64_t* labels,
+                              int ignore_index, float threshold, uint8_t* pred, uint8_t* pseudo, int64_t* counts, void* stream);
+
 /* ---- input side of multi-scale evaluation: F.interpolate(x, (Ho, Wo), mode='bilinear', align_corners=True) (utility.py:197) ----
  * x [B][C][H][W] fp32 NCHW (the loader's layout, what mi_stem_f32 consumes) -> out [B*(1+with_mirror)][C][Ho][Wo].  with_mirror != 0:
  * image b's horizontally mirrored copy (torch.flip(resized, [3]), utility.py:204: the mirror of the RESIZED image) is written as image B + b

@@ -400,19 +400,11 @@ __device__ __forceinline__ float add_rounded_product(float acc, float a, float b
     return acc + p;
 }
 
-// Waves per SIMD the register budget is held to.  A pixel has 4 x K corner loads in flight besides the P x K sums: one pixel per lane runs at
-// 4 waves, two pixels per lane (8-byte stores, 512 contiguous bytes per wave and class plane) at 2.  Four pixels per lane spill.  No variant here does.
-template <int KT, int P>
-__global__ __launch_bounds__(256, P == 1 ? 4 : 2) void upsample_softmax_multi_kernel(ProbSrcs srcs, int n, float* __restrict__ probs, int Krt, int H, int W,
-                                                                     float div_a, float div_b) {
-    const int K = KT > 0 ? KT : Krt;
-    constexpr int KR = KT > 0 ? KT : KMAX;
-    static_assert(P == 1 || P == 2, "one or two pixels per lane");
-    const int WP = W / P;                                  // P == 2 only when W is even
-    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= (long)H * WP) return;
-    const int xb = (int)(idx % WP) * P, y = (int)(idx / WP);
-    float acc[P][KR];
+// The per-pixel arithmetic of the multi-scale tails, shared by the probability kernel and the predict-and-score kernel so that the two cannot
+// drift apart: acc[p][k] = ((p_0 + ... + p_{n-1}) / div_a) / div_b for the P pixels (y, xb .. xb+P-1), summed in source order from rounded
+// products, with true divisions (the second one skipped when div_b == 1).
+template <int KR, int P>
+__device__ __forceinline__ void multi_probs(const ProbSrcs& srcs, int n, int K, int W, int y, int xb, float div_a, float div_b, float (&acc)[P][KR]) {
 #pragma unroll
     for (int p = 0; p < P; ++p)
 #pragma unroll
@@ -432,21 +424,129 @@ __global__ __launch_bounds__(256, P == 1 ? 4 : 2) void upsample_softmax_multi_ke
             __builtin_amdgcn_sched_barrier(0);      // one pixel's loads at a time: interleaving the P pixels costs P times the registers
         }
     }
+#pragma unroll
+    for (int k = 0; k < KR; ++k) {
+        if (k < K) {
+#pragma unroll
+            for (int p = 0; p < P; ++p) {
+                acc[p][k] = acc[p][k] / div_a;
+                if (div_b != 1.f) acc[p][k] = acc[p][k] / div_b;
+            }
+        }
+    }
+}
+
+// Waves per SIMD the register budget is held to.  A pixel has 4 x K corner loads in flight besides the P x K sums: one pixel per lane runs at
+// 4 waves, two pixels per lane (8-byte stores, 512 contiguous bytes per wave and class plane) at 2.  Four pixels per lane spill.  No variant here does.
+template <int KT, int P>
+__global__ __launch_bounds__(256, P == 1 ? 4 : 2) void upsample_softmax_multi_kernel(ProbSrcs srcs, int n, float* __restrict__ probs, int Krt, int H, int W,
+                                                                     float div_a, float div_b) {
+    const int K = KT > 0 ? KT : Krt;
+    constexpr int KR = KT > 0 ? KT : KMAX;
+    static_assert(P == 1 || P == 2, "one or two pixels per lane");
+    const int WP = W / P;                                  // P == 2 only when W is even
+    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= (long)H * WP) return;
+    const int xb = (int)(idx % WP) * P, y = (int)(idx / WP);
+    float acc[P][KR];
+    multi_probs<KR, P>(srcs, n, K, W, y, xb, div_a, div_b, acc);
     float* o = probs + (long)y * W + xb;
 #pragma unroll
     for (int k = 0; k < KR; ++k) {
         if (k < K) {
-            float r[P];
-#pragma unroll
-            for (int p = 0; p < P; ++p) {
-                r[p] = acc[p][k] / div_a;
-                if (div_b != 1.f) r[p] = r[p] / div_b;
-            }
             float* ok = o + (long)k * H * W;
             if constexpr (P == 2)
-                *reinterpret_cast<float2*>(ok) = make_float2(r[0], r[1]);                  // W even and probs 8-byte aligned (the launcher checks)
+                *reinterpret_cast<float2*>(ok) = make_float2(acc[0][k], acc[1][k]);        // W even and probs 8-byte aligned (the launcher checks)
             else
-                ok[0] = r[0];
+                ok[0] = acc[0][k];
+        }
+    }
+}
+
+// Evaluation tail without the probability map: the same K values per pixel as upsample_softmax_multi_kernel (multi_probs), reduced in registers to
+// pred = the LOWEST class index among their maxima (torch.max(dim) / numpy.argmax), pseudo = max >= threshold ? pred : 255, and - with labels -
+// the integers host/metrics.py derives from pred.  One LDS add per pixel: cell gt * K + pd where the label gt lies in [0, K) (confusion_matrix;
+// 255 and ignore_index lie outside [0, K)), cell K * K + pd where it does not and is not ignore_index.  From these, per class k:
+//   area_intersection = cmt[k][k], area_target = row sum k, area_output = column sum k + the extra cell k.
+// A workgroup sees at most 512 pixels, so its 32-bit LDS counters cannot overflow; it flushes one 64-bit global add per non-zero cell.  Integer sums
+// do not depend on arrival order: the counts are bit-reproducible.  counts: [K*K] cmt, [K] intersection, [K] output, [K] target; added to.
+template <int KT, int P>
+__global__ __launch_bounds__(256, P == 1 ? 4 : 2) void upsample_predict_score_kernel(ProbSrcs srcs, int n, int Krt, int H, int W, float div_a, float div_b,
+                                                                     const long long* __restrict__ labels, int ignore_index, float threshold,
+                                                                     uint8_t* __restrict__ pred, uint8_t* __restrict__ pseudo,
+                                                                     unsigned long long* __restrict__ counts) {
+    const int K = KT > 0 ? KT : Krt;
+    constexpr int KR = KT > 0 ? KT : KMAX;
+    static_assert(P == 1 || P == 2, "one or two pixels per lane");
+    __shared__ unsigned tab[KR * KR + KR];
+    const int tid = threadIdx.x;
+    if (counts) {                                          // uniform over the grid
+        for (int c = tid; c < K * K + K; c += 256) tab[c] = 0u;
+        __syncthreads();
+    }
+    const int WP = W / P;                                  // P == 2 only when W is even
+    const long idx = (long)blockIdx.x * 256 + tid;
+    if (idx < (long)H * WP) {
+        const int xb = (int)(idx % WP) * P, y = (int)(idx / WP);
+        float acc[P][KR];
+        multi_probs<KR, P>(srcs, n, K, W, y, xb, div_a, div_b, acc);
+        uint8_t pd[P], ps[P];
+#pragma unroll
+        for (int p = 0; p < P; ++p) {
+            float best = acc[p][0];
+            int arg = 0;
+#pragma unroll
+            for (int k = 1; k < KR; ++k) {
+                if (k < K && acc[p][k] > best) {           // strict: the first of equal maxima stays
+                    best = acc[p][k];
+                    arg = k;
+                }
+            }
+            pd[p] = (uint8_t)arg;
+            ps[p] = best >= threshold ? (uint8_t)arg : (uint8_t)255;
+        }
+        const long o = (long)y * W + xb;
+        if constexpr (P == 2) {                            // W even: o even; pred / pseudo 2-byte, labels 16-byte aligned (the launcher checks)
+            *reinterpret_cast<uchar2*>(pred + o) = make_uchar2(pd[0], pd[1]);
+            if (pseudo) *reinterpret_cast<uchar2*>(pseudo + o) = make_uchar2(ps[0], ps[1]);
+        } else {
+            pred[o] = pd[0];
+            if (pseudo) pseudo[o] = ps[0];
+        }
+        if (counts) {
+            long long gt[P];
+            if constexpr (P == 2) {
+                const longlong2 g = *reinterpret_cast<const longlong2*>(labels + o);
+                gt[0] = g.x;
+                gt[1] = g.y;
+            } else {
+                gt[0] = labels[o];
+            }
+#pragma unroll
+            for (int p = 0; p < P; ++p) {
+                if ((unsigned long long)gt[p] < (unsigned long long)K)
+                    atomicAdd(&tab[(int)gt[p] * K + pd[p]], 1u);
+                else if (gt[p] != (long long)ignore_index)
+                    atomicAdd(&tab[K * K + pd[p]], 1u);
+            }
+        }
+    }
+    if (counts) {
+        __syncthreads();
+        for (int c = tid; c < K * K; c += 256) {
+            const unsigned v = tab[c];
+            if (v) atomicAdd(&counts[c], (unsigned long long)v);
+        }
+        if (tid < K) {
+            unsigned row = 0u, col = 0u;
+            for (int j = 0; j < K; ++j) {
+                row += tab[tid * K + j];
+                col += tab[j * K + tid];
+            }
+            const unsigned diag = tab[tid * K + tid], out = col + tab[K * K + tid];
+            if (diag) atomicAdd(&counts[K * K + tid], (unsigned long long)diag);
+            if (out) atomicAdd(&counts[K * K + K + tid], (unsigned long long)out);
+            if (row) atomicAdd(&counts[K * K + 2 * K + tid], (unsigned long long)row);
         }
     }
 }
@@ -617,6 +717,37 @@ extern "C" int mi_upsample_softmax_multi(const MiProbSource* src, int n, float* 
     }
 #undef MI_LAUNCH_MULTI
     MI_CHECK_LAUNCH("mi_upsample_softmax_multi");
+    return MI_OK;
+}
+
+extern "C" int mi_upsample_predict_score(const MiProbSource* src, int n, int K, int H, int W, float div_a, float div_b, const int64_t* labels,
+                                         int ignore_index, float threshold, uint8_t* pred, uint8_t* pseudo, int64_t* counts, void* stream) {
+    MI_REQUIRE(src && pred, "mi_upsample_predict_score: null operand");
+    MI_REQUIRE(n >= 1 && n <= MAX_PROB_SRC, "mi_upsample_predict_score: 1 <= n <= 16 sources");
+    MI_REQUIRE(K > 0 && K <= KMAX && H > 0 && W > 0, "mi_upsample_predict_score: bad dimension (K <= 32)");
+    MI_REQUIRE(div_a != 0.f && div_b != 0.f, "mi_upsample_predict_score: zero divisor");
+    MI_REQUIRE((labels != nullptr) == (counts != nullptr), "mi_upsample_predict_score: labels and counts go together");
+    MI_REQUIRE(ignore_index < 0 || ignore_index >= K, "mi_upsample_predict_score: ignore_index inside [0, K)");
+    MI_REQUIRE(threshold >= 0.f && threshold <= 1.f, "mi_upsample_predict_score: threshold outside [0, 1]");
+    ProbSrcs srcs;
+    for (int i = 0; i < MAX_PROB_SRC; ++i) {
+        const MiProbSource& m = src[i < n ? i : 0];       // unused slots repeat source 0: never read, never uninitialised
+        MI_REQUIRE(m.low && m.h > 0 && m.w > 0, "mi_upsample_predict_score: bad source");
+        srcs.s[i] = ProbSrc{m.low, make_axis(m.h, H), make_axis(m.w, W), m.mirror != 0};
+    }
+    const bool wide = W % 2 == 0 && (reinterpret_cast<uintptr_t>(pred) & 1) == 0 && (reinterpret_cast<uintptr_t>(pseudo) & 1) == 0 &&
+                      (reinterpret_cast<uintptr_t>(labels) & 15) == 0;
+    const unsigned nb = nblk((long)H * (wide ? W / 2 : W), 256);
+#define MI_LAUNCH_SCORE(KT, P)                                                                                                                 \
+    hipLaunchKernelGGL((upsample_predict_score_kernel<KT, P>), dim3(nb), dim3(256), 0, (hipStream_t)stream, srcs, n, K, H, W, div_a, div_b, \
+                       reinterpret_cast<const long long*>(labels), ignore_index, threshold, pred, pseudo, reinterpret_cast<unsigned long long*>(counts))
+    if (K == 19) {
+        if (wide) MI_LAUNCH_SCORE(19, 2); else MI_LAUNCH_SCORE(19, 1);
+    } else {
+        if (wide) MI_LAUNCH_SCORE(0, 2); else MI_LAUNCH_SCORE(0, 1);
+    }
+#undef MI_LAUNCH_SCORE
+    MI_CHECK_LAUNCH("mi_upsample_predict_score");
     return MI_OK;
 }
 

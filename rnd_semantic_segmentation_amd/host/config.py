@@ -13,6 +13,7 @@ from ast import literal_eval
 import yaml
 
 _VALID = (tuple, list, str, int, float, bool, type(None))
+_RANGES = {"TEST.PSEUDO_THRESHOLD": (0.0, 1.0)}      # closed intervals a merged value has to lie in
 
 
 class CfgNode(dict):
@@ -77,6 +78,8 @@ class CfgNode(dict):
 
     @staticmethod
     def _coerce(new, old, key):
+        if key in _RANGES and isinstance(new, (int, float)) and not isinstance(new, bool) and not _RANGES[key][0] <= new <= _RANGES[key][1]:
+            raise ValueError("Value {} of config key {} lies outside [{}, {}]".format(new, key, *_RANGES[key]))
         if old is None or new is None or type(new) is type(old):
             return new
         for a, b in ((list, tuple), (tuple, list)):
@@ -166,8 +169,10 @@ def default_tree():
             "DECAY_EPOCH": 50, "GAMMA": 0.1, "CHECKPOINT_PERIOD": 5, "BATCH_SIZE": 8, "BATCH_SIZE_VAL": 1,
         },
         # not in the reference: PRECISION fp32 = exact evaluation path, bf16 = training engine; SCALES / FLIP other than these defaults make
-        # ASPPTester call multi_scale_inference (utility.py:193-209) instead of inference(flip=False)
-        "TEST": {"BATCH_SIZE": 1, "PRECISION": "fp32", "SCALES": (1.0,), "FLIP": False},
+        # ASPPTester call multi_scale_inference (utility.py:193-209) instead of inference(flip=False); FUSED_SCORE True = argmax, threshold and
+        # metric counts in the evaluation tail's kernel (False = the probability map and torch ops: same numbers and files);
+        # PSEUDO_THRESHOLD in [0, 1]: saved masks hold 255 where the winning probability is below it (0 = the reference's plain argmax)
+        "TEST": {"BATCH_SIZE": 1, "PRECISION": "fp32", "SCALES": (1.0,), "FLIP": False, "FUSED_SCORE": True, "PSEUDO_THRESHOLD": 0.0},
         "OUTPUT_DIR": ".",
         "resume": "",
         "PSEUDO_DIR": "",

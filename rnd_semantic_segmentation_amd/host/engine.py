@@ -783,18 +783,24 @@ class AsppEngine:
         self._sig = None
         self._have_dgrad = False
 
+    @staticmethod
+    def _room(t):
+        """Elements of t's storage from t's first element on."""
+        return t.untyped_storage().nbytes() // t.element_size() - t.storage_offset()
+
     def _w4(self):
         ws = [getattr(self.owner.conv2d_list, str(i)).weight for i in range(4)]
         n = ws[0].numel()
         base = ws[0].data_ptr()
-        if all(w.data_ptr() == base + 4 * n * i for i, w in enumerate(ws)):
+        # one flat store: consecutive addresses INSIDE the first weight's storage (separately allocated tensors can sit back to back by chance)
+        if all(w.data_ptr() == base + 4 * n * i for i, w in enumerate(ws)) and self._room(ws[0]) >= 4 * n:
             return torch.as_strided(ws[0].detach(), (4,) + tuple(ws[0].shape), (n,) + tuple(ws[0].stride())), ws
         return torch.stack([w.detach() for w in ws]).contiguous(), ws
 
     def _b4(self):
         bs = [getattr(self.owner.conv2d_list, str(i)).bias for i in range(4)]
         base = bs[0].data_ptr()
-        if all(b.data_ptr() == base + 4 * self.K * i for i, b in enumerate(bs)):
+        if all(b.data_ptr() == base + 4 * self.K * i for i, b in enumerate(bs)) and self._room(bs[0]) >= 4 * self.K:
             return torch.as_strided(bs[0].detach(), (4, self.K), (self.K, 1)), bs
         return torch.stack([b.detach() for b in bs]).contiguous(), bs
 

@@ -24,7 +24,8 @@ from .. import _lib
 from .. import gk
 from .. import kernels as K
 from . import arch
-from .metrics import AverageMeter, adjust_learning_rate, confusion_matrix, dump_json, intersectionAndUnionGPU, require_single_scale
+from .metrics import (AverageMeter, adjust_learning_rate, confusion_matrix, dump_json, intersectionAndUnionGPU, require_plain_argmax,
+                      require_single_scale)
 from .plugin import BaseTrainer
 from .pranet import FlatAdam, _acc, _Engine, _grad_target, _Run, _rup32, _tile_route, _Unit
 
@@ -643,6 +644,7 @@ class GALDTester:
 
     def __init__(self, cfg, device, test_loader, logger, palette, saveres=False, trainid2name=None):
         require_single_scale(cfg, "GALDTester")
+        require_plain_argmax(cfg, "GALDTester")
         self.cfg, self.logger, self.test_loader, self.device = cfg, logger, test_loader, device
         self.palette, self.saveres, self.trainid2name = palette, saveres, trainid2name
         self.encoder = GCPAEncoder()

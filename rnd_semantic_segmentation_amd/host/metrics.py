@@ -12,10 +12,13 @@ Differences that are deliberate and documented:
  * multi_scale_inference() on the engine runs one resize (+ mirror) launch and one backbone + head pass per scale, then ONE kernel
    (mi_upsample_softmax_multi) that interpolates every low-resolution logit map, takes the softmax, sums in the reference's order and
    divides: the result is written once instead of being accumulated through full-size tensors.
+ * predict_and_score() on the engine never builds the probability map: mi_upsample_predict_score takes the argmax of the same per-pixel values in
+   registers, applies the pseudo-label threshold and counts the confusion matrix and the areas against the label in the same launch.
 """
 import json
 import logging
 import os
+import types
 from collections import OrderedDict, defaultdict, deque
 
 import numpy as np
@@ -242,6 +245,83 @@ def require_single_scale(cfg, who):
     if scales != (1.0,) or flip:
         raise NotImplementedError("%s: TEST.SCALES %r / TEST.FLIP %r - multi-scale, flip-averaged evaluation exists for the DeepLab "
                                   "(feature extractor, classifier) pair only (ASPPTester); leave both at their defaults" % (who, scales, flip))
+
+
+def score_settings(cfg):
+    """(fused, threshold) of cfg.TEST (FUSED_SCORE / PSEUDO_THRESHOLD are not reference keys; absent = True / 0.0 = the reference's plain
+    argmax masks)."""
+    fused = bool(cfg.TEST.FUSED_SCORE) if "FUSED_SCORE" in cfg.TEST else True
+    threshold = float(cfg.TEST.PSEUDO_THRESHOLD) if "PSEUDO_THRESHOLD" in cfg.TEST else 0.0
+    if not 0.0 <= threshold <= 1.0:
+        raise ValueError("TEST.PSEUDO_THRESHOLD %r lies outside [0, 1]" % (threshold,))
+    return fused, threshold
+
+
+def require_plain_argmax(cfg, who):
+    """Pseudo-label thresholding is built into the DeepLab evaluation tail only: other testers refuse the key rather than ignore it."""
+    _, threshold = score_settings(cfg)
+    if threshold != 0.0:
+        raise NotImplementedError("%s: TEST.PSEUDO_THRESHOLD %r - thresholded pseudo-labels exist for the DeepLab (feature extractor, "
+                                  "classifier) pair only (ASPPTester); leave it at 0" % (who, threshold))
+
+
+class ScoreResult(object):
+    """What predict_and_score returns for one image: pred / pseudo uint8 [H,W] on the inputs' device (pseudo None for threshold 0), cmt int64
+    [K,K] on the CPU as confusion_matrix returns it, intersection / union / target / output float32 [K] on the CPU holding the integers
+    intersectionAndUnionGPU returns."""
+    __slots__ = ("pred", "pseudo", "cmt", "intersection", "union", "target", "output")
+
+    def __init__(self, pred, pseudo, cmt, intersection, union, target, output):
+        self.pred, self.pseudo, self.cmt = pred, pseudo, cmt
+        self.intersection, self.union, self.target, self.output = intersection, union, target, output
+
+
+def scores_from_counts(counts, K, pred, pseudo):
+    """ScoreResult from the [K*K + 3K] int64 counts (cmt, intersection, output, target: the layout of mi_upsample_predict_score)."""
+    counts = counts.cpu()                                   # the one device-to-host copy
+    cmt = counts[:K * K].reshape(K, K).clone()
+    ai, ao, at = [counts[K * K + i * K:K * K + (i + 1) * K].float() for i in range(3)]
+    return ScoreResult(pred, pseudo, cmt, ai, ao + at - ai, at, ao)
+
+
+def predict_and_score(feature_extractor, classifier, image, label, flip=False, scales=(1.0,), *, num_classes, ignore_index=255, threshold=0.0):
+    """One image of ASPPTester.test(): inference(flip=False) (scales == (1.0,), no flip) or multi_scale_inference, then the argmax mask, the
+    pseudo-label mask (argmax where the winning probability >= threshold, else 255; None for threshold 0), confusion_matrix and
+    intersectionAndUnionGPU against label[:1].  On the engine (a classifier with predict_mask_multi, CUDA tensors) the backbone passes are
+    those of inference / multi_scale_inference and everything after the logits is ONE kernel, which never writes the probability map; the
+    integers are the same.  A substituted / foreign classifier or CPU tensors run the literal composition."""
+    K = int(num_classes)
+    if not 0.0 <= float(threshold) <= 1.0:
+        raise ValueError("threshold %r lies outside [0, 1]" % (threshold,))
+    scales = tuple(scales)
+    single = scales == (1.0,) and not flip
+    size = tuple(label.shape[-2:])
+    y0 = label[:1]                                          # inference() keeps image 0 only (utility.py:190)
+    if hasattr(classifier, "predict_mask_multi") and image.is_cuda:
+        kw = dict(labels=y0[0].long().contiguous(), ignore_index=int(ignore_index), threshold=float(threshold), want_pseudo=threshold != 0)
+        with torch.no_grad():
+            if single:
+                pred, pseudo, counts = classifier.predict_mask(feature_extractor(image), size, **kw)
+            else:
+                from .. import kernels
+                sizes, _, divisors = multi_scale_plan(image.shape[-2:], flip, scales)
+                x0 = image[:1].float().contiguous()
+                feats = [feature_extractor(kernels.image_resize_ac(x0, hw, with_mirror=flip)) for hw in sizes]
+                mirrors = [(False, True) if flip else (False,)] * len(sizes)
+                pred, pseudo, counts = classifier.predict_mask_multi(feats, mirrors, size, divisors, **kw)
+        return scores_from_counts(counts, K, pred, pseudo)
+    if single:
+        output = inference(feature_extractor, classifier, image, label, flip=False)
+    else:
+        output = multi_scale_inference(feature_extractor, classifier, image, label, flip=flip, scales=list(scales))
+    top = output.max(1)
+    pred = top[1]
+    pseudo = None
+    if threshold != 0:
+        pseudo = torch.where(top[0] >= threshold, pred, torch.full_like(pred, 255))[0].to(torch.uint8)
+    cmt = confusion_matrix(types.SimpleNamespace(MODEL=types.SimpleNamespace(NUM_CLASSES=K)), torch.flatten(pred), torch.flatten(y0))
+    ai, union, at, ao = [t.cpu() for t in intersectionAndUnionGPU(pred.clone(), y0.long(), K, ignore_index)]
+    return ScoreResult(pred[0].to(torch.uint8), pseudo, cmt, ai, union, at, ao)
 
 
 # ----------------------------------------------------------------------------- io / logging

@@ -254,26 +254,55 @@ class ASPP_Classifier_V2(nn.Module):
             probs, _ = kernels.upsample_softmax(low, tuple(int(s) for s in size), want_pred=False)
         return probs
 
+    def _lows_multi(self, feats, mirrors, who):
+        """The 1/8-resolution logits of every image of every feature map as one source list (fp32 / bf16 branch of predict_probs)."""
+        lows, flags = [], []
+        for feat, mm in zip(feats, mirrors):
+            _require_gpu(feat, "ASPP_Classifier_V2")
+            if feat.shape[0] != len(mm):
+                raise ValueError("%s: %d images but %d mirror flags" % (who, feat.shape[0], len(mm)))
+            if self.precision == "fp32":
+                low = self._low_fp32(feat)
+            else:
+                self._engine.prepare(False)
+                low = self._engine.forward(self._nhwc(feat))
+            lows += list(low.unbind(0))
+            flags += list(mm)
+        return lows, flags
+
     def predict_probs_multi(self, feats, mirrors, size, divisors):
         """The tail of multi_scale_inference (utility.py:193-209) in one kernel.  feats: feature maps [b,C,h,w] (one per scale, any sizes);
         mirrors[i][j]: whether image j of feats[i] saw the horizontally mirrored input; every image is one source, in that order.
         Returns ((p_0 + p_1 + ...) / divisors[0]) / divisors[1] as [1,K,H,W] fp32, p = softmax(interpolate(logits, size)), mirrored
         sources mirrored back."""
         from .. import kernels
-        lows, flags = [], []
         with torch.no_grad():
-            for feat, mm in zip(feats, mirrors):
-                _require_gpu(feat, "ASPP_Classifier_V2")
-                if feat.shape[0] != len(mm):
-                    raise ValueError("predict_probs_multi: %d images but %d mirror flags" % (feat.shape[0], len(mm)))
-                if self.precision == "fp32":
-                    low = self._low_fp32(feat)
-                else:
-                    self._engine.prepare(False)
-                    low = self._engine.forward(self._nhwc(feat))
-                lows += list(low.unbind(0))
-                flags += list(mm)
+            lows, flags = self._lows_multi(feats, mirrors, "predict_probs_multi")
             return kernels.upsample_softmax_multi(lows, flags, tuple(int(s) for s in size), float(divisors[0]), float(divisors[1]))
+
+    def predict_mask_multi(self, feats, mirrors, size, divisors, labels=None, ignore_index=255, threshold=0.0, want_pseudo=False):
+        """predict_probs_multi(feats, mirrors, size, divisors).max(1) without the probability map: (pred, pseudo, counts) of
+        kernels.upsample_predict_score - the argmax mask, the thresholded pseudo-label mask and, with labels [H,W] int64, the confusion matrix
+        and intersection / output / target areas."""
+        from .. import kernels
+        with torch.no_grad():
+            lows, flags = self._lows_multi(feats, mirrors, "predict_mask_multi")
+            return kernels.upsample_predict_score(lows, flags, tuple(int(s) for s in size), float(divisors[0]), float(divisors[1]), labels=labels,
+                                                  ignore_index=ignore_index, threshold=threshold, want_pseudo=want_pseudo)
+
+    def predict_mask(self, x, size, labels=None, ignore_index=255, threshold=0.0, want_pseudo=False):
+        """predict_probs(x, size)[:1].max(1) without the probability map: the whole batch goes through the head as in predict_probs, image 0's
+        logits are scored (inference() keeps image 0, utility.py:190)."""
+        _require_gpu(x, "ASPP_Classifier_V2")
+        from .. import kernels
+        with torch.no_grad():
+            if self.precision == "fp32":
+                low = self._low_fp32(x)
+            else:
+                self._engine.prepare(False)
+                low = self._engine.forward(self._nhwc(x))
+            return kernels.upsample_predict_score([low[0]], [False], tuple(int(s) for s in size), 1.0, 1.0, labels=labels,
+                                                  ignore_index=ignore_index, threshold=threshold, want_pseudo=want_pseudo)
 
 
 class CrossEntropyLoss(nn.Module):

@@ -1377,8 +1377,9 @@ class PranetTester:
     {background, polyp} by which of (1 - p, p) is larger -> intersection / union meters."""
 
     def __init__(self, cfg, device, test_loader, logger):
-        from .metrics import require_single_scale
+        from .metrics import require_plain_argmax, require_single_scale
         require_single_scale(cfg, "PranetTester")
+        require_plain_argmax(cfg, "PranetTester")
         self.cfg, self.logger, self.test_loader, self.device = cfg, logger, test_loader, device
         self.model = PraNet()
         self.model.to(device)

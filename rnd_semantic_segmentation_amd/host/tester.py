@@ -7,7 +7,7 @@ import numpy as np
 import torch
 
 from .metrics import (AverageMeter, confusion_matrix, dump_json, inference, intersectionAndUnionGPU, multi_scale_inference,
-                      strip_prefix_if_present, tta_settings)
+                      predict_and_score, score_settings, strip_prefix_if_present, tta_settings)
 from .modules import build_classifier, build_feature_extractor
 
 
@@ -42,11 +42,16 @@ class ASPPTester:
 
     def save_distill(self, output, name):
         """aspp_tester.py:33-45: palette PNG of the argmax mask under PSEUDO_DIR/inference/<dataset>."""
+        self.save_mask(output.cpu().numpy().squeeze().argmax(0).astype(np.uint8), name)
+
+    def save_mask(self, mask, name):
+        """The file save_distill writes, from a [H,W] uint8 mask (tensor or array) that is already an argmax / pseudo-label map."""
         from PIL import Image
         folder = os.path.join(self.cfg.PSEUDO_DIR, "inference", self.cfg.DATASETS.TEST)
         os.makedirs(folder, exist_ok=True)
-        pred = output.cpu().numpy().squeeze().argmax(0).astype(np.uint8)
-        mask = Image.fromarray(pred)
+        if isinstance(mask, torch.Tensor):
+            mask = mask.cpu().numpy()
+        mask = Image.fromarray(np.ascontiguousarray(mask, dtype=np.uint8))
         mask.putpalette(list(self.palette))
         mask.save(os.path.join(folder, name[0] + ".png"))
 
@@ -58,16 +63,30 @@ class ASPPTester:
         cmt = torch.zeros(num_classes, num_classes, dtype=torch.int64)
         scales, flip = tta_settings(self.cfg)
         single = scales == (1.0,) and not flip
+        fused, threshold = score_settings(self.cfg)
+        # one kernel after the logits (argmax, threshold, counts) instead of the probability map and the torch-op metrics: same integers, same files
+        fused = fused and self.device.type == "cuda" and hasattr(self.classifier, "predict_mask_multi")
         for x, y, name in self.test_loader:
             x = x.to(self.device, non_blocking=True)
             y = y.to(self.device, non_blocking=True).long()
+            if fused:
+                r = predict_and_score(self.feature_extractor, self.classifier, x, y, flip=flip, scales=scales, num_classes=num_classes,
+                                      ignore_index=self.cfg.INPUT.IGNORE_LABEL, threshold=threshold)
+                if self.saveres:
+                    self.save_mask(r.pred if r.pseudo is None else r.pseudo, name)
+                cmt = cmt + r.cmt
+                self.meter.update(*[t.numpy() for t in (r.intersection, r.union, r.target, r.output)])
+                continue
             if single:
                 output = inference(self.feature_extractor, self.classifier, x, y, flip=False)     # [1,K,H,W]
             else:                                          # the call aspp_tester.py:61 keeps commented out
                 output = multi_scale_inference(self.feature_extractor, self.classifier, x, y, flip=flip, scales=list(scales))
             pred = output.max(1)[1]
-            if self.saveres:
+            if self.saveres and threshold == 0:
                 self.save_distill(output, name)
+            elif self.saveres:
+                top = output.max(1)
+                self.save_mask(torch.where(top[0] >= threshold, pred, torch.full_like(pred, 255))[0], name)
             y0 = y[:1]                                    # inference() keeps image 0 only (utility.py:190)
             cmt = cmt + confusion_matrix(self.cfg, torch.flatten(pred), torch.flatten(y0))
             inter, union, target, res = intersectionAndUnionGPU(pred, y0, num_classes, self.cfg.INPUT.IGNORE_LABEL)

@@ -451,6 +451,42 @@ def upsample_softmax_multi(lows, mirrors, size, div_a, div_b=1.0):
     return probs
 
 
+def upsample_predict_score(lows, mirrors, size, div_a, div_b=1.0, labels=None, ignore_index=255, threshold=0.0, want_pseudo=False):
+    """The evaluation tail without the probability map (mi_upsample_predict_score): the per-pixel values of upsample_softmax_multi(lows, mirrors,
+    size, div_a, div_b), reduced in registers.  Returns (pred, pseudo, counts): pred uint8 [H,W] = the lowest class index among the maxima,
+    pseudo uint8 [H,W] = pred where the maximum >= threshold else 255 (None unless want_pseudo), counts int64 [K*K + 3K] on the device = confusion
+    matrix, area_intersection, area_output, area_target of pred against labels [H,W] int64 (None without labels; split_counts names the parts)."""
+    n = len(lows)
+    if not 1 <= n <= 16 or len(mirrors) != n:
+        raise _lib.MiError("upsample_predict_score: 1..16 sources with one mirror flag each (got %d / %d)" % (n, len(mirrors)))
+    K = lows[0].shape[-1]
+    dev = lows[0].device
+    src = (_lib.MiProbSource * n)()
+    for i, (low, m) in enumerate(zip(lows, mirrors)):
+        _chk(low, torch.float32, "lows[%d]" % i)
+        if low.dim() != 3 or low.shape[-1] != K or low.device != dev:
+            raise _lib.MiError("lows[%d] must be [h,w,%d] on %s, got %s on %s" % (i, K, dev, tuple(low.shape), low.device))
+        src[i].low, src[i].h, src[i].w, src[i].mirror = low.data_ptr(), low.shape[0], low.shape[1], int(bool(m))
+    H, W = size
+    counts = None
+    if labels is not None:
+        _chk(labels, torch.int64, "labels")
+        if tuple(labels.shape) != (H, W) or labels.device != dev:
+            raise _lib.MiError("labels must be [%d,%d] on %s, got %s on %s" % (H, W, dev, tuple(labels.shape), labels.device))
+        counts = torch.zeros(K * K + 3 * K, dtype=torch.int64, device=dev)
+    pred = torch.empty((H, W), dtype=torch.uint8, device=dev)
+    pseudo = torch.empty((H, W), dtype=torch.uint8, device=dev) if want_pseudo else None
+    check(_lib.lib().mi_upsample_predict_score(ctypes.cast(src, ctypes.c_void_p), n, K, H, W, float(div_a), float(div_b), _p(labels),
+                                               int(ignore_index), float(threshold), _p(pred), _p(pseudo), _p(counts), _stream()),
+          "mi_upsample_predict_score")
+    return pred, pseudo, counts
+
+
+def split_counts(counts, K):
+    """The layout of mi_upsample_predict_score's counts (include/mi355seg.h): (cmt [K,K], intersection [K], output [K], target [K])."""
+    return counts[:K * K].reshape(K, K), counts[K * K:K * K + K], counts[K * K + K:K * K + 2 * K], counts[K * K + 2 * K:K * K + 3 * K]
+
+
 def image_resize_ac(x, size, with_mirror=False):
     """F.interpolate(x, size, mode='bilinear', align_corners=True) on [B,C,H,W] fp32 NCHW; with_mirror appends torch.flip(resized, [3]) of
     image b as image B + b (one launch)."""
