@@ -87,8 +87,20 @@ int mi_conv_gemm(const void* a, const void* wp, void* out,
  * stride 1, Ha == Ho, Wa == Wo, Ca % 32 == 0.  mi_conv_gemm picks it by its own cost model; this entry point exists so that
  * the two main loops can be compared on one shape in one process.  mtg: 16-row MFMA tiles per wave (8 or 10 -> 256 or 320
  * tile rows), 0 = choose. */
-/* which main loop mi_conv_gemm takes for a shape: 1 = igemm_pp_kernel (wide tile), 0 = igemm_nt_kernel (measurement tools) */
+/* which main loop mi_conv_gemm takes for a shape: 1 = igemm_pp_kernel (wide tile), 0 = igemm_nt_kernel (measurement tools): the `kernel` field of
+ * mi_conv_gemm_plan for a padding of at most 32 rows.  A pure query: arguments mi_conv_gemm would refuse answer 0 and do not touch mi_last_error.  Since the
+ * query became a view of the plan it answers 1 for every valid Ca % 64 != 0 launch (they run on igemm_pp_kernel whatever M is; the rule alone used to answer 0
+ * for the small ones). */
 int mi_conv_gemm_route(int B, int Ha, int Wa, int Ca, int Ho, int Wo, int N, int ksize, int stride, int flags);
+/* The instantiation mi_conv_gemm / mi_conv_gemm_stats (pp_mtg = -1) or mi_conv_gemm_pp (pp_mtg = its mtg: 0, 8 or 10) launches for these arguments, from the
+ * planning function the launches call, on the host (no GPU, no launch).  plan: int[MI_CPLAN_LEN] = {kernel (MI_CPLAN_*), tile height (igemm_nt_kernel: MT 4..6,
+ * 32 * MT rows x 128 columns; igemm_pp_kernel: MTG 8 | 10, 32 * MTG rows x 256 columns), unit-stride gather, prefetched residual rows, staged epilogue,
+ * compile-time epilogue flag set (-1: the generic epilogue that reads `flags`), K order (igemm_pp_kernel: 1 = channel-chunk-major), row tiles, column tiles,
+ * rounds of the grid on the workgroup slots the tile picker assumed, those slots}. */
+#define MI_CPLAN_NT 0         /* igemm_nt_kernel<MT, UNIT, PREF, 64, EPI, 2, STG> */
+#define MI_CPLAN_PP 1         /* igemm_pp_kernel<MTG, EPI> */
+#define MI_CPLAN_LEN 11
+int mi_conv_gemm_plan(int B, int Ha, int Wa, int Ca, int Ho, int Wo, int N, int ksize, int stride, int pad, int dil, int flags, int pp_mtg, int* plan);
 int mi_conv_gemm_pp(const void* a, const void* wp, void* out,
                     int B, int Ha, int Wa, int Ca, int Ho, int Wo, int N,
                     int ksize, int stride, int pad, int dil, int gather_mode,
@@ -125,6 +137,17 @@ size_t mi_conv_wgrad_workspace(int B, int Ho, int Wo, int O, int I, int ksize);
  * (opt-in), 2 wgrad_p3_kernel (opt-in), 3 wgrad_q3_kernel (3x3 stride 1: the three taps of a kernel row fused, 64 x 128 tile),
  * 4 wgrad_s4_kernel (1x1 stride 1: 32-pixel stages, three in flight) */
 int mi_conv_wgrad_route(int B, int Ha, int Wa, int I, int Ho, int Wo, int O, int ksize, int stride, int pad, int dil, int out_map);
+/* The launch mi_conv_wgrad (deferred = 0) or mi_conv_wgrad_partial (deferred = 1) makes for these arguments with a workspace of mi_conv_wgrad_workspace bytes,
+ * from the planning function the launches call, on the host.  plan: int[MI_WPLAN_LEN] = {kernel (MI_WPLAN_*: mi_conv_wgrad_route's numbers), addressing mode
+ * (wgrad_tn_kernel<MODE>: 0 general gather, 1 unit stride, 2 pointwise; wgrad_tn256_kernel<MODE>: 1 | 2; else 0), K splits S, K steps per split (q3: slabs of
+ * 64 padded pixels), pixels per K step, o tiles, i tiles, deferred}. */
+#define MI_WPLAN_TN 0
+#define MI_WPLAN_TN256 1
+#define MI_WPLAN_P3 2         /* experiment builds only */
+#define MI_WPLAN_Q3 3
+#define MI_WPLAN_S4 4
+#define MI_WPLAN_LEN 8
+int mi_conv_wgrad_plan(int B, int Ha, int Wa, int I, int Ho, int Wo, int O, int ksize, int stride, int pad, int dil, int out_map, int deferred, int* plan);
 int mi_conv_wgrad(const void* dy, const void* x, float* dw,
                   int B, int Ha, int Wa, int I, int Ho, int Wo, int O,
                   int ksize, int stride, int pad, int dil,

@@ -307,29 +307,37 @@ void launch_one(dim3 grid, hipStream_t stream, const IgemmParams& p) {
 }
 
 // hot epilogue sets: 69 = FrozenBN + ReLU + sign bits (conv1 / conv2 forward), 71 = the same + residual (conv3 forward),
-// 128 = ReLU-backward from sign bits (data gradients), 130 = the same + residual-gradient add (conv1 data gradient)
+// 128 = ReLU-backward from sign bits (data gradients), 130 = the same + residual-gradient add (conv1 data gradient).
+// epi / staged: the plan's choice (mi_conv_plan, below) - this switch only maps it to the instantiation
 template <int MT, bool UNIT, bool PREF, int BKT, int NWN>
-void launch_variant(dim3 grid, hipStream_t stream, const IgemmParams& p) {
-    const int fl = p.flags;
-    const bool staged = staged_on();
+void launch_variant(dim3 grid, hipStream_t stream, const IgemmParams& p, int epi, bool staged) {
     if constexpr (UNIT) {
         if constexpr (!PREF && NWN == 2 && BKT == 64) {
             if (staged) {     // the residual sets only: 5-7 % faster staged; without a residual tile to read it is a wash
-                if (fl == 71) return launch_one<MT, UNIT, PREF, BKT, 71, NWN, true>(grid, stream, p);
-                if (fl == 130) return launch_one<MT, UNIT, PREF, BKT, 130, NWN, true>(grid, stream, p);
+                if (epi == 71) return launch_one<MT, UNIT, PREF, BKT, 71, NWN, true>(grid, stream, p);
+                if (epi == 130) return launch_one<MT, UNIT, PREF, BKT, 130, NWN, true>(grid, stream, p);
             }
         }
         if constexpr (!PREF) {
-            if (fl == 69) return launch_one<MT, UNIT, PREF, BKT, 69, NWN>(grid, stream, p);
-            if (fl == 128) return launch_one<MT, UNIT, PREF, BKT, 128, NWN>(grid, stream, p);
+            if (epi == 69) return launch_one<MT, UNIT, PREF, BKT, 69, NWN>(grid, stream, p);
+            if (epi == 128) return launch_one<MT, UNIT, PREF, BKT, 128, NWN>(grid, stream, p);
         }
-        if (fl == 71) return launch_one<MT, UNIT, PREF, BKT, 71, NWN>(grid, stream, p);
-        if (fl == 130) return launch_one<MT, UNIT, PREF, BKT, 130, NWN>(grid, stream, p);
+        if (epi == 71) return launch_one<MT, UNIT, PREF, BKT, 71, NWN>(grid, stream, p);
+        if (epi == 130) return launch_one<MT, UNIT, PREF, BKT, 130, NWN>(grid, stream, p);
     }
     if constexpr (!PREF && NWN == 2) {
-        if (fl == MI_EPI_STATS) return launch_one<MT, UNIT, PREF, BKT, MI_EPI_STATS, NWN>(grid, stream, p);      // plain store + BatchNorm tile statistics
+        if (epi == MI_EPI_STATS) return launch_one<MT, UNIT, PREF, BKT, MI_EPI_STATS, NWN>(grid, stream, p);      // plain store + BatchNorm tile statistics
     }
     launch_one<MT, UNIT, PREF, BKT, -1, NWN>(grid, stream, p);
+}
+
+// The dispatch rule between the two main loops, without the exact 32-bit offset bound of igemm_pp_kernel (which needs pad and dil: mi_conv_plan)
+bool pp_by_rule(int B, int Ha, int Wa, int Ca, int Ho, int Wo, int N, int ksize, int stride, int flags) {
+    const int pp_on = mi_sw().igemm_pp;
+    const int min_k = mi_sw().igemm_pp_mink;         // 512: in the step 704 -> 2048 (ASPP data gradient) 246 vs 280 us, 512 -> 1024 101 vs 116; K = 256: no difference
+    const long M = (long)B * Ho * Wo;
+    return pp_on && stride == 1 && Ha == Ho && Wa == Wo && !(flags & (MI_EPI_RESIDUAL | MI_EPI_MASK | MI_EPI_LEAKY)) && (long)ksize * ksize * Ca >= min_k &&
+           Ca % 32 == 0 && M >= 320 * 64 && N >= 256;
 }
 
 }  // namespace
@@ -338,16 +346,154 @@ extern "C" int mi_conv_gemm_pp(const void* a, const void* wp, void* out, int B, 
                                int stride, int pad, int dil, int gather_mode, const float* scale, const float* bias, const void* res,
                                const void* msk, void* mask_out, int flags, int zgw, float alpha, int mtg, void* stream);
 
-// 1 = the launch goes to the wide-tile ping-pong main loop (igemm_pp_kernel), 0 = to igemm_nt_kernel
-extern "C" int mi_conv_gemm_route(int B, int Ha, int Wa, int Ca, int Ho, int Wo, int N, int ksize, int stride, int flags) {
-    const int pp_on = mi_sw().igemm_pp;
-    const int min_k = mi_sw().igemm_pp_mink;         // 512: in the step 704 -> 2048 (ASPP data gradient) 246 vs 280 us, 512 -> 1024 101 vs 116; K = 256: no difference
+// Every decision of a conv launch in one place: which main loop, which tile, which instantiation.  mi_conv_gemm_impl and mi_conv_gemm_pp_impl launch what
+// this says; mi_conv_gemm_plan reports it (host only).
+// (the refusals are written to `why`, not to the library's last error: mi_conv_gemm_route is a pure query)
+#define PLAN_REQUIRE(cond, ...)                      \
+    do {                                             \
+        if (!(cond)) {                               \
+            snprintf(why, PLAN_WHY_LEN, __VA_ARGS__); \
+            return MI_EINVAL;                        \
+        }                                            \
+    } while (0)
+constexpr int PLAN_WHY_LEN = 256;
+static int conv_plan(int B, int Ha, int Wa, int Ca, int Ho, int Wo, int N, int ksize, int stride, int pad, int dil, int flags, int pp_mtg, MiConvPlan* pl,
+                     char* why) {
+    PLAN_REQUIRE(B > 0 && Ha > 0 && Wa > 0 && Ho > 0 && Wo > 0 && N > 0, "mi_conv_gemm: non-positive dimension");
+    PLAN_REQUIRE(Ca > 0 && Ca % 32 == 0, "mi_conv_gemm: Ca=%d must be a multiple of 32", Ca);
+    PLAN_REQUIRE(ksize == 1 || ksize == 3, "mi_conv_gemm: ksize=%d (1 or 3)", ksize);
+    PLAN_REQUIRE(stride >= 1 && dil >= 1 && pad >= 0, "mi_conv_gemm: bad stride/dil/pad");
     const long M = (long)B * Ho * Wo;
-    // igemm_pp_kernel addresses its operands with 32-bit buffer offsets: 2 GiB tensors stay on the pointer-arithmetic kernel
-    const long a_bytes = (long)B * Ha * Wa * Ca * 2 + 64L * (Wa + 1) * Ca * 2, w_bytes = (long)ksize * ksize * N * Ca * 2;
-    if (a_bytes >= (1L << 31) - (1L << 20) || w_bytes >= (1L << 31) - (1L << 20)) return 0;
-    return pp_on && stride == 1 && Ha == Ho && Wa == Wo && !(flags & (MI_EPI_RESIDUAL | MI_EPI_MASK | MI_EPI_LEAKY)) && (long)ksize * ksize * Ca >= min_k &&
-           Ca % 32 == 0 && M >= 320 * 64 && N >= 256;
+    PLAN_REQUIRE(M < (1L << 31) && (long)B * Ha * Wa < (1L << 31), "mi_conv_gemm: pixel count overflows int32");
+    const bool same = stride == 1 && Ha == Ho && Wa == Wo;
+    // igemm_pp_kernel addresses its operands with 32-bit buffer offsets (bit 31 marks a padded chunk): operands and the largest tap excursion must stay
+    // below 2 GiB; larger tensors stay on the pointer-arithmetic kernel
+    const long lim = (1L << 31) - (1L << 20);
+    const long a_bytes = (long)B * Ha * Wa * Ca * 2 + 2L * ((long)(ksize - 1) * dil + pad) * (Wa + 1) * Ca * 2, w_bytes = (long)ksize * ksize * N * Ca * 2;
+    const bool fits32 = a_bytes < lim && w_bytes < lim;
+    const bool fits32_rule = (long)B * Ha * Wa * Ca * 2 + 64L * (Wa + 1) * Ca * 2 < lim;      // the dispatch rule's own margin: a tap excursion of 32 rows
+    // Ca % 64 == 0: either main loop.  Ca % 32 == 0 only (the 32-padded operands of the general family's packs: HarDNet's 466 -> 480 channel
+    // gathers): the 32-channel slabs of igemm_pp_kernel take it, whatever the dispatch rule says - stride-1 / same-size launches without a residual tile
+    const bool pp_only = Ca % 64 != 0;
+    bool pp = pp_mtg >= 0;
+    if (pp_mtg < 0) {
+        if (pp_only) {
+            PLAN_REQUIRE(same && !(flags & (MI_EPI_RESIDUAL | MI_EPI_MASK | MI_EPI_LEAKY)),
+                       "mi_conv_gemm: Ca=%d is not a multiple of 64: stride-1, same-size launches without residual / mask / LeakyReLU only", Ca);
+            PLAN_REQUIRE(fits32, "mi_conv_gemm: Ca=%d is not a multiple of 64 and the operands exceed the 2 GiB the 32-channel main loop addresses", Ca);
+            pp = true;
+        } else {
+            // Long contractions without a residual tile go to the wide-tile ping-pong main loop (igemm_pp.hip): 7.0 instead of 13-14
+            // L2 bytes per kFLOP.  Measured per shape against this kernel in one process (tools/ppexp.py, B = 8, 97 x 97): 3x3 256 +16 %,
+            // 3x3 512 +13 %, 1x1 2048->512 +18 %, 1x1 1024->256 / 1024->2048 / ASPP forward +6 %; the short contractions (K < 512)
+            // are epilogue-bound and stay here.  MI_IGEMM_PP=0 switches the dispatch off.
+            pp = fits32 && fits32_rule && pp_by_rule(B, Ha, Wa, Ca, Ho, Wo, N, ksize, stride, flags);
+        }
+    }
+    MiConvPlan& r = *pl;
+    r = MiConvPlan{};
+    if (pp) {
+        PLAN_REQUIRE(same, "mi_conv_gemm_pp: stride-1, same-size convolutions only");
+        PLAN_REQUIRE(fits32, "mi_conv_gemm_pp: operand larger than 2 GiB");
+        int mtg = pp_mtg;
+        if (mtg != 8 && mtg != 10) {           // fewest rounds on 256 CUs, then the least padding
+            auto rounds = [&](int bm) { return (((M + bm - 1) / bm) * ((N + 255) / 256) + 255) / 256; };
+            mtg = rounds(320) < rounds(256) ? 10 : (rounds(256) < rounds(320) ? 8 : (((M + 319) / 320) * 320 <= ((M + 255) / 256) * 256 ? 10 : 8));
+        }
+        r.kernel = MI_CPLAN_PP;
+        r.mt = mtg;
+        r.bn = 256;
+        r.unit = 1;
+        r.korder = ksize > 1 ? mi_sw().pp_korder : 0;              // MI_IGEMM_PP_KORDER=0: tap-major contraction (the order of igemm_nt_kernel; bit-equal to it)
+        r.epi = (flags == 69 || flags == 128 || flags == 0 || flags == 1 || flags == 48 || flags == MI_EPI_STATS) ? flags : -1;
+        r.m_tiles = (int)((M + 32 * mtg - 1) / (32 * mtg));
+        r.n_tiles = (N + 255) / 256;
+        r.slots = 256;
+        r.rounds = (int)(((long)r.m_tiles * r.n_tiles + 255) / 256);
+        return MI_OK;
+    }
+    const bool unit = same && ksize * ksize <= 9;
+    const int force_mt = mi_sw().igemm_mt, force_bn = mi_sw().igemm_bn, pref_on = mi_sw().igemm_pref;
+    // Modelled time of one launch with tile bm x bn: rounds on the resident-workgroup slots x workgroups sharing a CU x per-K-step
+    // tile time, where a CU's share of the L2 request rate serves (bm+bn)*128 B per step (~47.6 GB/s per CU measured) and its
+    // MFMA pipes need bm*bn*128 FLOP at ~9.8 TFLOP/s per CU; the two overlap imperfectly (20 % of the shorter one is exposed).
+    auto cost = [&](int bm, int bn) {
+        const int per_cu = bn == 256 ? 1 : 2;
+        const long tiles = ((M + bm - 1) / bm) * ((N + bn - 1) / bn);
+        const long rounds = (tiles + 256 * per_cu - 1) / (256 * per_cu);
+        const double t_l2 = (bm + bn) * 128.0 / 47.6e3, t_mfma = bm * (double)bn * 128.0 / 9.77e6;      // microseconds
+        return rounds * per_cu * ((t_l2 > t_mfma ? t_l2 : t_mfma) + 0.2 * (t_l2 > t_mfma ? t_mfma : t_l2));
+    };
+    // The 256-wide tile is selectable (MI_IGEMM_BN=256) but not the default: with this loop structure (one barrier and a full
+    // vmcnt(0) drain per K-step) it measured 2-8 % slower than the 128-wide tiles on every shape of the network (bench 216 vs
+    // 223.5 images/s) although it moves 30 % fewer L2 bytes - the single resident workgroup has nothing to overlap its drains
+    // with.  It is the geometry a deeper-pipelined schedule (counted vmcnt, prefetch in flight across barriers) needs.
+#ifdef MI_EXPERIMENTS
+    const bool wide_ok = unit && N % 256 == 0 && !(flags & MI_EPI_ZSPLIT) && force_bn == 256;
+#else
+    const bool wide_ok = false;                          // the 256-wide tile is compiled into experiment builds only
+    (void)force_bn;
+#endif
+    int mt_sel = 4, bn = 128;
+    double best = cost(128, 128);
+    for (int mt = 5; mt <= 6; ++mt)
+        if (cost(32 * mt, 128) < best * 0.999) best = cost(32 * mt, 128), mt_sel = mt;
+    if (force_mt >= 4 && force_mt <= 6) mt_sel = force_mt, best = cost(32 * mt_sel, 128);
+    if (wide_ok) {
+        int wmt = 0;
+        double wbest = force_bn == 256 ? 1e30 : best;
+        for (int mt = 4; mt <= 6; ++mt)
+            if ((force_mt == 0 || force_mt == mt) && cost(32 * mt, 256) < wbest * 0.999) wbest = cost(32 * mt, 256), wmt = mt;
+        if (wmt) mt_sel = wmt, bn = 256;
+    }
+    const bool hot_set = flags == 71 || flags == 130;
+    const bool pref = bn == 128 && pref_on && unit && (flags & MI_EPI_RESIDUAL) && N % 16 == 0 && !(staged_on() && hot_set);
+    if (!unit) mt_sel = 4;                               // the general (strided) gather exists in the 128-row shape only
+    if (pref && mt_sel == 6) mt_sel = 5;                 // the prefetched rows cost 8 VGPRs per 16-row MFMA tile
+    const int bm = mt_sel * 32;
+    r.kernel = MI_CPLAN_NT;
+    r.mt = mt_sel;
+    r.bn = bn;
+    r.unit = unit;
+    r.pref = pref && bn == 128;
+    // the instantiation: launch_variant maps (epi, staged) to it
+    r.staged = unit && !pref && bn == 128 && staged_on() && hot_set;
+    if (unit && (hot_set || (!pref && (flags == 69 || flags == 128)))) r.epi = flags;
+    else if (!pref && bn == 128 && flags == MI_EPI_STATS) r.epi = MI_EPI_STATS;
+    else r.epi = -1;
+    r.m_tiles = (int)((M + bm - 1) / bm);
+    r.n_tiles = (N + bn - 1) / bn;
+    r.slots = bn == 256 ? 256 : 512;
+    r.rounds = (int)(((long)r.m_tiles * r.n_tiles + r.slots - 1) / r.slots);
+    return MI_OK;
+}
+#undef PLAN_REQUIRE
+
+int mi_conv_plan(int B, int Ha, int Wa, int Ca, int Ho, int Wo, int N, int ksize, int stride, int pad, int dil, int flags, int pp_mtg, MiConvPlan* pl) {
+    char why[PLAN_WHY_LEN];
+    const int rc = conv_plan(B, Ha, Wa, Ca, Ho, Wo, N, ksize, stride, pad, dil, flags, pp_mtg, pl, why);
+    return rc == MI_OK ? MI_OK : mi_set_error(rc, "%s", why);
+}
+
+extern "C" int mi_conv_gemm_plan(int B, int Ha, int Wa, int Ca, int Ho, int Wo, int N, int ksize, int stride, int pad, int dil, int flags, int pp_mtg, int* plan) {
+    MI_REQUIRE(plan, "mi_conv_gemm_plan: null plan");
+    MI_REQUIRE(pp_mtg == -1 || pp_mtg == 0 || pp_mtg == 8 || pp_mtg == 10, "mi_conv_gemm_plan: pp_mtg=%d (-1: mi_conv_gemm, 0 | 8 | 10: mi_conv_gemm_pp)", pp_mtg);
+    MiConvPlan r;
+    const int rc = mi_conv_plan(B, Ha, Wa, Ca, Ho, Wo, N, ksize, stride, pad, dil, flags, pp_mtg, &r);
+    if (rc != MI_OK) return rc;
+    const int v[MI_CPLAN_LEN] = {r.kernel, r.mt, r.unit, r.pref, r.staged, r.epi, r.korder, r.m_tiles, r.n_tiles, r.rounds, r.slots};
+    for (int k = 0; k < MI_CPLAN_LEN; ++k) plan[k] = v[k];
+    return MI_OK;
+}
+
+// 1 = the launch goes to the wide-tile ping-pong main loop (igemm_pp_kernel), 0 = to igemm_nt_kernel: a view of the plan for callers that do not know
+// the padding - the tap excursion of the 32-bit offset bound is taken as 32 rows (every dilation <= 16 of a 3x3 with pad == dil).  A pure query: arguments no
+// plan exists for answer 0 and leave mi_last_error alone.  Ca % 64 != 0 answers 1 (those launches run on igemm_pp_kernel whatever the rule says).
+extern "C" int mi_conv_gemm_route(int B, int Ha, int Wa, int Ca, int Ho, int Wo, int N, int ksize, int stride, int flags) {
+    MiConvPlan r;
+    char why[PLAN_WHY_LEN];
+    if (conv_plan(B, Ha, Wa, Ca, Ho, Wo, N, ksize, stride, 32 - (ksize == 3 ? 2 : 0), 1, flags, -1, &r, why) != MI_OK) return 0;
+    return r.kernel == MI_CPLAN_PP;
 }
 
 extern "C" int mi_conv_gemm(const void* a, const void* wp, void* out, int B, int Ha, int Wa, int Ca, int Ho, int Wo, int N,
@@ -387,11 +533,8 @@ int mi_conv_gemm_impl(const void* a, const void* wp, void* out, int B, int Ha, i
     MI_REQUIRE(a && wp && out, "mi_conv_gemm: null operand");
     MI_REQUIRE(((flags & MI_EPI_STATS) != 0) == (st != nullptr) && (!st || flags == MI_EPI_STATS), "mi_conv_gemm: MI_EPI_STATS comes alone, through mi_conv_gemm_stats");
     MI_REQUIRE(B > 0 && Ha > 0 && Wa > 0 && Ho > 0 && Wo > 0 && N > 0, "mi_conv_gemm: non-positive dimension");
-    // Ca % 64 == 0: either main loop.  Ca % 32 == 0 only (the 32-padded operands of the general family's packs: HarDNet's 466 -> 480 channel
-    // gathers): the 32-channel slabs of igemm_pp_kernel take it, whatever the dispatch rule says - stride-1 / same-size launches without a residual tile
-    const bool pp_only = Ca > 0 && Ca % 64 != 0;
     MI_REQUIRE(Ca > 0 && Ca % 32 == 0, "mi_conv_gemm: Ca=%d must be a multiple of 32", Ca);
-    MI_REQUIRE(!pp_only || (stride == 1 && Ha == Ho && Wa == Wo && !(flags & (MI_EPI_RESIDUAL | MI_EPI_MASK | MI_EPI_LEAKY))),
+    MI_REQUIRE(Ca % 64 == 0 || (stride == 1 && Ha == Ho && Wa == Wo && !(flags & (MI_EPI_RESIDUAL | MI_EPI_MASK | MI_EPI_LEAKY))),
                "mi_conv_gemm: Ca=%d is not a multiple of 64: stride-1, same-size launches without residual / mask / LeakyReLU only", Ca);
     MI_REQUIRE(N % 8 == 0, "mi_conv_gemm: N=%d must be a multiple of 8", N);
     MI_REQUIRE(ksize == 1 || ksize == 3, "mi_conv_gemm: ksize=%d (1 or 3)", ksize);
@@ -412,19 +555,12 @@ int mi_conv_gemm_impl(const void* a, const void* wp, void* out, int B, int Ha, i
     if (gather_mode == MI_GATHER_FWD) {
         MI_REQUIRE((Ho - 1) * stride - pad < Ha && (Wo - 1) * stride - pad < Wa, "mi_conv_gemm: output larger than the input supports");
     }
-    // Long contractions without a residual tile go to the wide-tile ping-pong main loop (igemm_pp.hip): 7.0 instead of 13-14
-    // L2 bytes per kFLOP.  Measured per shape against this kernel in one process (tools/ppexp.py, B = 8, 97 x 97): 3x3 256 +16 %,
-    // 3x3 512 +13 %, 1x1 2048->512 +18 %, 1x1 1024->256 / 1024->2048 / ASPP forward +6 %; the short contractions (K < 512)
-    // are epilogue-bound and stay here.  MI_IGEMM_PP=0 switches the dispatch off.
-    if (pp_only) {
-        MI_REQUIRE((long)B * Ha * Wa * Ca * 2 + 2L * ((long)(ksize - 1) * dil + pad) * (Wa + 1) * Ca * 2 < (1L << 31) - (1L << 20) &&
-                       (long)ksize * ksize * N * Ca * 2 < (1L << 31) - (1L << 20),
-                   "mi_conv_gemm: Ca=%d is not a multiple of 64 and the operands exceed the 2 GiB the 32-channel main loop addresses", Ca);
-        return mi_conv_gemm_pp_impl(a, wp, out, B, Ha, Wa, Ca, Ho, Wo, N, ksize, stride, pad, dil, gather_mode, scale, bias, res, msk, mask_out, flags, zgw,
-                                    alpha, 0, stream, st);
+    MiConvPlan pl;
+    {
+        const int rc = mi_conv_plan(B, Ha, Wa, Ca, Ho, Wo, N, ksize, stride, pad, dil, flags, -1, &pl);
+        if (rc != MI_OK) return rc;
     }
-    if (mi_conv_gemm_route(B, Ha, Wa, Ca, Ho, Wo, N, ksize, stride, flags) &&
-        (long)B * Ha * Wa * Ca * 2 + 2L * ((long)(ksize - 1) * dil + pad) * (Wa + 1) * Ca * 2 < (1L << 31) - (1L << 20))     // its exact 32-bit offset bound
+    if (pl.kernel == MI_CPLAN_PP)            // mtg 0: mi_conv_gemm_pp_impl plans the same launch again (mi_conv_plan with pp_mtg = 0)
         return mi_conv_gemm_pp_impl(a, wp, out, B, Ha, Wa, Ca, Ho, Wo, N, ksize, stride, pad, dil, gather_mode, scale, bias, res, msk, mask_out, flags, zgw,
                                     alpha, 0, stream, st);
     IgemmParams p;
@@ -455,70 +591,33 @@ int mi_conv_gemm_impl(const void* a, const void* wp, void* out, int B, int Ha, i
     p.flags = flags;
     p.zgw = zgw > 0 ? zgw : 4;
     p.alpha = alpha;
-    const bool unit = stride == 1 && Ha == Ho && Wa == Wo && ksize * ksize <= 9;
-    const int force_mt = mi_sw().igemm_mt, force_bn = mi_sw().igemm_bn, pref_on = mi_sw().igemm_pref;
-    // Modelled time of one launch with tile bm x bn: rounds on the resident-workgroup slots x workgroups sharing a CU x per-K-step
-    // tile time, where a CU's share of the L2 request rate serves (bm+bn)*128 B per step (~47.6 GB/s per CU measured) and its
-    // MFMA pipes need bm*bn*128 FLOP at ~9.8 TFLOP/s per CU; the two overlap imperfectly (20 % of the shorter one is exposed).
-    auto cost = [&](int bm, int bn) {
-        const int per_cu = bn == 256 ? 1 : 2;
-        const long tiles = ((M + bm - 1) / bm) * ((N + bn - 1) / bn);
-        const long rounds = (tiles + 256 * per_cu - 1) / (256 * per_cu);
-        const double t_l2 = (bm + bn) * 128.0 / 47.6e3, t_mfma = bm * (double)bn * 128.0 / 9.77e6;      // microseconds
-        return rounds * per_cu * ((t_l2 > t_mfma ? t_l2 : t_mfma) + 0.2 * (t_l2 > t_mfma ? t_mfma : t_l2));
-    };
-    // The 256-wide tile is selectable (MI_IGEMM_BN=256) but not the default: with this loop structure (one barrier and a full
-    // vmcnt(0) drain per K-step) it measured 2-8 % slower than the 128-wide tiles on every shape of the network (bench 216 vs
-    // 223.5 images/s) although it moves 30 % fewer L2 bytes - the single resident workgroup has nothing to overlap its drains
-    // with.  It is the geometry a deeper-pipelined schedule (counted vmcnt, prefetch in flight across barriers) needs.
-#ifdef MI_EXPERIMENTS
-    const bool wide_ok = unit && N % 256 == 0 && !(flags & MI_EPI_ZSPLIT) && force_bn == 256;
-#else
-    const bool wide_ok = false;                          // the 256-wide tile is compiled into experiment builds only
-    (void)force_bn;
-#endif
-    int mt_sel = 4, bn = 128;
-    double best = cost(128, 128);
-    for (int mt = 5; mt <= 6; ++mt)
-        if (cost(32 * mt, 128) < best * 0.999) best = cost(32 * mt, 128), mt_sel = mt;
-    if (force_mt >= 4 && force_mt <= 6) mt_sel = force_mt, best = cost(32 * mt_sel, 128);
-    if (wide_ok) {
-        int wmt = 0;
-        double wbest = force_bn == 256 ? 1e30 : best;
-        for (int mt = 4; mt <= 6; ++mt)
-            if ((force_mt == 0 || force_mt == mt) && cost(32 * mt, 256) < wbest * 0.999) wbest = cost(32 * mt, 256), wmt = mt;
-        if (wmt) mt_sel = wmt, bn = 256;
-    }
-    const bool hot_set = flags == 71 || flags == 130;
-    const bool pref = bn == 128 && pref_on && unit && (flags & MI_EPI_RESIDUAL) && N % 16 == 0 && !(staged_on() && hot_set);
-    if (!unit) mt_sel = 4;                               // the general (strided) gather exists in the 128-row shape only
-    if (pref && mt_sel == 6) mt_sel = 5;                 // the prefetched rows cost 8 VGPRs per 16-row MFMA tile
-    const int bm = mt_sel * 32;
-    p.m_tiles = (int)((M + bm - 1) / bm);
-    p.n_tiles = (N + bn - 1) / bn;
+    p.m_tiles = pl.m_tiles;
+    p.n_tiles = pl.n_tiles;
     const dim3 grid(p.m_tiles * p.n_tiles);
     if (st) st->nparts = 2 * p.m_tiles;                  // one partial row per wave row (MT*16 rows)
     const hipStream_t sq = (hipStream_t)stream;
-    if (!unit)
-        launch_variant<4, false, false, 64, 2>(grid, sq, p);
+    const int epi = pl.epi;
+    const bool stg = pl.staged != 0;
+    if (!pl.unit)
+        launch_variant<4, false, false, 64, 2>(grid, sq, p, epi, stg);
 #ifdef MI_EXPERIMENTS
-    else if (bn == 256 && mt_sel == 6)
-        launch_variant<6, true, false, 64, 4>(grid, sq, p);
-    else if (bn == 256 && mt_sel == 5)
-        launch_variant<5, true, false, 64, 4>(grid, sq, p);
-    else if (bn == 256)
-        launch_variant<4, true, false, 64, 4>(grid, sq, p);
+    else if (pl.bn == 256 && pl.mt == 6)
+        launch_variant<6, true, false, 64, 4>(grid, sq, p, epi, stg);
+    else if (pl.bn == 256 && pl.mt == 5)
+        launch_variant<5, true, false, 64, 4>(grid, sq, p, epi, stg);
+    else if (pl.bn == 256)
+        launch_variant<4, true, false, 64, 4>(grid, sq, p, epi, stg);
 #endif
-    else if (pref && mt_sel == 5)
-        launch_variant<5, true, true, 64, 2>(grid, sq, p);
-    else if (pref)
-        launch_variant<4, true, true, 64, 2>(grid, sq, p);
-    else if (mt_sel == 6)
-        launch_variant<6, true, false, 64, 2>(grid, sq, p);
-    else if (mt_sel == 5)
-        launch_variant<5, true, false, 64, 2>(grid, sq, p);
+    else if (pl.pref && pl.mt == 5)
+        launch_variant<5, true, true, 64, 2>(grid, sq, p, epi, stg);
+    else if (pl.pref)
+        launch_variant<4, true, true, 64, 2>(grid, sq, p, epi, stg);
+    else if (pl.mt == 6)
+        launch_variant<6, true, false, 64, 2>(grid, sq, p, epi, stg);
+    else if (pl.mt == 5)
+        launch_variant<5, true, false, 64, 2>(grid, sq, p, epi, stg);
     else
-        launch_variant<4, true, false, 64, 2>(grid, sq, p);
+        launch_variant<4, true, false, 64, 2>(grid, sq, p, epi, stg);
     MI_CHECK_LAUNCH("mi_conv_gemm");
     return MI_OK;
 }

@@ -625,14 +625,15 @@ void launch_pp(dim3 grid, hipStream_t stream, const IgemmParams& p) {
     hipLaunchKernelGGL(kern, grid, dim3(512), lds, stream, p);
 }
 
+// epi: the plan's compile-time epilogue set (mi_conv_plan, igemm_nt.hip), -1 = generic
 template <int MTG, bool RR>
-void launch_pp_flags(dim3 grid, hipStream_t stream, const IgemmParams& p) {
-    if (p.flags == 69) return launch_pp<MTG, 69, RR>(grid, stream, p);       // FrozenBN + ReLU + sign bits (conv forward)
-    if (p.flags == 128) return launch_pp<MTG, 128, RR>(grid, stream, p);     // ReLU backward from sign bits (data gradient)
-    if (p.flags == 0) return launch_pp<MTG, 0, RR>(grid, stream, p);         // plain bf16 store (downsample data gradient, ASPP data gradient)
-    if (p.flags == 1) return launch_pp<MTG, 1, RR>(grid, stream, p);         // FrozenBN only (downsample forward)
-    if (p.flags == 48) return launch_pp<MTG, 48, RR>(grid, stream, p);       // fp32 tap planes (ASPP forward)
-    if (p.flags == MI_EPI_STATS) return launch_pp<MTG, MI_EPI_STATS, RR>(grid, stream, p);      // plain store + BatchNorm tile statistics
+void launch_pp_flags(dim3 grid, hipStream_t stream, const IgemmParams& p, int epi) {
+    if (epi == 69) return launch_pp<MTG, 69, RR>(grid, stream, p);       // FrozenBN + ReLU + sign bits (conv forward)
+    if (epi == 128) return launch_pp<MTG, 128, RR>(grid, stream, p);     // ReLU backward from sign bits (data gradient)
+    if (epi == 0) return launch_pp<MTG, 0, RR>(grid, stream, p);         // plain bf16 store (downsample data gradient, ASPP data gradient)
+    if (epi == 1) return launch_pp<MTG, 1, RR>(grid, stream, p);         // FrozenBN only (downsample forward)
+    if (epi == 48) return launch_pp<MTG, 48, RR>(grid, stream, p);       // fp32 tap planes (ASPP forward)
+    if (epi == MI_EPI_STATS) return launch_pp<MTG, MI_EPI_STATS, RR>(grid, stream, p);      // plain store + BatchNorm tile statistics
     launch_pp<MTG, -1, RR>(grid, stream, p);
 }
 
@@ -702,7 +703,7 @@ int mi_conv_gemm_pp_impl(const void* a, const void* wp, void* out, int B, int Ha
     p.alpha = alpha;
     p.stats = st ? st->partial : nullptr;
     p.pilot = st ? st->pilot : nullptr;
-    p.korder = ksize > 1 ? mi_sw().pp_korder : 0;              // MI_IGEMM_PP_KORDER=0: tap-major contraction (the order of igemm_nt_kernel; bit-equal to it)
+    p.korder = 0;                                              // set from the plan below
 #ifdef MI_PP_TRACE
     p.korder |= mi_sw().pp_trace_wg << 8;
 #endif
@@ -727,35 +728,32 @@ int mi_conv_gemm_pp_impl(const void* a, const void* wp, void* out, int B, int Ha
     }
 #endif
     if (mtg == 3) return mi_set_error(MI_EINVAL, "mi_conv_gemm_pp: mtg 3 (shared-window kernel, experiment builds only) needs a 3x3 conv with pad == dil <= 8 and flags 69 or 128");
-    {   // 32-bit buffer offsets (bit 31 marks a padded chunk): operands and the largest tap excursion must stay below 2 GiB
-        const long a_bytes = (long)B * Ha * Wa * Ca * 2 + 2L * ((long)(ksize - 1) * dil + pad) * (Wa + 1) * Ca * 2;
-        const long w_bytes = (long)ksize * ksize * N * Ca * 2;
-        MI_REQUIRE(a_bytes < (1L << 31) - (1L << 20) && w_bytes < (1L << 31) - (1L << 20), "mi_conv_gemm_pp: operand larger than 2 GiB");
-    }
     bool rolling = mi_sw().pp_loop != 0;   // MI_IGEMM_PP_LOOP (read in experiment builds only); an explicit mtg of 108 / 110 (8 / 10) selects the rolling (ping-pong) loop
     if (mtg == 108 || mtg == 110) rolling = true, mtg -= 100;
     else if (mtg == 8 || mtg == 10) rolling = false;
-    if (mtg != 8 && mtg != 10) {           // fewest rounds on 256 CUs, then the least padding
-        auto rounds = [&](int bm) { return (((M + bm - 1) / bm) * ((N + 255) / 256) + 255) / 256; };
-        mtg = rounds(320) < rounds(256) ? 10 : (rounds(256) < rounds(320) ? 8 : (((M + 319) / 320) * 320 <= ((M + 255) / 256) * 256 ? 10 : 8));
+    MiConvPlan pl;         // tile height, K order, epilogue instantiation, 2 GiB bound: mi_conv_plan (igemm_nt.hip)
+    {
+        const int rc = mi_conv_plan(B, Ha, Wa, Ca, Ho, Wo, N, ksize, stride, pad, dil, flags, (mtg == 8 || mtg == 10) ? mtg : 0, &pl);
+        if (rc != MI_OK) return rc;
     }
-    const int bm = 32 * mtg;
-    p.m_tiles = (int)((M + bm - 1) / bm);
-    p.n_tiles = (N + 255) / 256;
+    mtg = pl.mt;
+    p.korder |= pl.korder;
+    p.m_tiles = pl.m_tiles;
+    p.n_tiles = pl.n_tiles;
     const dim3 grid(p.m_tiles * p.n_tiles);
     if (st) st->nparts = 2 * p.m_tiles;                    // one partial row per wave group (MTG*16 rows)
 #ifdef MI_EXPERIMENTS      // the rolling loop does not win (header): experiment builds only (tools/experiments/build.sh, tools/rrexp.py)
     if (rolling) {
-        if (mtg == 10) launch_pp_flags<10, true>(grid, (hipStream_t)stream, p);
-        else launch_pp_flags<8, true>(grid, (hipStream_t)stream, p);
+        if (mtg == 10) launch_pp_flags<10, true>(grid, (hipStream_t)stream, p, pl.epi);
+        else launch_pp_flags<8, true>(grid, (hipStream_t)stream, p, pl.epi);
         MI_CHECK_LAUNCH("mi_conv_gemm_pp (rolling loop)");
         return MI_OK;
     }
 #else
     if (rolling) return mi_set_error(MI_EINVAL, "mi_conv_gemm_pp: the rolling main loop (mtg 108 / 110, MI_IGEMM_PP_LOOP=1) exists in experiment builds only");
 #endif
-    if (mtg == 10) launch_pp_flags<10, false>(grid, (hipStream_t)stream, p);
-    else launch_pp_flags<8, false>(grid, (hipStream_t)stream, p);
+    if (mtg == 10) launch_pp_flags<10, false>(grid, (hipStream_t)stream, p, pl.epi);
+    else launch_pp_flags<8, false>(grid, (hipStream_t)stream, p, pl.epi);
     MI_CHECK_LAUNCH("mi_conv_gemm_pp");
     return MI_OK;
 }

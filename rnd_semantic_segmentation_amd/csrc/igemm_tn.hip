@@ -1282,23 +1282,101 @@ static int launch_p3(const void* dy, const void* x, float* ws, int H, int W, int
 #endif
 }
 
-// which kernel mi_conv_wgrad launches for a shape: 0 wgrad_tn_kernel (128 x 128 per tap), 1 wgrad_tn256_kernel, 2 wgrad_p3_kernel,
-// 3 wgrad_q3_kernel, 4 wgrad_s4_kernel (measurement tools; same rules as the dispatch below)
-extern "C" int mi_conv_wgrad_route(int B, int Ha, int Wa, int I, int Ho, int Wo, int O, int ksize, int stride, int pad, int dil, int out_map) {
+// Every decision of a weight-gradient launch in one place: kernel, addressing mode, K split, tiles.  mi_conv_wgrad_impl launches what this says;
+// mi_conv_wgrad_plan / mi_conv_wgrad_route report it (host only).  deferred: the mi_conv_wgrad_partial form (it runs beside a data-gradient chain).
+struct WgradPlan {
+    int kernel;            // MI_WPLAN_TN | _TN256 | _P3 | _Q3 | _S4
+    int mode;              // tn: MODE of wgrad_tn_kernel (0 general gather, 1 unit stride, 2 pointwise with 32-bit offsets); tn256: 1 | 2; else 0
+    int S;                 // K splits
+    int steps;             // K steps per split (q3 / p3: slabs of P3_KS padded pixels per split)
+    int step_rows;         // pixels per K step
+    int o_tiles, i_tiles;
+    int deferred;
+    P3Plan p3;             // q3 / p3 only
+};
+static void wgrad_plan(int B, int Ha, int Wa, int I, int Ho, int Wo, int O, int ksize, int stride, int pad, int dil, int out_map, bool deferred,
+                       size_t workspace_bytes, WgradPlan& w) {
+    w = WgradPlan{};
+    w.deferred = deferred;
+    const long M = (long)B * Ho * Wo;
+    const int T = ksize * ksize;
+    const bool same = stride == 1 && Ha == Ho && Wa == Wo;
+    // 3x3, stride 1, pad == dilation <= 8: the fused-row kernels (three taps per x window).
+    // MI_WGRAD_P3: 0 = never (default), 1 = by the plan's own rule, 2 = whenever the geometry allows (tests: tiny shapes).
+    // Opt-in because it does not win yet: at 256 -> 256, d = 2, M = 75 272 it takes 127 us against 131 us for the per-tap
+    // kernel (512 -> 512: 404 vs 405).  Its parts, measured with the MI_P3_DBG toggles (tools/wgexp.py): MFMAs alone 42 us,
+    // LDS->register reads 25 us, DMA alone 49 us - the same with L2-hot rows (~43 GB/s per CU; a bare stream of the same shape
+    // reaches 120 GB/s from the L2, tools/micro/l2lds.hip, so the DMA issue beside the partner's MFMAs is what was measured) -,
+    // partial-plane stores 14 us, slab reducer 23 us.  With the DMA at 115 % of the MFMA time the ping-pong's read segments
+    // (which carry the DMA issue) outlast the MFMA segments and the two hardly overlap (main loop 80 us).
 #ifdef MI_EXPERIMENTS
     const int p3_mode = mi_sw().wgrad_p3;
 #else
     const int p3_mode = 0;                       // the 8-wave fused-row kernel is not in the product library
 #endif
+    // the 4-wave fused-row kernel: MI_WGRAD_Q3 0 = never, 1 = by the plan's rule (default), 2 = whenever the geometry allows (tests)
     const int q3_mode = mi_sw().wgrad_q3;
-    const bool fused_ok = out_map == 0 && ksize == 3 && stride == 1 && Ha == Ho && Wa == Wo && pad == dil;
-    P3Plan pl;
-    if (fused_ok && q3_mode && !p3_mode && p3_plan(B, Ho, Wo, O, I, dil, q3_mode == 2, pl, true)) return 3;
-    if (fused_ok && p3_mode && p3_plan(B, Ho, Wo, O, I, dil, p3_mode == 2, pl)) return 2;
-    if (use_tn256(O, I, ksize, pad, stride, Ha, Ho, Wa, Wo)) return 1;
-    const long M = (long)B * Ho * Wo;
-    if (mi_sw().wgrad_s4 && ksize == 1 && pad == 0 && stride == 1 && Ha == Ho && Wa == Wo && M * (O > I ? O : I) * 2 < (1L << 31)) return 4;
-    return 0;
+    const bool fused_ok = out_map == 0 && ksize == 3 && same && pad == dil;
+    for (int q3 = 1; q3 >= 0; --q3) {
+        const int mode = q3 ? (p3_mode ? 0 : q3_mode) : p3_mode;
+        if (!fused_ok || !mode) continue;
+        P3Plan pl;
+        if (p3_plan(B, Ho, Wo, O, I, dil, mode == 2, pl, q3 != 0, q3 && deferred) && (size_t)pl.S * 9 * O * I * sizeof(float) <= workspace_bytes) {
+            w.kernel = q3 ? MI_WPLAN_Q3 : MI_WPLAN_P3;
+            w.S = pl.S;
+            w.steps = pl.slabs_per_split;
+            w.step_rows = P3_KS;
+            w.o_tiles = pl.o_tiles;
+            w.i_tiles = pl.i_tiles;
+            w.p3 = pl;
+            return;
+        }
+    }
+    w.o_tiles = (O + TO - 1) / TO;
+    // MODE 2 / the deep stream address a split's rows through 32-bit buffer offsets: operands of 2 GiB or more take the pointer-arithmetic kernel
+    const bool small32 = (long)M * (O > I ? O : I) * 2 < (1L << 31);
+    const bool pointwise = same && ksize == 1 && pad == 0;
+    if (use_tn256(O, I, ksize, pad, stride, Ha, Ho, Wa, Wo)) {
+        w.kernel = MI_WPLAN_TN256;
+        w.mode = pointwise ? 2 : 1;
+        w.i_tiles = (I + TI2 - 1) / TI2;
+        w.S = pick_splits256(M, w.o_tiles * w.i_tiles * T);
+        w.step_rows = KP2;
+    } else if (mi_sw().wgrad_s4 && pointwise && small32) {      // MI_WGRAD_S4=0: the 64-pixel double-buffer kernel for the 1x1 / stride-1 weight gradients too
+        w.kernel = MI_WPLAN_S4;
+        w.i_tiles = (I + TI - 1) / TI;
+        w.S = pick_splits_s4(M, w.o_tiles * w.i_tiles);
+        w.step_rows = KP4;
+    } else {
+        w.kernel = MI_WPLAN_TN;
+        w.mode = pointwise && small32 ? 2 : (same ? 1 : 0);
+        w.i_tiles = (I + TI - 1) / TI;
+        w.S = pick_splits(M, w.o_tiles * w.i_tiles * T);
+        w.step_rows = KP;
+    }
+    const long steps = (M + w.step_rows - 1) / w.step_rows;
+    w.steps = (int)((steps + w.S - 1) / w.S);
+}
+
+// which kernel mi_conv_wgrad launches for a shape: 0 wgrad_tn_kernel (128 x 128 per tap), 1 wgrad_tn256_kernel, 2 wgrad_p3_kernel,
+// 3 wgrad_q3_kernel, 4 wgrad_s4_kernel (measurement tools): the kernel of mi_conv_wgrad_plan's one-call plan
+extern "C" int mi_conv_wgrad_route(int B, int Ha, int Wa, int I, int Ho, int Wo, int O, int ksize, int stride, int pad, int dil, int out_map) {
+    WgradPlan w;
+    wgrad_plan(B, Ha, Wa, I, Ho, Wo, O, ksize, stride, pad, dil, out_map, false, mi_conv_wgrad_workspace(B, Ho, Wo, O, I, ksize), w);
+    return w.kernel;
+}
+
+extern "C" int mi_conv_wgrad_plan(int B, int Ha, int Wa, int I, int Ho, int Wo, int O, int ksize, int stride, int pad, int dil, int out_map, int deferred,
+                                  int* plan) {
+    MI_REQUIRE(plan, "mi_conv_wgrad_plan: null plan");
+    MI_REQUIRE(B > 0 && Ha > 0 && Wa > 0 && Ho > 0 && Wo > 0 && O > 0 && I > 0, "mi_conv_wgrad_plan: non-positive dimension");
+    MI_REQUIRE(ksize == 1 || ksize == 3, "mi_conv_wgrad_plan: ksize");
+    MI_REQUIRE(stride >= 1 && dil >= 1 && pad >= 0, "mi_conv_wgrad_plan: bad stride/dil/pad");
+    WgradPlan w;       // the workspace a caller must bring (mi_conv_wgrad_workspace) holds every plan's partial planes
+    wgrad_plan(B, Ha, Wa, I, Ho, Wo, O, ksize, stride, pad, dil, out_map, deferred != 0, mi_conv_wgrad_workspace(B, Ho, Wo, O, I, ksize), w);
+    const int v[MI_WPLAN_LEN] = {w.kernel, w.mode, w.S, w.steps, w.step_rows, w.o_tiles, w.i_tiles, w.deferred};
+    for (int k = 0; k < MI_WPLAN_LEN; ++k) plan[k] = v[k];
+    return MI_OK;
 }
 
 // One reducer launch (defer == nullptr: right behind the main kernel, as always) or a job for mi_conv_wgrad_reduce (defer != nullptr)
@@ -1334,36 +1412,13 @@ static int mi_conv_wgrad_impl(const void* dy, const void* x, float* dw, int B, i
     MI_REQUIRE(M < (1L << 31) && (long)B * Ha * Wa < (1L << 31), "mi_conv_wgrad: pixel count overflows int32");
     const size_t need = mi_conv_wgrad_workspace(B, Ho, Wo, O, I, ksize);
     if (workspace_bytes < need) return mi_set_error(MI_ENOMEM, "mi_conv_wgrad: workspace %zu < %zu", workspace_bytes, need);
-    // 3x3, stride 1, pad == dilation <= 8: the fused-row kernel (three taps per x window, ping-pong main loop).
-    // MI_WGRAD_P3: 0 = never (default), 1 = by the plan's own rule, 2 = whenever the geometry allows (tests: tiny shapes).
-    // Opt-in because it does not win yet: at 256 -> 256, d = 2, M = 75 272 it takes 127 us against 131 us for the per-tap
-    // kernel (512 -> 512: 404 vs 405).  Its parts, measured with the MI_P3_DBG toggles (tools/wgexp.py): MFMAs alone 42 us,
-    // LDS->register reads 25 us, DMA alone 49 us - the same with L2-hot rows (~43 GB/s per CU; a bare stream of the same shape
-    // reaches 120 GB/s from the L2, tools/micro/l2lds.hip, so the DMA issue beside the partner's MFMAs is what was measured) -,
-    // partial-plane stores 14 us, slab reducer 23 us.  With the DMA at 115 % of the MFMA time the ping-pong's read segments
-    // (which carry the DMA issue) outlast the MFMA segments and the two hardly overlap (main loop 80 us).
-#ifdef MI_EXPERIMENTS
-    const int p3_mode = mi_sw().wgrad_p3;
-#else
-    const int p3_mode = 0;
-#endif
-    // the 4-wave fused-row kernel: MI_WGRAD_Q3 0 = never, 1 = by the plan's rule (default), 2 = whenever the geometry allows (tests)
-    const int q3_mode = mi_sw().wgrad_q3;
-    if (q3_mode && !p3_mode && out_map == 0 && ksize == 3 && stride == 1 && Ha == Ho && Wa == Wo && pad == dil) {
-        P3Plan pl;
-        if (p3_plan(B, Ho, Wo, O, I, dil, q3_mode == 2, pl, true, defer != nullptr) && (size_t)pl.S * 9 * O * I * sizeof(float) <= workspace_bytes) {
-            launch_p3(dy, x, (float*)workspace, Ho, Wo, O, I, dil, pl, B * Ho, (hipStream_t)stream, true);
-            MI_CHECK_LAUNCH("mi_conv_wgrad (fused 3x3 rows, 4 waves)");
-            return wgrad_finish(defer, (hipStream_t)stream, (const float*)workspace, dw, scale_o, pl.S, 9, O, I, accumulate, 0, 1, O);
-        }
-    }
-    if (p3_mode && out_map == 0 && ksize == 3 && stride == 1 && Ha == Ho && Wa == Wo && pad == dil) {
-        P3Plan pl;
-        if (p3_plan(B, Ho, Wo, O, I, dil, p3_mode == 2, pl) && (size_t)pl.S * 9 * O * I * sizeof(float) <= workspace_bytes) {
-            launch_p3(dy, x, (float*)workspace, Ho, Wo, O, I, dil, pl, B * Ho, (hipStream_t)stream);
-            MI_CHECK_LAUNCH("mi_conv_wgrad (fused 3x3 rows)");
-            return wgrad_finish(defer, (hipStream_t)stream, (const float*)workspace, dw, scale_o, pl.S, 9, O, I, accumulate, 0, 1, O);
-        }
+    WgradPlan w;
+    wgrad_plan(B, Ha, Wa, I, Ho, Wo, O, ksize, stride, pad, dil, out_map, defer != nullptr, workspace_bytes, w);
+    if (w.kernel == MI_WPLAN_Q3 || w.kernel == MI_WPLAN_P3) {
+        if (launch_p3(dy, x, (float*)workspace, Ho, Wo, O, I, dil, w.p3, B * Ho, (hipStream_t)stream, w.kernel == MI_WPLAN_Q3) != 0)
+            return mi_set_error(MI_EINVAL, "mi_conv_wgrad: the 8-wave fused-row kernel exists in experiment builds only");
+        MI_CHECK_LAUNCH("mi_conv_wgrad (fused 3x3 rows)");
+        return wgrad_finish(defer, (hipStream_t)stream, (const float*)workspace, dw, scale_o, w.S, 9, O, I, accumulate, 0, 1, O);
     }
     WgradParams p;
     p.dY = (const __bf16*)dy;
@@ -1381,55 +1436,39 @@ static int mi_conv_wgrad_impl(const void* dy, const void* x, float* dw, int B, i
     p.stride = stride;
     p.pad = pad;
     p.dil = dil;
-    p.o_tiles = (O + TO - 1) / TO;
-    const bool wide = use_tn256(O, I, ksize, pad, stride, Ha, Ho, Wa, Wo);
-    if (wide) {
-        p.i_tiles = (I + TI2 - 1) / TI2;
-        p.S = pick_splits256(M, p.o_tiles * p.i_tiles * p.T);
-        const long steps2 = (M + KP2 - 1) / KP2;
-        p.rows_per_split = (int)(((steps2 + p.S - 1) / p.S) * KP2);
+    p.o_tiles = w.o_tiles;
+    p.i_tiles = w.i_tiles;
+    p.S = w.S;
+    p.rows_per_split = w.steps * w.step_rows;
+    const hipStream_t sq = (hipStream_t)stream;
+    if (w.kernel == MI_WPLAN_TN256) {
         static std::atomic<uint64_t> attr2[2];
         mi_allow_dynamic_lds((const void*)wgrad_tn256_kernel<1>, LDS2_BYTES, attr2[0]);
         mi_allow_dynamic_lds((const void*)wgrad_tn256_kernel<2>, LDS2_BYTES, attr2[1]);
         const unsigned nb = (unsigned)(p.o_tiles * p.i_tiles * p.T * p.S);
-        if (ksize == 1 && pad == 0)
-            hipLaunchKernelGGL(wgrad_tn256_kernel<2>, dim3(nb), dim3(256), LDS2_BYTES, (hipStream_t)stream, p);
+        if (w.mode == 2)
+            hipLaunchKernelGGL(wgrad_tn256_kernel<2>, dim3(nb), dim3(256), LDS2_BYTES, sq, p);
         else
-            hipLaunchKernelGGL(wgrad_tn256_kernel<1>, dim3(nb), dim3(256), LDS2_BYTES, (hipStream_t)stream, p);
+            hipLaunchKernelGGL(wgrad_tn256_kernel<1>, dim3(nb), dim3(256), LDS2_BYTES, sq, p);
         MI_CHECK_LAUNCH("mi_conv_wgrad (128 x 256 tile)");
-    }
-    const int s4_mode = mi_sw().wgrad_s4;                 // MI_WGRAD_S4=0: the 64-pixel double-buffer kernel for the 1x1 / stride-1 weight gradients too
-    const bool deep = !wide && s4_mode && ksize == 1 && pad == 0 && stride == 1 && Ha == Ho && Wa == Wo && (long)M * (O > I ? O : I) * 2 < (1L << 31);
-    if (deep) {
-        p.i_tiles = (I + TI - 1) / TI;
-        p.S = pick_splits_s4(M, p.o_tiles * p.i_tiles);
-        const long steps4 = (M + KP4 - 1) / KP4;
-        p.rows_per_split = (int)(((steps4 + p.S - 1) / p.S) * KP4);
+    } else if (w.kernel == MI_WPLAN_S4) {
         static std::atomic<uint64_t> attr4;
         mi_allow_dynamic_lds((const void*)wgrad_s4_kernel, LDS4_BYTES, attr4);
-        hipLaunchKernelGGL(wgrad_s4_kernel, dim3((unsigned)(p.o_tiles * p.i_tiles * p.S)), dim3(256), LDS4_BYTES, (hipStream_t)stream, p);
+        hipLaunchKernelGGL(wgrad_s4_kernel, dim3((unsigned)(p.o_tiles * p.i_tiles * p.S)), dim3(256), LDS4_BYTES, sq, p);
         MI_CHECK_LAUNCH("mi_conv_wgrad (1x1 deep stream)");
-    }
-    if (!wide && !deep) {
-    p.i_tiles = (I + TI - 1) / TI;
-    p.S = pick_splits(M, p.o_tiles * p.i_tiles * p.T);
-    const long steps = (M + KP - 1) / KP;
-    p.rows_per_split = (int)(((steps + p.S - 1) / p.S) * KP);
-    static std::atomic<uint64_t> attr_set[3];
-    mi_allow_dynamic_lds((const void*)wgrad_tn_kernel<0>, LDS_BYTES, attr_set[0]);
-    mi_allow_dynamic_lds((const void*)wgrad_tn_kernel<1>, LDS_BYTES, attr_set[1]);
-    mi_allow_dynamic_lds((const void*)wgrad_tn_kernel<2>, LDS_BYTES, attr_set[2]);
-    const unsigned nblocks = (unsigned)(p.o_tiles * p.i_tiles * p.T * p.S);
-    const bool unit = stride == 1 && Ha == Ho && Wa == Wo;
-    // MODE 2 addresses a split's rows through 32-bit buffer offsets: operands of 2 GiB or more take the pointer-arithmetic kernel
-    const bool small32 = (long)M * (O > I ? O : I) * 2 < (1L << 31);
-    if (unit && ksize == 1 && pad == 0 && small32)
-        hipLaunchKernelGGL(wgrad_tn_kernel<2>, dim3(nblocks), dim3(256), LDS_BYTES, (hipStream_t)stream, p);
-    else if (unit)
-        hipLaunchKernelGGL(wgrad_tn_kernel<1>, dim3(nblocks), dim3(256), LDS_BYTES, (hipStream_t)stream, p);
-    else
-        hipLaunchKernelGGL(wgrad_tn_kernel<0>, dim3(nblocks), dim3(256), LDS_BYTES, (hipStream_t)stream, p);
-    MI_CHECK_LAUNCH("mi_conv_wgrad");
+    } else {
+        static std::atomic<uint64_t> attr_set[3];
+        mi_allow_dynamic_lds((const void*)wgrad_tn_kernel<0>, LDS_BYTES, attr_set[0]);
+        mi_allow_dynamic_lds((const void*)wgrad_tn_kernel<1>, LDS_BYTES, attr_set[1]);
+        mi_allow_dynamic_lds((const void*)wgrad_tn_kernel<2>, LDS_BYTES, attr_set[2]);
+        const unsigned nblocks = (unsigned)(p.o_tiles * p.i_tiles * p.T * p.S);
+        if (w.mode == 2)
+            hipLaunchKernelGGL(wgrad_tn_kernel<2>, dim3(nblocks), dim3(256), LDS_BYTES, sq, p);
+        else if (w.mode == 1)
+            hipLaunchKernelGGL(wgrad_tn_kernel<1>, dim3(nblocks), dim3(256), LDS_BYTES, sq, p);
+        else
+            hipLaunchKernelGGL(wgrad_tn_kernel<0>, dim3(nblocks), dim3(256), LDS_BYTES, sq, p);
+        MI_CHECK_LAUNCH("mi_conv_wgrad");
     }
     int o_real = O;
     if (out_map == 1) o_real = 36 * ncls;

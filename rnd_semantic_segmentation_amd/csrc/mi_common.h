@@ -70,6 +70,19 @@ int mi_conv_gemm_impl(const void* a, const void* wp, void* out, int B, int Ha, i
 int mi_conv_gemm_pp_impl(const void* a, const void* wp, void* out, int B, int Ha, int Wa, int Ca, int Ho, int Wo, int N, int ksize, int stride, int pad,
                          int dil, int gather_mode, const float* scale, const float* bias, const void* res, const void* msk, void* mask_out, int flags,
                          int zgw, float alpha, int mtg, void* stream, MiConvStats* st);
+// What a conv launch runs (igemm_nt.hip: mi_conv_plan): mi_conv_gemm_impl / mi_conv_gemm_pp_impl launch exactly this, mi_conv_gemm_plan reports it.
+struct MiConvPlan {
+    int kernel;            // MI_CPLAN_NT (igemm_nt_kernel) | MI_CPLAN_PP (igemm_pp_kernel)
+    int mt;                // nt: MT (4..6, tile rows = 32 * MT); pp: MTG (8 | 10)
+    int bn;                // tile columns: nt 128 (256: experiment builds), pp 256
+    int unit, pref, staged;      // nt: unit-stride gather, prefetched residual rows, staged (LDS) epilogue
+    int epi;               // compile-time epilogue flag set of the instantiation; -1: the generic epilogue (flags read from the parameters)
+    int korder;            // pp: IgemmParams::korder
+    int m_tiles, n_tiles;
+    int slots, rounds;     // workgroup slots the tile picker assumed and the rounds the grid takes on them
+};
+// pp_mtg < 0: mi_conv_gemm's dispatch between the two main loops; >= 0: mi_conv_gemm_pp with that tile height (0: choose, 8 | 10)
+int mi_conv_plan(int B, int Ha, int Wa, int Ca, int Ho, int Wo, int N, int ksize, int stride, int pad, int dil, int flags, int pp_mtg, MiConvPlan* pl);
 // BatchNorm finalize arguments (mi_bn_finalize's), for launches that finalize in the same kernel as their last reduction level
 struct MiBnFinal {
     const float* pilot;

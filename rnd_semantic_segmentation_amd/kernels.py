@@ -4,6 +4,7 @@ Layout: every activation handled here is an NHWC-contiguous tensor [B,H,W,C]
 (bf16 unless stated).  Callers that hold NCHW-shaped channels_last tensors pass
 `x.permute(0, 2, 3, 1)` (a free view).
 """
+import collections
 import ctypes
 
 import torch
@@ -48,6 +49,58 @@ def _chk(t, dtype, name):
     if not t.is_contiguous():
         raise _lib.MiError("%s must be contiguous" % name)
     return t
+
+
+# Optional record of what the conv launches of this module ran (the protocol of gk.ROUTES): set to a set() to collect the ConvPlan / WgradPlan of every
+# conv_gemm, conv_gemm_stats and conv_wgrad call (the host queries below, which share their planning functions with the launches); None = no overhead.
+ROUTES = None
+
+
+class ConvPlan(collections.namedtuple("ConvPlan", "flags kernel mt unit pref staged epi korder m_tiles n_tiles rounds slots")):
+    """flags (the epilogue flags of the call), then include/mi355seg.h mi_conv_gemm_plan's descriptor (MI_CPLAN_LEN fields, in its order).  `name` separates
+    every instantiation the product library launches; a generic epilogue (epi -1) is named by the flags it reads, g<flags>."""
+    __slots__ = ()
+
+    @property
+    def name(self):
+        epi = "stats" if self.epi == 512 else ("e%d" % self.epi if self.epi >= 0 else "g%d" % self.flags)
+        if self.kernel == 1:
+            return "pp.mtg%d.%s.k%d" % (self.mt, epi, self.korder)
+        return "nt.mt%d.%s%s.%s%s" % (self.mt, "unit" if self.unit else "gen", ".pref" if self.pref else "", epi, ".stg" if self.staged else "")
+
+
+class WgradPlan(collections.namedtuple("WgradPlan", "out_map kernel mode S steps step_rows o_tiles i_tiles deferred")):
+    """out_map of the call, then include/mi355seg.h mi_conv_wgrad_plan's descriptor (MI_WPLAN_LEN fields, in its order).  `name`: main kernel (with its
+    addressing mode), .aspp for the scattering reducer of out_map 1, .deferred for the mi_conv_wgrad_partial form."""
+    __slots__ = ()
+
+    @property
+    def name(self):
+        k = ("tn.m%d" % self.mode, "tn256.m%d" % self.mode, "p3", "q3", "s4")[self.kernel]
+        return k + (".aspp" if self.out_map else "") + (".deferred" if self.deferred else "")
+
+
+CPLAN_LEN, WPLAN_LEN = len(ConvPlan._fields) - 1, len(WgradPlan._fields) - 1        # MI_CPLAN_LEN, MI_WPLAN_LEN (tests/test_host_conv_routes.py)
+
+
+def conv_gemm_plan(a_shape, N, out_hw, ksize=1, stride=1, pad=0, dil=1, flags=0, wide=None):
+    """What conv_gemm (wide: its `wide`) / conv_gemm_stats (flags 512) launch for an a of shape [B,Ha,Wa,Ca]: host only.  wide: None, 0, 8 or 10 - the
+    query knows the product library's tile heights only, so while ROUTES records, conv_gemm(wide=108 | 110) (the rolling loop of experiment builds) and
+    arguments no plan exists for raise here, before the launch that would have refused them."""
+    B, Ha, Wa, Ca = a_shape
+    r = (ctypes.c_int * CPLAN_LEN)()
+    check(_lib.lib().mi_conv_gemm_plan(B, Ha, Wa, Ca, out_hw[0], out_hw[1], N, ksize, stride, pad, dil, flags, -1 if wide is None else int(wide), r),
+          "mi_conv_gemm_plan")
+    return ConvPlan(flags, *r)
+
+
+def conv_wgrad_plan(dy_shape, x_shape, ksize=1, stride=1, pad=0, dil=1, out_map=0, deferred=False):
+    """What conv_wgrad (deferred: its batch= form) launches for dy [B,Ho,Wo,O] and x [B,Ha,Wa,I]: host only."""
+    B, Ho, Wo, O = dy_shape
+    _, Ha, Wa, I = x_shape
+    r = (ctypes.c_int * WPLAN_LEN)()
+    check(_lib.lib().mi_conv_wgrad_plan(B, Ha, Wa, I, Ho, Wo, O, ksize, stride, pad, dil, out_map, int(deferred), r), "mi_conv_wgrad_plan")
+    return WgradPlan(out_map, *r)
 
 
 def pack_weight_fwd(w, out=None):
@@ -134,6 +187,8 @@ def conv_gemm(a, wp, out_hw, ksize=1, stride=1, pad=0, dil=1, mode=GATHER_FWD, s
     n_real = N * flop_cols // zsplit if (zsplit and flop_cols) else N
     ca_real = flop_cols if (Ca == ASPP_KPAD and flop_cols) else Ca
     flops = 2.0 * B * Ho * Wo * n_real * ca_real * ksize * ksize
+    if ROUTES is not None:
+        ROUTES.add(conv_gemm_plan(a.shape, N, out_hw, ksize, stride, pad, dil, flags, wide))
     if wide is not None:
         check(_lib.lib().mi_conv_gemm_pp(_p(a), _p(wp), _p(out), B, Ha, Wa, Ca, Ho, Wo, N, ksize, stride, pad, dil, mode, _p(scale), _p(bias), _p(res),
                                          _p(msk), _p(mask_out), flags, zsplit, float(leaky), int(wide), _stream()), "mi_conv_gemm_pp")
@@ -151,11 +206,12 @@ def conv_gemm(a, wp, out_hw, ksize=1, stride=1, pad=0, dil=1, mode=GATHER_FWD, s
 _ws_cache = {}
 
 
-def conv_gemm_stats(a, wp, out_hw, ksize, stride, pad, dil, pilot, bn=None):
+def conv_gemm_stats(a, wp, out_hw, ksize, stride, pad, dil, pilot, bn=None, out=None, sums=None):
     """conv_gemm with a plain bf16 store that also returns the BatchNorm statistics of its output, taken in the epilogue: (out, sums, fin) with
     sums[0][n] = sum (out - pilot[n]), sums[1][n] = sum (out - pilot[n])^2 ([2, N] fp32) - bn_colsum2(out, pilot) without the extra read.
     bn (an nn.BatchNorm2d whose statistics are NOT shared across ranks): the last reduction launch also finalizes them (bn_finalize's result `fin`
-    and running-statistics update, count = the pixels of this tensor); otherwise fin is None."""
+    and running-statistics update, count = the pixels of this tensor); otherwise fin is None.  out / sums: tensors to write into (tests: carved from
+    sentinel-filled allocations)."""
     _chk(a, torch.bfloat16, "a")
     _chk(wp, torch.bfloat16, "wp")
     _chk(pilot, torch.float32, "pilot")
@@ -164,8 +220,14 @@ def conv_gemm_stats(a, wp, out_hw, ksize, stride, pad, dil, pilot, bn=None):
     if T != ksize * ksize or Cw != Ca:
         raise _lib.MiError("packed weight %s does not match ksize=%d, Ca=%d" % (tuple(wp.shape), ksize, Ca))
     Ho, Wo = out_hw
-    out = torch.empty((B, Ho, Wo, N), dtype=torch.bfloat16, device=a.device)
-    sums = torch.empty((2, N), dtype=torch.float32, device=a.device)
+    if out is None:
+        out = torch.empty((B, Ho, Wo, N), dtype=torch.bfloat16, device=a.device)
+    if sums is None:
+        sums = torch.empty((2, N), dtype=torch.float32, device=a.device)
+    _chk(out, torch.bfloat16, "out")
+    _chk(sums, torch.float32, "sums")
+    if out.numel() != B * Ho * Wo * N or sums.numel() != 2 * N:
+        raise _lib.MiError("out / sums have %d / %d elements, the conv writes %d / %d" % (out.numel(), sums.numel(), B * Ho * Wo * N, 2 * N))
     ws = _workspace(int(_lib.lib().mi_conv_gemm_stats_workspace(B * Ho * Wo, N)), a.device, "conv_stats")
     fin, fa = None, (None, None, None, None, None, 0.0, 0.0, None)
     if bn is not None:
@@ -176,6 +238,8 @@ def conv_gemm_stats(a, wp, out_hw, ksize, stride, pad, dil, pilot, bn=None):
         fa = (_p(bn.weight.detach()), _p(bn.bias.detach()), _p(bn.running_mean) if track else None, _p(bn.running_var) if track else None,
               _p(bn.num_batches_tracked) if track else None, float(bn.momentum or 0.0), float(bn.eps), _p(fin))
     flops = 2.0 * B * Ho * Wo * N * Ca * ksize * ksize
+    if ROUTES is not None:
+        ROUTES.add(conv_gemm_plan(a.shape, N, out_hw, ksize, stride, pad, dil, 512))
     _timed("igemm_stats", flops, lambda: check(_lib.lib().mi_conv_gemm_stats(_p(a), _p(wp), _p(out), B, Ha, Wa, Ca, Ho, Wo, N, ksize, stride, pad, dil, _p(pilot),
                                                                              _p(sums), _p(ws), ws.numel(), *fa, _stream()), "mi_conv_gemm_stats"),
            ("fwd", ksize, Ca, N, B * Ho * Wo, 512, dil))
@@ -286,6 +350,8 @@ def conv_wgrad(dy, x, dw, ksize=1, stride=1, pad=0, dil=1, scale=None, accumulat
     if PROFILE is not None:
         kern = ("wgrad_tn_kernel", "wgrad_tn256_kernel", "wgrad_p3_kernel", "wgrad_q3_kernel", "wgrad_s4_kernel")[
             L.mi_conv_wgrad_route(B, Ha, Wa, I, Ho, Wo, O, ksize, stride, pad, dil, out_map)] + "+reduce"
+    if ROUTES is not None:
+        ROUTES.add(conv_wgrad_plan(dy.shape, x.shape, ksize, stride, pad, dil, out_map, batch is not None))
     if batch is not None:
         idx, job = batch.slot()
         ws = _workspace(need, dy.device, "wgrad_b%d" % idx)             # its slabs must survive until the flush: one buffer per batch slot and stream
