@@ -8,7 +8,7 @@ aggregation modules, four deep-supervision heads - forward AND backward as a tap
   FAM                          reference core/models/classifiers/gcpacc/gcpa_gald.py:47-107
   GALDTrainer                  reference core/trainers/gald_trainer.py:13-112
 
-Same engine as host/pranet.py (NHWC bf16 activations, concatenations as channel-slice views where the link pattern allows, BatchNorm2d on
+Same engine as PraNet, host/tape.py (NHWC bf16 activations, concatenations as channel-slice views where the link pattern allows, BatchNorm2d on
 batch statistics from the conv's tile sums, one flat fp32 parameter / gradient buffer per module, Adam in one launch).  What is new here:
 ReLU6, max pools with a stored argmax, the depthwise stride-2 convs, the attention core (one workgroup per pixel instead of the reference's
 permute / contiguous / bmm chain), parameters shared between two applications of a module (the criss-cross module runs twice: gradients
@@ -27,24 +27,17 @@ from . import arch
 from .metrics import (AverageMeter, adjust_learning_rate, confusion_matrix, dump_json, intersectionAndUnionGPU, require_plain_argmax,
                       require_single_scale)
 from .plugin import BaseTrainer
-from .pranet import FlatAdam, _acc, _Engine, _grad_target, _Run, _rup32, _tile_route, _Unit
+from .tape import Engine, FlatAdam, Run, Unit, acc, grad_target, rup32, tile_route
 
 
-class _GaldRun(_Run):
+class _GaldRun(Run):
     WGRAD_STREAM = True           # GALD trains eagerly and its weight gradients are few and large: +1.5 % with them beside the data-gradient chain
     def maxpool(self, x, k, stride, pad):
         H, W = x.t.shape[1], x.t.shape[2]
         if self.f32:
             return self.var(gk.gpool_f32(x.t, k, stride, pad, 2), False)
         o, idx = gk.gmaxpool(x.t, k, stride, pad)
-        ov = self.var(o)
-
-        def back():
-            if ov.g is not None:
-                _acc(x, gk.gmaxpool_bwd(ov.g, idx, (H, W), k, stride, pad, dx=_grad_target(x)), True)
-                ov.g = None
-        self.record(back)
-        return ov
+        return self.node(o, lambda g: acc(x, gk.gmaxpool_bwd(g, idx, (H, W), k, stride, pad, dx=grad_target(x)), True))
 
     def dw_bn_relu(self, x, u):
         """Conv2d(C, C, 3, groups=C, stride=2) with bias -> BatchNorm2d -> ReLU (GALDNet.py:127-136); u.weight is [C,1,3,3]."""
@@ -60,55 +53,38 @@ class _GaldRun(_Run):
         M = y.shape[0] * y.shape[1] * y.shape[2]
         fin = gk.gbn_finalize(st, C, M, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.momentum, bn.eps)
         o = gk.gbn_apply(y, fin[2], fin[3], 1)
-        ov = self.var(o)
 
-        def back():
-            g = ov.g
-            ov.g = None
-            if g is None:
-                return
+        def back(g):
             dbeta, dgamma = net._grad_of(bn.bias), net._grad_of(bn.weight)
             gk.gbn_bwd_sums(g, y, o, fin[0], fin[1], dbeta, dgamma)
             dy = gk.gbn_bwd_apply(g, y, o, fin[0], fin[1], bn.weight, dbeta, dgamma, M)
             dx = gk.gdwconv_backward(dy, x.t, u.weight.detach(), net._grad_of(u.weight), net._grad_of(u.bias), 2, 0, need_dx=x.needs)
             if dx is not None:
-                _acc(x, dx, True)
-        self.record(back)
-        return ov
+                acc(x, dx, True)
+        return self.node(o, back)
 
     def gate(self, x, g):
         """x + x * sigmoid(g) (GALDNet.py:150-157)"""
         if self.f32:
             return self.var(gk.gpoint_f32(gk.PW_GATE, x.t, g.t), False)
-        ov = self.var(gk.ggate(x.t, g.t))
 
-        def back():
-            if ov.g is None:
-                return
-            dx, dg = gk.ggate_bwd(x.t, g.t, ov.g)
-            ov.g = None
-            _acc(x, dx, True)
-            _acc(g, dg, True)
-        self.record(back)
-        return ov
+        def back(go):
+            dx, dg = gk.ggate_bwd(x.t, g.t, go)
+            acc(x, dx, True)
+            acc(g, dg, True)
+        return self.node(gk.ggate(x.t, g.t), back)
 
     def mulrelu(self, a, b, out=None):
         """relu(a * b) (gcpa_gald.py:88-101)"""
         if self.f32:
             return self.var(gk.gpoint_f32(gk.PW_MULRELU, a.t, b.t, out=out), False)
         o = gk.gbinary(gk.OP_MULRELU, a.t, b.t, out=out)
-        ov = self.var(o)
 
-        def back():
-            g = ov.g
-            ov.g = None
-            if g is None:
-                return
+        def back(g):
             gm = gk.gbinary(gk.OP_RELU_MASK, g, o)
-            _acc(a, gk.gbinary(gk.OP_MUL, gm, b.t), True)
-            _acc(b, gk.gbinary(gk.OP_MUL, gm, a.t), True)
-        self.record(back)
-        return ov
+            acc(a, gk.gbinary(gk.OP_MUL, gm, b.t), True)
+            acc(b, gk.gbinary(gk.OP_MUL, gm, a.t), True)
+        return self.node(o, back)
 
     def ce_head(self, low, labels, ignore_index, inv_t=None):
         """criterion(F.interpolate(low, size=labels.shape[-2:], mode="bilinear"), labels) (gcpa_cc2.py:78-81 + gald_trainer.py:76-79) fused: the
@@ -117,14 +93,7 @@ class _GaldRun(_Run):
         src = low.t if inv_t is None else low.t * inv_t
         loss_out, dlow = K.upsample_ce(src, labels, want_grad=self.rec, ignore_index=ignore_index, align_corners=False)
         _count_bad_labels(self.net, loss_out)
-        ov = self.var(loss_out[0].clone())
-
-        def back():
-            if ov.g is not None:
-                _acc(low, dlow * (ov.g if inv_t is None else ov.g * inv_t), True)
-                ov.g = None
-        self.record(back)
-        return ov
+        return self.node(loss_out[0].clone(), lambda g: acc(low, dlow * (g if inv_t is None else g * inv_t), True))
 
     def criss_cross(self, x, uq, uk, uv, gamma):
         """CrissCrossAttention.forward (ccnet.py:56-127): gamma * aggregate + x."""
@@ -137,26 +106,20 @@ class _GaldRun(_Run):
         C = agg.shape[-1]
         gvec = gamma.detach().expand(C).contiguous()
         zero = net._zeros(C)
-        ov = self.var(gk.gbn_apply(agg, gvec, zero, 0, add=x.t))
 
-        def back():
-            g = ov.g
-            ov.g = None
-            if g is None:
-                return
-            _acc(x, g, False)                                              # the residual
+        def back(g):
+            acc(x, g, False)                                               # the residual
             dagg = gk.gbn_apply(g, gvec, zero, 0)
             per_c = torch.empty(C, dtype=torch.float32, device=g.device)
             gk.gbn_bwd_sums(g, agg, None, zero, net._ones(C), torch.empty_like(per_c), per_c)      # sum_m g[m][c] * agg[m][c]
-            slot, acc = net._grad_slot(gamma)
+            slot, accum = net._grad_slot(gamma)
             s = per_c.sum().reshape(1)
-            slot.add_(s) if acc else slot.copy_(s)
+            slot.add_(s) if accum else slot.copy_(s)
             dq, dk, dv = gk.gcca_bwd(q.t, k.t, v.t, att, dagg)
-            _acc(q, dq, True)
-            _acc(k, dk, True)
-            _acc(v, dv, True)
-        self.record(back)
-        return ov
+            acc(q, dq, True)
+            acc(k, dk, True)
+            acc(v, dv, True)
+        return self.node(gk.gbn_apply(agg, gvec, zero, 0, add=x.t), back)
 
 
 def _count_bad_labels(holder, loss_out):
@@ -201,7 +164,7 @@ def _hard_link(layer, base_ch, growth, mul):
 
 
 def _conv_layer(name, cin, cout, k=3, stride=1):
-    return _Unit(name + ".conv", name + ".norm", cin, cout, k, stride, k // 2)
+    return Unit(name + ".conv", name + ".norm", cin, cout, k, stride, k // 2)
 
 
 def _hard_block(run, x, layers, links, out_ch):
@@ -222,9 +185,9 @@ def _hard_block(run, x, layers, links, out_ch):
         if len(lk) > 1:
             widths = [x.t.shape[-1] if j == 0 else layers[j - 1].cout for j in lk]
             cin = sum(widths)
-            # a layer the MFMA-tile kernels take (pranet._tile_route: the big gathered layers, 466 -> 168 ...) reads a gather buffer of the 32-padded
+            # a layer the MFMA-tile kernels take (tape.tile_route: the big gathered layers, 466 -> 168 ...) reads a gather buffer of the 32-padded
             # channel count, pad channels zero: the kernels' operand as it is
-            cbuf = _rup32(cin) if (not run.f32 and _tile_route(u, B * H * W)) else cin
+            cbuf = rup32(cin) if (not run.f32 and tile_route(u, B * H * W)) else cin
             buf = gk.new(B, H, W, cbuf, x.t.device, x.t.dtype)
             if cbuf != cin:
                 buf[..., cin:].zero_()
@@ -268,7 +231,7 @@ def _hard_block_units(prefix, cin, growth, mul, n):
     return layers, links, out_ch
 
 
-class GCPAEncoder(_Engine):
+class GCPAEncoder(Engine):
     """HarDNet-68 trunk (gcpa_cc2.py:16-23); forward(x [B,3,H,W]) -> the four features at 1/4 (128), 1/8 (320), 1/16 (640), 1/32 (1024),
     bf16, NCHW-shaped views of NHWC memory.  The reference loads 'pretrained/hardnet68.pth', which the image lacks: weights keep the module
     defaults unless a checkpoint is loaded."""
@@ -318,10 +281,10 @@ class GCPAEncoder(_Engine):
 
 def _fam_units(prefix, c_left, c_down, c_right, c):
     n = prefix
-    u = dict(conv0=_Unit(n + "conv0", n + "bn0", c_left, c, 3, 1, 1), conv1=_Unit(n + "conv1", n + "bn1", c_down, c, 3, 1, 1),
-             conv2=_Unit(n + "conv2", n + "bn2", c_right, c, 3, 1, 1), conv_d1=_Unit(n + "conv_d1", None, c, c, 3, 1, 1),
-             conv_d2=_Unit(n + "conv_d2", None, c, c, 3, 1, 1), conv_l=_Unit(n + "conv_l", None, c, c, 3, 1, 1),
-             conv3=_Unit(n + "conv3", n + "bn3", 3 * c, c, 3, 1, 1))
+    u = dict(conv0=Unit(n + "conv0", n + "bn0", c_left, c, 3, 1, 1), conv1=Unit(n + "conv1", n + "bn1", c_down, c, 3, 1, 1),
+             conv2=Unit(n + "conv2", n + "bn2", c_right, c, 3, 1, 1), conv_d1=Unit(n + "conv_d1", None, c, c, 3, 1, 1),
+             conv_d2=Unit(n + "conv_d2", None, c, c, 3, 1, 1), conv_l=Unit(n + "conv_l", None, c, c, 3, 1, 1),
+             conv3=Unit(n + "conv3", n + "bn3", 3 * c, c, 3, 1, 1))
     for k in ("conv0", "conv1", "conv2", "conv3"):
         u[k].bias = True                                     # nn.Conv2d default: these convs carry a bias in front of their BatchNorm
     return u, [u[k] for k in ("conv0", "conv1", "conv2", "conv_d1", "conv_d2", "conv_l", "conv3")]
@@ -349,7 +312,7 @@ def _local_attention(run, x, units):
 
 
 def _lam_units(prefix, c):
-    units = [_Unit("%sdconv%d.0" % (prefix, j), "%sdconv%d.1" % (prefix, j), c, c, 3, 2, 0) for j in (1, 2, 3)]
+    units = [Unit("%sdconv%d.0" % (prefix, j), "%sdconv%d.1" % (prefix, j), c, c, 3, 2, 0) for j in (1, 2, 3)]
     for u in units:
         u.bias, u.depthwise = True, True
     return units
@@ -357,11 +320,11 @@ def _lam_units(prefix, c):
 
 def _cca_units(prefix, c):
     """[gamma entry, query, key, value] in the reference's state_dict order (a module's own parameters precede its children's)."""
-    return [(prefix + "gamma", torch.zeros(1)), _Unit(prefix + "query_conv", None, c, c // 8, 1), _Unit(prefix + "key_conv", None, c, c // 8, 1),
-            _Unit(prefix + "value_conv", None, c, c, 1)]
+    return [(prefix + "gamma", torch.zeros(1)), Unit(prefix + "query_conv", None, c, c // 8, 1), Unit(prefix + "key_conv", None, c, c // 8, 1),
+            Unit(prefix + "value_conv", None, c, c, 1)]
 
 
-class GCPADecoder(_Engine):
+class GCPADecoder(Engine):
     """gcpa_cc2.py:25-83.  forward(x, feats) -> (out5, out4, out3, out2): class logits [B,19,H,W] fp32 (NCHW-shaped views of NHWC memory).
     GaldFada's entries: loss() (the source loss on out2 alone) and low2() (the target logits, no tape)."""
     RUN = _GaldRun
@@ -374,9 +337,9 @@ class GCPADecoder(_Engine):
         for name, cl in (("fam45", 640), ("fam34", 320), ("fam23", 128)):
             self._fam[name], flat = _fam_units(name + ".", cl, c, c, c)
             order += flat
-        self._lin = {i: _Unit("linear%d" % i, None, c, num_classes, 3, 1, 1) for i in (5, 4, 3, 2)}
+        self._lin = {i: Unit("linear%d" % i, None, c, num_classes, 3, 1, 1) for i in (5, 4, 3, 2)}
         order += [self._lin[i] for i in (5, 4, 3, 2)]
-        self._conva = _Unit("conva.0", "conva.1", 1024, c, 3, 1, 1)
+        self._conva = Unit("conva.0", "conva.1", 1024, c, 3, 1, 1)
         order.append(self._conva)
         cca = _cca_units("long_relation.", c)
         self._cca = cca[1:]
@@ -449,7 +412,7 @@ class GCPADecoder(_Engine):
 # ------------------------------------------------------------------------------------------------ the building blocks as stand-alone modules
 # Same constructor arguments and state_dict keys as the reference's classes, the SAME graph functions the two networks above are made of
 # (tests/test_gpu_gald.py runs them against the reference's own module fixtures, g13_gald_modules).
-class HarDBlock(_Engine):
+class HarDBlock(Engine):
     """hardnet_68.py:86-160 (the plain variant HarDNet-68 uses: keepBase False, no depthwise layers)."""
     RUN = _GaldRun
 
@@ -468,7 +431,7 @@ class HarDBlock(_Engine):
         return [_hard_block(run, x, *self._arg)]
 
 
-class FAM(_Engine):
+class FAM(Engine):
     """gcpa_gald.py:47-107: forward(left, down, right)."""
     RUN = _GaldRun
 
@@ -482,7 +445,7 @@ class FAM(_Engine):
         return [_fam_block(run, self._U, self._c, left, down, right)]
 
 
-class CrissCrossAttention(_Engine):
+class CrissCrossAttention(Engine):
     """contextagg/ccnet.py:37-127.  `recurrence` (default 1, not a constructor argument of the reference) applies the module that many times inside
     ONE graph with shared parameters - what GCPADecoder does with its `long_relation` (gcpa_cc2.py:56-57)."""
     RUN = _GaldRun
@@ -500,7 +463,7 @@ class CrissCrossAttention(_Engine):
         return [x]
 
 
-class LocalAttenModule(_Engine):
+class LocalAttenModule(Engine):
     """contextagg/GALDNet.py:124-157."""
     RUN = _GaldRun
 
@@ -576,8 +539,6 @@ class GALDTrainer(BaseTrainer):
             if key in self.checkpoint:
                 self.logger.info("Loading %s from %s" % (key.replace("_", " "), self.cfg.resume))
                 opt.load_state_dict(self.checkpoint[key])
-                opt._m = None
-                opt._ensure_moments()
         if "iteration" in self.checkpoint:
             self.iteration = self.checkpoint["iteration"]
         if "epoch" in self.checkpoint:

@@ -123,7 +123,7 @@ def _gald_cases():
         # HarDNet-68's third block: 16 layers, growth 20 (widths 20 .. 160, inputs up to 466 channels: 4-byte aligned slices everywhere)
         ("hdb_16", "hdb16", lambda: gald.HarDBlock(256, 20, 1.7, 16), lambda: rg.HarDBlock(256, 20, 1.7, 16), [np.maximum(_u("hdb16.x", (2, 256, 22, 22), 3), 0)]),
         # the same block on 16 928 pixels: its two big gathered layers (368 -> 98 and 466 -> 168 channels, 11 and 24 GFLOP) read gather buffers padded to
-        # 384 / 480 channels and run on the MFMA-tile kernels as 384 -> 128 and 480 -> 192 convs (pranet._tile_route; the test checks that they did)
+        # 384 / 480 channels and run on the MFMA-tile kernels as 384 -> 128 and 480 -> 192 convs (tape.tile_route; the test checks that they did)
         ("hdb_16_pad", "hdb16", lambda: gald.HarDBlock(256, 20, 1.7, 16), lambda: rg.HarDBlock(256, 20, 1.7, 16), [np.maximum(_u("hdb16p.x", (2, 256, 92, 92), 3), 0)]),
     ]
 
@@ -427,18 +427,18 @@ def test_applies_with_extra_destinations_leave_every_bit_of_a_block_unchanged(wh
 
 
 def test_shared_unit_queued_then_beside_accumulates_both_applications():
-    """One conv + BatchNorm unit applied twice with shared parameters, under GALD's run class (weight gradients of >= _SIDE_MIN_WORK on the side stream,
+    """One conv + BatchNorm unit applied twice with shared parameters, under GALD's run class (weight gradients of >= SIDE_MIN_WORK on the side stream,
     the smaller ones queued): first at 2 x 320 x 320 (8.5 GFLOP of weight gradient: the side stream, at once), then at 2 x 64 x 64 (0.3 GFLOP: the queue).
     Backward meets the queued application first and writes its slot (overwrite), the direct one accumulates: the queue must be flushed before it, or the
     later flush overwrites the accumulated sum.  48 channels keep both on the general kernels.  Parameter gradients against float64 torch."""
-    from rnd_semantic_segmentation_amd.host import engine, gald, pranet
+    from rnd_semantic_segmentation_amd.host import engine, gald, tape
 
-    class Twice(pranet._Engine):
+    class Twice(tape.Engine):
         RUN = gald._GaldRun
 
         def __init__(self):
             super().__init__()
-            self._u = pranet._Unit("conv", "bn", 48, 48, 3, 1, 1)
+            self._u = tape.Unit("conv", "bn", 48, 48, 3, 1, 1)
             self._register([self._u])
 
         def _graph(self, run, big, small):
@@ -449,7 +449,7 @@ def test_shared_unit_queued_then_beside_accumulates_both_applications():
     synth.load_formula_weights(mod, prefix="twice.", bn_bias=synth.COND_BN_BIAS)
     mod.cuda().train()
     work = lambda hw: 2.0 * 2 * hw * hw * 48 * 48 * 9
-    assert work(64) < pranet._SIDE_MIN_WORK <= work(320)
+    assert work(64) < tape.SIDE_MIN_WORK <= work(320)
     xs = [torch.from_numpy(np.maximum(_u("twice.x%d" % hw, (2, 48, hw, hw), 3), 0)).bfloat16() for hw in (320, 64)]
     rs = [torch.from_numpy(_u("twice.r%d" % hw, (2, 48, hw, hw))) for hw in (320, 64)]
     outs = mod(*[x.cuda() for x in xs])

@@ -307,43 +307,43 @@ def test_pranet_warmup_cosine_schedule_equals_the_references_scheduler_chain():
 
 
 def test_tile_route_of_the_tape_engines_is_consistent_with_the_padded_gathers():
-    """host/pranet.py:_tile_route decides, from shapes alone, which convs of the tape engines (PraNet, GALD) go to the MFMA-tile kernels: 64-multiples on
+    """host/tape.py:tile_route decides, from shapes alone, which convs of the tape engines (PraNet, GALD) go to the MFMA-tile kernels: 64-multiples on
     both sides as before, and (round 5) stride-1 layers whose channel counts pad to 32-multiples with < 1.6x the work, >= 16 384 pixels and >= 8 GFLOP -
-    HarDNet-68's big gathered layers.  gald._hard_block pads a gather buffer exactly when this predicate holds, and _mfma_tile_ok takes the conv only when
+    HarDNet-68's big gathered layers.  gald._hard_block pads a gather buffer exactly when this predicate holds, and mfma_tile_ok takes the conv only when
     its input has the padded width: the two must agree or the general kernel would be handed a tensor wider than the conv's Cin."""
-    from rnd_semantic_segmentation_amd.host import gald, pranet
-    rup = pranet._rup32
+    from rnd_semantic_segmentation_amd.host import gald, tape
+    rup = tape.rup32
     assert [rup(c) for c in (1, 32, 33, 466, 480)] == [32, 32, 64, 480, 480]
     layers, links, out_ch = gald._hard_block_units("b.", 256, 20, 1.7, 16)           # HarDNet-68's third block (hardnet_68.py:163-262: growth 20, 16 layers)
     assert out_ch == 328 and [(u.cin, u.cout) for u in layers][15] == (466, 168) and len(links[15]) == 5
     px = 6 * 90 * 160                                                                 # the block's map at 6 x 720 x 1280
-    routed = [(u.cin, u.cout) for u, lk in zip(layers, links) if len(lk) > 1 and pranet._tile_route(u, px)]
+    routed = [(u.cin, u.cout) for u, lk in zip(layers, links) if len(lk) > 1 and tape.tile_route(u, px)]
     assert routed == [(310, 58), (368, 98), (466, 168)], routed                      # (152 -> 58 pads to 160 -> 64: only the 256-column loop could take it)
     # too few pixels, too little work, too much padding, strided, depthwise: the general kernel keeps them
-    assert not pranet._tile_route(layers[15], 16383)
-    assert not pranet._tile_route(pranet._Unit("c", "n", 96, 96, 3, 1, 1), 30976)                 # 5 GFLOP (PraNet's 96 -> 96 at 44 x 44 x 16)
-    assert not pranet._tile_route(pranet._Unit("c", "n", 102, 40, 3, 1, 1), 345600)               # 2.0x the work when padded
-    assert not pranet._tile_route(pranet._Unit("c", "n", 466, 168, 3, 2, 1), px)
-    assert pranet._tile_route(pranet._Unit("c", "n", 256, 256, 3, 1, 1), 16384)                   # 64-multiples: as before, any stride
-    assert pranet._tile_route(pranet._Unit("c", "n", 128, 64, 3, 2, 1), 16384)
+    assert not tape.tile_route(layers[15], 16383)
+    assert not tape.tile_route(tape.Unit("c", "n", 96, 96, 3, 1, 1), 30976)                 # 5 GFLOP (PraNet's 96 -> 96 at 44 x 44 x 16)
+    assert not tape.tile_route(tape.Unit("c", "n", 102, 40, 3, 1, 1), 345600)               # 2.0x the work when padded
+    assert not tape.tile_route(tape.Unit("c", "n", 466, 168, 3, 2, 1), px)
+    assert tape.tile_route(tape.Unit("c", "n", 256, 256, 3, 1, 1), 16384)                   # 64-multiples: as before, any stride
+    assert tape.tile_route(tape.Unit("c", "n", 128, 64, 3, 2, 1), 16384)
     # the input the MFMA-tile kernels take for a padded layer is the padded gather buffer, nothing else
     u = layers[15]
-    ok = lambda c: pranet._mfma_tile_ok(u, torch.empty((6, 90, 160, c), dtype=torch.bfloat16, device="meta"))
+    ok = lambda c: tape.mfma_tile_ok(u, torch.empty((6, 90, 160, c), dtype=torch.bfloat16, device="meta"))
     assert ok(480) and not ok(466) and not ok(512)
 
 
 def test_conv_bn_refuses_relu6_with_a_residual_before_any_launch():
-    """_Run.conv_bn's residual backward masks with OP_RELU_MASK (out > 0), which would keep the gradient where ReLU6 clamped to 6 (torch's hardtanh
+    """Run.conv_bn's residual backward masks with OP_RELU_MASK (out > 0), which would keep the gradient where ReLU6 clamped to 6 (torch's hardtanh
     backward drops it there).  No layer combines the two, so the pair is refused at entry - before any operand is touched or any kernel launched."""
     from rnd_semantic_segmentation_amd import _lib
-    from rnd_semantic_segmentation_amd.host import pranet
-    run = pranet._Run(object(), True, True)
+    from rnd_semantic_segmentation_amd.host import tape
+    run = tape.Run(object(), True, True)
     with pytest.raises(_lib.MiError, match="ReLU6"):
         run.conv_bn(None, None, 6, add=object())
 
 
 class _TapeOnFakeStreams:
-    """The tape's weight-gradient scheduling (engine.WgradScheduler + pranet._WgradQueue, GALD's run class: side stream on) on CPU tensors: the side
+    """The tape's weight-gradient scheduling (engine.WgradScheduler + tape._WgradQueue, GALD's run class: side stream on) on CPU tensors: the side
     stream is a recording fake, the general-kernel weight gradients are fakes that write slot (+)= sum(dy) * sum(x) at once, in enqueue order, and
     log which stream they were enqueued on and which tensors they touched."""
 
@@ -356,8 +356,8 @@ class _TapeOnFakeStreams:
 
     def __init__(self, monkeypatch):
         from rnd_semantic_segmentation_amd import gk
-        from rnd_semantic_segmentation_amd.host import engine, pranet
-        self.pranet, self.log, self.touched, self.kept, self.born_on_side = pranet, [], [], [], []
+        from rnd_semantic_segmentation_amd.host import engine, tape
+        self.tape, self.log, self.touched, self.kept, self.born_on_side = tape, [], [], [], []
         self.main, self.side = self.Stream("main", self.log), self.Stream("side", self.log)
         self.current = [self.main]
 
@@ -389,9 +389,9 @@ class _TapeOnFakeStreams:
         monkeypatch.setattr(gk, "gconv_wgrad_multi", lambda jobs: [wgrad(dy, x, dw, geom, acc) for dy, x, dw, geom, acc in jobs])
         monkeypatch.setattr(engine.WgradScheduler, "on", classmethod(lambda cls, device: cls(self.side)))
 
-        class Run(pranet._Run):
+        class Run(tape.Run):
             WGRAD_STREAM = True
-        self.net = type("Net", (), {"_grad_slot": pranet._Engine._grad_slot})()
+        self.net = type("Net", (), {"_grad_slot": tape.Engine._grad_slot})()
         self.Run = Run
 
     def store(self, *params):
@@ -403,7 +403,7 @@ class _TapeOnFakeStreams:
         """applications: (unit, x NHWC bf16, dy NHWC bf16) in FORWARD order; the tape replays them in reverse."""
         run = self.Run(self.net, True, True)
         for u, x, dy in applications:
-            run.record(lambda u=u, x=x, dy=dy: run._conv_backward(self.pranet._Var(x, needs=False), u, dy))
+            run.record(lambda u=u, x=x, dy=dy: run._conv_backward(self.tape.Var(x, needs=False), u, dy))
         run.backward()
 
 
@@ -413,8 +413,8 @@ def test_tape_scratch_of_a_deferred_weight_gradient_is_handed_over_or_allocated_
     is queued and written into a scratch tensor for all eight channels first; that scratch once came from the main stream at tape time and was released
     while the side stream still used it."""
     f = _TapeOnFakeStreams(monkeypatch)
-    from rnd_semantic_segmentation_amd.host import pranet
-    stem, mid = pranet._Unit("stem", None, 3, 32, 3, 2, 1), pranet._Unit("mid", None, 32, 32, (1, 3), 1, (0, 1))
+    from rnd_semantic_segmentation_amd.host import tape
+    stem, mid = tape.Unit("stem", None, 3, 32, 3, 2, 1), tape.Unit("mid", None, 32, 32, (1, 3), 1, (0, 1))
     stem.weight, mid.weight = torch.nn.Parameter(torch.randn(32, 3, 3, 3)), torch.nn.Parameter(torch.randn(32, 32, 1, 3))
     st = f.store(stem.weight, mid.weight)
     img = torch.zeros(2, 16, 16, 8, dtype=torch.bfloat16)
@@ -438,16 +438,86 @@ def test_tape_queued_overwrite_then_direct_accumulate_to_one_slot_flushes_first(
     the application whose weight gradient is queued first (overwrite) and then one large enough to go to the side stream directly (accumulate), the
     queue must be flushed before the direct write - otherwise the accumulate runs first and the later overwrite loses it."""
     f = _TapeOnFakeStreams(monkeypatch)
-    from rnd_semantic_segmentation_amd.host import pranet
-    u = pranet._Unit("cc", None, 48, 48, 3, 1, 1)
+    from rnd_semantic_segmentation_amd.host import tape
+    u = tape.Unit("cc", None, 48, 48, 3, 1, 1)
     u.weight = torch.nn.Parameter(torch.randn(48, 48, 3, 3))
     f.store(u.weight)
     big, small = torch.randn(1, 16, 16, 48).bfloat16(), torch.randn(1, 8, 8, 48).bfloat16()
     dy_big, dy_small = torch.randn(1, 16, 16, 48).bfloat16(), torch.randn(1, 8, 8, 48).bfloat16()
     work = lambda x: 2.0 * x.shape[1] * x.shape[2] * 48 * 48 * 9
-    monkeypatch.setattr(pranet, "_SIDE_MIN_WORK", (work(big) + work(small)) / 2)
+    monkeypatch.setattr(tape, "SIDE_MIN_WORK", (work(big) + work(small)) / 2)
     f.backward([(u, big, dy_big), (u, small, dy_small)])                           # backward: the small (queued) application first
     writes = [e for e in f.log if e[0] == "wgrad"]
     assert [(s, acc) for _, s, _, acc in writes] == [("side", False), ("side", True)], writes
     want = dy_small.float().sum() * small.float().sum() + dy_big.float().sum() * big.float().sum()
     assert torch.allclose(u.weight.grad, want.expand_as(u.weight), rtol=1e-5)
+
+
+def test_run_node_replays_in_reverse_where_a_gradient_arrived_and_lets_go_of_it():
+    """Run.node is the one rule for when a tape node's gradient is consumed: on replay the node's function gets the gradient that reached its
+    variable, after the variable has let go of it; a node no gradient reached is skipped.  x -> a -> b with a gradient on b, and c (of a) with none."""
+    from rnd_semantic_segmentation_amd.host import tape
+    run = tape.Run(object(), True, True)
+    ran, held = [], []
+    x = run.var(torch.ones(3))
+
+    def back_of(name, v, src, scale):
+        def back(g):
+            ran.append(name)
+            held.append(v[0].g)                      # what the node's own variable still holds while its function runs
+            tape.acc(src, g * scale, True)
+        return back
+    va, vb, vc = [None], [None], [None]
+    va[0] = a = run.node(x.t * 2, back_of("a", va, x, 2.0))
+    vb[0] = b = run.node(a.t + 1, back_of("b", vb, a, 1.0))
+    vc[0] = c = run.node(a.t * 0, back_of("c", vc, a, 0.0))
+    assert len(run.tape) == 3
+    b.g, b.own = torch.full((3,), 5.0), True
+    run.backward()
+    assert ran == ["b", "a"]                         # reverse recording order; c got no gradient and did not run
+    assert held == [None, None]
+    assert a.g is None and b.g is None and c.g is None
+    assert torch.equal(x.g, torch.full((3,), 10.0)) and run.tape == []
+    off = tape.Run(object(), True, False)            # no tape wanted: nothing recorded, the variable needs no gradient
+    assert not off.node(torch.ones(1), lambda g: None).needs and off.tape == []
+
+
+def test_tape_module_imports_neither_net():
+    """host/tape.py is the engine both nets are written against: importing it must not pull in either of them."""
+    import subprocess
+    import sys
+    pkg = "rnd_semantic_segmentation_amd.host."
+    code = "import sys; import %stape; print([m for m in (%r, %r) if m in sys.modules])" % (pkg, pkg + "pranet", pkg + "gald")
+    r = subprocess.run([sys.executable, "-c", code], cwd=os.path.dirname(os.path.dirname(os.path.abspath(__file__))), capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    assert r.stdout.strip() == "[]", r.stdout
+
+
+def test_flat_adam_load_state_dict_adopts_moments_and_steps_itself():
+    """A checkpoint's exp_avg / exp_avg_sq / step loaded into a fresh FlatAdam are in its flat moment buffers and its step count when
+    load_state_dict returns - no further call by the caller (the trainers' resume path) - and state_dict() gives them back."""
+    from rnd_semantic_segmentation_amd.host import engine, tape
+
+    def fresh():
+        ps = [torch.nn.Parameter(torch.randn(5, 3)), torch.nn.Parameter(torch.randn(7))]
+        store = engine.FlatStore([("p%d" % i, p) for i, p in enumerate(ps)], "cpu")
+        net = type("Net", (), {"parameters": lambda self: iter(ps), "ensure_flat": lambda self: store, "_store": store})()
+        return ps, tape.FlatAdam(net, 1e-3)
+    ps, _ = fresh()
+    donor = torch.optim.Adam(ps, 1e-3)
+    for k in range(3):
+        for p in ps:
+            p.grad = torch.randn_like(p)
+        donor.step()
+    sd = donor.state_dict()
+    assert all(int(s["step"]) == 3 and float(s["exp_avg"].abs().max()) > 0 for s in sd["state"].values())
+    qs, opt = fresh()
+    opt.load_state_dict(sd)
+    assert opt._steps == 3 and opt._psteps is None
+    for i, q in enumerate(qs):
+        lo, hi = q._mi_off, q._mi_off + q.numel()
+        assert torch.equal(opt._m[lo:hi].view_as(q), sd["state"][i]["exp_avg"]) and torch.equal(opt._v[lo:hi].view_as(q), sd["state"][i]["exp_avg_sq"])
+        assert opt.state[q]["exp_avg"].data_ptr() == opt._m[lo:hi].data_ptr()          # the per-parameter state IS the flat buffer
+    again = opt.state_dict()
+    for i in sd["state"]:
+        assert int(again["state"][i]["step"]) == 3 and torch.equal(again["state"][i]["exp_avg"], sd["state"][i]["exp_avg"])

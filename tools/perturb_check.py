@@ -18,18 +18,18 @@ CASES = {
     # PraNet: the second 3x3 of every Res2Net group conv gets dilation 2 (same output shape: pad follows) - a tap offset
     "pranet_tap_offset": """
         from rnd_semantic_segmentation_amd.host import pranet
-        _orig = pranet._res2net_units
+        _orig = pranet.res2net_units
         def units(*a, **k):
             us, blocks = _orig(*a, **k)
             u = blocks[5]["convs"][1]
             g = list(u.geom); g[4] = g[5] = 2; g[6] = g[7] = 2; u.geom = tuple(g)
             return us, blocks
-        pranet._res2net_units = units
+        pranet.res2net_units = units
     """,
     # PraNet: the partial decoder's first upsampling uses align_corners=False
     "pranet_resize_convention": """
-        from rnd_semantic_segmentation_amd.host import pranet
-        _orig = pranet._Run.resize
+        from rnd_semantic_segmentation_amd.host import tape
+        _orig = tape.Run.resize
         state = {"n": 0}
         def resize(self, x, factor, align, size=None):
             if factor == 2 and align:
@@ -37,17 +37,17 @@ CASES = {
                 if state["n"] == 1:
                     align = False
             return _orig(self, x, factor, align, size=size)
-        pranet._Run.resize = resize
+        tape.Run.resize = resize
     """,
     # PraNet: the residual of one bottleneck is dropped (out = relu(bn3(conv3(...))) without + x)
     "pranet_missing_residual": """
-        from rnd_semantic_segmentation_amd.host import pranet
-        _orig = pranet._Run.conv_bn
-        def conv_bn(self, x, u, relu, add=None, out=None, out_f32=False):
+        from rnd_semantic_segmentation_amd.host import tape
+        _orig = tape.Run.conv_bn
+        def conv_bn(self, x, u, relu, add=None, **kw):
             if u.key == "resnet.layer3.2.conv3":
                 add = None
-            return _orig(self, x, u, relu, add=add, out=out, out_f32=out_f32)
-        pranet._Run.conv_bn = conv_bn
+            return _orig(self, x, u, relu, add=add, **kw)
+        tape.Run.conv_bn = conv_bn
     """,
     # GALD: layer 6 of every 8+-layer HarDBlock reads layers (3, 4) instead of (5, 4) - same channel counts (14 / 16 / 20 / 40-wide), another tensor
     "gald_link_index": """
