@@ -228,6 +228,23 @@ int mi_upsample_ce_ex(const float* low, const int64_t* labels, float* loss_out /
                       int B, int h, int w, int K, int H, int W, int ignore_index, float grad_scale, int align_corners,
                       void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- fused upsample + generalized Dice loss (GeneralizedDiceLoss, reference core/utils/utility.py:399-447, label form) ----
+ * Operands and restrictions as mi_upsample_ce_ex.  With p = softmax(bilinear(low)) and t = onehot(labels), both zero where the label is
+ * ignore_index:  T_c = sum t, I_c = sum p t, P2_c = sum p^2, w_c = 1 / (T_c^2 + eps) | 1 / (T_c + eps) | 1 / (sqrt(T_c) + eps) by weight_type,
+ * loss = 1 - 2 sum_c w_c I_c / (sum_c w_c (P2_c + T_c) + eps).  Labels outside [0, K) that are not ignore_index are left out and counted.
+ * loss_out (four floats): [0] = loss, [1] = valid pixels, [2] = out-of-range labels, [3] = 0.
+ * dlow (may be NULL: loss only) [B][h][w][K] = d loss / d low * grad_scale.  sums (may be NULL) [3K] fp32: T_c, I_c, P2_c (T_c exact below 2^24).
+ * Launches: a reduction pass, a one-workgroup finalize that leaves the loss and the gradient's 2K coefficients in device memory, and - with dlow -
+ * the gradient pass (two launches, along x then y), which recomputes the softmax from `low`.  Nothing is read back in between: the call can be
+ * captured in a HIP graph.  Deterministic (fixed summation order, no floating-point atomics, T_c counted in integers). */
+#define MI_GDL_SQUARE 0
+#define MI_GDL_IDENTITY 1
+#define MI_GDL_SQRT 2
+size_t mi_upsample_gdl_workspace(int B, int h, int w, int K, int H, int W);
+int mi_upsample_gdl(const float* low, const int64_t* labels, float* loss_out /*[4]*/, float* dlow, float* sums /*[3K]*/,
+                    int B, int h, int w, int K, int H, int W, int ignore_index, int weight_type, float eps, float grad_scale,
+                    int align_corners, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- inference tail: upsample to label size + softmax over classes (utility.py:185-186) ---------
  * probs [B][K][H][W] fp32; pred (optional, may be NULL) [B][H][W] uint8 argmax (first max wins). */
 int mi_upsample_softmax(const float* low, float* probs, uint8_t* pred, int B, int h, int w, int K, int H, int W, void* stream);

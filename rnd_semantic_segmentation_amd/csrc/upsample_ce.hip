@@ -196,6 +196,44 @@ __global__ void ce_bwd_kernel(const float* __restrict__ logits, const int64_t* _
 // their column support in ascending x:  tmp[b][y][j][k] = sum_x wx(x,j) d[x][k].
 constexpr int JT = 32;              // the largest tile; the launcher narrows it for large upsample factors (pick_jt)
 
+// What the x-tile kernels (upce_pass1_kernel, gdl_grad_kernel) share.  A workgroup owns the low-res columns [j0, j1) of output row y of image b:
+// its pixels are those with x0 in [j0-1, j1-1], starting at xa.
+// tile_stage: pstart[q] = first pixel (relative to xa) whose x0 >= j0 - 1 + q, and the touched source columns (from cbase) interpolated along y into vrow.
+__device__ __forceinline__ void tile_stage(const float* __restrict__ low, int K, const Axis& ay, const Axis& ax, int b, int y, int j0, int j1, int xa,
+                                           int* pstart, float* vrow, int& cbase) {
+    const int h = ay.n_in, w = ax.n_in;
+    int y0, y1;
+    float ly;
+    ay.src(y, y0, y1, ly);
+    const float* row0 = low + ((long)b * h + y0) * w * K;
+    const float* row1 = low + ((long)b * h + y1) * w * K;
+    cbase = max(j0 - 1, 0);
+    const int ncol = min(j1, w - 1) - cbase + 1;          // source columns this tile touches
+    if (threadIdx.x < j1 - j0 + 2) pstart[threadIdx.x] = ax.first_with_i0_ge(j0 - 1 + (int)threadIdx.x) - xa;
+    for (int e = threadIdx.x; e < ncol * K; e += 256) {
+        const long o = (long)cbase * K + e;
+        vrow[e] = (1.f - ly) * row0[o] + ly * row1[o];
+    }
+}
+
+// tile_gather_x: trow[j][k] = sum_x wx(x,j) dbuf[x][k] for the tile's columns, (j,k) items over the threads, each in ascending x (trow: row (b, y) of tmp).
+__device__ __forceinline__ void tile_gather_x(const float* dbuf, const float* lam, const int* pstart, float* __restrict__ trow, int K, int j0, int j1,
+                                              int w, int npx) {
+    const int nj = j1 - j0;
+    for (int item = threadIdx.x; item < nj * K; item += 256) {
+        const int jj = item / K, k = item - jj * K;
+        const int j = j0 + jj;
+        float s = 0.f;
+        // pixels with x0 == j-1 contribute lam to j (as x1), then pixels with x0 == j contribute 1-lam (and lam too when x1 is
+        // clamped onto j at the right edge); same weights and the same ascending-x order as a per-pixel test of x0 / x1
+        const int p0 = max(pstart[jj], 0), p1 = min(max(pstart[jj + 1], 0), npx), p2 = min(pstart[jj + 2], npx);
+        for (int px = p0; px < p1; ++px) s += (0.f + lam[px]) * dbuf[(long)px * K + k];
+        const bool edge = j == w - 1;
+        for (int px = p1; px < p2; ++px) s += ((1.f - lam[px]) + (edge ? lam[px] : 0.f)) * dbuf[(long)px * K + k];
+        trow[(long)j * K + k] = s;
+    }
+}
+
 // KT > 0: the class count is a compile-time constant (19 for Cityscapes: exact-length register loops instead of 32 predicated
 // iterations); KT == 0: K is read from the arguments.
 template <int KT>
@@ -216,17 +254,8 @@ __global__ __launch_bounds__(256) void upce_pass1_kernel(const float* __restrict
     const int j0 = jt * jt_cols, j1 = min(w, j0 + jt_cols);
     const int xa = ax.first_with_i0_ge(j0 - 1), xb = ax.first_with_i0_ge(j1);   // pixels with x0 in [j0-1, j1-1]
     const int npx = xb - xa;
-    int y0, y1;
-    float ly;
-    ay.src(y, y0, y1, ly);
-    const float* row0 = low + ((long)b * h + y0) * w * K;
-    const float* row1 = low + ((long)b * h + y1) * w * K;
-    const int cbase = max(j0 - 1, 0), ncol = min(j1, w - 1) - cbase + 1;          // source columns this tile touches
-    if (threadIdx.x < j1 - j0 + 2) pstart[threadIdx.x] = ax.first_with_i0_ge(j0 - 1 + (int)threadIdx.x) - xa;
-    for (int e = threadIdx.x; e < ncol * K; e += 256) {
-        const long o = (long)cbase * K + e;
-        vrow[e] = (1.f - ly) * row0[o] + ly * row1[o];
-    }
+    int cbase;
+    tile_stage(low, K, ay, ax, b, y, j0, j1, xa, pstart, vrow, cbase);
     __syncthreads();
     float loss = 0.f, cnt = 0.f;
     for (int px = threadIdx.x; px < npx; px += 256) {
@@ -273,21 +302,7 @@ __global__ __launch_bounds__(256) void upce_pass1_kernel(const float* __restrict
         }
     }
     __syncthreads();
-    if (tmp) {
-        const int nj = j1 - j0;
-        for (int item = threadIdx.x; item < nj * K; item += 256) {
-            const int jj = item / K, k = item - jj * K;
-            const int j = j0 + jj;
-            float s = 0.f;
-            // pixels with x0 == j-1 contribute lam to j (as x1), then pixels with x0 == j contribute 1-lam (and lam too when x1 is
-            // clamped onto j at the right edge); same weights and the same ascending-x order as a per-pixel test of x0 / x1
-            const int p0 = max(pstart[jj], 0), p1 = min(max(pstart[jj + 1], 0), npx), p2 = min(pstart[jj + 2], npx);
-            for (int px = p0; px < p1; ++px) s += (0.f + lam[px]) * dbuf[(long)px * K + k];
-            const bool edge = j == w - 1;
-            for (int px = p1; px < p2; ++px) s += ((1.f - lam[px]) + (edge ? lam[px] : 0.f)) * dbuf[(long)px * K + k];
-            tmp[(((long)b * H + y) * w + j) * K + k] = s;
-        }
-    }
+    if (tmp) tile_gather_x(dbuf, lam, pstart, tmp + ((long)b * H + y) * w * K, K, j0, j1, w, npx);
     block_sum2(loss, cnt, red);
     if (threadIdx.x == 0) {
         const long pidx = ((long)b * H + y) * gridDim.x + jt;
@@ -314,7 +329,271 @@ __global__ void upce_pass2_kernel(const float* __restrict__ tmp, const float* __
         const float wy = (y0 == i ? 1.f - ly : 0.f) + (y1 == i ? ly : 0.f);
         s += wy * tmp[((long)b * H + y) * per_row + jk];
     }
-    dlow[idx] = s * (grad_scale / loss_out[1]);
+    dlow[idx] = s * (loss_out ? grad_scale / loss_out[1] : grad_scale);      // (no loss_out: the Dice gradient, whose coefficients carry its normalisation)
+}
+
+// ------------------------------------------------------------------------------------------------ generalized Dice, fused with the upsample
+// GeneralizedDiceLoss (reference core/utils/utility.py:399-447, label form) on z = bilinear(low), m = (label != ignore_index):
+//   p = softmax_k(z) m, t = onehot(label) m;  T_c = sum t, I_c = sum p t, P2_c = sum p^2;  w_c = 1 / (T_c^2 + eps) | 1 / (T_c + eps) | 1 / (sqrt(T_c) + eps)
+//   Num = sum_c w_c I_c, Den = sum_c w_c (P2_c + T_c) + eps, loss = 1 - 2 Num / Den
+//   d loss / d z_k = p_k (g_k - sum_j g_j p_j) on valid pixels, g_c = a_c t_c + b_c p_c, a_c = -2 w_c / Den, b_c = 4 Num w_c / Den^2
+// The coefficients depend on sums over the whole batch, so the gradient is a second pass that recomputes the softmax from `low`:
+//   gdl_reduce_kernel (per-workgroup partial T / I / P2) -> gdl_finalize_kernel (one workgroup: loss, a_c, b_c in device memory) ->
+//   gdl_grad_kernel (d loss / d z gathered along x, the skeleton of upce_pass1_kernel) -> upce_pass2_kernel (gathered along y).
+// Fixed summation order everywhere; T_c and the bad-label count are integers.
+constexpr int GDL_XT = 256;          // output pixels of one row per workgroup in the reduction pass: one per thread and row
+
+__device__ __forceinline__ float wave_sum(float v) {          // xor butterfly: both partners add the same two values, every lane ends with the same bits
+    for (int m = 32; m > 0; m >>= 1) v += __shfl_xor(v, m);
+    return v;
+}
+__device__ __forceinline__ unsigned wave_sum(unsigned v) {
+    for (int m = 32; m > 0; m >>= 1) v += (unsigned)__shfl_xor((int)v, m);
+    return v;
+}
+
+// One workgroup per (b, `rows` output rows, GDL_XT output columns); a thread keeps one column and walks the rows with its 3K sums in registers.
+// partial: [workgroup][3K + 1] 32-bit words - T_c (unsigned), the bad-label count (unsigned), I_c (float), P2_c (float).
+template <int KT>
+__global__ __launch_bounds__(256) void gdl_reduce_kernel(const float* __restrict__ low, const int64_t* __restrict__ labels, unsigned* __restrict__ partial,
+                                                         int Krt, Axis ay, Axis ax, int ignore_index, int rows, int ncol_max) {
+    const int K = KT > 0 ? KT : Krt;
+    constexpr int KR = KT > 0 ? KT : KMAX;
+    extern __shared__ __attribute__((aligned(16))) float sh[];
+    float* vrow = sh;                                                          // [ncol_max][K] source row already interpolated along y
+    unsigned* red = reinterpret_cast<unsigned*>(sh + (long)ncol_max * K);      // [4][3K + 1]
+    const int H = ay.n_out, W = ax.n_out, h = ay.n_in, w = ax.n_in;
+    const int NC = 3 * K + 1, tid = threadIdx.x, b = blockIdx.z;
+    const int xa = blockIdx.x * GDL_XT, xb = min(W, xa + GDL_XT);
+    const int ya = blockIdx.y * rows, yb = min(H, ya + rows);
+    int cbase, clast, unused;
+    float lx = 0.f;
+    ax.src(xa, cbase, unused, lx);
+    ax.src(xb - 1, unused, clast, lx);
+    const int ncol = min(clast - cbase + 1, ncol_max);      // upsampling: x0 advances by at most one per pixel, so GDL_XT pixels touch at most GDL_XT + 1 columns
+    const int x = xa + tid;
+    int x0 = cbase, x1 = cbase;
+    if (x < xb) ax.src(x, x0, x1, lx);
+    float p2[KR], it[KR];
+    unsigned tc[KR], bad = 0u;
+#pragma unroll
+    for (int k = 0; k < KR; ++k) {
+        p2[k] = 0.f;
+        it[k] = 0.f;
+        tc[k] = 0u;
+    }
+    for (int y = ya; y < yb; ++y) {
+        int y0, y1;
+        float ly;
+        ay.src(y, y0, y1, ly);
+        const float* row0 = low + (((long)b * h + y0) * w + cbase) * K;
+        const float* row1 = low + (((long)b * h + y1) * w + cbase) * K;
+        for (int e = tid; e < ncol * K; e += 256) vrow[e] = (1.f - ly) * row0[e] + ly * row1[e];
+        __syncthreads();
+        if (x < xb) {
+            const long lab = labels[((long)b * H + y) * W + x];
+            if (lab != ignore_index && lab >= 0 && lab < K) {
+                const float* c0 = vrow + (x0 - cbase) * K;
+                const float* c1 = vrow + (x1 - cbase) * K;
+                float v[KR];
+                float mx = -3.0e38f;
+#pragma unroll
+                for (int k = 0; k < KR; ++k) {
+                    if (k < K) {
+                        v[k] = (1.f - lx) * c0[k] + lx * c1[k];
+                        mx = fmaxf(mx, v[k]);
+                    }
+                }
+                float se = 0.f;
+#pragma unroll
+                for (int k = 0; k < KR; ++k) {
+                    if (k < K) {
+                        v[k] = __expf(v[k] - mx);
+                        se += v[k];
+                    }
+                }
+                const float rse = 1.f / se;
+#pragma unroll
+                for (int k = 0; k < KR; ++k) {
+                    if (k < K) {
+                        const float p = v[k] * rse;
+                        p2[k] += p * p;
+                        if (k == lab) {
+                            it[k] += p;
+                            tc[k] += 1u;
+                        }
+                    }
+                }
+            } else if (lab != ignore_index) {
+                bad += 1u;
+            }
+        }
+        __syncthreads();          // the next row overwrites vrow
+    }
+    const int lane = tid & 63, wv = tid >> 6;
+#pragma unroll
+    for (int k = 0; k < KR; ++k) {
+        if (k < K) {
+            const unsigned t = wave_sum(tc[k]);
+            const float a = wave_sum(it[k]), q = wave_sum(p2[k]);
+            if (lane == 0) {
+                red[wv * NC + k] = t;
+                red[wv * NC + K + 1 + k] = __float_as_uint(a);
+                red[wv * NC + 2 * K + 1 + k] = __float_as_uint(q);
+            }
+        }
+    }
+    bad = wave_sum(bad);
+    if (lane == 0) red[wv * NC + K] = bad;
+    __syncthreads();
+    if (tid < NC) {
+        const long wg = ((long)b * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
+        unsigned r;
+        if (tid <= K)
+            r = red[tid] + red[NC + tid] + red[2 * NC + tid] + red[3 * NC + tid];
+        else
+            r = __float_as_uint(((__uint_as_float(red[tid]) + __uint_as_float(red[NC + tid])) + __uint_as_float(red[2 * NC + tid])) +
+                                __uint_as_float(red[3 * NC + tid]));
+        partial[wg * NC + tid] = r;
+    }
+}
+
+__device__ __forceinline__ double gdl_weight(double T, int weight_type, double eps) {
+    return 1.0 / ((weight_type == 0 ? T * T : weight_type == 1 ? T : sqrt(T)) + eps);
+}
+
+// One workgroup of GDL_FIN_WAVES waves: the partial rows summed in a fixed order (wave w takes rows w, w + 16, ... with four loads in flight; integers in
+// 64 bits, floats in fp64), then the loss and the 2K gradient coefficients.  loss_out: loss, valid pixels, bad labels, 0.  sums (nullable): [3K] T, I, P2.
+// The loop is a chain of memory round trips, hence 16 waves with four loads in flight each: 16 us for the 990 rows of a 6 x 720 x 1280 head.
+constexpr int GDL_FIN_WAVES = 16;
+__global__ __launch_bounds__(64 * GDL_FIN_WAVES) void gdl_finalize_kernel(const unsigned* __restrict__ partial, int n, int K, int weight_type, float eps,
+                                                                          float* __restrict__ loss_out, float* __restrict__ coef, float* __restrict__ sums) {
+    __shared__ double red[GDL_FIN_WAVES][3 * KMAX + 1];
+    __shared__ double tot[3 * KMAX + 1];
+    __shared__ double nd[2];
+    const int NC = 3 * K + 1, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    constexpr int S = GDL_FIN_WAVES;
+    for (int c = lane; c < NC; c += 64) {
+        const unsigned* col = partial + c;
+        double s = 0.0;
+        int i = wv;
+        if (c <= K) {
+            unsigned long long u = 0ull;
+            for (; i + 3 * S < n; i += 4 * S)
+                u += ((unsigned long long)col[(long)i * NC] + col[(long)(i + S) * NC]) + ((unsigned long long)col[(long)(i + 2 * S) * NC] + col[(long)(i + 3 * S) * NC]);
+            for (; i < n; i += S) u += col[(long)i * NC];
+            s = (double)u;
+        } else {
+            for (; i + 3 * S < n; i += 4 * S)
+                s += ((double)__uint_as_float(col[(long)i * NC]) + (double)__uint_as_float(col[(long)(i + S) * NC])) +
+                     ((double)__uint_as_float(col[(long)(i + 2 * S) * NC]) + (double)__uint_as_float(col[(long)(i + 3 * S) * NC]));
+            for (; i < n; i += S) s += (double)__uint_as_float(col[(long)i * NC]);
+        }
+        red[wv][c] = s;
+    }
+    __syncthreads();
+    if (tid < NC) {
+        double s = 0.0;
+        for (int w = 0; w < S; ++w) s += red[w][tid];
+        tot[tid] = s;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        double num = 0.0, den = 0.0, valid = 0.0;
+        for (int c = 0; c < K; ++c) {
+            const double T = tot[c], wc = gdl_weight(T, weight_type, (double)eps);
+            num += wc * tot[K + 1 + c];
+            den += wc * (tot[2 * K + 1 + c] + T);
+            valid += T;
+        }
+        den += (double)eps;
+        nd[0] = num;
+        nd[1] = den;
+        loss_out[0] = (float)(1.0 - 2.0 * num / den);      // every pixel ignored: num = 0, den = eps, the loss is exactly 1
+        loss_out[1] = (float)valid;
+        loss_out[2] = (float)tot[K];
+        loss_out[3] = 0.f;
+    }
+    __syncthreads();
+    if (tid < K) {
+        const double num = nd[0], den = nd[1], wc = gdl_weight(tot[tid], weight_type, (double)eps);
+        coef[tid] = (float)(-2.0 * wc / den);
+        coef[K + tid] = (float)(4.0 * num * wc / (den * den));
+        if (sums) {
+            sums[tid] = (float)tot[tid];
+            sums[K + tid] = (float)tot[K + 1 + tid];
+            sums[2 * K + tid] = (float)tot[2 * K + 1 + tid];
+        }
+    }
+}
+
+// The tiling of upce_pass1_kernel (one workgroup per (b, y, jt_cols low-res columns), pixels of the tile's column support in LDS, gathered per (j, k) in
+// ascending x: tile_stage / tile_gather_x) with d = d loss / d z of the Dice loss from the coefficients the finalize left in `coef` ([K] a_c, [K] b_c).
+template <int KT>
+__global__ __launch_bounds__(256) void gdl_grad_kernel(const float* __restrict__ low, const int64_t* __restrict__ labels, const float* __restrict__ coef,
+                                                       float* __restrict__ tmp, int Krt, Axis ay, Axis ax, int ignore_index, int npx_max, int jt_cols) {
+    const int K = KT > 0 ? KT : Krt;
+    constexpr int KR = KT > 0 ? KT : KMAX;
+    extern __shared__ __attribute__((aligned(16))) float sh[];
+    float* dbuf = sh;                                           // [npx_max][K]
+    float* lam = sh + (long)npx_max * K;                        // [npx_max]  lambda_x
+    int* pstart = reinterpret_cast<int*>(lam + npx_max);        // [JT+3] first pixel (relative to xa) whose x0 >= j0 - 1 + q
+    float* vrow = reinterpret_cast<float*>(pstart + JT + 4);    // [JT+2][K] low-res row already interpolated along y
+    const int H = ay.n_out, W = ax.n_out, h = ay.n_in, w = ax.n_in;
+    const int jt = blockIdx.x, y = blockIdx.y, b = blockIdx.z;
+    const int j0 = jt * jt_cols, j1 = min(w, j0 + jt_cols);
+    const int xa = ax.first_with_i0_ge(j0 - 1), xb = ax.first_with_i0_ge(j1);   // pixels with x0 in [j0-1, j1-1]
+    const int npx = min(xb - xa, npx_max);
+    int cbase;
+    tile_stage(low, K, ay, ax, b, y, j0, j1, xa, pstart, vrow, cbase);
+    __syncthreads();
+    for (int px = threadIdx.x; px < npx; px += 256) {
+        const int x = xa + px;
+        int x0, x1;
+        float lx;
+        ax.src(x, x0, x1, lx);
+        lam[px] = lx;
+        const long lab = labels[((long)b * H + y) * W + x];
+        float* d = dbuf + (long)px * K;
+        if (lab == ignore_index || lab < 0 || lab >= K) {
+            for (int k = 0; k < K; ++k) d[k] = 0.f;
+            continue;
+        }
+        const float* c0 = vrow + (x0 - cbase) * K;
+        const float* c1 = vrow + (x1 - cbase) * K;
+        float v[KR];
+        float mx = -3.0e38f;
+#pragma unroll
+        for (int k = 0; k < KR; ++k) {
+            if (k < K) {
+                v[k] = (1.f - lx) * c0[k] + lx * c1[k];
+                mx = fmaxf(mx, v[k]);
+            }
+        }
+        float se = 0.f;
+#pragma unroll
+        for (int k = 0; k < KR; ++k) {
+            if (k < K) {
+                v[k] = __expf(v[k] - mx);
+                se += v[k];
+            }
+        }
+        const float rse = 1.f / se;
+        float s = 0.f;                    // sum_j g_j p_j
+#pragma unroll
+        for (int k = 0; k < KR; ++k) {
+            if (k < K) {
+                v[k] *= rse;
+                s += (coef[K + k] * v[k] + (k == lab ? coef[k] : 0.f)) * v[k];
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < KR; ++k) {
+            if (k < K) d[k] = v[k] * ((coef[K + k] * v[k] + (k == lab ? coef[k] : 0.f)) - s);
+        }
+    }
+    __syncthreads();
+    tile_gather_x(dbuf, lam, pstart, tmp + ((long)b * H + y) * w * K, K, j0, j1, w, npx);
 }
 
 // ------------------------------------------------------------------------------------------------ inference tails
@@ -682,6 +961,81 @@ extern "C" int mi_upsample_ce_ex(const float* low, const int64_t* labels, float*
         hipLaunchKernelGGL(upce_pass2_kernel, dim3(nblk((long)B * h * w * K, 256)), dim3(256), 0, (hipStream_t)stream, (const float*)tmp, loss_out,
                            dlow, B, K, ay, w, grad_scale);
         MI_CHECK_LAUNCH("mi_upsample_ce pass2");
+    }
+    return MI_OK;
+}
+
+namespace {
+// The reduction pass's grid: GDL_XT-column tiles, and as many rows per workgroup as keep the launch near 1024 workgroups (4 per CU, what the kernel's
+// registers let a CU hold: one round; and the partial rows the one-workgroup finalize has to add stay a few hundred KB at 6 x 720 x 1280).
+struct GdlPlan {
+    int tiles_x, rows, row_groups;
+    size_t nwg;
+};
+inline GdlPlan gdl_plan(int B, int H, int W) {
+    GdlPlan p;
+    p.tiles_x = (W + GDL_XT - 1) / GDL_XT;
+    const long units = (long)B * H * p.tiles_x;
+    long rows = (units + 1023) / 1024;
+    p.rows = (int)(rows < 1 ? 1 : (rows > H ? H : rows));
+    p.row_groups = (H + p.rows - 1) / p.rows;
+    p.nwg = (size_t)B * p.row_groups * p.tiles_x;
+    return p;
+}
+inline size_t up256(size_t n) { return (n + 255) & ~(size_t)255; }
+}  // namespace
+
+extern "C" size_t mi_upsample_gdl_workspace(int B, int h, int w, int K, int H, int W) {
+    if (B <= 0 || h <= 0 || w <= 0 || K <= 0 || H <= 0 || W <= 0) return 0;
+    const GdlPlan p = gdl_plan(B, H, W);
+    return up256(p.nwg * (3 * (size_t)K + 1) * sizeof(unsigned)) + up256(2 * (size_t)K * sizeof(float)) + (size_t)B * H * w * K * sizeof(float);
+}
+
+extern "C" int mi_upsample_gdl(const float* low, const int64_t* labels, float* loss_out, float* dlow, float* sums, int B, int h, int w, int K, int H,
+                               int W, int ignore_index, int weight_type, float eps, float grad_scale, int align_corners, void* workspace,
+                               size_t workspace_bytes, void* stream) {
+    MI_REQUIRE(low && labels && loss_out && workspace, "mi_upsample_gdl: null operand");
+    MI_REQUIRE(B > 0 && h > 0 && w > 0 && H > 0 && W > 0 && K > 0 && K <= KMAX, "mi_upsample_gdl: bad dimension (K <= 32)");
+    MI_REQUIRE(H >= h && W >= w, "mi_upsample_gdl: only upsampling (H >= h, W >= w) is supported");
+    MI_REQUIRE(H <= 65535 && B <= 65535, "mi_upsample_gdl: grid dimension overflow");
+    MI_REQUIRE(weight_type >= MI_GDL_SQUARE && weight_type <= MI_GDL_SQRT, "mi_upsample_gdl: weight_type is MI_GDL_SQUARE, MI_GDL_IDENTITY or MI_GDL_SQRT");
+    MI_REQUIRE(eps > 0.f, "mi_upsample_gdl: eps must be positive");
+    if (workspace_bytes < mi_upsample_gdl_workspace(B, h, w, K, H, W)) return mi_set_error(MI_ENOMEM, "mi_upsample_gdl: workspace too small");
+    const Axis ay = make_axis(h, H, align_corners), ax = make_axis(w, W, align_corners);
+    const GdlPlan pl = gdl_plan(B, H, W);
+    unsigned* partial = (unsigned*)workspace;
+    float* coef = (float*)((char*)workspace + up256(pl.nwg * (3 * (size_t)K + 1) * sizeof(unsigned)));
+    float* tmp = (float*)((char*)coef + up256(2 * (size_t)K * sizeof(float)));
+    const int ncol_max = w < GDL_XT + 2 ? w : GDL_XT + 2;
+    const size_t lds1 = ((size_t)ncol_max * K + 4 * (3 * (size_t)K + 1)) * 4;          // <= 34 KB
+    const int jt_cols = pick_jt(w, W);
+    const int npx_max = pass1_npx_max(ax, jt_cols);
+    const size_t lds3 = (size_t)npx_max * K * 4 + (size_t)npx_max * 4 + (JT + 4) * 4 + (size_t)(JT + 2) * K * 4;
+    MI_REQUIRE(!dlow || lds3 <= 160 * 1024, "mi_upsample_gdl: upsample factor too large for one LDS tile (%zu B)", lds3);
+    const dim3 g1(pl.tiles_x, pl.row_groups, B);
+    if (K == 19)
+        hipLaunchKernelGGL(gdl_reduce_kernel<19>, g1, dim3(256), lds1, (hipStream_t)stream, low, labels, partial, K, ay, ax, ignore_index, pl.rows, ncol_max);
+    else
+        hipLaunchKernelGGL(gdl_reduce_kernel<0>, g1, dim3(256), lds1, (hipStream_t)stream, low, labels, partial, K, ay, ax, ignore_index, pl.rows, ncol_max);
+    MI_CHECK_LAUNCH("mi_upsample_gdl reduce");
+    hipLaunchKernelGGL(gdl_finalize_kernel, dim3(1), dim3(64 * GDL_FIN_WAVES), 0, (hipStream_t)stream, (const unsigned*)partial, (int)pl.nwg, K, weight_type, eps, loss_out,
+                       coef, sums);
+    MI_CHECK_LAUNCH("mi_upsample_gdl finalize");
+    if (dlow) {
+        static std::atomic<uint64_t> lds_set[2];
+        mi_allow_dynamic_lds((const void*)gdl_grad_kernel<19>, MI_LDS_MAX, lds_set[0]);
+        mi_allow_dynamic_lds((const void*)gdl_grad_kernel<0>, MI_LDS_MAX, lds_set[1]);
+        const int tiles = (w + jt_cols - 1) / jt_cols;
+        if (K == 19)
+            hipLaunchKernelGGL(gdl_grad_kernel<19>, dim3(tiles, H, B), dim3(256), lds3, (hipStream_t)stream, low, labels, (const float*)coef, tmp, K, ay, ax,
+                               ignore_index, npx_max, jt_cols);
+        else
+            hipLaunchKernelGGL(gdl_grad_kernel<0>, dim3(tiles, H, B), dim3(256), lds3, (hipStream_t)stream, low, labels, (const float*)coef, tmp, K, ay, ax,
+                               ignore_index, npx_max, jt_cols);
+        MI_CHECK_LAUNCH("mi_upsample_gdl gradient");
+        hipLaunchKernelGGL(upce_pass2_kernel, dim3(nblk((long)B * h * w * K, 256)), dim3(256), 0, (hipStream_t)stream, (const float*)tmp,
+                           (const float*)nullptr, dlow, B, K, ay, w, grad_scale);
+        MI_CHECK_LAUNCH("mi_upsample_gdl gradient rows");
     }
     return MI_OK;
 }

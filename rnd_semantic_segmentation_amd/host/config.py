@@ -14,6 +14,7 @@ import yaml
 
 _VALID = (tuple, list, str, int, float, bool, type(None))
 _RANGES = {"TEST.PSEUDO_THRESHOLD": (0.0, 1.0)}      # closed intervals a merged value has to lie in
+_CHOICES = {"SOLVER.LOSS": ("ce", "gdl"), "SOLVER.GDL_WEIGHT": ("square", "identity", "sqrt")}      # the only values a merged key may take
 
 
 class CfgNode(dict):
@@ -80,6 +81,8 @@ class CfgNode(dict):
     def _coerce(new, old, key):
         if key in _RANGES and isinstance(new, (int, float)) and not isinstance(new, bool) and not _RANGES[key][0] <= new <= _RANGES[key][1]:
             raise ValueError("Value {} of config key {} lies outside [{}, {}]".format(new, key, *_RANGES[key]))
+        if key in _CHOICES and new not in _CHOICES[key]:
+            raise ValueError("Value {!r} of config key {} is not one of {}".format(new, key, ", ".join(_CHOICES[key])))
         if old is None or new is None or type(new) is type(old):
             return new
         for a, b in ((list, tuple), (tuple, list)):
@@ -167,6 +170,9 @@ def default_tree():
             "EPOCHS": 5, "MAX_ITER": 16000, "STOP_ITER": 10000, "LR_METHOD": "poly", "BASE_LR": 0.02, "BASE_LR_D": 0.008,
             "LR_POWER": 0.9, "MOMENTUM": 0.9, "WEIGHT_DECAY": 0.0005, "WEIGHT_DECAY_BIAS": 0, "DECAY_RATE": 0.1,
             "DECAY_EPOCH": 50, "GAMMA": 0.1, "CHECKPOINT_PERIOD": 5, "BATCH_SIZE": 8, "BATCH_SIZE_VAL": 1,
+            # not in the reference: LOSS "ce" = the trainers' cross-entropy, "gdl" = GeneralizedDiceLoss (utility.py:399-447) on GALD's four heads
+            # (GALDTrainer only: the lines gald_trainer.py:70-73 toggles); GDL_WEIGHT = its weight_type, "square" | "identity" | "sqrt"
+            "LOSS": "ce", "GDL_WEIGHT": "square",
         },
         # not in the reference: PRECISION fp32 = exact evaluation path, bf16 = training engine; SCALES / FLIP other than these defaults make
         # ASPPTester call multi_scale_inference (utility.py:193-209) instead of inference(flip=False); FUSED_SCORE True = argmax, threshold and

@@ -95,6 +95,15 @@ class _GaldRun(Run):
         _count_bad_labels(self.net, loss_out)
         return self.node(loss_out[0].clone(), lambda g: acc(low, dlow * (g if inv_t is None else g * inv_t), True))
 
+    def gdl_head(self, low, labels, ignore_index, weight_type, inv_t=None):
+        """GeneralizedDiceLoss(F.interpolate(low, size=labels.shape[-2:], mode="bilinear"), labels, weight_type=...) (utility.py:399-447 on the outputs
+        of gcpa_cc2.py:78-81; the lines gald_trainer.py:70-73 toggles) fused, shaped like ce_head: mi_upsample_gdl never writes the full-resolution logits
+        or probabilities, and its gradient pass has run by the time the loss exists (the coefficients stay on the device)."""
+        src = low.t if inv_t is None else low.t * inv_t
+        loss_out, dlow, _ = K.upsample_gdl(src, labels, want_grad=self.rec, ignore_index=ignore_index, weight_type=weight_type, align_corners=False)
+        _count_bad_labels(self.net, loss_out)
+        return self.node(loss_out[0].clone(), lambda g: acc(low, dlow * (g if inv_t is None else g * inv_t), True))
+
     def criss_cross(self, x, uq, uk, uv, gamma):
         """CrissCrossAttention.forward (ccnet.py:56-127): gamma * aggregate + x."""
         net = self.net
@@ -369,6 +378,8 @@ class GCPADecoder(Engine):
         lows = [run.tap("linear%d" % i, run.conv_bias(v, self._lin[i])) for i, v in ((5, top), (4, o4), (3, o3), (2, o2))]
         labels = self.__dict__.get("_ce_labels")
         if labels is not None:                                                                 # the trainer's fused path: four scalar losses
+            if self.__dict__.get("_gdl_weight") is not None:
+                return [run.gdl_head(v, labels, self._ce_ignore, self._gdl_weight) for v in lows]
             return [run.ce_head(v, labels, self._ce_ignore) for v in lows]
         size = (x.t.shape[1], x.t.shape[2])
         return [run.tap("out%d" % i, run.resize(v, None, False, size=size)) for i, v in enumerate(lows)]      # F.interpolate(..., size=x.size()[2:], mode="bilinear")
@@ -376,14 +387,20 @@ class GCPADecoder(Engine):
     def forward(self, x, feats):
         return super().forward(x, *feats)
 
-    def losses(self, x, feats, labels, ignore_index=255):
-        """(loss5, loss4, loss3, loss2) = criterion(out_i, labels) of gald_trainer.py:76-79 without materialising the four [B,19,H,W] logit tensors
-        (upsample + cross-entropy fused, mi_upsample_ce_ex): what GALDTrainer.train_step calls."""
+    def losses(self, x, feats, labels, ignore_index=255, criterion="ce", weight_type="square"):
+        """(loss5, loss4, loss3, loss2) = criterion(out_i, labels) of gald_trainer.py:76-79 without materialising the four [B,19,H,W] logit tensors:
+        what GALDTrainer.train_step calls.  criterion "ce": upsample + cross-entropy fused (mi_upsample_ce_ex); "gdl": upsample +
+        GeneralizedDiceLoss(weight_type) fused (mi_upsample_gdl; gald_trainer.py:70-73)."""
+        if criterion not in ("ce", "gdl"):
+            raise ValueError("criterion must be 'ce' or 'gdl', got %r" % (criterion,))
+        if criterion == "gdl" and weight_type not in K.GDL_WEIGHT_TYPES:
+            raise ValueError("Check out the weight_type: %r (one of %s)" % (weight_type, ", ".join(K.GDL_WEIGHT_TYPES)))
         self._ce_labels, self._ce_ignore = labels.long().contiguous(), int(ignore_index)
+        self._gdl_weight = weight_type if criterion == "gdl" else None
         try:
             return super().forward(x, *feats)
         finally:
-            self._ce_labels = None
+            self._ce_labels = self._gdl_weight = None
 
     def loss(self, x, feats, label, ignore_index=255, temperature=1.0):
         """criterion(self(x, feats)[-1].div(temperature), label) of gald_fada.py:80-88 fused: out2 alone (linear5/4/3 are not run and get no
@@ -514,10 +531,14 @@ class GALDTrainer(BaseTrainer):
     weighted 1 / 0.8 / 0.6 / 0.4 (out2 .. out5), checkpoint {'epoch', 'iteration', 'encoder', 'decoder', 'optimizer_enc', 'optimizer_dec'} as
     Gald-<epoch>.pth."""
 
+    LOSSES = ("ce", "gdl")
+
     def __init__(self, name, cfg, train_loader, local_rank, logger=None):
         super().__init__(name, cfg, train_loader, local_rank, logger)
 
     def init_params(self):
+        self.loss_name = getattr(self.cfg.SOLVER, "LOSS", "ce")                  # (not in the reference's config: host/config.py)
+        self.gdl_weight = getattr(self.cfg.SOLVER, "GDL_WEIGHT", "square")
         self.encoder = GCPAEncoder().to(self.device)
         self.decoder = GCPADecoder(self.cfg.MODEL.NUM_CLASSES).to(self.device)
         self.encoder.ensure_flat()
@@ -555,7 +576,8 @@ class GALDTrainer(BaseTrainer):
         self.optimizer_dec.zero_grad()
         src_input = src_input.to(self.device, non_blocking=True)
         src_label = src_label.to(self.device, non_blocking=True).long()
-        loss5, loss4, loss3, loss2 = self.decoder.losses(src_input, self.encoder(src_input), src_label)          # = criterion(out_i, label), fused
+        loss5, loss4, loss3, loss2 = self.decoder.losses(src_input, self.encoder(src_input), src_label, criterion=self.loss_name,
+                                                         weight_type=self.gdl_weight)                            # = criterion(out_i, label), fused
         loss = loss2 * 1 + loss3 * 0.8 + loss4 * 0.6 + loss5 * 0.4
         loss.backward()
         self.optimizer_enc.step()

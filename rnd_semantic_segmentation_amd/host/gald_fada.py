@@ -22,6 +22,7 @@ import torch.nn.functional as F
 from .fada import FADAAdapter, PixelDiscriminator
 from .gald import GALDTrainer, take_bad_labels
 from .metrics import MetricLogger, adjust_learning_rate, dump_json, setup_logger, soft_label_cross_entropy
+from .plugin import require_loss
 
 
 class GaldFada:
@@ -33,6 +34,7 @@ class GaldFada:
     FUSED = True        # False: the literal order of operations on materialised tensors (the in-repo A/B of the fused kernels)
 
     def __init__(self, name, cfg, src_train_loader, tgt_train_loader, local_rank):
+        require_loss(cfg, type(self).__name__)          # its source loss is GCPADecoder.loss: cross-entropy on out2
         self.cfg = cfg
         self.logger = setup_logger(name + "_train", cfg.OUTPUT_DIR, local_rank)
         self.gald = self.trainer_cls(name, cfg, src_train_loader, local_rank, self.logger)

@@ -334,6 +334,45 @@ def soft_label_cross_entropy(pred, soft_label, pixel_weights=None):
     return torch.mean(pixel_weights * torch.sum(loss, dim=1))
 
 
+class _GeneralizedDiceFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, output, target, eps, weight_type, ignore_label):
+        from .. import kernels as K
+        nhwc = output.permute(0, 2, 3, 1).contiguous()          # (GCPADecoder's outputs ARE NHWC memory: no copy)
+        # the fused kernel at h == H, w == W: every interpolation weight is 0, the upsample is the identity
+        out, d, _ = K.upsample_gdl(nhwc, target.contiguous(), want_grad=ctx.needs_input_grad[0], ignore_index=ignore_label, weight_type=weight_type,
+                                   eps=eps, align_corners=False)
+        ctx.d = d
+        ctx.mark_non_differentiable(out)
+        return out[0].clone(), out
+
+    @staticmethod
+    def backward(ctx, gout, _gcounts):
+        d, ctx.d = ctx.d, None
+        return (d * gout).permute(0, 3, 1, 2), None, None, None, None
+
+
+def GeneralizedDiceLoss(output, target, eps=1e-5, weight_type='square', ignore_label=255, with_counts=False):
+    """utility.py:399-447, label form, on the HIP kernels (mi_upsample_gdl): output [N,C,H,W] fp32 logits on the GPU, target [N,H,W] labels.
+    Unlike the reference it leaves `target` as it is (utility.py:421 overwrites its ignored entries with C), and labels outside [0, C) that are
+    not ignore_label are left out and counted where F.one_hot would raise: with_counts=True (not in the reference) returns (loss, counts) with
+    counts the call's own float32 [4] device tensor loss, valid pixels, such labels, 0 (kernels.check_labels).  The one-hot [N,C,H,W] target
+    form and CPU tensors are refused."""
+    if weight_type not in ("square", "identity", "sqrt"):
+        raise ValueError('Check out the weight_type: ', weight_type)
+    if output.dim() != 4:
+        raise ValueError("GeneralizedDiceLoss: output must be [N,C,H,W] logits, got %s" % (tuple(output.shape),))
+    if target.dim() != 3:
+        raise NotImplementedError("GeneralizedDiceLoss: only the label form target [N,H,W] is implemented (got %s: the one-hot [N,C,H,W] form is not)"
+                                  % (tuple(target.shape),))
+    if not (output.is_cuda and target.is_cuda):
+        raise NotImplementedError("GeneralizedDiceLoss runs on the MI355X only (got %s / %s tensors): no CPU path exists" % (output.device, target.device))
+    if tuple(target.shape) != (output.shape[0],) + tuple(output.shape[2:]):
+        raise ValueError("GeneralizedDiceLoss: target %s does not match output %s" % (tuple(target.shape), tuple(output.shape)))
+    loss, counts = _GeneralizedDiceFn.apply(output.float(), target.long(), float(eps), weight_type, int(ignore_label))
+    return (loss, counts) if with_counts else loss
+
+
 def load_json(path):
     with open(path, "r") as f:
         return json.load(f)

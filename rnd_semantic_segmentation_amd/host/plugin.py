@@ -10,8 +10,20 @@ import torch.nn as nn
 from .metrics import setup_logger
 
 
+def require_loss(cfg, who, supported=("ce",)):
+    """SOLVER.LOSS (not in the reference) names the segmentation criterion; only GALDTrainer knows one besides cross-entropy."""
+    loss = getattr(getattr(cfg, "SOLVER", None), "LOSS", "ce")
+    if loss not in supported:
+        raise NotImplementedError("{} trains with SOLVER.LOSS 'ce' only (got {!r}); the generalized Dice loss ('gdl') is wired into GALD: "
+                                  "GALDTrainer (configs/gald_src_dice.yaml)".format(who, loss))
+    return loss
+
+
 class BaseTrainer:
+    LOSSES = ("ce",)          # the SOLVER.LOSS values the trainer implements
+
     def __init__(self, name, cfg, train_loader, local_rank, logger=None):
+        require_loss(cfg, type(self).__name__, self.LOSSES)
         self.cfg = cfg
         self.logger = setup_logger(name + "_train", cfg.OUTPUT_DIR, local_rank) if logger is None else logger
         self.train_loader = train_loader

@@ -477,6 +477,28 @@ def upsample_ce(low, labels, want_grad=True, grad_scale=1.0, ignore_index=255, a
     return out, dlow
 
 
+GDL_WEIGHT_TYPES = {"square": 0, "identity": 1, "sqrt": 2}          # MI_GDL_* of include/mi355seg.h
+
+
+def upsample_gdl(low, labels, want_grad=True, grad_scale=1.0, ignore_index=255, weight_type="square", eps=1e-5, align_corners=True, want_sums=False):
+    """Fused upsample + GeneralizedDiceLoss (reference utility.py:399-447, label form).  Returns (loss_out[4] = loss, valid pixels, bad labels, 0;
+    dlow or None; sums[3K] = T, I, P2 or None).  Nothing is read back between its launches."""
+    _chk(low, torch.float32, "low")
+    _chk(labels, torch.int64, "labels")
+    if weight_type not in GDL_WEIGHT_TYPES:
+        raise ValueError("Check out the weight_type: %r (one of %s)" % (weight_type, ", ".join(GDL_WEIGHT_TYPES)))
+    B, h, w, K = low.shape
+    _, H, W = labels.shape
+    L = _lib.lib()
+    ws = _workspace(L.mi_upsample_gdl_workspace(B, h, w, K, H, W), low.device, "upgdl")
+    out = torch.empty(4, dtype=torch.float32, device=low.device)
+    dlow = torch.empty_like(low) if want_grad else None
+    sums = torch.empty(3 * K, dtype=torch.float32, device=low.device) if want_sums else None
+    check(L.mi_upsample_gdl(_p(low), _p(labels), _p(out), _p(dlow), _p(sums), B, h, w, K, H, W, ignore_index, GDL_WEIGHT_TYPES[weight_type], float(eps),
+                            float(grad_scale), int(bool(align_corners)), _p(ws), ws.numel(), _stream()), "mi_upsample_gdl")
+    return out, dlow, sums
+
+
 def check_labels(loss_out, num_classes, what="labels"):
     """Raise if the CE kernels saw labels outside [0, num_classes) that are not ignore_index (torch's device assert).
     Synchronises (reads one float): call it where the loss value is fetched anyway."""

@@ -1,5 +1,13 @@
 """GALD (HarDNet-68 + GCPA decoder; configs/gald_src.yaml: batch 6, 1280 x 720 crops) training-step throughput on one MI355X: encoder + decoder forward,
-four cross-entropies, backward, both Adam steps.  `python tools/gald_bench.py [--batch 6] [--height 720] [--width 1280] [--steps 10]`."""
+four head losses, backward, both Adam steps.
+
+    python tools/gald_bench.py [--batch 6] [--height 720] [--width 1280] [--steps 10] [--loss ce|gdl] [--literal] [--alternate ROUNDS]
+
+--loss ce: the four fused upsample + cross-entropy heads (the default); --loss gdl: the four fused upsample + generalized Dice heads
+(configs/gald_src_dice.yaml).  --literal (with gdl): the composition without the fused kernel - decoder(x, feats) materialises the four [B,19,H,W]
+outputs, each goes as fp32 NCHW through the reference's GeneralizedDiceLoss written with torch ops, autograd does the backward.
+--alternate N: ce, gdl and gdl --literal one after the other, N times over, in this one process (one JSON line per variant and round), so that
+the three are compared on one box under the same conditions; the peak of allocated memory is reset before every variant."""
 import argparse
 import json
 import os
@@ -7,9 +15,29 @@ import sys
 import time
 
 import torch
+import torch.nn.functional as F
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from rnd_semantic_segmentation_amd.host import gald, pranet, synth  # noqa: E402
+
+
+def torch_gdl(output, target, eps=1e-5, weight_type="square", ignore_label=255):
+    """GeneralizedDiceLoss of utility.py:399-447 (label form) with torch ops on a materialised [N,C,H,W] tensor; `target` is left as it is."""
+    C = output.shape[1]
+    p = torch.softmax(output, 1)
+    m = target != ignore_label
+    p = p * m.unsqueeze(1)
+    t = F.one_hot(torch.where(m, target, torch.full_like(target, C)), C + 1)[..., :C].permute(0, 3, 1, 2)
+    ts = t.sum((0, 2, 3))
+    if weight_type == "square":
+        w = 1. / (ts * ts + eps)
+    elif weight_type == "identity":
+        w = 1. / (ts + eps)
+    else:
+        w = 1. / (torch.sqrt(ts.float()) + eps)
+    inter = ((p * t).sum((0, 2, 3)) * w).sum()
+    den = ((p * p + t * t).sum((0, 2, 3)) * w).sum() + eps
+    return 1 - 2. * inter / den
 
 
 def main():
@@ -19,36 +47,54 @@ def main():
     ap.add_argument("--width", type=int, default=1280)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--loss", choices=("ce", "gdl"), default="ce")
+    ap.add_argument("--literal", action="store_true", help="with --loss gdl: materialised outputs through a torch-op Dice loss with autograd")
+    ap.add_argument("--alternate", type=int, default=0, metavar="ROUNDS", help="run ce, gdl and gdl --literal in turn, ROUNDS times, in this process")
     a = ap.parse_args()
+    if a.literal and a.loss != "gdl":
+        ap.error("--literal goes with --loss gdl")
     torch.manual_seed(0)
     enc, dec = gald.GCPAEncoder().cuda().train(), gald.GCPADecoder().cuda().train()
     enc.ensure_flat()
     dec.ensure_flat()
     oe, od = pranet.FlatAdam(enc, 1e-4), pranet.FlatAdam(dec, 1e-3)
-    crit = gald.CrossEntropyNHWC(255)
     x = torch.from_numpy(synth.synth_image(a.batch, a.height, a.width, seed=9)).cuda()
     lab = torch.from_numpy(synth.synth_label(a.batch, a.height, a.width, 19, seed=9)).cuda().long()
 
-    def step():
+    def step(loss_name, literal):
         oe.zero_grad()
         od.zero_grad()
-        l5, l4, l3, l2 = dec.losses(x, enc(x), lab)          # the trainer's path: upsample + cross-entropy fused
+        if literal:
+            l5, l4, l3, l2 = [torch_gdl(o.float().contiguous(), lab) for o in dec(x, enc(x))]
+        else:
+            l5, l4, l3, l2 = dec.losses(x, enc(x), lab, criterion=loss_name)          # the trainer's path: upsample + loss fused
         loss = l2 * 1 + l3 * 0.8 + l4 * 0.6 + l5 * 0.4
         loss.backward()
         oe.step()
         od.step()
         return loss
 
-    for _ in range(a.warmup):
-        loss = step()
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(a.steps):
-        loss = step()
-    torch.cuda.synchronize()
-    dt = (time.perf_counter() - t0) / a.steps
-    print(json.dumps({"metric": "GALD train images/s", "value": round(a.batch / dt, 2), "ms_per_step": round(dt * 1e3, 2), "batch": a.batch, "size": [a.height, a.width],
-                      "loss": round(float(loss), 4), "max_mem_gb": round(torch.cuda.max_memory_allocated() / 2 ** 30, 2)}))
+    def measure(loss_name, literal, warmup):
+        torch.cuda.synchronize()
+        torch.cuda.reset_peak_memory_stats()
+        for _ in range(warmup):
+            loss = step(loss_name, literal)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(a.steps):
+            loss = step(loss_name, literal)
+        torch.cuda.synchronize()
+        dt = (time.perf_counter() - t0) / a.steps
+        print(json.dumps({"metric": "GALD train images/s", "value": round(a.batch / dt, 2), "ms_per_step": round(dt * 1e3, 2), "batch": a.batch,
+                          "size": [a.height, a.width], "loss_name": loss_name + ("-literal" if literal else ""), "loss": round(float(loss.detach()), 4),
+                          "max_mem_gb": round(torch.cuda.max_memory_allocated() / 2 ** 30, 2)}), flush=True)
+
+    if a.alternate:
+        for r in range(a.alternate):
+            for loss_name, literal in (("ce", False), ("gdl", False), ("gdl", True)):
+                measure(loss_name, literal, a.warmup if r == 0 else 1)
+    else:
+        measure(a.loss, a.literal, a.warmup)
 
 
 if __name__ == "__main__":
