@@ -533,6 +533,17 @@ int mi_gce(const float* logits, long ld, const int64_t* labels, long M, int K, i
  * fixed summation order). */
 int mi_gresize(const void* x, long ldx, void* out, long ldo, int f32, int B, int H, int W, int C, int Ho, int Wo, int align_corners, float scale_h, float scale_w,
                int backward, void* stream);
+/* The kernel instance mi_gresize launches for these arguments, from the planning function the launch itself calls (no GPU, no launch; x and out count for
+ * their alignment only and are never dereferenced).  route: int[MI_GRESIZE_ROUTE_LEN] = {kernel (MI_GRESIZE_*), f32, grid size in workgroups of 256}. */
+#define MI_GRESIZE_FWD 0          /* gresize_fwd_kernel<T>: thread per output element */
+#define MI_GRESIZE_FWD8 1         /* gresize_fwd8_kernel: bf16, thread per (output pixel, 8 channels) */
+#define MI_GRESIZE_BWD_GATHER 2   /* gresize_bwd_kernel<T>: thread per source element */
+#define MI_GRESIZE_BWD_WAVE 3     /* gresize_bwd_wave_kernel<T>: wave per source element */
+#define MI_GRESIZE_BWD_PIX 4      /* gresize_bwd_pix_kernel<T>: wave per source pixel, lanes over the channels */
+#define MI_GRESIZE_BWD8 5         /* gresize_bwd8_kernel: bf16, thread per (source pixel, 8 channels) */
+#define MI_GRESIZE_ROUTE_LEN 3
+int mi_gresize_route(const void* x, long ldx, const void* out, long ldo, int f32, int B, int H, int W, int C, int Ho, int Wo, int align_corners, float scale_h,
+                     float scale_w, int backward, int* route);
 /* reverse attention (PraNet_Res2Net.py:131-133): out[m][c] = (1 - sigmoid(gate[m])) * feat[m][c], gate fp32 [M]; backward: dfeat and dgate */
 int mi_gra_fwd(const float* gate, const void* feat, long ldfeat, void* out, long ldo, long M, int C, void* stream);
 int mi_gra_bwd(const float* gate, const void* feat, long ldfeat, const void* dy, long lddy, void* dfeat, long lddf, float* dgate, long M, int C, void* stream);

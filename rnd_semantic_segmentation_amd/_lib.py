@@ -112,6 +112,7 @@ SIGNATURES = {
     "mi_gce_workspace": (Z, [L]),
     "mi_gce": (I, [P, L, P, L, I, I, P, P, L, F, P, Z, P]),
     "mi_gresize": (I, [P, L, P, L, I] + [I] * 7 + [F, F, I, P]),
+    "mi_gresize_route": (I, [P, L, P, L, I] + [I] * 7 + [F, F, I, P]),
     "mi_gra_fwd": (I, [P, P, L, P, L, L, I, P]),
     "mi_gra_bwd": (I, [P, P, L, P, L, P, L, P, L, I, P]),
     "mi_gdwconv_stats_elems": (Z, [I] * 4),

@@ -1029,6 +1029,41 @@ inline int grid_for(long n) {
     return (int)(b < 1 ? 1 : (b > 16384 ? 16384 : b));
 }
 
+// The instance a resize launch runs, as planned by gresize_plan: mi_gresize launches what it says, mi_gresize_route reports it (host only: the operand
+// pointers count for their alignment alone).
+struct GResizeRoute {
+    int kernel;               // MI_GRESIZE_*
+    int f32;
+    unsigned grid;            // workgroups of 256 threads
+};
+GResizeRoute gresize_plan(const void* x, long ldx, const void* out, long ldo, int f32, int B, int H, int W, int C, int Ho, int Wo, float scale_h, float scale_w,
+                          int backward) {
+    GResizeRoute r{};
+    r.f32 = f32 ? 1 : 0;
+    const bool vec8 = !f32 && C % 8 == 0 && ldx % 8 == 0 && ldo % 8 == 0 && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(out)) & 15) == 0;
+    if (!backward) {
+        r.kernel = vec8 ? MI_GRESIZE_FWD8 : MI_GRESIZE_FWD;
+        r.grid = (unsigned)grid_for((long)B * Ho * Wo * (vec8 ? C / 8 : C));
+        return r;
+    }
+    const long nsrc = (long)B * H * W * C;
+    const float mag = (scale_h > 0.f ? 1.f / scale_h : (float)Ho) * (scale_w > 0.f ? 1.f / scale_w : (float)Wo);
+    if (vec8 && mag <= 256.f) {                      // bf16 feature maps with 16-byte views: thread per (source pixel, 8 channels)
+        r.kernel = MI_GRESIZE_BWD8;
+        r.grid = (unsigned)(((long)B * H * W * (C / 8) + 255) / 256);
+    } else if (C >= 8 && mag >= 4.f) {               // feature maps / class logits: one wave per source pixel, lanes over the channels
+        r.kernel = MI_GRESIZE_BWD_PIX;
+        r.grid = (unsigned)(((long)B * H * W + 3) / 4);
+    } else if (mag >= 16.f && nsrc <= (1L << 22)) {  // many candidates per source element, few source elements: one wave each
+        r.kernel = MI_GRESIZE_BWD_WAVE;
+        r.grid = (unsigned)((nsrc + 3) / 4);
+    } else {
+        r.kernel = MI_GRESIZE_BWD_GATHER;
+        r.grid = (unsigned)grid_for(nsrc);
+    }
+    return r;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1265,37 +1300,44 @@ int mi_gresize(const void* x, long ldx, void* out, long ldo, int f32, int B, int
     MI_REQUIRE(B > 0 && H > 0 && W > 0 && C > 0 && Ho > 0 && Wo > 0 && ldx >= C && ldo >= C, "mi_gresize: bad shape");
     ResizeP q{B, H, W, C, Ho, Wo, align_corners, scale_h, scale_w, ldx, ldo};
     hipStream_t s = (hipStream_t)stream;
-    const bool vec8 = !f32 && C % 8 == 0 && ldx % 8 == 0 && ldo % 8 == 0 && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(out)) & 15) == 0;
-    if (!backward) {
-        if (vec8) {
-            hipLaunchKernelGGL(gresize_fwd8_kernel, dim3(grid_for((long)B * Ho * Wo * (C / 8))), dim3(256), 0, s, (const __bf16*)x, (__bf16*)out, q);
-            MI_CHECK_LAUNCH("gresize_fwd8_kernel");
-            return MI_OK;
-        }
-        const dim3 grid(grid_for((long)B * Ho * Wo * C));
-        if (f32) hipLaunchKernelGGL((gresize_fwd_kernel<float>), grid, dim3(256), 0, s, (const float*)x, (float*)out, q);
-        else hipLaunchKernelGGL((gresize_fwd_kernel<__bf16>), grid, dim3(256), 0, s, (const __bf16*)x, (__bf16*)out, q);
-    } else {       // x = dx (written), out = dout (read)
-        const long nsrc = (long)B * H * W * C;
-        const float mag = (scale_h > 0.f ? 1.f / scale_h : (float)Ho) * (scale_w > 0.f ? 1.f / scale_w : (float)Wo);
-        if (vec8 && mag <= 256.f) {                      // bf16 feature maps with 16-byte views: thread per (source pixel, 8 channels)
-            const long items = (long)B * H * W * (C / 8);
-            hipLaunchKernelGGL(gresize_bwd8_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, s, (const __bf16*)out, (__bf16*)const_cast<void*>(x), q);
-        } else if (C >= 8 && mag >= 4.f) {               // feature maps / class logits: one wave per source pixel, lanes over the channels
-            const dim3 grid((unsigned)(((long)B * H * W + 3) / 4));
-            if (f32) hipLaunchKernelGGL((gresize_bwd_pix_kernel<float>), grid, dim3(256), 0, s, (const float*)out, (float*)const_cast<void*>(x), q);
-            else hipLaunchKernelGGL((gresize_bwd_pix_kernel<__bf16>), grid, dim3(256), 0, s, (const __bf16*)out, (__bf16*)const_cast<void*>(x), q);
-        } else if (mag >= 16.f && nsrc <= (1L << 22)) {  // many candidates per source element, few source elements: one wave each
-            const dim3 grid((unsigned)((nsrc + 3) / 4));
-            if (f32) hipLaunchKernelGGL((gresize_bwd_wave_kernel<float>), grid, dim3(256), 0, s, (const float*)out, (float*)const_cast<void*>(x), q);
-            else hipLaunchKernelGGL((gresize_bwd_wave_kernel<__bf16>), grid, dim3(256), 0, s, (const __bf16*)out, (__bf16*)const_cast<void*>(x), q);
-        } else {
-            const dim3 grid(grid_for(nsrc));
-            if (f32) hipLaunchKernelGGL((gresize_bwd_kernel<float>), grid, dim3(256), 0, s, (const float*)out, (float*)const_cast<void*>(x), q);
-            else hipLaunchKernelGGL((gresize_bwd_kernel<__bf16>), grid, dim3(256), 0, s, (const __bf16*)out, (__bf16*)const_cast<void*>(x), q);
-        }
+    const GResizeRoute r = gresize_plan(x, ldx, out, ldo, f32, B, H, W, C, Ho, Wo, scale_h, scale_w, backward);
+    const dim3 grid(r.grid);
+    // backward: x = dx (written), out = dout (read)
+#define RS(KERNEL, T, SRC, DST) hipLaunchKernelGGL(KERNEL, grid, dim3(256), 0, s, (const T*)(SRC), (T*)const_cast<void*>((const void*)(DST)), q)
+    switch (r.kernel) {
+    case MI_GRESIZE_FWD8: RS(gresize_fwd8_kernel, __bf16, x, out); break;
+    case MI_GRESIZE_FWD:
+        if (f32) RS((gresize_fwd_kernel<float>), float, x, out);
+        else RS((gresize_fwd_kernel<__bf16>), __bf16, x, out);
+        break;
+    case MI_GRESIZE_BWD8: RS(gresize_bwd8_kernel, __bf16, out, x); break;
+    case MI_GRESIZE_BWD_PIX:
+        if (f32) RS((gresize_bwd_pix_kernel<float>), float, out, x);
+        else RS((gresize_bwd_pix_kernel<__bf16>), __bf16, out, x);
+        break;
+    case MI_GRESIZE_BWD_WAVE:
+        if (f32) RS((gresize_bwd_wave_kernel<float>), float, out, x);
+        else RS((gresize_bwd_wave_kernel<__bf16>), __bf16, out, x);
+        break;
+    default:
+        if (f32) RS((gresize_bwd_kernel<float>), float, out, x);
+        else RS((gresize_bwd_kernel<__bf16>), __bf16, out, x);
+        break;
     }
+#undef RS
     MI_CHECK_LAUNCH("gresize_kernel");
+    return MI_OK;
+}
+
+int mi_gresize_route(const void* x, long ldx, const void* out, long ldo, int f32, int B, int H, int W, int C, int Ho, int Wo, int align_corners, float scale_h,
+                     float scale_w, int backward, int* route) {
+    MI_REQUIRE(route, "mi_gresize_route: null route");
+    MI_REQUIRE(x && out, "mi_gresize_route: null operand");
+    MI_REQUIRE(B > 0 && H > 0 && W > 0 && C > 0 && Ho > 0 && Wo > 0 && ldx >= C && ldo >= C, "mi_gresize_route: bad shape");
+    (void)align_corners;          // (the convention is in the scales; kept so that the query takes mi_gresize's own arguments)
+    const GResizeRoute r = gresize_plan(x, ldx, out, ldo, f32, B, H, W, C, Ho, Wo, scale_h, scale_w, backward);
+    const int v[MI_GRESIZE_ROUTE_LEN] = {r.kernel, r.f32, (int)r.grid};
+    for (int k = 0; k < MI_GRESIZE_ROUTE_LEN; ++k) route[k] = v[k];
     return MI_OK;
 }
 

@@ -425,6 +425,38 @@ def resize_scales(in_hw, out_hw, align_corners, scale_factor=None):
     return one(in_hw[0], out_hw[0]), one(in_hw[1], out_hw[1])
 
 
+# Opt-in recorder of the resize instances (tests): None, or a set to which gresize and gresize_bwd add the GResizeRoute of every launch.  Kept apart from
+# ROUTES, whose contents the conv tables account for.
+RESIZE_ROUTES = None
+
+
+class GResizeRoute(collections.namedtuple("GResizeRoute", "kernel f32 grid")):
+    """include/mi355seg.h mi_gresize_route's descriptor (MI_GRESIZE_ROUTE_LEN fields, in its order); `name` is the kernel instance as profilers print it."""
+    __slots__ = ()
+    KERNELS = ("gresize_fwd_kernel", "gresize_fwd8_kernel", "gresize_bwd_kernel", "gresize_bwd_wave_kernel", "gresize_bwd_pix_kernel", "gresize_bwd8_kernel")
+    FWD, FWD8, BWD_GATHER, BWD_WAVE, BWD_PIX, BWD8 = range(6)          # MI_GRESIZE_*
+
+    @property
+    def name(self):
+        k = self.KERNELS[self.kernel]
+        return k if self.kernel in (self.FWD8, self.BWD8) else "%s<%s>" % (k, "float" if self.f32 else "__bf16")
+
+
+GRESIZE_ROUTE_LEN = len(GResizeRoute._fields)
+
+
+def gresize_route(x_addr, ldx, out_addr, ldo, f32, in_shape, out_hw, align_corners, scale_factor=None, backward=False):
+    """The instance mi_gresize launches for a [B,H,W,C] input view at address x_addr (pixel stride ldx; backward: d loss / d input) and the [B,Ho,Wo,C] view
+    at out_addr (ldo; backward: d loss / d output): host only, the addresses count for their alignment alone."""
+    B, H, W, C = in_shape
+    Ho, Wo = out_hw
+    sh, sw = resize_scales((H, W), out_hw, align_corners, scale_factor)
+    r = (ctypes.c_int * GRESIZE_ROUTE_LEN)()
+    check(_lib.lib().mi_gresize_route(ctypes.c_void_p(x_addr), ldx, ctypes.c_void_p(out_addr), ldo, int(f32), B, H, W, C, Ho, Wo, int(align_corners), sh, sw,
+                                      int(backward), r), "mi_gresize_route")
+    return GResizeRoute(*r)
+
+
 def gresize(x, out_hw, align_corners, scale_factor=None, out=None):
     B, H, W, C = x.shape
     Ho, Wo = out_hw
@@ -433,6 +465,8 @@ def gresize(x, out_hw, align_corners, scale_factor=None, out=None):
     sh, sw = resize_scales((H, W), out_hw, align_corners, scale_factor)
     px, ldx = view(x)
     po, ldo = view(out, x.dtype)
+    if RESIZE_ROUTES is not None:
+        RESIZE_ROUTES.add(gresize_route(x.data_ptr(), ldx, out.data_ptr(), ldo, x.dtype == torch.float32, x.shape, out_hw, align_corners, scale_factor))
     check(_L().mi_gresize(px, ldx, po, ldo, int(x.dtype == torch.float32), B, H, W, C, Ho, Wo, int(align_corners), sh, sw, 0, _stream()), "mi_gresize")
     return out
 
@@ -445,6 +479,9 @@ def gresize_bwd(dout, in_hw, align_corners, scale_factor=None, dx=None):
     sh, sw = resize_scales((H, W), (Ho, Wo), align_corners, scale_factor)
     px, ldx = view(dx, dout.dtype)
     po, ldo = view(dout)
+    if RESIZE_ROUTES is not None:
+        RESIZE_ROUTES.add(gresize_route(dx.data_ptr(), ldx, dout.data_ptr(), ldo, dout.dtype == torch.float32, (B, H, W, C), (Ho, Wo), align_corners, scale_factor,
+                                        backward=True))
     check(_L().mi_gresize(px, ldx, po, ldo, int(dout.dtype == torch.float32), B, H, W, C, Ho, Wo, int(align_corners), sh, sw, 1, _stream()), "mi_gresize(bwd)")
     return dx
 
