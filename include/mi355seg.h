@@ -245,6 +245,22 @@ int mi_upsample_gdl(const float* low, const int64_t* labels, float* loss_out /*[
                     int B, int h, int w, int K, int H, int W, int ignore_index, int weight_type, float eps, float grad_scale,
                     int align_corners, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- fused upsample + Tversky + binary cross-entropy (TverskyLoss / BinaryCrossEntropyLoss / CompoundLoss, reference
+ * core/models/classifiers/attn/loss.py:7-27, 42-74) for one-channel logits ----
+ * low [B][h][w] fp32 logits, mask [B][H][W] fp32 in [0, 1] (may be soft), H >= h, W >= w, either bilinear convention; h == H, w == W is the identity.
+ * With z = bilinear(low), p = sigmoid(z), N = B H W:  TP = sum p y, FN = sum y (1 - p), FP = sum p (1 - y) over the whole batch,
+ * tversky = 1 - (TP + eps) / (TP + alpha FN + (1 - alpha) FP + eps), bce = 1/N sum [max(z, 0) - z y + log1p(exp(-|z|))],
+ * loss = w_tversky tversky + w_bce bce.  0 <= alpha <= 1, eps > 0.
+ * loss_out (four floats): [0] = loss, [1] = tversky, [2] = bce, [3] = 0.  sums (may be NULL) [3] fp32: TP, FN, FP.
+ * dlow (may be NULL: loss only, same loss bits) [B][h][w] = d loss / d low * grad_scale.
+ * Launches: a reduction pass, a one-workgroup finalize that leaves the loss and the gradient's three coefficients in device memory, and - with dlow -
+ * the gradient pass (two launches, along x then y), which recomputes z from `low`.  Nothing is read back in between: the call can be captured in a
+ * HIP graph.  Deterministic (fixed summation order, no floating-point atomics). */
+size_t mi_upsample_tversky_bce_workspace(int B, int h, int w, int H, int W);
+int mi_upsample_tversky_bce(const float* low, const float* mask, float* loss_out /*[4]*/, float* dlow, float* sums /*[3]*/,
+                            int B, int h, int w, int H, int W, float alpha, float eps, float w_tversky, float w_bce, float grad_scale,
+                            int align_corners, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- inference tail: upsample to label size + softmax over classes (utility.py:185-186) ---------
  * probs [B][K][H][W] fp32; pred (optional, may be NULL) [B][H][W] uint8 argmax (first max wins). */
 int mi_upsample_softmax(const float* low, float* probs, uint8_t* pred, int B, int h, int w, int K, int H, int W, void* stream);

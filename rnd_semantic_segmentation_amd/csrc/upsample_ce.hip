@@ -596,6 +596,158 @@ __global__ __launch_bounds__(256) void gdl_grad_kernel(const float* __restrict__
     tile_gather_x(dbuf, lam, pstart, tmp + ((long)b * H + y) * w * K, K, j0, j1, w, npx);
 }
 
+// ------------------------------------------------------------------------------------------------ Tversky + binary cross-entropy, fused with the upsample
+// CompoundLoss([TverskyLoss(alpha, eps), BinaryCrossEntropyLoss()], [w_t, w_b]) (reference core/models/classifiers/attn/loss.py:7-27, 42-74) on
+// z = bilinear(low) for ONE channel, y = mask in [0, 1] (may be soft), p = sigmoid(z), q = p (1 - p), N = B H W:
+//   TP = sum p y, FN = sum y (1 - p), FP = sum p (1 - y) over the whole batch;  D = TP + alpha FN + (1 - alpha) FP + eps
+//   tversky = 1 - (TP + eps) / D;  bce = 1/N sum [max(z, 0) - z y + log1p(exp(-|z|))];  loss = w_t tversky + w_b bce
+//   d loss / d z = w_t q (c1 - c0 y) + w_b / N (p - y),  c0 = 1 / D, c1 = (1 - alpha)(TP + eps) / D^2      (dD/dz = (1 - alpha) q whatever y is)
+// The launches of mi_upsample_gdl with K = 1:  tvb_reduce_kernel (per-workgroup partial TP / FN / FP / bce) -> tvb_finalize_kernel (one workgroup: the
+// loss and w_t c0, w_t c1, w_b / N in device memory) -> tvb_grad_kernel (d loss / d z gathered along x: tile_stage / tile_gather_x) -> upce_pass2_kernel.
+// exp(-|z|) <= 1 everywhere, so saturated logits stay finite; 1 - p is formed from the same exponential, not by subtraction.
+constexpr int TVB_NC = 4;          // TP, FN, FP, the bce sum
+
+__device__ __forceinline__ double wave_sum(double v) {
+    for (int m = 32; m > 0; m >>= 1) v += __shfl_xor(v, m);
+    return v;
+}
+
+// p = sigmoid(z), np = 1 - p, e = exp(-|z|)
+__device__ __forceinline__ void sigmoid_pair(float z, float& p, float& np, float& e) {
+    e = __expf(-fabsf(z));
+    const float r = 1.f / (1.f + e), er = e * r;
+    p = z >= 0.f ? r : er;
+    np = z >= 0.f ? er : r;
+}
+
+// The grid of gdl_reduce_kernel: one workgroup per (b, `rows` output rows, GDL_XT output columns), a thread keeps one column and walks the rows.
+// partial: [workgroup][4] floats.
+__global__ __launch_bounds__(256) void tvb_reduce_kernel(const float* __restrict__ low, const float* __restrict__ mask, float* __restrict__ partial, Axis ay,
+                                                         Axis ax, int rows) {
+    __shared__ float vrow[GDL_XT + 2];          // source row already interpolated along y
+    __shared__ float red[4][TVB_NC];
+    const int H = ay.n_out, W = ax.n_out, h = ay.n_in, w = ax.n_in;
+    const int tid = threadIdx.x, b = blockIdx.z;
+    const int xa = blockIdx.x * GDL_XT, xb = min(W, xa + GDL_XT);
+    const int ya = blockIdx.y * rows, yb = min(H, ya + rows);
+    int cbase, clast, unused;
+    float lx = 0.f;
+    ax.src(xa, cbase, unused, lx);
+    ax.src(xb - 1, unused, clast, lx);
+    const int ncol = min(clast - cbase + 1, GDL_XT + 2);      // upsampling: x0 advances by at most one per pixel
+    const int x = xa + tid;
+    int x0 = cbase, x1 = cbase;
+    if (x < xb) ax.src(x, x0, x1, lx);
+    float tp = 0.f, fn = 0.f, fp = 0.f, bce = 0.f;
+    for (int y = ya; y < yb; ++y) {
+        int y0, y1;
+        float ly;
+        ay.src(y, y0, y1, ly);
+        const float* row0 = low + ((long)b * h + y0) * w + cbase;
+        const float* row1 = low + ((long)b * h + y1) * w + cbase;
+        for (int e = tid; e < ncol; e += 256) vrow[e] = (1.f - ly) * row0[e] + ly * row1[e];
+        __syncthreads();
+        if (x < xb) {
+            const float t = mask[((long)b * H + y) * W + x];
+            const float z = (1.f - lx) * vrow[x0 - cbase] + lx * vrow[x1 - cbase];
+            float p, np, e;
+            sigmoid_pair(z, p, np, e);
+            tp += p * t;
+            fn += t * np;
+            fp += p * (1.f - t);
+            bce += (fmaxf(z, 0.f) - z * t) + log1pf(e);
+        }
+        __syncthreads();          // the next row overwrites vrow
+    }
+    const int lane = tid & 63, wv = tid >> 6;
+    tp = wave_sum(tp), fn = wave_sum(fn), fp = wave_sum(fp), bce = wave_sum(bce);
+    if (lane == 0) {
+        red[wv][0] = tp;
+        red[wv][1] = fn;
+        red[wv][2] = fp;
+        red[wv][3] = bce;
+    }
+    __syncthreads();
+    if (tid < TVB_NC) {
+        const long wg = ((long)b * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
+        partial[wg * TVB_NC + tid] = ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
+    }
+}
+
+// One workgroup: the partial rows added in fp64 in a fixed order (thread t takes rows t, t + 256, ...; butterfly per wave; the four waves in order), then
+// loss_out = loss, tversky, bce, 0; coef = w_t c0, w_t c1, w_b / N; sums (nullable) = TP, FN, FP.
+__global__ __launch_bounds__(256) void tvb_finalize_kernel(const float* __restrict__ partial, int n, double npix, float alpha, float eps, float w_t, float w_b,
+                                                           float* __restrict__ loss_out, float* __restrict__ coef, float* __restrict__ sums) {
+    __shared__ double red[4][TVB_NC];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    double s[TVB_NC] = {0.0, 0.0, 0.0, 0.0};
+    for (int i = tid; i < n; i += 256) {
+        const float4 v = reinterpret_cast<const float4*>(partial)[i];
+        s[0] += (double)v.x;
+        s[1] += (double)v.y;
+        s[2] += (double)v.z;
+        s[3] += (double)v.w;
+    }
+#pragma unroll
+    for (int c = 0; c < TVB_NC; ++c) {
+        s[c] = wave_sum(s[c]);
+        if (lane == 0) red[wv][c] = s[c];
+    }
+    __syncthreads();
+    if (tid == 0) {
+        double tot[TVB_NC];
+        for (int c = 0; c < TVB_NC; ++c) tot[c] = ((red[0][c] + red[1][c]) + red[2][c]) + red[3][c];
+        const double a = (double)alpha, e = (double)eps, tpe = tot[0] + e;
+        const double D = tot[0] + a * tot[1] + (1.0 - a) * tot[2] + e;          // >= eps > 0
+        const double tversky = 1.0 - tpe / D, bce = tot[3] / npix;
+        loss_out[0] = (float)((double)w_t * tversky + (double)w_b * bce);
+        loss_out[1] = (float)tversky;
+        loss_out[2] = (float)bce;
+        loss_out[3] = 0.f;
+        coef[0] = (float)((double)w_t / D);
+        coef[1] = (float)((double)w_t * (1.0 - a) * tpe / (D * D));
+        coef[2] = (float)((double)w_b / npix);
+        if (sums) {
+            sums[0] = (float)tot[0];
+            sums[1] = (float)tot[1];
+            sums[2] = (float)tot[2];
+        }
+    }
+}
+
+// The tiling of gdl_grad_kernel with one channel: d = d loss / d z from the three coefficients the finalize left in `coef`.
+__global__ __launch_bounds__(256) void tvb_grad_kernel(const float* __restrict__ low, const float* __restrict__ mask, const float* __restrict__ coef,
+                                                       float* __restrict__ tmp, Axis ay, Axis ax, int npx_max, int jt_cols) {
+    extern __shared__ __attribute__((aligned(16))) float sh[];
+    float* dbuf = sh;                                           // [npx_max]
+    float* lam = sh + npx_max;                                  // [npx_max]  lambda_x
+    int* pstart = reinterpret_cast<int*>(lam + npx_max);        // [JT+3] first pixel (relative to xa) whose x0 >= j0 - 1 + q
+    float* vrow = reinterpret_cast<float*>(pstart + JT + 4);    // [JT+2] low-res row already interpolated along y
+    const int H = ay.n_out, W = ax.n_out, w = ax.n_in;
+    const int jt = blockIdx.x, y = blockIdx.y, b = blockIdx.z;
+    const int j0 = jt * jt_cols, j1 = min(w, j0 + jt_cols);
+    const int xa = ax.first_with_i0_ge(j0 - 1), xb = ax.first_with_i0_ge(j1);   // pixels with x0 in [j0-1, j1-1]
+    const int npx = min(xb - xa, npx_max);
+    int cbase;
+    tile_stage(low, 1, ay, ax, b, y, j0, j1, xa, pstart, vrow, cbase);
+    __syncthreads();
+    const float c0 = coef[0], c1 = coef[1], cb = coef[2];
+    for (int px = threadIdx.x; px < npx; px += 256) {
+        const int x = xa + px;
+        int x0, x1;
+        float lx;
+        ax.src(x, x0, x1, lx);
+        lam[px] = lx;
+        const float t = mask[((long)b * H + y) * W + x];
+        const float z = (1.f - lx) * vrow[x0 - cbase] + lx * vrow[x1 - cbase];
+        float p, np, e;
+        sigmoid_pair(z, p, np, e);
+        dbuf[px] = (p * np) * (c1 - c0 * t) + cb * (p - t);
+    }
+    __syncthreads();
+    tile_gather_x(dbuf, lam, pstart, tmp + ((long)b * H + y) * w, 1, j0, j1, w, npx);
+}
+
 // ------------------------------------------------------------------------------------------------ inference tails
 // The per-source arithmetic of both inference tails: the bilinear (align_corners) sample of the NHWC map `low` (one image) at output pixel
 // (y, x), then v[k] = exp(value - max); returns 1 / sum (the probabilities are v[k] * result) and the first arg max.
@@ -1036,6 +1188,48 @@ extern "C" int mi_upsample_gdl(const float* low, const int64_t* labels, float* l
         hipLaunchKernelGGL(upce_pass2_kernel, dim3(nblk((long)B * h * w * K, 256)), dim3(256), 0, (hipStream_t)stream, (const float*)tmp,
                            (const float*)nullptr, dlow, B, K, ay, w, grad_scale);
         MI_CHECK_LAUNCH("mi_upsample_gdl gradient rows");
+    }
+    return MI_OK;
+}
+
+extern "C" size_t mi_upsample_tversky_bce_workspace(int B, int h, int w, int H, int W) {
+    if (B <= 0 || h <= 0 || w <= 0 || H <= 0 || W <= 0) return 0;
+    const GdlPlan p = gdl_plan(B, H, W);
+    return up256(p.nwg * TVB_NC * sizeof(float)) + up256(3 * sizeof(float)) + (size_t)B * H * w * sizeof(float);
+}
+
+extern "C" int mi_upsample_tversky_bce(const float* low, const float* mask, float* loss_out, float* dlow, float* sums, int B, int h, int w, int H, int W,
+                                       float alpha, float eps, float w_tversky, float w_bce, float grad_scale, int align_corners, void* workspace,
+                                       size_t workspace_bytes, void* stream) {
+    MI_REQUIRE(low && mask && loss_out && workspace, "mi_upsample_tversky_bce: null operand");
+    MI_REQUIRE(B > 0 && h > 0 && w > 0 && H > 0 && W > 0, "mi_upsample_tversky_bce: bad dimension");
+    MI_REQUIRE(H >= h && W >= w, "mi_upsample_tversky_bce: only upsampling (H >= h, W >= w) is supported");
+    MI_REQUIRE(H <= 65535 && B <= 65535, "mi_upsample_tversky_bce: grid dimension overflow");
+    MI_REQUIRE(alpha >= 0.f && alpha <= 1.f, "mi_upsample_tversky_bce: alpha outside [0, 1]");          // (a NaN fails both comparisons)
+    MI_REQUIRE(eps > 0.f, "mi_upsample_tversky_bce: eps must be positive");
+    if (workspace_bytes < mi_upsample_tversky_bce_workspace(B, h, w, H, W)) return mi_set_error(MI_ENOMEM, "mi_upsample_tversky_bce: workspace too small");
+    const Axis ay = make_axis(h, H, align_corners), ax = make_axis(w, W, align_corners);
+    const GdlPlan pl = gdl_plan(B, H, W);
+    float* partial = (float*)workspace;
+    float* coef = (float*)((char*)workspace + up256(pl.nwg * TVB_NC * sizeof(float)));
+    float* tmp = (float*)((char*)coef + up256(3 * sizeof(float)));
+    const int jt_cols = pick_jt(w, W);
+    const int npx_max = pass1_npx_max(ax, jt_cols);
+    const size_t lds3 = (size_t)npx_max * 8 + (JT + 4) * 4 + (size_t)(JT + 2) * 4;
+    MI_REQUIRE(!dlow || lds3 <= 64 * 1024, "mi_upsample_tversky_bce: upsample factor too large for one LDS tile (%zu B)", lds3);
+    hipLaunchKernelGGL(tvb_reduce_kernel, dim3(pl.tiles_x, pl.row_groups, B), dim3(256), 0, (hipStream_t)stream, low, mask, partial, ay, ax, pl.rows);
+    MI_CHECK_LAUNCH("mi_upsample_tversky_bce reduce");
+    hipLaunchKernelGGL(tvb_finalize_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const float*)partial, (int)pl.nwg, (double)B * H * W, alpha, eps,
+                       w_tversky, w_bce, loss_out, coef, sums);
+    MI_CHECK_LAUNCH("mi_upsample_tversky_bce finalize");
+    if (dlow) {
+        const int tiles = (w + jt_cols - 1) / jt_cols;
+        hipLaunchKernelGGL(tvb_grad_kernel, dim3(tiles, H, B), dim3(256), lds3, (hipStream_t)stream, low, mask, (const float*)coef, tmp, ay, ax, npx_max,
+                           jt_cols);
+        MI_CHECK_LAUNCH("mi_upsample_tversky_bce gradient");
+        hipLaunchKernelGGL(upce_pass2_kernel, dim3(nblk((long)B * h * w, 256)), dim3(256), 0, (hipStream_t)stream, (const float*)tmp, (const float*)nullptr,
+                           dlow, B, 1, ay, w, grad_scale);
+        MI_CHECK_LAUNCH("mi_upsample_tversky_bce gradient rows");
     }
     return MI_OK;
 }

@@ -4,7 +4,7 @@ so the reference's own scripts / plugins (`from core.configs import cfg`,
 run on the MI355X engine unchanged.  Installed by the tiny top-level `core/` and `base/` packages.
 
 Mapped: the DeepLabV2 hot path, its FADA adversarial step, the PraNet path (row N3) and the GALD / GCPA path (row N4); the
-other model families of the reference (attn, vgg, the FADA combos of gald / attn) are out of scope and raise ImportError with that message.
+other model families of the reference (attn - its loss module apart: host/losses.py -, vgg, the FADA combos of gald / attn) are out of scope and raise ImportError with that message.
 """
 import importlib
 import importlib.abc
@@ -32,6 +32,7 @@ ALIASES = {
     "core.testers.pranet_tester": _PKG + "pranet",                    # core/testers/pranet_tester.py
     "core.models.classifiers.pranet.PraNet_Res2Net": _PKG + "pranet", # PraNet, RFB_modified, aggregation
     "core.models.classifiers.pranet.Res2Net_v1b": _PKG + "pranet",    # Bottle2neck
+    "core.models.classifiers.attn.loss": _PKG + "losses",            # TverskyLoss, BinaryCrossEntropyLoss, CompoundLoss, MultiscaleLoss (attn/loss.py)
     "core.utils.utils": _PKG + "pranet",                              # clip_gradient, AvgMeter (core/utils/utils.py:6-38)
     "core.trainers.gald_trainer": _PKG + "gald",                      # core/trainers/gald_trainer.py
     "core.models.classifiers.gcpacc.gcpa_cc2": _PKG + "gald",         # GCPAEncoder, GCPADecoder
@@ -47,7 +48,7 @@ ALIASES = {
     "base.base_trainer": _PKG + "plugin",                             # base/base_trainer.py
     "base.base_model": _PKG + "plugin",                               # base/base_model.py
 }
-PACKAGES = {"core.models", "core.models.classifiers", "core.models.classifiers.aspp", "core.models.classifiers.pranet", "core.models.classifiers.gcpacc", "core.models.classifiers.gcpacc.encoders", "core.models.classifiers.gcpacc.contextagg", "core.components", "core.trainers", "core.adapters", "core.combos",
+PACKAGES = {"core.models", "core.models.classifiers", "core.models.classifiers.aspp", "core.models.classifiers.pranet", "core.models.classifiers.attn", "core.models.classifiers.gcpacc", "core.models.classifiers.gcpacc.encoders", "core.models.classifiers.gcpacc.contextagg", "core.components", "core.trainers", "core.adapters", "core.combos",
             "core.testers", "core.utils", "core.datasets"}
 
 

@@ -13,8 +13,8 @@ from ast import literal_eval
 import yaml
 
 _VALID = (tuple, list, str, int, float, bool, type(None))
-_RANGES = {"TEST.PSEUDO_THRESHOLD": (0.0, 1.0)}      # closed intervals a merged value has to lie in
-_CHOICES = {"SOLVER.LOSS": ("ce", "gdl"), "SOLVER.GDL_WEIGHT": ("square", "identity", "sqrt")}      # the only values a merged key may take
+_RANGES = {"TEST.PSEUDO_THRESHOLD": (0.0, 1.0), "SOLVER.TVERSKY_ALPHA": (0.0, 1.0)}      # closed intervals a merged value has to lie in
+_CHOICES = {"SOLVER.LOSS": ("ce", "gdl", "tversky"), "SOLVER.GDL_WEIGHT": ("square", "identity", "sqrt")}      # the only values a merged key may take
 
 
 class CfgNode(dict):
@@ -172,7 +172,9 @@ def default_tree():
             "DECAY_EPOCH": 50, "GAMMA": 0.1, "CHECKPOINT_PERIOD": 5, "BATCH_SIZE": 8, "BATCH_SIZE_VAL": 1,
             # not in the reference: LOSS "ce" = the trainers' cross-entropy, "gdl" = GeneralizedDiceLoss (utility.py:399-447) on GALD's four heads
             # (GALDTrainer only: the lines gald_trainer.py:70-73 toggles); GDL_WEIGHT = its weight_type, "square" | "identity" | "sqrt"
-            "LOSS": "ce", "GDL_WEIGHT": "square",
+            # "tversky" = MultiscaleLoss(CompoundLoss([TverskyLoss(TVERSKY_ALPHA), BinaryCrossEntropyLoss()])) (attn/loss.py, as attn_trainer.py combines
+            # them) on PraNet's four side outputs (PraNetTrainer only, whose "ce" is its own structure loss)
+            "LOSS": "ce", "GDL_WEIGHT": "square", "TVERSKY_ALPHA": 0.7,
         },
         # not in the reference: PRECISION fp32 = exact evaluation path, bf16 = training engine; SCALES / FLIP other than these defaults make
         # ASPPTester call multi_scale_inference (utility.py:193-209) instead of inference(flip=False); FUSED_SCORE True = argmax, threshold and

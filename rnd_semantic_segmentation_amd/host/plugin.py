@@ -10,12 +10,16 @@ import torch.nn as nn
 from .metrics import setup_logger
 
 
+_LOSS_HOME = {"gdl": "the generalized Dice loss ('gdl') is wired into GALD: GALDTrainer (configs/gald_src_dice.yaml)",
+              "tversky": "the Tversky + BCE loss ('tversky') is wired into PraNet: PraNetTrainer (configs/pranet_src_polyp_tversky.yaml)"}
+
+
 def require_loss(cfg, who, supported=("ce",)):
-    """SOLVER.LOSS (not in the reference) names the segmentation criterion; only GALDTrainer knows one besides cross-entropy."""
+    """SOLVER.LOSS (not in the reference) names the segmentation criterion; GALDTrainer and PraNetTrainer each know one besides their default."""
     loss = getattr(getattr(cfg, "SOLVER", None), "LOSS", "ce")
     if loss not in supported:
-        raise NotImplementedError("{} trains with SOLVER.LOSS 'ce' only (got {!r}); the generalized Dice loss ('gdl') is wired into GALD: "
-                                  "GALDTrainer (configs/gald_src_dice.yaml)".format(who, loss))
+        raise NotImplementedError("{} trains with SOLVER.LOSS {} only (got {!r}); {}".format(
+            who, " / ".join(repr(s) for s in supported), loss, _LOSS_HOME.get(loss, "no trainer implements it")))
     return loss
 
 

@@ -122,6 +122,14 @@ class _PraNetRun(Run):
             acc(gate, dgate, True)
         return self.node(gk.gra_fwd(gate.t, feat.t), back)
 
+    def tversky_head(self, low, mask, alpha, eps, weights):
+        """CompoundLoss([TverskyLoss(alpha, eps), BinaryCrossEntropyLoss()], weights)(F.interpolate(low, size=mask.shape[-2:], mode="bilinear"), mask)
+        (attn/loss.py on a side output of PraNet_Res2Net.py:127-170) fused, shaped like GALD's gdl_head: mi_upsample_tversky_bce never writes the
+        full-resolution map, and its gradient pass has run by the time the loss exists (the coefficients stay on the device)."""
+        B, h, w, _ = low.t.shape
+        loss_out, dlow, _ = K.upsample_tversky_bce(low.t.reshape(B, h, w), mask, want_grad=self.rec, alpha=alpha, eps=eps, weights=weights, align_corners=False)
+        return self.node(loss_out[0].clone(), lambda g: acc(low, dlow.view(B, h, w, 1) * g, True))
+
 
 # ------------------------------------------------------------------------------------------------ graph pieces
 def _bottle2neck(run, x, blk):
@@ -326,24 +334,60 @@ class PraNet(Engine):
         run.tap("rfb2", x2r), run.tap("rfb3", x3r), run.tap("rfb4", x4r)
         coarse = run.tap("coarse", _aggregation(run, self._agg, self.channel, x4r, x3r, x2r))           # ra5_feat: 1/8 resolution, one channel, fp32
         rs = lambda v, f: run.resize(v, f, False)                                    # F.interpolate(..., mode='bilinear'): align_corners False
-        maps = [rs(coarse, 8)]
+        tv = self.__dict__.get("_tversky")
+        head = rs if tv is None else (lambda v, f: run.tversky_head(v, *tv))          # losses(): the map's last resize and its loss in one kernel
+        maps = [head(coarse, 8)]
         g = run.tap("ra4", _reverse_branch(run, rs(coarse, 0.25), x4, self._ra[4]))
-        maps.append(rs(g, 32))
+        maps.append(head(g, 32))
         g = run.tap("ra3", _reverse_branch(run, rs(g, 2), x3, self._ra[3]))
-        maps.append(rs(g, 16))
+        maps.append(head(g, 16))
         g = run.tap("ra2", _reverse_branch(run, rs(g, 2), x2, self._ra[2]))
-        maps.append(rs(g, 8))
+        maps.append(head(g, 8))
+        if tv is not None:
+            return maps                                                              # four scalar losses
         return [run.tap("map%d" % i, m) for i, m in enumerate(maps)]
+
+    def losses(self, x, gts, alpha=0.7, eps=1.0, weights=(0.5, 0.5)):
+        """(loss5, loss4, loss3, loss2) = CompoundLoss([TverskyLoss(alpha, eps), BinaryCrossEntropyLoss()], weights)(lateral_map_i, gts) (attn/loss.py)
+        without materialising the four [B,1,H,W] maps: each head's final upsample, its loss and the gradient are one fused call on the low-resolution
+        map (mi_upsample_tversky_bce).  gts [B,1,H,W] or [B,H,W], values in [0, 1], the size of x."""
+        if not 0.0 <= float(alpha) <= 1.0 or not float(eps) > 0.0 or len(weights) != 2:
+            raise ValueError("PraNet.losses: alpha in [0, 1], eps > 0 and weights = (tversky, bce), got %r / %r / %r" % (alpha, eps, weights))
+        if gts.dim() not in (3, 4) or (gts.dim() == 4 and gts.shape[1] != 1) or (gts.shape[0], gts.shape[-2], gts.shape[-1]) != (x.shape[0], x.shape[2], x.shape[3]):
+            raise ValueError("PraNet.losses: gts must be [B,1,H,W] or [B,H,W] of the images' size %s, got %s" % (tuple(x.shape), tuple(gts.shape)))
+        mask = gts.detach().float().reshape(gts.shape[0], gts.shape[-2], gts.shape[-1]).contiguous()
+        self._tversky = (mask, float(alpha), float(eps), (float(weights[0]), float(weights[1])))
+        try:
+            return super().forward(x)
+        finally:
+            self._tversky = None
 
 
 # ------------------------------------------------------------------------------------------------ schedule / trainer / tester
+def step_losses(net, images, gts, criterion="ce", alpha=0.7, literal=False):
+    """The four losses (lateral 5, 4, 3, 2) of one step.  "ce": the trainer's own structure loss on the four maps (pranet_trainer.py:50-54);
+    "tversky": CompoundLoss([TverskyLoss(alpha), BinaryCrossEntropyLoss()]) per side output, the terms MultiscaleLoss adds up (attn/loss.py; every
+    head's label is `gts`) - fused with the heads' upsamples (PraNet.losses), or with literal=True (tests and tools/pranet_bench.py only) the
+    composition without the fusion: net(images) materialises the four maps, each goes through the host/losses.py modules."""
+    if criterion == "ce":
+        return [structure_loss(o, gts) for o in net(images)]
+    if criterion != "tversky":
+        raise ValueError("criterion must be 'ce' or 'tversky', got %r" % (criterion,))
+    if literal:
+        from .losses import BinaryCrossEntropyLoss, CompoundLoss, TverskyLoss
+        crit = CompoundLoss([TverskyLoss(alpha=alpha), BinaryCrossEntropyLoss()])
+        return [crit(o, gts) for o in net(images)]
+    return list(net.losses(images, gts, alpha=alpha))
+
+
 class GraphedStep:
-    """One whole optimizer step of pranet_trainer.py:39-60 - weight pack, forward, four structure losses, backward, clamped Adam: ~1 800
+    """One whole optimizer step of pranet_trainer.py:39-60 - weight pack, forward, four losses (step_losses), backward, clamped Adam: ~1 800
     launches - captured once as a HIP graph and replayed: the host cost of a step becomes one graph launch.  Inputs are copied into static
     buffers; the learning rate and Adam's step count live in device memory (FlatAdam.set_device_hyper)."""
 
-    def __init__(self, net, opt, images, gts, warmup=3):
+    def __init__(self, net, opt, images, gts, warmup=3, criterion="ce", alpha=0.7, literal=False):
         self.net, self.opt = net, opt
+        self.criterion, self.alpha, self.literal = criterion, alpha, literal
         self.x, self.gt = images.detach().clone(), gts.detach().clone()
         net.ensure_flat()
         side = torch.cuda.Stream()
@@ -363,7 +407,7 @@ class GraphedStep:
 
     def _core(self):
         self.opt.zero_grad()
-        ls = [structure_loss(o, self.gt) for o in self.net(self.x)]
+        ls = step_losses(self.net, self.x, self.gt, self.criterion, self.alpha, self.literal)
         (ls[3] + ls[2] + ls[1] + ls[0]).backward()
         self.opt.step()
         return [l.detach() for l in ls]
@@ -424,12 +468,17 @@ class AvgMeter:
 class PraNetTrainer(BaseTrainer):
     """pranet_trainer.py:12-104: Adam(BASE_LR / 8), three passes per batch (the reference's multi-scale loop, whose rescale is a no-op:
     it resizes to trainsize whatever the rate - Appendix B), structure loss on the four side outputs, gradient clamp 0.5, warm-up + cosine
-    schedule per epoch, checkpoint {'epoch', 'model', 'optimizer'} as PraNet-<epoch>.pth."""
+    schedule per epoch, checkpoint {'epoch', 'model', 'optimizer'} as PraNet-<epoch>.pth.  SOLVER.LOSS "ce" (default) is that structure loss;
+    "tversky" replaces it with the Tversky + BCE compound of attn/loss.py on the same four outputs (step_losses), everything else unchanged."""
+
+    LOSSES = ("ce", "tversky")
 
     def __init__(self, name, cfg, train_loader, local_rank, logger=None):
         super().__init__(name, cfg, train_loader, local_rank, logger)
 
     def init_params(self):
+        self.loss_name = getattr(self.cfg.SOLVER, "LOSS", "ce")                  # (not in the reference's config: host/config.py)
+        self.tversky_alpha = float(getattr(self.cfg.SOLVER, "TVERSKY_ALPHA", 0.7))
         self.trainsize = self.cfg.INPUT.TRAINSIZE
         self.model = PraNet().to(self.device)
         self.model.ensure_flat()
@@ -455,12 +504,16 @@ class PraNetTrainer(BaseTrainer):
             if st["step"] is not None and st["shape"] == (tuple(images.shape), tuple(gts.shape)):
                 return [l.clone() for l in st["step"](images, gts)]
             if st["step"] is None and st["eager"] >= self.GRAPH_WARMUP:
-                st["step"], st["shape"] = GraphedStep(self.model, self.optimizer, images, gts, warmup=0), (tuple(images.shape), tuple(gts.shape))
+                st["step"] = GraphedStep(self.model, self.optimizer, images, gts, warmup=0, criterion=self.loss_name, alpha=self.tversky_alpha)
+                st["shape"] = (tuple(images.shape), tuple(gts.shape))
                 return [l.clone() for l in st["step"](images, gts)]
             st["eager"] += 1
         self.optimizer.zero_grad()
-        outs = self.model(images)
-        losses = [self.structure_loss(o, gts) for o in outs]
+        if self.loss_name == "ce":
+            outs = self.model(images)
+            losses = [self.structure_loss(o, gts) for o in outs]
+        else:
+            losses = step_losses(self.model, images, gts, self.loss_name, self.tversky_alpha)
         loss = losses[3] + losses[2] + losses[1] + losses[0]
         loss.backward()
         self.optimizer.step()                                       # clip_gradient(optimizer, 0.5) is fused into the update

@@ -499,6 +499,29 @@ def upsample_gdl(low, labels, want_grad=True, grad_scale=1.0, ignore_index=255, 
     return out, dlow, sums
 
 
+def upsample_tversky_bce(low, mask, want_grad=True, grad_scale=1.0, alpha=0.7, eps=1.0, weights=(0.5, 0.5), align_corners=False, want_sums=False):
+    """Fused upsample + CompoundLoss([TverskyLoss(alpha, eps), BinaryCrossEntropyLoss()], weights) (reference attn/loss.py) for one-channel logits:
+    low [B,h,w] fp32, mask [B,H,W] fp32 in [0, 1] (H >= h, W >= w; the same size: no upsample).  Returns (loss_out[4] = loss, tversky, bce, 0;
+    dlow [B,h,w] or None; sums[3] = TP, FN, FP or None).  Nothing is read back between its launches."""
+    _chk(low, torch.float32, "low")
+    _chk(mask, torch.float32, "mask")
+    if low.dim() != 3 or mask.dim() != 3 or mask.shape[0] != low.shape[0] or mask.device != low.device:
+        raise _lib.MiError("upsample_tversky_bce: low [B,h,w] and mask [B,H,W] on one device, got %s on %s and %s on %s"
+                           % (tuple(low.shape), low.device, tuple(mask.shape), mask.device))
+    if len(weights) != 2:
+        raise ValueError("upsample_tversky_bce: weights = (tversky, bce), got %r" % (weights,))
+    B, h, w = low.shape
+    _, H, W = mask.shape
+    L = _lib.lib()
+    ws = _workspace(L.mi_upsample_tversky_bce_workspace(B, h, w, H, W), low.device, "uptvb")
+    out = torch.empty(4, dtype=torch.float32, device=low.device)
+    dlow = torch.empty_like(low) if want_grad else None
+    sums = torch.empty(3, dtype=torch.float32, device=low.device) if want_sums else None
+    check(L.mi_upsample_tversky_bce(_p(low), _p(mask), _p(out), _p(dlow), _p(sums), B, h, w, H, W, float(alpha), float(eps), float(weights[0]),
+                                    float(weights[1]), float(grad_scale), int(bool(align_corners)), _p(ws), ws.numel(), _stream()), "mi_upsample_tversky_bce")
+    return out, dlow, sums
+
+
 def check_labels(loss_out, num_classes, what="labels"):
     """Raise if the CE kernels saw labels outside [0, num_classes) that are not ignore_index (torch's device assert).
     Synchronises (reads one float): call it where the loss value is fetched anyway."""
