@@ -228,6 +228,20 @@ int mi_upsample_ce_ex(const float* low, const int64_t* labels, float* loss_out /
                       int B, int h, int w, int K, int H, int W, int ignore_index, float grad_scale, int align_corners,
                       void* workspace, size_t workspace_bytes, void* stream);
 
+/* The same with torch.nn.CrossEntropyLoss's two other arguments, weight= (one factor per class) and label_smoothing=.  With z = bilinear(low),
+ * p = softmax(z), y = label, valid = label not ignore_index and inside [0, K), s = label_smoothing, Wsum = sum_c w_c:
+ *   S    = sum_valid w_y
+ *   loss = [ (1-s) sum_valid w_y (-log p_y) + s/K sum_valid sum_c w_c (-log p_c) ] / S
+ *   d loss / d z_k = valid [ (1-s) w_y (p_k - [k==y]) + s/K (p_k Wsum - w_k) ] / S
+ * (the smoothing term counts every valid pixel, also one whose own class has weight 0; S == 0 gives a nan loss, as torch does).
+ * class_weights: [K] fp32 in DEVICE memory, read on every call (a captured graph sees later values), or NULL = all 1.  0 <= label_smoothing <= 1.
+ * loss_out: [0] = loss, [1] = S, [2] = out-of-range labels, [3] = scratch.  dlow may be NULL (loss only, same loss bits); an entry of dlow that
+ * no valid pixel touches is exactly 0, also when S == 0.  Workspace, restrictions, launch count and determinism as mi_upsample_ce_ex; with
+ * class_weights == NULL and label_smoothing == 0 the results are those of mi_upsample_ce_ex bit for bit. */
+int mi_upsample_ce_w(const float* low, const int64_t* labels, const float* class_weights /*[K]*/, float* loss_out /*[4]*/, float* dlow,
+                     int B, int h, int w, int K, int H, int W, int ignore_index, float label_smoothing, float grad_scale, int align_corners,
+                     void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- fused upsample + generalized Dice loss (GeneralizedDiceLoss, reference core/utils/utility.py:399-447, label form) ----
  * Operands and restrictions as mi_upsample_ce_ex.  With p = softmax(bilinear(low)) and t = onehot(labels), both zero where the label is
  * ignore_index:  T_c = sum t, I_c = sum p t, P2_c = sum p^2, w_c = 1 / (T_c^2 + eps) | 1 / (T_c + eps) | 1 / (sqrt(T_c) + eps) by weight_type,

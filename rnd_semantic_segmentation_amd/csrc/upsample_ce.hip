@@ -7,6 +7,7 @@
 // 1/8-resolution logits (5.7 MB at B=8, 769x769) and labels and never writes the 360 MB [B,19,769,769] tensor.
 // Every reduction has a fixed summation order (no float atomics) so results are bitwise reproducible.
 #include "mi_common.h"
+#include <cmath>
 
 namespace {
 
@@ -236,10 +237,22 @@ __device__ __forceinline__ void tile_gather_x(const float* dbuf, const float* la
 
 // KT > 0: the class count is a compile-time constant (19 for Cityscapes: exact-length register loops instead of 32 predicated
 // iterations); KT == 0: K is read from the arguments.
-template <int KT>
+// MODE == UPCE_WEIGHTED (mi_upsample_ce_w): torch's CrossEntropyLoss(weight=, label_smoothing=s).  Per valid pixel, with lp_c = (z_c - max) - log(sum exp):
+//   loss term = (1-s) w_y (-lp_y) + s/K sum_c w_c (-lp_c),  d_k = (1-s) w_y (p_k - [k==y]) + s/K (p_k Wsum - w_k),  "count" = w_y  (so that the
+// finalize divides by S = sum_valid w_y and pass 2 by loss_out[1] as ever).  wce.cw (NULL: all 1) is read from device memory by every workgroup into
+// LDS - K floats, a label-indexed ds_read per pixel instead of a global load - with Wsum behind them, added in class order.
+// MODE == UPCE_PLAIN compiles none of it: wce is an unused kernel argument.
+enum { UPCE_PLAIN = 0, UPCE_WEIGHTED = 1 };
+struct WceArgs {
+    const float* cw;      // [K] class weights on the device, or NULL
+    float keep;           // 1 - s
+    float smooth;         // s / K
+};
+
+template <int KT, int MODE = UPCE_PLAIN>
 __global__ __launch_bounds__(256) void upce_pass1_kernel(const float* __restrict__ low, const int64_t* __restrict__ labels,
                                                          float* __restrict__ partial, float* __restrict__ tmp, int B, int Krt, Axis ay,
-                                                         Axis ax, int ignore_index, int npx_max, unsigned* __restrict__ bad, int jt_cols) {
+                                                         Axis ax, int ignore_index, int npx_max, unsigned* __restrict__ bad, int jt_cols, WceArgs wce) {
     const int K = KT > 0 ? KT : Krt;
     constexpr int KR = KT > 0 ? KT : KMAX;          // register array length
     extern __shared__ __attribute__((aligned(16))) float sh[];
@@ -256,6 +269,16 @@ __global__ __launch_bounds__(256) void upce_pass1_kernel(const float* __restrict
     const int npx = xb - xa;
     int cbase;
     tile_stage(low, K, ay, ax, b, y, j0, j1, xa, pstart, vrow, cbase);
+    float* wsh = vrow + (JT + 2) * K;               // UPCE_WEIGHTED: [K] class weights, then Wsum
+    if constexpr (MODE == UPCE_WEIGHTED) {
+        if (threadIdx.x < K) wsh[threadIdx.x] = wce.cw ? wce.cw[threadIdx.x] : 1.f;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            float t = 0.f;
+            for (int k = 0; k < K; ++k) t += wsh[k];
+            wsh[K] = t;
+        }
+    }
     __syncthreads();
     float loss = 0.f, cnt = 0.f;
     for (int px = threadIdx.x; px < npx; px += 256) {
@@ -283,15 +306,35 @@ __global__ __launch_bounds__(256) void upce_pass1_kernel(const float* __restrict
             }
         }
         float se = 0.f, picked = 0.f;          // picked = x[label] - max BEFORE the exponential: exp() of it underflows to 0 for
-#pragma unroll                                // a confidently wrong pixel (|logit| gap > 87) and log(0) would make the loss inf
+        float wz = 0.f;                        // a confidently wrong pixel (|logit| gap > 87) and log(0) would make the loss inf
+#pragma unroll                                // wz (UPCE_WEIGHTED) = sum_c w_c (z_c - max), before the exponential for the same reason
         for (int k = 0; k < KR; ++k) {
             if (k < K) {
                 if (k == lab) picked = v[k] - mx;
+                if constexpr (MODE == UPCE_WEIGHTED) wz += wsh[k] * (v[k] - mx);
                 v[k] = __expf(v[k] - mx);
                 se += v[k];
             }
         }
         const float rse = 1.f / se;
+        if constexpr (MODE == UPCE_WEIGHTED) {
+            const float wy = wsh[lab], wsum = wsh[K];
+            const float hard = wce.keep * wy;
+#pragma unroll
+            for (int k = 0; k < KR; ++k) {
+                if (k < K) {
+                    const float t = v[k] * rse - (k == lab ? 1.f : 0.f);
+                    d[k] = hard * t + wce.smooth * ((v[k] * rse) * wsum - wsh[k]);
+                }
+            }
+            if (x0 >= j0) {
+                const float lse = __logf(se);
+                const float nll = lse - picked;
+                loss += hard * nll + wce.smooth * (wsum * lse - wz);          // sum_c w_c (-lp_c) = Wsum lse - sum_c w_c (z_c - max)
+                cnt += wy;
+            }
+            continue;
+        }
 #pragma unroll
         for (int k = 0; k < KR; ++k) {
             if (k < K) d[k] = v[k] * rse - (k == lab ? 1.f : 0.f);
@@ -312,8 +355,11 @@ __global__ __launch_bounds__(256) void upce_pass1_kernel(const float* __restrict
 }
 
 // pass 2: dlow[b][i][j][k] = grad_scale / n_valid * sum_y wy(y,i) tmp[b][y][j][k]   (ascending y)
-__global__ void upce_pass2_kernel(const float* __restrict__ tmp, const float* __restrict__ loss_out, float* __restrict__ dlow, int B, int K,
-                                  Axis ay, int w, float grad_scale) {
+// ZERO_STAYS: a sum that is exactly 0 stays 0 whatever the divisor (torch leaves the gradient of ignored pixels at 0 when no pixel counts, S = 0;
+// 0 * (grad_scale / 0) would be nan).  Any other sum is scaled as before.
+template <bool ZERO_STAYS>
+__device__ __forceinline__ void pass2_body(const float* __restrict__ tmp, const float* __restrict__ loss_out, float* __restrict__ dlow, int B, int K,
+                                           const Axis& ay, int w, float grad_scale) {
     const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
     const int H = ay.n_out, h = ay.n_in;
     const long per_row = (long)w * K;
@@ -329,7 +375,18 @@ __global__ void upce_pass2_kernel(const float* __restrict__ tmp, const float* __
         const float wy = (y0 == i ? 1.f - ly : 0.f) + (y1 == i ? ly : 0.f);
         s += wy * tmp[((long)b * H + y) * per_row + jk];
     }
-    dlow[idx] = s * (loss_out ? grad_scale / loss_out[1] : grad_scale);      // (no loss_out: the Dice gradient, whose coefficients carry its normalisation)
+    const float r = s * (loss_out ? grad_scale / loss_out[1] : grad_scale);      // (no loss_out: the Dice gradient, whose coefficients carry its normalisation)
+    dlow[idx] = (ZERO_STAYS && s == 0.f) ? 0.f : r;
+}
+
+__global__ void upce_pass2_kernel(const float* __restrict__ tmp, const float* __restrict__ loss_out, float* __restrict__ dlow, int B, int K,
+                                  Axis ay, int w, float grad_scale) {
+    pass2_body<false>(tmp, loss_out, dlow, B, K, ay, w, grad_scale);
+}
+
+__global__ void wce_pass2_kernel(const float* __restrict__ tmp, const float* __restrict__ loss_out, float* __restrict__ dlow, int B, int K,
+                                 Axis ay, int w, float grad_scale) {
+    pass2_body<true>(tmp, loss_out, dlow, B, K, ay, w, grad_scale);
 }
 
 // ------------------------------------------------------------------------------------------------ generalized Dice, fused with the upsample
@@ -1102,10 +1159,10 @@ extern "C" int mi_upsample_ce_ex(const float* low, const int64_t* labels, float*
     if (hipMemsetAsync(bad, 0, sizeof(unsigned), (hipStream_t)stream) != hipSuccess) return mi_set_error(MI_EHIP, "mi_upsample_ce: memset");
     if (K == 19)
         hipLaunchKernelGGL(upce_pass1_kernel<19>, dim3(tiles, H, B), dim3(256), lds, (hipStream_t)stream, low, labels, partial, tmp, B, K, ay,
-                           ax, ignore_index, npx_max, bad, jt_cols);
+                           ax, ignore_index, npx_max, bad, jt_cols, WceArgs{nullptr, 1.f, 0.f});
     else
         hipLaunchKernelGGL(upce_pass1_kernel<0>, dim3(tiles, H, B), dim3(256), lds, (hipStream_t)stream, low, labels, partial, tmp, B, K, ay,
-                           ax, ignore_index, npx_max, bad, jt_cols);
+                           ax, ignore_index, npx_max, bad, jt_cols, WceArgs{nullptr, 1.f, 0.f});
     MI_CHECK_LAUNCH("mi_upsample_ce pass1");
     hipLaunchKernelGGL(ce_finalize_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const float*)partial, B * H * tiles, loss_out);
     MI_CHECK_LAUNCH("mi_upsample_ce finalize");
@@ -1113,6 +1170,63 @@ extern "C" int mi_upsample_ce_ex(const float* low, const int64_t* labels, float*
         hipLaunchKernelGGL(upce_pass2_kernel, dim3(nblk((long)B * h * w * K, 256)), dim3(256), 0, (hipStream_t)stream, (const float*)tmp, loss_out,
                            dlow, B, K, ay, w, grad_scale);
         MI_CHECK_LAUNCH("mi_upsample_ce pass2");
+    }
+    return MI_OK;
+}
+
+// CrossEntropyLoss(weight=, ignore_index=, label_smoothing=) on the upsampled logits: the launches of mi_upsample_ce_ex with the weighted
+// instantiation of pass 1 (the weights travel as a device pointer, so a captured graph sees later values) and the pass 2 that keeps exact zeros.
+// Without weights and smoothing pass 1 is the PLAIN instantiation, the very code mi_upsample_ce_ex launches: the compiler contracts the two
+// instantiations differently (the plain <19> interpolates with two rounded products, the weighted one with an fma), so only the same code object
+// makes "the defaults give mi_upsample_ce_ex's bits" hold whatever a later compiler does.
+extern "C" int mi_upsample_ce_w(const float* low, const int64_t* labels, const float* class_weights, float* loss_out, float* dlow, int B, int h, int w,
+                                int K, int H, int W, int ignore_index, float label_smoothing, float grad_scale, int align_corners, void* workspace,
+                                size_t workspace_bytes, void* stream) {
+    MI_REQUIRE(low && labels && loss_out && workspace, "mi_upsample_ce_w: null operand");
+    MI_REQUIRE(B > 0 && h > 0 && w > 0 && H > 0 && W > 0 && K > 0 && K <= KMAX, "mi_upsample_ce_w: bad dimension (K <= 32)");
+    MI_REQUIRE(H >= h && W >= w, "mi_upsample_ce_w: only upsampling (H >= h, W >= w) is supported");
+    MI_REQUIRE(H <= 65535 && B <= 65535, "mi_upsample_ce_w: grid dimension overflow");
+    MI_REQUIRE(std::isfinite(label_smoothing), "mi_upsample_ce_w: label_smoothing is not finite");
+    MI_REQUIRE(label_smoothing >= 0.f && label_smoothing <= 1.f, "mi_upsample_ce_w: label_smoothing outside [0, 1]");
+    MI_REQUIRE(std::isfinite(grad_scale), "mi_upsample_ce_w: grad_scale is not finite");
+    if (workspace_bytes < mi_upsample_ce_workspace(B, h, w, K, H, W)) return mi_set_error(MI_ENOMEM, "mi_upsample_ce_w: workspace too small");
+    const Axis ay = make_axis(h, H, align_corners), ax = make_axis(w, W, align_corners);
+    const int jt_cols = pick_jt(w, W);
+    const int tiles = (w + jt_cols - 1) / jt_cols;
+    float* partial = (float*)workspace;
+    const size_t poff = (((size_t)B * H * tiles * 2 * sizeof(float)) + 255) & ~(size_t)255;
+    float* tmp = dlow ? (float*)((char*)workspace + poff) : nullptr;
+    const int npx_max = pass1_npx_max(ax, jt_cols);
+    const bool plain = !class_weights && label_smoothing == 0.f;
+    const size_t lds = (size_t)npx_max * K * 4 + (size_t)npx_max * 8 + 512 * 4 + (JT + 4) * 4 + (size_t)(JT + 2) * K * 4 + (plain ? 0 : (size_t)(K + 1) * 4);
+    MI_REQUIRE(lds <= 160 * 1024, "mi_upsample_ce_w: upsample factor too large for one LDS tile (%zu B)", lds);
+    static std::atomic<uint64_t> lds_set[4];
+    mi_allow_dynamic_lds((const void*)upce_pass1_kernel<19, UPCE_WEIGHTED>, MI_LDS_MAX, lds_set[0]);
+    mi_allow_dynamic_lds((const void*)upce_pass1_kernel<0, UPCE_WEIGHTED>, MI_LDS_MAX, lds_set[1]);
+    mi_allow_dynamic_lds((const void*)upce_pass1_kernel<19>, MI_LDS_MAX, lds_set[2]);
+    mi_allow_dynamic_lds((const void*)upce_pass1_kernel<0>, MI_LDS_MAX, lds_set[3]);
+    const WceArgs wce{class_weights, 1.f - label_smoothing, label_smoothing / (float)K};
+    unsigned* bad = reinterpret_cast<unsigned*>(loss_out + 3);
+    if (hipMemsetAsync(bad, 0, sizeof(unsigned), (hipStream_t)stream) != hipSuccess) return mi_set_error(MI_EHIP, "mi_upsample_ce_w: memset");
+    if (plain && K == 19)
+        hipLaunchKernelGGL(upce_pass1_kernel<19>, dim3(tiles, H, B), dim3(256), lds, (hipStream_t)stream, low, labels, partial, tmp, B, K, ay, ax, ignore_index,
+                           npx_max, bad, jt_cols, wce);
+    else if (plain)
+        hipLaunchKernelGGL(upce_pass1_kernel<0>, dim3(tiles, H, B), dim3(256), lds, (hipStream_t)stream, low, labels, partial, tmp, B, K, ay, ax, ignore_index,
+                           npx_max, bad, jt_cols, wce);
+    else if (K == 19)
+        hipLaunchKernelGGL((upce_pass1_kernel<19, UPCE_WEIGHTED>), dim3(tiles, H, B), dim3(256), lds, (hipStream_t)stream, low, labels, partial, tmp, B, K,
+                           ay, ax, ignore_index, npx_max, bad, jt_cols, wce);
+    else
+        hipLaunchKernelGGL((upce_pass1_kernel<0, UPCE_WEIGHTED>), dim3(tiles, H, B), dim3(256), lds, (hipStream_t)stream, low, labels, partial, tmp, B, K,
+                           ay, ax, ignore_index, npx_max, bad, jt_cols, wce);
+    MI_CHECK_LAUNCH("mi_upsample_ce_w pass1");
+    hipLaunchKernelGGL(ce_finalize_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const float*)partial, B * H * tiles, loss_out);
+    MI_CHECK_LAUNCH("mi_upsample_ce_w finalize");
+    if (dlow) {
+        hipLaunchKernelGGL(wce_pass2_kernel, dim3(nblk((long)B * h * w * K, 256)), dim3(256), 0, (hipStream_t)stream, (const float*)tmp, loss_out, dlow, B, K,
+                           ay, w, grad_scale);
+        MI_CHECK_LAUNCH("mi_upsample_ce_w pass2");
     }
     return MI_OK;
 }

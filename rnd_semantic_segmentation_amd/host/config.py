@@ -13,7 +13,7 @@ from ast import literal_eval
 import yaml
 
 _VALID = (tuple, list, str, int, float, bool, type(None))
-_RANGES = {"TEST.PSEUDO_THRESHOLD": (0.0, 1.0), "SOLVER.TVERSKY_ALPHA": (0.0, 1.0)}      # closed intervals a merged value has to lie in
+_RANGES = {"TEST.PSEUDO_THRESHOLD": (0.0, 1.0), "SOLVER.TVERSKY_ALPHA": (0.0, 1.0), "SOLVER.LABEL_SMOOTHING": (0.0, 1.0)}      # closed intervals a merged value has to lie in
 _CHOICES = {"SOLVER.LOSS": ("ce", "gdl", "tversky"), "SOLVER.GDL_WEIGHT": ("square", "identity", "sqrt")}      # the only values a merged key may take
 
 
@@ -175,6 +175,10 @@ def default_tree():
             # "tversky" = MultiscaleLoss(CompoundLoss([TverskyLoss(TVERSKY_ALPHA), BinaryCrossEntropyLoss()])) (attn/loss.py, as attn_trainer.py combines
             # them) on PraNet's four side outputs (PraNetTrainer only, whose "ce" is its own structure loss)
             "LOSS": "ce", "GDL_WEIGHT": "square", "TVERSKY_ALPHA": 0.7,
+            # not in the reference either: CLASS_WEIGHTS (empty, or one non-negative factor per class: tools/class_weights.py prints them) and
+            # LABEL_SMOOTHING in [0, 1] are CrossEntropyLoss's weight= and label_smoothing= for LOSS "ce" of ASPPTrainer, GALDTrainer and both FADA
+            # combos, inside the fused upsample + cross-entropy heads (mi_upsample_ce_w); any other loss or trainer refuses them (plugin.ce_options)
+            "CLASS_WEIGHTS": (), "LABEL_SMOOTHING": 0.0,
         },
         # not in the reference: PRECISION fp32 = exact evaluation path, bf16 = training engine; SCALES / FLIP other than these defaults make
         # ASPPTester call multi_scale_inference (utility.py:193-209) instead of inference(flip=False); FUSED_SCORE True = argmax, threshold and

@@ -887,16 +887,18 @@ class AsppLossFn(torch.autograd.Function):
     [B,K,H,W] logits.  The loss gradient w.r.t. the low-resolution logits is produced in the same pass."""
 
     @staticmethod
-    def forward(ctx, x, labels, eng, ignore_index, temperature, *params):
+    def forward(ctx, x, labels, eng, ignore_index, temperature, class_weights, label_smoothing, *params):
+        """class_weights ([K] fp32 on the device, or None) / label_smoothing: CrossEntropyLoss(weight=, label_smoothing=), K.upsample_ce."""
         train = any(ctx.needs_input_grad)
         eng.prepare(train)
         low = eng.forward(x)
         eng.last_low = low                   # FADA derives its soft labels from these (aspp_fada.py:85-87)
         if temperature != 1.0:               # criterion(pred.div(T), label): bilinear upsampling commutes with the scaling
             loss_out, dlow = K.upsample_ce(low * (1.0 / temperature), labels, want_grad=train, grad_scale=1.0 / temperature,
-                                           ignore_index=ignore_index)
+                                           ignore_index=ignore_index, class_weights=class_weights, label_smoothing=label_smoothing)
         else:
-            loss_out, dlow = K.upsample_ce(low, labels, want_grad=train, ignore_index=ignore_index)
+            loss_out, dlow = K.upsample_ce(low, labels, want_grad=train, ignore_index=ignore_index, class_weights=class_weights,
+                                           label_smoothing=label_smoothing)
         ctx.eng, ctx.x, ctx.dlow = eng, (x if train else None), dlow
         ctx.loss_out = eng.last_loss_out = loss_out          # [loss, n_valid, out-of-range labels, -]: see K.check_labels
         # every step's count goes into a persistent device counter (the kernel zeroes its own per call): the trainer reads it once per logging
@@ -912,7 +914,7 @@ class AsppLossFn(torch.autograd.Function):
         dlow = ctx.dlow * gout
         dx = ctx.eng.backward(ctx.x, dlow, ctx.needs_input_grad[0])
         ctx.x = ctx.dlow = None
-        return (dx, None, None, None, None) + (None,) * (len(ctx.needs_input_grad) - 5)
+        return (dx, None, None, None, None, None, None) + (None,) * (len(ctx.needs_input_grad) - 7)
 
 
 class UpsampleFn(torch.autograd.Function):

@@ -391,7 +391,7 @@ class AsppFada:
             fea = a.feature_extractor(torch.cat((src_input, tgt_input), 0))
             halves = fea.detach()
             src_fea = halves[:ns].requires_grad_(True)
-            loss_seg = a.classifier.loss(src_fea, src_label, self.cfg.INPUT.IGNORE_LABEL, temperature=T)
+            loss_seg = a.classifier.loss(src_fea, src_label, self.cfg.INPUT.IGNORE_LABEL, temperature=T, **a.ce_kwargs)
             src_low = a.classifier.last_low
             self._overlap(True)                                 # every gradient a backward below touches is final when it returns
             loss_seg.backward()                                 # classifier gradients + d source features
@@ -427,7 +427,7 @@ class AsppFada:
             f.optimizer_D.step()
         elif fused:
             src_fea = a.feature_extractor(src_input)
-            loss_seg = a.classifier.loss(src_fea, src_label, self.cfg.INPUT.IGNORE_LABEL, temperature=T)
+            loss_seg = a.classifier.loss(src_fea, src_label, self.cfg.INPUT.IGNORE_LABEL, temperature=T, **a.ce_kwargs)
             src_low = a.classifier.last_low                     # 1/8-resolution logits (detached) -> soft labels
             self._overlap(False)                                # backbone gradients are final only after the target pass
             loss_seg.backward()
@@ -455,7 +455,7 @@ class AsppFada:
         else:                                                   # literal order of operations for foreign modules
             src_fea = a.feature_extractor(src_input)
             src_pred = a.classifier(src_fea, src_size).div(T)
-            loss_seg = F.cross_entropy(src_pred, src_label, ignore_index=self.cfg.INPUT.IGNORE_LABEL)
+            loss_seg = F.cross_entropy(src_pred, src_label, ignore_index=self.cfg.INPUT.IGNORE_LABEL, weight=a.ce_weights, label_smoothing=a.ce_smoothing)
             self._overlap(False)
             loss_seg.backward()
             src_soft = F.softmax(src_pred, dim=1).detach()

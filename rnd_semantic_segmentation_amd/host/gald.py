@@ -86,12 +86,14 @@ class _GaldRun(Run):
             acc(b, gk.gbinary(gk.OP_MUL, gm, a.t), True)
         return self.node(o, back)
 
-    def ce_head(self, low, labels, ignore_index, inv_t=None):
+    def ce_head(self, low, labels, ignore_index, inv_t=None, class_weights=None, label_smoothing=0.0):
         """criterion(F.interpolate(low, size=labels.shape[-2:], mode="bilinear"), labels) (gcpa_cc2.py:78-81 + gald_trainer.py:76-79) fused: the
         full-resolution logits are never written; d loss / d low comes out of the same pass.  inv_t: criterion(out.div(T), labels) of
-        gald_fada.py:85-88 as the same kernel on low * (1 / T) - bilinear upsampling is linear, so scaling before it is scaling after it."""
+        gald_fada.py:85-88 as the same kernel on low * (1 / T) - bilinear upsampling is linear, so scaling before it is scaling after it.
+        class_weights / label_smoothing: the criterion's weight= and label_smoothing= (mi_upsample_ce_w)."""
         src = low.t if inv_t is None else low.t * inv_t
-        loss_out, dlow = K.upsample_ce(src, labels, want_grad=self.rec, ignore_index=ignore_index, align_corners=False)
+        loss_out, dlow = K.upsample_ce(src, labels, want_grad=self.rec, ignore_index=ignore_index, align_corners=False, class_weights=class_weights,
+                                       label_smoothing=label_smoothing)
         _count_bad_labels(self.net, loss_out)
         return self.node(loss_out[0].clone(), lambda g: acc(low, dlow * (g if inv_t is None else g * inv_t), True))
 
@@ -374,45 +376,54 @@ class GCPADecoder(Engine):
             self.last_low = low2.t.detach().permute(0, 3, 1, 2)
             if out2 == "low":
                 return [low2]
-            return [run.ce_head(low2, self._ce_labels, self._ce_ignore, inv_t=out2)]
+            return [run.ce_head(low2, self._ce_labels, self._ce_ignore, inv_t=out2, **self._ce_extra())]
         lows = [run.tap("linear%d" % i, run.conv_bias(v, self._lin[i])) for i, v in ((5, top), (4, o4), (3, o3), (2, o2))]
         labels = self.__dict__.get("_ce_labels")
         if labels is not None:                                                                 # the trainer's fused path: four scalar losses
             if self.__dict__.get("_gdl_weight") is not None:
                 return [run.gdl_head(v, labels, self._ce_ignore, self._gdl_weight) for v in lows]
-            return [run.ce_head(v, labels, self._ce_ignore) for v in lows]
+            return [run.ce_head(v, labels, self._ce_ignore, **self._ce_extra()) for v in lows]
         size = (x.t.shape[1], x.t.shape[2])
         return [run.tap("out%d" % i, run.resize(v, None, False, size=size)) for i, v in enumerate(lows)]      # F.interpolate(..., size=x.size()[2:], mode="bilinear")
 
     def forward(self, x, feats):
         return super().forward(x, *feats)
 
-    def losses(self, x, feats, labels, ignore_index=255, criterion="ce", weight_type="square"):
+    def _ce_extra(self):
+        """The cross-entropy's weight= / label_smoothing= of the running losses() / loss() call, as ce_head's keywords."""
+        return {"class_weights": self.__dict__.get("_ce_weights"), "label_smoothing": self.__dict__.get("_ce_smoothing") or 0.0}
+
+    def losses(self, x, feats, labels, ignore_index=255, criterion="ce", weight_type="square", class_weights=None, label_smoothing=0.0):
         """(loss5, loss4, loss3, loss2) = criterion(out_i, labels) of gald_trainer.py:76-79 without materialising the four [B,19,H,W] logit tensors:
-        what GALDTrainer.train_step calls.  criterion "ce": upsample + cross-entropy fused (mi_upsample_ce_ex); "gdl": upsample +
+        what GALDTrainer.train_step calls.  criterion "ce": upsample + cross-entropy fused (mi_upsample_ce_ex; with class_weights [K] fp32 on the
+        device or label_smoothing, CrossEntropyLoss(weight=, label_smoothing=): mi_upsample_ce_w); "gdl": upsample +
         GeneralizedDiceLoss(weight_type) fused (mi_upsample_gdl; gald_trainer.py:70-73)."""
         if criterion not in ("ce", "gdl"):
             raise ValueError("criterion must be 'ce' or 'gdl', got %r" % (criterion,))
+        if criterion != "ce" and (class_weights is not None or float(label_smoothing) != 0.0):
+            raise ValueError("class_weights / label_smoothing belong to criterion 'ce', got %r" % (criterion,))
         if criterion == "gdl" and weight_type not in K.GDL_WEIGHT_TYPES:
             raise ValueError("Check out the weight_type: %r (one of %s)" % (weight_type, ", ".join(K.GDL_WEIGHT_TYPES)))
         self._ce_labels, self._ce_ignore = labels.long().contiguous(), int(ignore_index)
         self._gdl_weight = weight_type if criterion == "gdl" else None
+        self._ce_weights, self._ce_smoothing = class_weights, float(label_smoothing)
         try:
             return super().forward(x, *feats)
         finally:
-            self._ce_labels = self._gdl_weight = None
+            self._ce_labels = self._gdl_weight = self._ce_weights = self._ce_smoothing = None
 
-    def loss(self, x, feats, label, ignore_index=255, temperature=1.0):
+    def loss(self, x, feats, label, ignore_index=255, temperature=1.0, class_weights=None, label_smoothing=0.0):
         """criterion(self(x, feats)[-1].div(temperature), label) of gald_fada.py:80-88 fused: out2 alone (linear5/4/3 are not run and get no
         gradient), upsampled with align_corners=False and cross-entropy in one pass on linear2 * (1 / temperature) - the same kernel as losses():
         bilinear upsampling is linear, so dividing the low-resolution logits divides the upsampled ones.  Leaves the 1/4-resolution linear2 logits
         [B,K,h,w] fp32 (detached, before the division) in `self.last_low`."""
         self._ce_labels, self._ce_ignore = label.long().contiguous(), int(ignore_index)
         self._out2 = 1.0 / float(temperature)
+        self._ce_weights, self._ce_smoothing = class_weights, float(label_smoothing)
         try:
             return super().forward(x, *feats)
         finally:
-            self._ce_labels = self._out2 = None
+            self._ce_labels = self._out2 = self._ce_weights = self._ce_smoothing = None
 
     def low2(self, x, feats):
         """The 1/4-resolution linear2 logits [B,K,h,w] fp32 (NCHW-shaped view of NHWC memory) without a tape, in the module's mode: in train() the
@@ -496,11 +507,15 @@ class LocalAttenModule(Engine):
 
 class _NhwcCEFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, logits_nchw, labels, ignore_index, holder):
+    def forward(ctx, logits_nchw, labels, ignore_index, holder, weight=None, label_smoothing=0.0):
         nhwc = logits_nchw.permute(0, 2, 3, 1)                                     # the decoder's outputs ARE NHWC memory: a free view
         if not nhwc.is_contiguous():
             nhwc = nhwc.contiguous()
-        out, d = gk.gce(nhwc, labels.contiguous(), ignore_index, want_grad=logits_nchw.requires_grad)
+        if weight is None and label_smoothing == 0.0:
+            out, d = gk.gce(nhwc, labels.contiguous(), ignore_index, want_grad=logits_nchw.requires_grad)
+        else:                                                                      # the fused upsample entry at the identity scale (h == H, w == W)
+            out, d = K.upsample_ce(nhwc, labels.contiguous(), want_grad=logits_nchw.requires_grad, ignore_index=ignore_index, align_corners=False,
+                                   class_weights=weight, label_smoothing=label_smoothing)
         if holder is not None:
             _count_bad_labels(holder, out)
         ctx.d = d
@@ -510,20 +525,29 @@ class _NhwcCEFn(torch.autograd.Function):
     def backward(ctx, gout):
         d = ctx.d
         ctx.d = None
-        return (d * gout).permute(0, 3, 1, 2), None, None, None
+        return (d * gout).permute(0, 3, 1, 2), None, None, None, None, None
 
 
 class CrossEntropyNHWC(nn.Module):
-    """torch.nn.CrossEntropyLoss(ignore_index=255) of gald_trainer.py:107 on the HIP kernel (logits [B,K,H,W] fp32, labels [B,H,W] int64)."""
+    """torch.nn.CrossEntropyLoss(ignore_index=255) of gald_trainer.py:107 on the HIP kernel (logits [B,K,H,W] fp32, labels [B,H,W] int64).
+    weight ([K], a buffer as in torch) / label_smoothing: torch's arguments of the same names, on mi_upsample_ce_w at the identity scale; the
+    default call stays on gk.gce."""
 
-    def __init__(self, ignore_index=255):
+    def __init__(self, ignore_index=255, weight=None, label_smoothing=0.0):
         super().__init__()
+        if not 0.0 <= float(label_smoothing) <= 1.0:
+            raise ValueError("label_smoothing must be between 0.0 and 1.0. Got: %r" % (label_smoothing,))
         self.ignore_index = ignore_index
+        self.label_smoothing = float(label_smoothing)
+        self.register_buffer("weight", None if weight is None else torch.as_tensor(weight, dtype=torch.float32).clone())
 
     def forward(self, logits, target):
         if not logits.is_cuda:
             raise _lib.MiError("CrossEntropyNHWC runs on the MI355X only")
-        return _NhwcCEFn.apply(logits.float(), target.long(), self.ignore_index, self)
+        w = self.weight
+        if w is not None and w.device != logits.device:
+            raise _lib.MiError("CrossEntropyNHWC: weight lives on %s, the logits on %s (move the module with .to())" % (w.device, logits.device))
+        return _NhwcCEFn.apply(logits.float(), target.long(), self.ignore_index, self, w, self.label_smoothing)
 
 
 class GALDTrainer(BaseTrainer):
@@ -546,7 +570,7 @@ class GALDTrainer(BaseTrainer):
         self.optimizer_enc = FlatAdam(self.encoder, self.cfg.SOLVER.BASE_LR)
         self.optimizer_dec = FlatAdam(self.decoder, self.cfg.SOLVER.BASE_LR * 10)
         self.iteration = 0
-        self.criterion = CrossEntropyNHWC(ignore_index=255)
+        self.criterion = CrossEntropyNHWC(ignore_index=255, weight=self.ce_weights, label_smoothing=self.ce_smoothing).to(self.device)
 
     def _save_checkpoint(self, epoch, save_path):
         torch.save({"epoch": epoch, "iteration": self.iteration, "encoder": self.encoder.state_dict(), "decoder": self.decoder.state_dict(),
@@ -577,7 +601,7 @@ class GALDTrainer(BaseTrainer):
         src_input = src_input.to(self.device, non_blocking=True)
         src_label = src_label.to(self.device, non_blocking=True).long()
         loss5, loss4, loss3, loss2 = self.decoder.losses(src_input, self.encoder(src_input), src_label, criterion=self.loss_name,
-                                                         weight_type=self.gdl_weight)                            # = criterion(out_i, label), fused
+                                                         weight_type=self.gdl_weight, **self.ce_kwargs)                          # = criterion(out_i, label), fused
         loss = loss2 * 1 + loss3 * 0.8 + loss4 * 0.6 + loss5 * 0.4
         loss.backward()
         self.optimizer_enc.step()

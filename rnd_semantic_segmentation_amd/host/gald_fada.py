@@ -87,7 +87,7 @@ class GaldFada:
         fused = self.FUSED and hasattr(dec, "loss") and hasattr(D, "soft_loss_grids")
         if fused:
             src_feats = enc(src_input)
-            loss_seg = dec.loss(src_input, src_feats, src_label, ignore, temperature=T)          # :80-88, out2 alone
+            loss_seg = dec.loss(src_input, src_feats, src_label, ignore, temperature=T, **g.ce_kwargs)          # :80-88, out2 alone
             src_low = dec.last_low                              # linear2 [B,K,H/4,W/4] (detached) -> the source soft labels, inside the kernel
             loss_seg.backward()
             tgt_feats = enc(tgt_input)
@@ -113,7 +113,7 @@ class GaldFada:
         else:                                                   # gald_fada.py:79-127 as written
             src_feats = enc(src_input)
             src_output = dec(src_input, src_feats)[-1].div(T)
-            loss_seg = F.cross_entropy(src_output, src_label, ignore_index=ignore)
+            loss_seg = F.cross_entropy(src_output, src_label, ignore_index=ignore, weight=g.ce_weights, label_smoothing=g.ce_smoothing)
             loss_seg.backward()
             src_soft = F.softmax(src_output, dim=1).detach()
             src_soft[src_soft > 0.9] = 0.9

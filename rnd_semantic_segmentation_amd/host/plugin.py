@@ -23,11 +23,42 @@ def require_loss(cfg, who, supported=("ce",)):
     return loss
 
 
+def ce_options(cfg, who, device=None):
+    """SOLVER.CLASS_WEIGHTS / SOLVER.LABEL_SMOOTHING (not in the reference) as (weights, smoothing) for the trainer `who`: torch.nn.CrossEntropyLoss's
+    weight= as a [NUM_CLASSES] fp32 tensor on `device`, or None when the key is empty, and its label_smoothing=.  Both belong to SOLVER.LOSS "ce" of the
+    trainers whose "ce" is the cross-entropy; everything else refuses them instead of ignoring them."""
+    solver = getattr(cfg, "SOLVER", None)
+    weights = tuple(getattr(solver, "CLASS_WEIGHTS", ()) or ())
+    smoothing = float(getattr(solver, "LABEL_SMOOTHING", 0.0))
+    if not weights and smoothing == 0.0:
+        return None, 0.0
+    loss = getattr(solver, "LOSS", "ce")
+    if loss != "ce":
+        raise NotImplementedError("SOLVER.CLASS_WEIGHTS / SOLVER.LABEL_SMOOTHING belong to SOLVER.LOSS 'ce' (got {!r} for {})".format(loss, who))
+    if who == "PraNetTrainer":
+        raise NotImplementedError("PraNetTrainer's SOLVER.LOSS 'ce' is its structure loss (weighted BCE + IoU), which has neither class weights nor "
+                                  "label smoothing; SOLVER.CLASS_WEIGHTS / SOLVER.LABEL_SMOOTHING are for ASPPTrainer, GALDTrainer and the FADA combos")
+    if not 0.0 <= smoothing <= 1.0:          # (a value merged into the config was checked there; this one was assigned)
+        raise ValueError("SOLVER.LABEL_SMOOTHING {} lies outside [0, 1]".format(smoothing))
+    if not weights:
+        return None, smoothing
+    nc = int(cfg.MODEL.NUM_CLASSES)
+    if len(weights) != nc:
+        raise ValueError("SOLVER.CLASS_WEIGHTS has {} entries, MODEL.NUM_CLASSES is {} (one weight per class, or none)".format(len(weights), nc))
+    vals = [float(v) for v in weights]
+    for i, v in enumerate(vals):
+        if not np.isfinite(v) or v < 0.0:
+            raise ValueError("SOLVER.CLASS_WEIGHTS[{}] = {} (every weight must be finite and not negative)".format(i, v))
+    return torch.tensor(vals, dtype=torch.float32, device=device), smoothing
+
+
 class BaseTrainer:
     LOSSES = ("ce",)          # the SOLVER.LOSS values the trainer implements
 
     def __init__(self, name, cfg, train_loader, local_rank, logger=None):
         require_loss(cfg, type(self).__name__, self.LOSSES)
+        who = "PraNetTrainer" if any(c.__name__ == "PraNetTrainer" for c in type(self).__mro__) else type(self).__name__
+        weights, self.ce_smoothing = ce_options(cfg, who)          # CrossEntropyLoss(weight=, label_smoothing=): refused early where they do not apply
         self.cfg = cfg
         self.logger = setup_logger(name + "_train", cfg.OUTPUT_DIR, local_rank) if logger is None else logger
         self.train_loader = train_loader
@@ -47,6 +78,9 @@ class BaseTrainer:
             self.with_cuda = False
             device = "cpu"
         self.device = torch.device(device)
+        self.ce_weights = None if weights is None else weights.to(self.device)          # created once, on the trainer's device
+        # keywords for the fused heads' .loss() / .losses(); empty at the defaults, so those calls stay exactly what they were
+        self.ce_kwargs = {"class_weights": self.ce_weights, "label_smoothing": self.ce_smoothing} if (weights is not None or self.ce_smoothing) else {}
         self.init_params()
         if cfg.resume:
             self.logger.info("Loading checkpoint from {}".format(self.cfg.resume))

@@ -42,6 +42,9 @@ class ASPPTrainer(BaseTrainer):
         self.feature_extractor.to(self.device)
         self.classifier = self.build_classifier(self.cfg)
         self.classifier.to(self.device)
+        if self.ce_kwargs and not (hasattr(self.classifier, "loss") and self.device.type == "cuda"):
+            raise NotImplementedError("SOLVER.CLASS_WEIGHTS / SOLVER.LABEL_SMOOTHING run inside the fused head (classifier.loss on the GPU); "
+                                      "this classifier / device trains through the unfused fallback, which does not know them")
         for m in (self.feature_extractor, self.classifier):
             if hasattr(m, "ensure_flat") and self.device.type == "cuda":
                 m.ensure_flat()
@@ -154,7 +157,7 @@ class ASPPTrainer(BaseTrainer):
         self.optimizer_fea.zero_grad()
         self.optimizer_cls.zero_grad()
         feat = self.feature_extractor(src_input)
-        loss = self.classifier.loss(feat, src_label, self.cfg.INPUT.IGNORE_LABEL)
+        loss = self.classifier.loss(feat, src_label, self.cfg.INPUT.IGNORE_LABEL, **self.ce_kwargs)
         loss.backward()
         self.optimizer_fea.step()
         self.optimizer_cls.step()
@@ -195,7 +198,7 @@ class ASPPTrainer(BaseTrainer):
         src_label = src_label.to(self.device, non_blocking=True).long()
         feat = self.feature_extractor(src_input)
         if hasattr(self.classifier, "loss"):
-            loss = self.classifier.loss(feat, src_label, self.cfg.INPUT.IGNORE_LABEL)
+            loss = self.classifier.loss(feat, src_label, self.cfg.INPUT.IGNORE_LABEL, **self.ce_kwargs)
         else:
             output = self.classifier(feat, src_label.shape[-2:])
             loss = torch.nn.functional.cross_entropy(output, src_label, ignore_index=self.cfg.INPUT.IGNORE_LABEL)

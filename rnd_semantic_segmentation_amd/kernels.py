@@ -462,8 +462,10 @@ def softmax_ce_bwd(logits, labels, loss_out, grad_scale=1.0, ignore_index=255):
     return d
 
 
-def upsample_ce(low, labels, want_grad=True, grad_scale=1.0, ignore_index=255, align_corners=True):
-    """Fused classifier-upsample + CrossEntropyLoss.  Returns (loss_out[4], dlow or None).  align_corners False: F.interpolate(size=) default."""
+def upsample_ce(low, labels, want_grad=True, grad_scale=1.0, ignore_index=255, align_corners=True, class_weights=None, label_smoothing=0.0):
+    """Fused classifier-upsample + CrossEntropyLoss.  Returns (loss_out[4], dlow or None).  align_corners False: F.interpolate(size=) default.
+    class_weights ([K] fp32 on low's device) / label_smoothing: CrossEntropyLoss(weight=, label_smoothing=) through mi_upsample_ce_w, where
+    loss_out[1] is the weight sum of the valid pixels; with both at their defaults the call is mi_upsample_ce_ex as ever."""
     _chk(low, torch.float32, "low")
     _chk(labels, torch.int64, "labels")
     B, h, w, K = low.shape
@@ -472,8 +474,16 @@ def upsample_ce(low, labels, want_grad=True, grad_scale=1.0, ignore_index=255, a
     ws = _workspace(L.mi_upsample_ce_workspace(B, h, w, K, H, W), low.device, "upce")
     out = torch.empty(4, dtype=torch.float32, device=low.device)
     dlow = torch.empty_like(low) if want_grad else None
-    check(L.mi_upsample_ce_ex(_p(low), _p(labels), _p(out), _p(dlow), B, h, w, K, H, W, ignore_index, float(grad_scale), int(bool(align_corners)),
-                              _p(ws), ws.numel(), _stream()), "mi_upsample_ce")
+    if class_weights is None and float(label_smoothing) == 0.0:
+        check(L.mi_upsample_ce_ex(_p(low), _p(labels), _p(out), _p(dlow), B, h, w, K, H, W, ignore_index, float(grad_scale), int(bool(align_corners)),
+                                  _p(ws), ws.numel(), _stream()), "mi_upsample_ce")
+        return out, dlow
+    if class_weights is not None:
+        _chk(class_weights, torch.float32, "class_weights")
+        if tuple(class_weights.shape) != (K,) or class_weights.device != low.device:
+            raise _lib.MiError("upsample_ce: class_weights must be [%d] on %s, got %s on %s" % (K, low.device, tuple(class_weights.shape), class_weights.device))
+    check(L.mi_upsample_ce_w(_p(low), _p(labels), _p(class_weights), _p(out), _p(dlow), B, h, w, K, H, W, ignore_index, float(label_smoothing),
+                             float(grad_scale), int(bool(align_corners)), _p(ws), ws.numel(), _stream()), "mi_upsample_ce_w")
     return out, dlow
 
 

@@ -2,12 +2,17 @@
 four head losses, backward, both Adam steps.
 
     python tools/gald_bench.py [--batch 6] [--height 720] [--width 1280] [--steps 10] [--loss ce|gdl] [--literal] [--alternate ROUNDS]
+                               [--class-weights median] [--label-smoothing S]
 
 --loss ce: the four fused upsample + cross-entropy heads (the default); --loss gdl: the four fused upsample + generalized Dice heads
 (configs/gald_src_dice.yaml).  --literal (with gdl): the composition without the fused kernel - decoder(x, feats) materialises the four [B,19,H,W]
 outputs, each goes as fp32 NCHW through the reference's GeneralizedDiceLoss written with torch ops, autograd does the backward.
---alternate N: ce, gdl and gdl --literal one after the other, N times over, in this one process (one JSON line per variant and round), so that
-the three are compared on one box under the same conditions; the peak of allocated memory is reset before every variant."""
+--class-weights median / --label-smoothing S (with ce): CrossEntropyLoss(weight=, label_smoothing=) inside the fused heads (mi_upsample_ce_w), the
+weights by median-frequency balancing (tools/class_weights.py) of the bench's own labels; with --literal: the four materialised outputs through
+F.cross_entropy(weight=, label_smoothing=) with autograd.
+--alternate N: ce, gdl and gdl --literal - and, when weights or smoothing are given, ce weighted fused and ce weighted literal - one after the other, N
+times over, in this one process (one JSON line per variant and round), so that they are compared on one box under the same conditions; the peak of
+allocated memory is reset before every variant."""
 import argparse
 import json
 import os
@@ -18,6 +23,7 @@ import torch
 import torch.nn.functional as F
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import class_weights as cw  # noqa: E402  (tools/class_weights.py)
 from rnd_semantic_segmentation_amd.host import gald, pranet, synth  # noqa: E402
 
 
@@ -48,26 +54,37 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--loss", choices=("ce", "gdl"), default="ce")
-    ap.add_argument("--literal", action="store_true", help="with --loss gdl: materialised outputs through a torch-op Dice loss with autograd")
-    ap.add_argument("--alternate", type=int, default=0, metavar="ROUNDS", help="run ce, gdl and gdl --literal in turn, ROUNDS times, in this process")
+    ap.add_argument("--literal", action="store_true", help="materialised outputs through a torch-op Dice loss / F.cross_entropy with autograd")
+    ap.add_argument("--alternate", type=int, default=0, metavar="ROUNDS", help="run the variants in turn, ROUNDS times, in this process")
+    ap.add_argument("--class-weights", choices=("median",), default=None, help="with ce: median-frequency class weights from the bench's own labels")
+    ap.add_argument("--label-smoothing", type=float, default=0.0, metavar="S", help="with ce: CrossEntropyLoss's label_smoothing")
     a = ap.parse_args()
-    if a.literal and a.loss != "gdl":
-        ap.error("--literal goes with --loss gdl")
+    weighted = a.class_weights is not None or a.label_smoothing != 0.0
+    if weighted and a.loss != "ce" and not a.alternate:
+        ap.error("--class-weights / --label-smoothing go with --loss ce")
     torch.manual_seed(0)
     enc, dec = gald.GCPAEncoder().cuda().train(), gald.GCPADecoder().cuda().train()
     enc.ensure_flat()
     dec.ensure_flat()
     oe, od = pranet.FlatAdam(enc, 1e-4), pranet.FlatAdam(dec, 1e-3)
     x = torch.from_numpy(synth.synth_image(a.batch, a.height, a.width, seed=9)).cuda()
-    lab = torch.from_numpy(synth.synth_label(a.batch, a.height, a.width, 19, seed=9)).cuda().long()
+    lab_host = synth.synth_label(a.batch, a.height, a.width, 19, seed=9)
+    lab = torch.from_numpy(lab_host).cuda().long()
+    weights = None
+    if a.class_weights == "median":
+        weights = torch.tensor(cw.class_weights(*cw.count_labels(lab_host, 19), "median"), dtype=torch.float32).cuda()
 
     def step(loss_name, literal):
         oe.zero_grad()
         od.zero_grad()
-        if literal:
+        extra = {"class_weights": weights, "label_smoothing": a.label_smoothing} if loss_name == "ce-weighted" else {}
+        if literal and loss_name == "gdl":
             l5, l4, l3, l2 = [torch_gdl(o.float().contiguous(), lab) for o in dec(x, enc(x))]
+        elif literal:
+            l5, l4, l3, l2 = [F.cross_entropy(o.float().contiguous(), lab, weight=extra.get("class_weights"), ignore_index=255,
+                                              label_smoothing=extra.get("label_smoothing", 0.0)) for o in dec(x, enc(x))]
         else:
-            l5, l4, l3, l2 = dec.losses(x, enc(x), lab, criterion=loss_name)          # the trainer's path: upsample + loss fused
+            l5, l4, l3, l2 = dec.losses(x, enc(x), lab, criterion="ce" if loss_name.startswith("ce") else loss_name, **extra)      # the trainer's path: fused
         loss = l2 * 1 + l3 * 0.8 + l4 * 0.6 + l5 * 0.4
         loss.backward()
         oe.step()
@@ -91,10 +108,11 @@ def main():
 
     if a.alternate:
         for r in range(a.alternate):
-            for loss_name, literal in (("ce", False), ("gdl", False), ("gdl", True)):
+            variants = (("ce", False), ("gdl", False), ("gdl", True)) + ((("ce-weighted", False), ("ce-weighted", True)) if weighted else ())
+            for loss_name, literal in variants:
                 measure(loss_name, literal, a.warmup if r == 0 else 1)
     else:
-        measure(a.loss, a.literal, a.warmup)
+        measure("ce-weighted" if weighted else a.loss, a.literal, a.warmup)
 
 
 if __name__ == "__main__":
