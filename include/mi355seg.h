@@ -242,6 +242,31 @@ int mi_upsample_ce_w(const float* low, const int64_t* labels, const float* class
                      int B, int h, int w, int K, int H, int W, int ignore_index, float label_smoothing, float grad_scale, int align_corners,
                      void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- fused upsample + cross-entropy with online hard example mining (OHEM: the OhemCrossEntropy2d criterion GALDNet, CCNet, OCNet and HRNet-Seg
+ * were published with) ----
+ * Operands and restrictions as mi_upsample_ce_ex, and B H W < 2^24.  With z = bilinear(low) in either convention, p = softmax(z), y = label,
+ * valid = label not ignore_index and inside [0, K), q_i = p_i[y_i] on valid pixels and n their count:
+ *   k      = min(min_kept, n)                                       (min_kept >= 1)
+ *   t      = max(thresh, k-th smallest q over the valid pixels)     (1-based; n == 0: t = thresh; 0 <= thresh <= 1)
+ *   kept_i = valid_i and q_i <= t                                   (ties at t are all kept, so at least k pixels are kept)
+ *   loss   = sum_kept (-log q_i) / n_kept                           (n_kept == 0, i.e. n == 0: nan, as the other heads)
+ *   d loss / d z_c at pixel i = kept_i (p_i[c] - [c == y_i]) / n_kept;  d loss / d low = transposed bilinear of that, times grad_scale
+ * The kept set is a constant of the backward pass: nothing differentiates through t.  min_kept counts full-resolution pixels of this one call
+ * (one head, one batch, one rank).  min_kept >= n gives the plain cross-entropy over the valid pixels.
+ * loss_out: [0] = loss, [1] = n_kept (an integer count, exact as a float below 2^24), [2] = out-of-range labels (left out and counted),
+ * [3] = the threshold t that was used.  dlow may be NULL (loss only, same loss bits); an entry of dlow that no kept pixel touches is exactly 0,
+ * also when n == 0.  prob (may be NULL): [B][H][W] fp32, receives q of every full-resolution pixel, 2.0 where the pixel is not valid.
+ * t is the exact order statistic of the fp32 q the kernel computed (a three-level radix select on their bit patterns, histograms merged with
+ * integer atomics); the pixels that receive gradient are exactly the n_kept that were counted, because both decisions read the same stored q.
+ * No floating-point atomic, every sum in a fixed order: two calls give the same bits.  Nothing is read back between the launches (one memset,
+ * 8 kernels for the loss, 2 more for dlow, one device copy for prob), so the call can be captured in a HIP graph; a replay reads low and
+ * labels anew.  Refused before any launch: what mi_upsample_ce_ex refuses, B H W >= 2^24, thresh outside [0, 1], min_kept < 1, a short
+ * workspace (MI_ENOMEM). */
+size_t mi_upsample_ce_ohem_workspace(int B, int h, int w, int K, int H, int W);
+int mi_upsample_ce_ohem(const float* low, const int64_t* labels, float* loss_out /*[4]*/, float* dlow, float* prob /*[B][H][W]*/,
+                        int B, int h, int w, int K, int H, int W, int ignore_index, float thresh, int64_t min_kept, float grad_scale,
+                        int align_corners, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- fused upsample + generalized Dice loss (GeneralizedDiceLoss, reference core/utils/utility.py:399-447, label form) ----
  * Operands and restrictions as mi_upsample_ce_ex.  With p = softmax(bilinear(low)) and t = onehot(labels), both zero where the label is
  * ignore_index:  T_c = sum t, I_c = sum p t, P2_c = sum p^2, w_c = 1 / (T_c^2 + eps) | 1 / (T_c + eps) | 1 / (sqrt(T_c) + eps) by weight_type,

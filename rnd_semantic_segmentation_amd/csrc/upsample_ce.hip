@@ -1348,6 +1348,395 @@ extern "C" int mi_upsample_tversky_bce(const float* low, const float* mask, floa
     return MI_OK;
 }
 
+namespace {
+// ------------------------------------------------------------------------------------------------ online hard example mining, fused with the upsample
+// Cross-entropy averaged over the hard pixels only (the OhemCrossEntropy2d of GALDNet / CCNet / OCNet / HRNet-Seg), on z = bilinear(low):
+//   q_i = softmax(z_i)[y_i] on valid pixels, n of them;  k = min(min_kept, n);  t = max(thresh, k-th smallest q);  kept_i = valid_i and q_i <= t
+//   loss = sum_kept (-log q_i) / n_kept;  d loss / d z_c = kept_i (p_i[c] - [c == y_i]) / n_kept      (nothing differentiates through t)
+// Launches (nothing is read back, so the call can be captured):
+//   memset of the histograms and counters
+//   ohem_prob_kernel      q (2.0 = not valid) and -log q of every full-resolution pixel into the workspace, the counts of valid and out-of-range pixels,
+//                         and the histogram of bits 31..21 of q (positive floats order as their unsigned bits).  The grid of gdl_reduce_kernel.
+//   ohem_scan_kernel 0    one workgroup: k, prefix scan of the 2048 bins, the bucket that holds the k-th smallest, the rank left inside it
+//   ohem_hist_kernel 1    histogram of bits 20..10 of the q whose bits 31..21 equal the chosen bucket;  ohem_scan_kernel 1
+//   ohem_hist_kernel 2    histogram of bits 9..0 of the q whose bits 31..10 equal the prefix;            ohem_scan_kernel 2: all 32 bits of the k-th smallest, t
+//   ohem_loss_kernel      per-workgroup sum of -log q and count over q <= t;  ohem_finalize_kernel: loss_out
+//   ohem_grad_kernel      gdl_grad_kernel's tiling with d = (q <= t) (p - onehot), the decision read from the STORED q: the pixels that receive gradient are
+//                         the n_kept that were counted;  wce_pass2_kernel divides by loss_out[1] = n_kept and keeps exact zeros.
+// Histograms live in LDS and are merged with integer atomics (order-independent); every float sum has a fixed order: two calls give the same bits.
+constexpr int OHEM_BINS = 2048;
+constexpr int OHEM_WGS = 1024;          // workgroups of the streaming passes over q (grid-stride)
+enum { OHEM_NVALID = 0, OHEM_BAD = 1, OHEM_PREFIX = 2, OHEM_RANK = 3, OHEM_T = 4, OHEM_STATE = 8 };          // the words behind the three histograms
+constexpr float OHEM_SENTINEL = 2.f;
+
+template <int KT>
+__global__ __launch_bounds__(256) void ohem_prob_kernel(const float* __restrict__ low, const int64_t* __restrict__ labels, float* __restrict__ qout,
+                                                        float* __restrict__ nllout, unsigned* __restrict__ hist, unsigned* __restrict__ state, int Krt, Axis ay,
+                                                        Axis ax, int ignore_index, int rows, int ncol_max) {
+    const int K = KT > 0 ? KT : Krt;
+    constexpr int KR = KT > 0 ? KT : KMAX;
+    extern __shared__ __attribute__((aligned(16))) float sh[];
+    float* vrow = sh;                                                          // [ncol_max][K] source row already interpolated along y
+    unsigned* lh = reinterpret_cast<unsigned*>(sh + (long)ncol_max * K);       // [OHEM_BINS]
+    const int H = ay.n_out, W = ax.n_out, h = ay.n_in, w = ax.n_in;
+    const int tid = threadIdx.x, b = blockIdx.z;
+    const int xa = blockIdx.x * GDL_XT, xb = min(W, xa + GDL_XT);
+    const int ya = blockIdx.y * rows, yb = min(H, ya + rows);
+    for (int e = tid; e < OHEM_BINS; e += 256) lh[e] = 0u;
+    int cbase, clast, unused;
+    float lx = 0.f;
+    ax.src(xa, cbase, unused, lx);
+    ax.src(xb - 1, unused, clast, lx);
+    const int ncol = min(clast - cbase + 1, ncol_max);
+    const int x = xa + tid;
+    int x0 = cbase, x1 = cbase;
+    if (x < xb) ax.src(x, x0, x1, lx);
+    unsigned nvalid = 0u, bad = 0u;
+    for (int y = ya; y < yb; ++y) {
+        int y0, y1;
+        float ly;
+        ay.src(y, y0, y1, ly);
+        const float* row0 = low + (((long)b * h + y0) * w + cbase) * K;
+        const float* row1 = low + (((long)b * h + y1) * w + cbase) * K;
+        for (int e = tid; e < ncol * K; e += 256) vrow[e] = (1.f - ly) * row0[e] + ly * row1[e];
+        __syncthreads();
+        if (x < xb) {
+            const long pix = ((long)b * H + y) * W + x;
+            const long lab = labels[pix];
+            float q = OHEM_SENTINEL, nll = 0.f;
+            if (lab != ignore_index && lab >= 0 && lab < K) {
+                const float* c0 = vrow + (x0 - cbase) * K;
+                const float* c1 = vrow + (x1 - cbase) * K;
+                float v[KR];
+                float mx = -3.0e38f;
+#pragma unroll
+                for (int k = 0; k < KR; ++k) {
+                    if (k < K) {
+                        v[k] = (1.f - lx) * c0[k] + lx * c1[k];
+                        mx = fmaxf(mx, v[k]);
+                    }
+                }
+                float se = 0.f, picked = 0.f, ey = 0.f;      // the loss term from picked = z_y - max before the exponential, as upce_pass1_kernel: finite when q underflows
+#pragma unroll
+                for (int k = 0; k < KR; ++k) {
+                    if (k < K) {
+                        if (k == lab) picked = v[k] - mx;
+                        v[k] = __expf(v[k] - mx);
+                        if (k == lab) ey = v[k];
+                        se += v[k];
+                    }
+                }
+                q = fminf(ey * (1.f / se), 1.f);
+                nll = __logf(se) - picked;
+                nvalid += 1u;
+                atomicAdd(&lh[__float_as_uint(q) >> 21], 1u);
+            } else if (lab != ignore_index) {
+                bad += 1u;
+            }
+            qout[pix] = q;
+            nllout[pix] = nll;
+        }
+        __syncthreads();          // the next row overwrites vrow
+    }
+    nvalid = wave_sum(nvalid);
+    bad = wave_sum(bad);
+    if ((tid & 63) == 0) {
+        if (nvalid) atomicAdd(&state[OHEM_NVALID], nvalid);
+        if (bad) atomicAdd(&state[OHEM_BAD], bad);
+    }
+    for (int e = tid; e < OHEM_BINS; e += 256) {
+        const unsigned c = lh[e];
+        if (c) atomicAdd(&hist[e], c);
+    }
+}
+
+// One workgroup.  level 0 / 1 / 2 looks at bits 31..21 / 20..10 / 9..0 (2048 / 2048 / 1024 bins).  rank = 1-based rank of the wanted value among the
+// values that share the prefix so far (level 0: k = min(kmin, n valid)); rank 0 (no valid pixel) picks bin 0 at every level, so t = thresh.
+__global__ __launch_bounds__(256) void ohem_scan_kernel(const unsigned* __restrict__ hist_all, unsigned* __restrict__ state, int level, unsigned kmin,
+                                                        float thresh) {
+    __shared__ unsigned sc[256];
+    const int tid = threadIdx.x;
+    const int per = level == 2 ? 4 : 8, width = level == 2 ? 10 : 11;
+    const unsigned* hist = hist_all + level * OHEM_BINS;
+    const unsigned rank = level == 0 ? min(kmin, state[OHEM_NVALID]) : state[OHEM_RANK];
+    const unsigned prefix = level == 0 ? 0u : state[OHEM_PREFIX];
+    unsigned c[8], sum = 0u;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        c[i] = i < per ? hist[tid * per + i] : 0u;
+        sum += c[i];
+    }
+    sc[tid] = sum;
+    __syncthreads();
+    for (int d = 1; d < 256; d <<= 1) {          // inclusive scan of the 256 thread sums
+        const unsigned v = tid >= d ? sc[tid - d] : 0u;
+        __syncthreads();
+        sc[tid] += v;
+        __syncthreads();
+    }
+    const unsigned incl = sc[tid], excl = incl - sum;
+    const bool mine = rank > 0u ? (excl < rank && rank <= incl) : tid == 0;          // exactly one thread
+    if (mine) {
+        unsigned cum = excl;
+        int bucket = tid * per;
+        if (rank > 0u) {
+            bool found = false;
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                if (i < per && !found) {
+                    if (cum + c[i] >= rank) {
+                        found = true;
+                        bucket = tid * per + i;
+                    } else {
+                        cum += c[i];
+                    }
+                }
+            }
+        }
+        const unsigned np = (prefix << width) | (unsigned)bucket;
+        state[OHEM_PREFIX] = np;
+        state[OHEM_RANK] = rank > 0u ? rank - cum : 0u;
+        if (level == 2) state[OHEM_T] = __float_as_uint(fmaxf(thresh, __uint_as_float(np)));
+    }
+}
+
+// Histogram of the next bit field of the values whose higher bits equal the prefix chosen so far.
+__global__ __launch_bounds__(256) void ohem_hist_kernel(const unsigned* __restrict__ qbits, int n, unsigned* __restrict__ hist_all,
+                                                        const unsigned* __restrict__ state, int level) {
+    __shared__ unsigned lh[OHEM_BINS];
+    const int tid = threadIdx.x;
+    const int hi = level == 1 ? 21 : 10, lo = level == 1 ? 10 : 0;
+    const unsigned mask = level == 1 ? 2047u : 1023u;
+    const unsigned prefix = state[OHEM_PREFIX];
+    for (int e = tid; e < OHEM_BINS; e += 256) lh[e] = 0u;
+    __syncthreads();
+    for (long i = (long)blockIdx.x * 256 + tid; i < n; i += (long)gridDim.x * 256) {
+        const unsigned u = qbits[i];
+        if ((u >> hi) == prefix) atomicAdd(&lh[(u >> lo) & mask], 1u);
+    }
+    __syncthreads();
+    unsigned* hist = hist_all + level * OHEM_BINS;
+    for (int e = tid; e < OHEM_BINS; e += 256) {
+        const unsigned c = lh[e];
+        if (c) atomicAdd(&hist[e], c);
+    }
+}
+
+// partial: [workgroup][2] words - the sum of -log q over the kept pixels (float), their count (unsigned).  A thread adds its pixels in ascending order,
+// the wave by butterfly, the four waves in order.
+__global__ __launch_bounds__(256) void ohem_loss_kernel(const float* __restrict__ q, const float* __restrict__ nll, int n, const unsigned* __restrict__ state,
+                                                        unsigned* __restrict__ partial) {
+    __shared__ float rs[4];
+    __shared__ unsigned rc[4];
+    const int tid = threadIdx.x;
+    const float t = __uint_as_float(state[OHEM_T]);
+    float s = 0.f;
+    unsigned c = 0u;
+    for (long i = (long)blockIdx.x * 256 + tid; i < n; i += (long)gridDim.x * 256) {
+        if (q[i] <= t) {
+            s += nll[i];
+            c += 1u;
+        }
+    }
+    s = wave_sum(s);
+    c = wave_sum(c);
+    if ((tid & 63) == 0) {
+        rs[tid >> 6] = s;
+        rc[tid >> 6] = c;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        partial[2 * blockIdx.x] = __float_as_uint(((rs[0] + rs[1]) + rs[2]) + rs[3]);
+        partial[2 * blockIdx.x + 1] = ((rc[0] + rc[1]) + rc[2]) + rc[3];
+    }
+}
+
+// One workgroup: the partial rows in fp64 / integers in a fixed order, then loss_out = loss, n_kept, out-of-range labels, t.
+__global__ __launch_bounds__(256) void ohem_finalize_kernel(const unsigned* __restrict__ partial, int nwg, const unsigned* __restrict__ state,
+                                                            float* __restrict__ loss_out) {
+    __shared__ double rs[4];
+    __shared__ unsigned rc[4];
+    const int tid = threadIdx.x;
+    double s = 0.0;
+    unsigned c = 0u;
+    for (int i = tid; i < nwg; i += 256) {
+        s += (double)__uint_as_float(partial[2 * i]);
+        c += partial[2 * i + 1];
+    }
+    s = wave_sum(s);
+    c = wave_sum(c);
+    if ((tid & 63) == 0) {
+        rs[tid >> 6] = s;
+        rc[tid >> 6] = c;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        const double tot = ((rs[0] + rs[1]) + rs[2]) + rs[3];
+        const unsigned kept = ((rc[0] + rc[1]) + rc[2]) + rc[3];
+        loss_out[0] = (float)(tot / (double)kept);          // 0 / 0 = nan when no pixel is valid, as the other heads
+        loss_out[1] = (float)kept;                          // exact: B H W < 2^24
+        loss_out[2] = (float)state[OHEM_BAD];
+        loss_out[3] = __uint_as_float(state[OHEM_T]);
+    }
+}
+
+// gdl_grad_kernel's tiling with d = kept (softmax - onehot); kept is read from the stored q (the sentinel of a pixel that is not valid lies above any t),
+// and a pixel that is not kept costs neither a label read nor a softmax.
+template <int KT>
+__global__ __launch_bounds__(256) void ohem_grad_kernel(const float* __restrict__ low, const int64_t* __restrict__ labels, const float* __restrict__ q,
+                                                        const unsigned* __restrict__ state, float* __restrict__ tmp, int Krt, Axis ay, Axis ax, int npx_max,
+                                                        int jt_cols) {
+    const int K = KT > 0 ? KT : Krt;
+    constexpr int KR = KT > 0 ? KT : KMAX;
+    extern __shared__ __attribute__((aligned(16))) float sh[];
+    float* dbuf = sh;                                           // [npx_max][K]
+    float* lam = sh + (long)npx_max * K;                        // [npx_max]  lambda_x
+    int* pstart = reinterpret_cast<int*>(lam + npx_max);        // [JT+3] first pixel (relative to xa) whose x0 >= j0 - 1 + q
+    float* vrow = reinterpret_cast<float*>(pstart + JT + 4);    // [JT+2][K] low-res row already interpolated along y
+    const int H = ay.n_out, W = ax.n_out, w = ax.n_in;
+    const int jt = blockIdx.x, y = blockIdx.y, b = blockIdx.z;
+    const int j0 = jt * jt_cols, j1 = min(w, j0 + jt_cols);
+    const int xa = ax.first_with_i0_ge(j0 - 1), xb = ax.first_with_i0_ge(j1);   // pixels with x0 in [j0-1, j1-1]
+    const int npx = min(xb - xa, npx_max);
+    int cbase;
+    tile_stage(low, K, ay, ax, b, y, j0, j1, xa, pstart, vrow, cbase);
+    __syncthreads();
+    const float t = __uint_as_float(state[OHEM_T]);
+    for (int px = threadIdx.x; px < npx; px += 256) {
+        const int x = xa + px;
+        int x0, x1;
+        float lx;
+        ax.src(x, x0, x1, lx);
+        lam[px] = lx;
+        const long pix = ((long)b * H + y) * W + x;
+        float* d = dbuf + (long)px * K;
+        if (!(q[pix] <= t)) {
+            for (int k = 0; k < K; ++k) d[k] = 0.f;
+            continue;
+        }
+        const long lab = labels[pix];
+        const float* c0 = vrow + (x0 - cbase) * K;
+        const float* c1 = vrow + (x1 - cbase) * K;
+        float v[KR];
+        float mx = -3.0e38f;
+#pragma unroll
+        for (int k = 0; k < KR; ++k) {
+            if (k < K) {
+                v[k] = (1.f - lx) * c0[k] + lx * c1[k];
+                mx = fmaxf(mx, v[k]);
+            }
+        }
+        float se = 0.f;
+#pragma unroll
+        for (int k = 0; k < KR; ++k) {
+            if (k < K) {
+                v[k] = __expf(v[k] - mx);
+                se += v[k];
+            }
+        }
+        const float rse = 1.f / se;
+#pragma unroll
+        for (int k = 0; k < KR; ++k) {
+            if (k < K) d[k] = v[k] * rse - (k == lab ? 1.f : 0.f);
+        }
+    }
+    __syncthreads();
+    tile_gather_x(dbuf, lam, pstart, tmp + ((long)b * H + y) * w * K, K, j0, j1, w, npx);
+}
+
+struct OhemLayout {
+    size_t q, nll, hist, partial, tmp, total;
+};
+inline OhemLayout ohem_layout(int B, int w, int K, int H, int W) {
+    OhemLayout l;
+    const size_t n = (size_t)B * H * W;
+    l.q = 0;
+    l.nll = l.q + up256(n * sizeof(float));
+    l.hist = l.nll + up256(n * sizeof(float));
+    l.partial = l.hist + up256((3 * OHEM_BINS + OHEM_STATE) * sizeof(unsigned));
+    l.tmp = l.partial + up256((size_t)OHEM_WGS * 2 * sizeof(unsigned));
+    l.total = l.tmp + (size_t)B * H * w * K * sizeof(float);
+    return l;
+}
+}  // namespace
+
+extern "C" size_t mi_upsample_ce_ohem_workspace(int B, int h, int w, int K, int H, int W) {
+    if (B <= 0 || h <= 0 || w <= 0 || K <= 0 || H <= 0 || W <= 0) return 0;
+    return ohem_layout(B, w, K, H, W).total;
+}
+
+extern "C" int mi_upsample_ce_ohem(const float* low, const int64_t* labels, float* loss_out, float* dlow, float* prob, int B, int h, int w, int K, int H,
+                                   int W, int ignore_index, float thresh, int64_t min_kept, float grad_scale, int align_corners, void* workspace,
+                                   size_t workspace_bytes, void* stream) {
+    MI_REQUIRE(low && labels && loss_out && workspace, "mi_upsample_ce_ohem: null operand");
+    MI_REQUIRE(B > 0 && h > 0 && w > 0 && H > 0 && W > 0 && K > 0 && K <= KMAX, "mi_upsample_ce_ohem: bad dimension (K <= 32)");
+    MI_REQUIRE(H >= h && W >= w, "mi_upsample_ce_ohem: only upsampling (H >= h, W >= w) is supported");
+    MI_REQUIRE(H <= 65535 && B <= 65535, "mi_upsample_ce_ohem: grid dimension overflow");
+    MI_REQUIRE((long)B * H * W < (1L << 24), "mi_upsample_ce_ohem: B H W must stay below 2^24 (n_kept is reported as a float)");
+    MI_REQUIRE(thresh >= 0.f && thresh <= 1.f, "mi_upsample_ce_ohem: thresh outside [0, 1]");          // (a NaN fails both comparisons)
+    MI_REQUIRE(min_kept >= 1, "mi_upsample_ce_ohem: min_kept must be at least 1");
+    MI_REQUIRE(std::isfinite(grad_scale), "mi_upsample_ce_ohem: grad_scale is not finite");
+    if (workspace_bytes < mi_upsample_ce_ohem_workspace(B, h, w, K, H, W)) return mi_set_error(MI_ENOMEM, "mi_upsample_ce_ohem: workspace too small");
+    const Axis ay = make_axis(h, H, align_corners), ax = make_axis(w, W, align_corners);
+    const OhemLayout lay = ohem_layout(B, w, K, H, W);
+    const GdlPlan pl = gdl_plan(B, H, W);
+    char* ws = (char*)workspace;
+    float* q = (float*)(ws + lay.q);
+    float* nll = (float*)(ws + lay.nll);
+    unsigned* hist = (unsigned*)(ws + lay.hist);
+    unsigned* state = hist + 3 * OHEM_BINS;
+    unsigned* partial = (unsigned*)(ws + lay.partial);
+    float* tmp = (float*)(ws + lay.tmp);
+    const int n = B * H * W;
+    const unsigned kmin = (unsigned)(min_kept < (int64_t)(1 << 24) ? min_kept : (int64_t)(1 << 24));          // k = min(min_kept, n) and n < 2^24
+    const int ncol_max = w < GDL_XT + 2 ? w : GDL_XT + 2;
+    const size_t lds1 = ((size_t)ncol_max * K + OHEM_BINS) * 4;          // <= 41 KB
+    const int jt_cols = pick_jt(w, W);
+    const int npx_max = pass1_npx_max(ax, jt_cols);
+    const size_t lds3 = (size_t)npx_max * K * 4 + (size_t)npx_max * 4 + (JT + 4) * 4 + (size_t)(JT + 2) * K * 4;
+    MI_REQUIRE(!dlow || lds3 <= 160 * 1024, "mi_upsample_ce_ohem: upsample factor too large for one LDS tile (%zu B)", lds3);
+    hipStream_t st = (hipStream_t)stream;
+    if (hipMemsetAsync(hist, 0, (3 * OHEM_BINS + OHEM_STATE) * sizeof(unsigned), st) != hipSuccess) return mi_set_error(MI_EHIP, "mi_upsample_ce_ohem: memset");
+    const dim3 g1(pl.tiles_x, pl.row_groups, B);
+    if (K == 19)
+        hipLaunchKernelGGL(ohem_prob_kernel<19>, g1, dim3(256), lds1, st, low, labels, q, nll, hist, state, K, ay, ax, ignore_index, pl.rows, ncol_max);
+    else
+        hipLaunchKernelGGL(ohem_prob_kernel<0>, g1, dim3(256), lds1, st, low, labels, q, nll, hist, state, K, ay, ax, ignore_index, pl.rows, ncol_max);
+    MI_CHECK_LAUNCH("mi_upsample_ce_ohem probability");
+    const unsigned nwg = nblk(n, 256) < (unsigned)OHEM_WGS ? nblk(n, 256) : (unsigned)OHEM_WGS;
+    for (int level = 0; level < 3; ++level) {
+        if (level > 0) {
+            hipLaunchKernelGGL(ohem_hist_kernel, dim3(nwg), dim3(256), 0, st, (const unsigned*)q, n, hist, (const unsigned*)state, level);
+            MI_CHECK_LAUNCH("mi_upsample_ce_ohem histogram");
+        }
+        hipLaunchKernelGGL(ohem_scan_kernel, dim3(1), dim3(256), 0, st, (const unsigned*)hist, state, level, kmin, thresh);
+        MI_CHECK_LAUNCH("mi_upsample_ce_ohem scan");
+    }
+    hipLaunchKernelGGL(ohem_loss_kernel, dim3(nwg), dim3(256), 0, st, (const float*)q, (const float*)nll, n, (const unsigned*)state, partial);
+    MI_CHECK_LAUNCH("mi_upsample_ce_ohem loss");
+    hipLaunchKernelGGL(ohem_finalize_kernel, dim3(1), dim3(256), 0, st, (const unsigned*)partial, (int)nwg, (const unsigned*)state, loss_out);
+    MI_CHECK_LAUNCH("mi_upsample_ce_ohem finalize");
+    if (dlow) {
+        static std::atomic<uint64_t> lds_set[2];
+        mi_allow_dynamic_lds((const void*)ohem_grad_kernel<19>, MI_LDS_MAX, lds_set[0]);
+        mi_allow_dynamic_lds((const void*)ohem_grad_kernel<0>, MI_LDS_MAX, lds_set[1]);
+        const int tiles = (w + jt_cols - 1) / jt_cols;
+        if (K == 19)
+            hipLaunchKernelGGL(ohem_grad_kernel<19>, dim3(tiles, H, B), dim3(256), lds3, st, low, labels, (const float*)q, (const unsigned*)state, tmp, K, ay, ax,
+                               npx_max, jt_cols);
+        else
+            hipLaunchKernelGGL(ohem_grad_kernel<0>, dim3(tiles, H, B), dim3(256), lds3, st, low, labels, (const float*)q, (const unsigned*)state, tmp, K, ay, ax,
+                               npx_max, jt_cols);
+        MI_CHECK_LAUNCH("mi_upsample_ce_ohem gradient");
+        hipLaunchKernelGGL(wce_pass2_kernel, dim3(nblk((long)B * h * w * K, 256)), dim3(256), 0, st, (const float*)tmp, (const float*)loss_out, dlow, B, K, ay, w,
+                           grad_scale);
+        MI_CHECK_LAUNCH("mi_upsample_ce_ohem gradient rows");
+    }
+    if (prob && hipMemcpyAsync(prob, q, (size_t)n * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess)
+        return mi_set_error(MI_EHIP, "mi_upsample_ce_ohem: copy of q");
+    return MI_OK;
+}
+
 extern "C" int mi_upsample_softmax(const float* low, float* probs, uint8_t* pred, int B, int h, int w, int K, int H, int W, void* stream) {
     MI_REQUIRE(low && probs && B > 0 && h > 0 && w > 0 && H > 0 && W > 0 && K > 0 && K <= KMAX, "mi_upsample_softmax: bad argument (K <= 32)");
     hipLaunchKernelGGL(upsample_softmax_kernel, dim3(nblk((long)B * H * W, 256)), dim3(256), 0, (hipStream_t)stream, low, probs, pred, B, K,

@@ -13,8 +13,9 @@ from ast import literal_eval
 import yaml
 
 _VALID = (tuple, list, str, int, float, bool, type(None))
-_RANGES = {"TEST.PSEUDO_THRESHOLD": (0.0, 1.0), "SOLVER.TVERSKY_ALPHA": (0.0, 1.0), "SOLVER.LABEL_SMOOTHING": (0.0, 1.0)}      # closed intervals a merged value has to lie in
-_CHOICES = {"SOLVER.LOSS": ("ce", "gdl", "tversky"), "SOLVER.GDL_WEIGHT": ("square", "identity", "sqrt")}      # the only values a merged key may take
+_RANGES = {"TEST.PSEUDO_THRESHOLD": (0.0, 1.0), "SOLVER.TVERSKY_ALPHA": (0.0, 1.0), "SOLVER.LABEL_SMOOTHING": (0.0, 1.0),
+           "SOLVER.OHEM_THRESH": (0.0, 1.0), "SOLVER.OHEM_MIN_KEPT": (1, float("inf"))}      # closed intervals a merged value has to lie in
+_CHOICES = {"SOLVER.LOSS": ("ce", "gdl", "tversky", "ohem"), "SOLVER.GDL_WEIGHT": ("square", "identity", "sqrt")}      # the only values a merged key may take
 
 
 class CfgNode(dict):
@@ -179,6 +180,11 @@ def default_tree():
             # LABEL_SMOOTHING in [0, 1] are CrossEntropyLoss's weight= and label_smoothing= for LOSS "ce" of ASPPTrainer, GALDTrainer and both FADA
             # combos, inside the fused upsample + cross-entropy heads (mi_upsample_ce_w); any other loss or trainer refuses them (plugin.ce_options)
             "CLASS_WEIGHTS": (), "LABEL_SMOOTHING": 0.0,
+            # LOSS "ohem" (ASPPTrainer, GALDTrainer) = online hard example mining, the criterion GALDNet, CCNet, OCNet and HRNet-Seg were published with:
+            # cross-entropy over the pixels whose probability of the true class is at most max(OHEM_THRESH, the OHEM_MIN_KEPT-th smallest of the call),
+            # inside the fused heads (mi_upsample_ce_ohem).  OHEM_MIN_KEPT counts full-resolution pixels of one head, one batch, one rank.  The two keys
+            # changed under any other LOSS are refused (plugin.ohem_options), as is "ohem" together with CLASS_WEIGHTS / LABEL_SMOOTHING.
+            "OHEM_THRESH": 0.7, "OHEM_MIN_KEPT": 100000,
         },
         # not in the reference: PRECISION fp32 = exact evaluation path, bf16 = training engine; SCALES / FLIP other than these defaults make
         # ASPPTester call multi_scale_inference (utility.py:193-209) instead of inference(flip=False); FUSED_SCORE True = argmax, threshold and

@@ -917,6 +917,27 @@ class AsppLossFn(torch.autograd.Function):
         return (dx, None, None, None, None, None, None) + (None,) * (len(ctx.needs_input_grad) - 7)
 
 
+class AsppOhemLossFn(AsppLossFn):
+    """AsppLossFn with the cross-entropy averaged over the hard pixels only (OHEM: K.upsample_ce_ohem); the backward is AsppLossFn's."""
+
+    @staticmethod
+    def forward(ctx, x, labels, eng, ignore_index, temperature, thresh, min_kept, *params):
+        train = any(ctx.needs_input_grad)
+        eng.prepare(train)
+        low = eng.forward(x)
+        eng.last_low = low
+        inv_t = 1.0 / temperature             # criterion(pred.div(T), label): the mining sees the scaled logits too
+        loss_out, dlow, _ = K.upsample_ce_ohem(low if temperature == 1.0 else low * inv_t, labels, thresh, min_kept, want_grad=train,
+                                               grad_scale=1.0 if temperature == 1.0 else inv_t, ignore_index=ignore_index)
+        ctx.eng, ctx.x, ctx.dlow = eng, (x if train else None), dlow
+        ctx.loss_out = eng.last_loss_out = loss_out          # [loss, n_kept, out-of-range labels, t]
+        bad = getattr(eng, "bad_labels", None)
+        if bad is None or bad.device != loss_out.device:
+            bad = eng.bad_labels = torch.zeros(1, dtype=torch.float32, device=loss_out.device)
+        bad.add_(loss_out[2:3])
+        return loss_out[0].clone()
+
+
 class UpsampleFn(torch.autograd.Function):
     """low [B,h,w,K] fp32 NHWC -> [B,K,H,W] fp32 NCHW, bilinear align_corners=True (classifier.py:31)."""
 

@@ -26,6 +26,7 @@ from . import arch, ddp, engine
 from .metrics import (MetricLogger, adjust_learning_rate, dump_json, setup_logger, soft_label_cross_entropy,  # noqa: F401
                       strip_prefix_if_present)
 from .modules import _require_gpu
+from .plugin import require_loss
 from .trainer import ASPPTrainer, _cpu_store
 
 LEAK = 0.2
@@ -333,6 +334,7 @@ class AsppFada:
     BATCHED = True
 
     def __init__(self, name, cfg, src_train_loader, tgt_train_loader, local_rank):
+        require_loss(cfg, type(self).__name__)          # its source loss is the cross-entropy at temperature T (ASPPTrainer alone also mines: "ohem")
         self.cfg = cfg
         self.logger = setup_logger(name + "_train", cfg.OUTPUT_DIR, local_rank)
         self.aspp = self.trainer_cls(name, cfg, src_train_loader, local_rank, self.logger)

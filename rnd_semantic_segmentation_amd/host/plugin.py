@@ -11,6 +11,8 @@ from .metrics import setup_logger
 
 
 _LOSS_HOME = {"gdl": "the generalized Dice loss ('gdl') is wired into GALD: GALDTrainer (configs/gald_src_dice.yaml)",
+              "ohem": "online hard example mining ('ohem') is wired into the fused cross-entropy heads of ASPPTrainer (configs/deeplabv2_r101_src_ohem.yaml) "
+                      "and GALDTrainer (configs/gald_src_ohem.yaml)",
               "tversky": "the Tversky + BCE loss ('tversky') is wired into PraNet: PraNetTrainer (configs/pranet_src_polyp_tversky.yaml)"}
 
 
@@ -33,6 +35,9 @@ def ce_options(cfg, who, device=None):
     if not weights and smoothing == 0.0:
         return None, 0.0
     loss = getattr(solver, "LOSS", "ce")
+    if loss == "ohem":
+        raise NotImplementedError("SOLVER.LOSS 'ohem' cannot be combined with SOLVER.CLASS_WEIGHTS / SOLVER.LABEL_SMOOTHING yet ({}): the mining "
+                                  "entry runs the plain cross-entropy".format(who))
     if loss != "ce":
         raise NotImplementedError("SOLVER.CLASS_WEIGHTS / SOLVER.LABEL_SMOOTHING belong to SOLVER.LOSS 'ce' (got {!r} for {})".format(loss, who))
     if who == "PraNetTrainer":
@@ -52,13 +57,36 @@ def ce_options(cfg, who, device=None):
     return torch.tensor(vals, dtype=torch.float32, device=device), smoothing
 
 
+OHEM_DEFAULTS = (0.7, 100000)          # SOLVER.OHEM_THRESH, SOLVER.OHEM_MIN_KEPT of host/config.py (GALDNet's published values)
+
+
+def ohem_options(cfg, who):
+    """SOLVER.OHEM_THRESH / SOLVER.OHEM_MIN_KEPT (not in the reference) as (thresh, min_kept) when SOLVER.LOSS is "ohem", else None.  The keys changed
+    while SOLVER.LOSS is something else are refused instead of ignored."""
+    solver = getattr(cfg, "SOLVER", None)
+    thresh = getattr(solver, "OHEM_THRESH", OHEM_DEFAULTS[0])
+    min_kept = getattr(solver, "OHEM_MIN_KEPT", OHEM_DEFAULTS[1])
+    loss = getattr(solver, "LOSS", "ce")
+    if loss != "ohem":
+        if (thresh, min_kept) != OHEM_DEFAULTS:
+            raise NotImplementedError("SOLVER.OHEM_THRESH / SOLVER.OHEM_MIN_KEPT belong to SOLVER.LOSS 'ohem' (got {!r} for {})".format(loss, who))
+        return None
+    if isinstance(thresh, bool) or not isinstance(thresh, (int, float)) or not 0.0 <= thresh <= 1.0:          # (a merged value was checked there; this one was assigned)
+        raise ValueError("SOLVER.OHEM_THRESH {!r} lies outside [0, 1]".format(thresh))
+    if isinstance(min_kept, bool) or not isinstance(min_kept, int) or min_kept < 1:
+        raise ValueError("SOLVER.OHEM_MIN_KEPT {!r} must be an integer >= 1".format(min_kept))
+    return float(thresh), int(min_kept)
+
+
 class BaseTrainer:
-    LOSSES = ("ce",)          # the SOLVER.LOSS values the trainer implements
+    LOSSES = ("ce",)          # the criteria the trainer implements, as SOLVER.LOSS values
+    MINED = ()                # SOLVER.LOSS values that are a LOSSES entry over mined pixels ("ohem" = "ce" over the hard pixels): accepted like LOSSES
 
     def __init__(self, name, cfg, train_loader, local_rank, logger=None):
-        require_loss(cfg, type(self).__name__, self.LOSSES)
+        require_loss(cfg, type(self).__name__, self.LOSSES + self.MINED)
         who = "PraNetTrainer" if any(c.__name__ == "PraNetTrainer" for c in type(self).__mro__) else type(self).__name__
         weights, self.ce_smoothing = ce_options(cfg, who)          # CrossEntropyLoss(weight=, label_smoothing=): refused early where they do not apply
+        self.ohem = ohem_options(cfg, who)                          # (thresh, min_kept) under SOLVER.LOSS "ohem", else None
         self.cfg = cfg
         self.logger = setup_logger(name + "_train", cfg.OUTPUT_DIR, local_rank) if logger is None else logger
         self.train_loader = train_loader
@@ -81,6 +109,8 @@ class BaseTrainer:
         self.ce_weights = None if weights is None else weights.to(self.device)          # created once, on the trainer's device
         # keywords for the fused heads' .loss() / .losses(); empty at the defaults, so those calls stay exactly what they were
         self.ce_kwargs = {"class_weights": self.ce_weights, "label_smoothing": self.ce_smoothing} if (weights is not None or self.ce_smoothing) else {}
+        if self.ohem is not None:
+            self.ce_kwargs = {"ohem": self.ohem}
         self.init_params()
         if cfg.resume:
             self.logger.info("Loading checkpoint from {}".format(self.cfg.resume))

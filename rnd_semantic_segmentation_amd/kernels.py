@@ -487,6 +487,46 @@ def upsample_ce(low, labels, want_grad=True, grad_scale=1.0, ignore_index=255, a
     return out, dlow
 
 
+def check_ohem(ohem):
+    """(thresh, min_kept) of an OHEM criterion, checked: 0 <= thresh <= 1, min_kept an integer >= 1."""
+    try:
+        thresh, min_kept = ohem
+        thresh, mk = float(thresh), int(min_kept)
+    except (TypeError, ValueError):
+        raise ValueError("ohem must be (thresh, min_kept), got %r" % (ohem,))
+    if not 0.0 <= thresh <= 1.0:
+        raise ValueError("ohem: thresh %r lies outside [0, 1]" % (thresh,))
+    if mk < 1 or mk != min_kept:
+        raise ValueError("ohem: min_kept must be an integer >= 1, got %r" % (min_kept,))
+    return thresh, mk
+
+
+def refuse_ohem_with_weights(ohem, class_weights, label_smoothing):
+    """OHEM together with CrossEntropyLoss's weight= / label_smoothing= is not built yet: every layer refuses the pair with this message."""
+    if ohem is not None and (class_weights is not None or float(label_smoothing) != 0.0):
+        raise NotImplementedError("ohem (online hard example mining) cannot be combined with class_weights / label_smoothing yet: "
+                                  "mi_upsample_ce_ohem mines on the plain cross-entropy")
+
+
+def upsample_ce_ohem(low, labels, thresh, min_kept, want_grad=True, grad_scale=1.0, ignore_index=255, align_corners=True, want_prob=False):
+    """Fused upsample + cross-entropy over the hard pixels only (OHEM, mi_upsample_ce_ohem): kept = valid and softmax[label] <= t,
+    t = max(thresh, min(min_kept, n valid)-th smallest softmax[label]).  Returns (loss_out[4] = loss, n_kept, bad labels, t; dlow or None;
+    prob [B,H,W] = softmax[label] of every pixel, 2.0 where it is not valid, or None).  Nothing is read back between its launches."""
+    _chk(low, torch.float32, "low")
+    _chk(labels, torch.int64, "labels")
+    thresh, min_kept = check_ohem((thresh, min_kept))
+    B, h, w, K = low.shape
+    _, H, W = labels.shape
+    L = _lib.lib()
+    ws = _workspace(L.mi_upsample_ce_ohem_workspace(B, h, w, K, H, W), low.device, "upohem")
+    out = torch.empty(4, dtype=torch.float32, device=low.device)
+    dlow = torch.empty_like(low) if want_grad else None
+    prob = torch.empty(B, H, W, dtype=torch.float32, device=low.device) if want_prob else None
+    check(L.mi_upsample_ce_ohem(_p(low), _p(labels), _p(out), _p(dlow), _p(prob), B, h, w, K, H, W, ignore_index, thresh, min_kept, float(grad_scale),
+                                int(bool(align_corners)), _p(ws), ws.numel(), _stream()), "mi_upsample_ce_ohem")
+    return out, dlow, prob
+
+
 GDL_WEIGHT_TYPES = {"square": 0, "identity": 1, "sqrt": 2}          # MI_GDL_* of include/mi355seg.h
 
 

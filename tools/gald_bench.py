@@ -1,8 +1,8 @@
 """GALD (HarDNet-68 + GCPA decoder; configs/gald_src.yaml: batch 6, 1280 x 720 crops) training-step throughput on one MI355X: encoder + decoder forward,
 four head losses, backward, both Adam steps.
 
-    python tools/gald_bench.py [--batch 6] [--height 720] [--width 1280] [--steps 10] [--loss ce|gdl] [--literal] [--alternate ROUNDS]
-                               [--class-weights median] [--label-smoothing S]
+    python tools/gald_bench.py [--batch 6] [--height 720] [--width 1280] [--steps 10] [--loss ce|gdl|ohem] [--literal] [--alternate ROUNDS]
+                               [--class-weights median] [--label-smoothing S] [--ohem-thresh T] [--ohem-min-kept M]
 
 --loss ce: the four fused upsample + cross-entropy heads (the default); --loss gdl: the four fused upsample + generalized Dice heads
 (configs/gald_src_dice.yaml).  --literal (with gdl): the composition without the fused kernel - decoder(x, feats) materialises the four [B,19,H,W]
@@ -10,6 +10,10 @@ outputs, each goes as fp32 NCHW through the reference's GeneralizedDiceLoss writ
 --class-weights median / --label-smoothing S (with ce): CrossEntropyLoss(weight=, label_smoothing=) inside the fused heads (mi_upsample_ce_w), the
 weights by median-frequency balancing (tools/class_weights.py) of the bench's own labels; with --literal: the four materialised outputs through
 F.cross_entropy(weight=, label_smoothing=) with autograd.
+--loss ohem: the four fused upsample + cross-entropy heads with online hard example mining (mi_upsample_ce_ohem; configs/gald_src_ohem.yaml), each head
+keeping the pixels whose probability of the true class is at most max(T, the M-th smallest of the head); with --literal: the four materialised outputs
+through a torch-op OHEM (softmax, gather, torch.kthvalue, masked F.cross_entropy) with autograd.  With --alternate the variants are ce, ohem and
+ohem --literal.
 --alternate N: ce, gdl and gdl --literal - and, when weights or smoothing are given, ce weighted fused and ce weighted literal - one after the other, N
 times over, in this one process (one JSON line per variant and round), so that they are compared on one box under the same conditions; the peak of
 allocated memory is reset before every variant."""
@@ -46,6 +50,17 @@ def torch_gdl(output, target, eps=1e-5, weight_type="square", ignore_label=255):
     return 1 - 2. * inter / den
 
 
+def torch_ohem(output, target, thresh, min_kept, ignore_label=255):
+    """OhemCrossEntropy2d as GALDNet / CCNet publish it, with torch ops on a materialised [N,C,H,W] tensor: the kept set is a constant (no_grad)."""
+    with torch.no_grad():
+        valid = target != ignore_label
+        q = torch.softmax(output, 1).gather(1, torch.where(valid, target, torch.zeros_like(target)).unsqueeze(1)).squeeze(1)[valid]
+        t = torch.clamp(torch.kthvalue(q, min(min_kept, q.numel())).values, min=thresh) if q.numel() else thresh
+        kept = torch.zeros_like(valid)
+        kept[valid] = q <= t
+    return F.cross_entropy(output, torch.where(kept, target, torch.full_like(target, ignore_label)), ignore_index=ignore_label)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=6)
@@ -53,11 +68,13 @@ def main():
     ap.add_argument("--width", type=int, default=1280)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--loss", choices=("ce", "gdl"), default="ce")
+    ap.add_argument("--loss", choices=("ce", "gdl", "ohem"), default="ce")
     ap.add_argument("--literal", action="store_true", help="materialised outputs through a torch-op Dice loss / F.cross_entropy with autograd")
     ap.add_argument("--alternate", type=int, default=0, metavar="ROUNDS", help="run the variants in turn, ROUNDS times, in this process")
     ap.add_argument("--class-weights", choices=("median",), default=None, help="with ce: median-frequency class weights from the bench's own labels")
     ap.add_argument("--label-smoothing", type=float, default=0.0, metavar="S", help="with ce: CrossEntropyLoss's label_smoothing")
+    ap.add_argument("--ohem-thresh", type=float, default=0.7, metavar="T", help="with ohem: SOLVER.OHEM_THRESH")
+    ap.add_argument("--ohem-min-kept", type=int, default=100000, metavar="M", help="with ohem: SOLVER.OHEM_MIN_KEPT")
     a = ap.parse_args()
     weighted = a.class_weights is not None or a.label_smoothing != 0.0
     if weighted and a.loss != "ce" and not a.alternate:
@@ -80,6 +97,10 @@ def main():
         extra = {"class_weights": weights, "label_smoothing": a.label_smoothing} if loss_name == "ce-weighted" else {}
         if literal and loss_name == "gdl":
             l5, l4, l3, l2 = [torch_gdl(o.float().contiguous(), lab) for o in dec(x, enc(x))]
+        elif literal and loss_name == "ohem":
+            l5, l4, l3, l2 = [torch_ohem(o.float().contiguous(), lab, a.ohem_thresh, a.ohem_min_kept) for o in dec(x, enc(x))]
+        elif loss_name == "ohem":
+            l5, l4, l3, l2 = dec.losses(x, enc(x), lab, criterion="ohem", ohem=(a.ohem_thresh, a.ohem_min_kept))
         elif literal:
             l5, l4, l3, l2 = [F.cross_entropy(o.float().contiguous(), lab, weight=extra.get("class_weights"), ignore_index=255,
                                               label_smoothing=extra.get("label_smoothing", 0.0)) for o in dec(x, enc(x))]
@@ -109,6 +130,8 @@ def main():
     if a.alternate:
         for r in range(a.alternate):
             variants = (("ce", False), ("gdl", False), ("gdl", True)) + ((("ce-weighted", False), ("ce-weighted", True)) if weighted else ())
+            if a.loss == "ohem":
+                variants = (("ce", False), ("ohem", False), ("ohem", True))
             for loss_name, literal in variants:
                 measure(loss_name, literal, a.warmup if r == 0 else 1)
     else:
