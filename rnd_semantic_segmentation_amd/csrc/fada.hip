@@ -2,52 +2,9 @@
 // cross-entropy with on-the-fly soft labels, Adam.  References: core/combos/aspp_fada.py:80-127,
 // core/utils/utility.py:172-177 (soft_label_cross_entropy), core/adapters/fada_adapter.py:24 (Adam betas .9/.99).
 // fp32 arithmetic, fixed summation orders (bitwise reproducible), HBM-bound.
-#include "mi_common.h"
+#include "upsample_common.h"      // Axis, the x-tile staging / gather of upce_pass1_kernel (KMAX, JT), nblk, pass1_npx_max
 
 namespace {
-
-constexpr int KMAX = 32;       // segmentation classes held in registers
-constexpr int JT = 32;         // low-res columns per workgroup (same tiling as upce_pass1)
-
-struct Axis {                  // source index as ATen computes it in fp32 (same as upsample_ce.hip): align_corners (off = 0): scale * dst;
-    float scale, off;          // otherwise (off = 0.5): max(scale * (dst + 0.5) - 0.5, 0)  (+/- 0.0f is exact: the align_corners bits are unchanged)
-    int n_in, n_out;
-    __device__ __forceinline__ float srcf(int dst) const {
-        const float f = scale * ((float)dst + off) - off;
-        return f < 0.f ? 0.f : f;
-    }
-    __device__ __forceinline__ void src(int dst, int& i0, int& i1, float& lam) const {
-        const float f = srcf(dst);
-        i0 = (int)f;
-        if (i0 > n_in - 1) i0 = n_in - 1;
-        i1 = (i0 < n_in - 1) ? i0 + 1 : i0;
-        lam = f - (float)i0;
-    }
-    __device__ __forceinline__ int first_with_i0_ge(int c) const {
-        if (c <= 0) return 0;
-        if (scale <= 0.f) return n_out;
-        if (c > n_in - 1) return n_out;
-        int d = (int)((float)c / scale) - 2;
-        if (d < 0) d = 0;
-        if (d > n_out) d = n_out;
-        while (d < n_out) {
-            int i0 = (int)srcf(d);
-            if (i0 > n_in - 1) i0 = n_in - 1;
-            if (i0 >= c) break;
-            ++d;
-        }
-        return d;
-    }
-};
-
-inline Axis make_axis(int n_in, int n_out, int align_corners = 1) {
-    Axis a;
-    a.n_in = n_in;
-    a.n_out = n_out;
-    a.off = align_corners ? 0.f : 0.5f;
-    a.scale = align_corners ? ((n_out > 1) ? (float)(n_in - 1) / (float)(n_out - 1) : 0.f) : (float)n_in / (float)n_out;      // (a size was given: in / out)
-    return a;
-}
 
 __device__ __forceinline__ void block_sum(float& a, float* red) {
     const int t = threadIdx.x;
@@ -73,12 +30,11 @@ __global__ __launch_bounds__(256) void softce_pass1_kernel(const float* __restri
     constexpr int KR = KT > 0 ? KT : KMAX;
     const int K2 = 2 * K;
     float* dbuf = sh;                                   // [npx_max][K2]
-    float* lam = dbuf + (long)npx_max * K2;             // [npx_max]
-    int* x0s = reinterpret_cast<int*>(lam + npx_max);   // [npx_max]
-    float* red = reinterpret_cast<float*>(x0s + npx_max);   // [256]
+    float* red = dbuf + (long)npx_max * K2;             // [256]
     int* pstart = reinterpret_cast<int*>(red + 256);    // [JT+3] first pixel (relative to xa) whose x0 >= j0 - 1 + q
     float* srow = red + 256 + JT + 4;                   // [JT+2][K]   seg logits interpolated along y
     float* drow = srow + (JT + 2) * K;                  // [JT+2][K2]  discriminator logits interpolated along y
+    float* lam = drow + (JT + 2) * K2;                  // [npx_max]   last: every region before it starts at an even offset (8-byte LDS accesses)
     const int H = ay.n_out, h = ay.n_in, w = ax.n_in;
     const int jt = blockIdx.x, y = blockIdx.y, b = blockIdx.z;
     const int j0 = jt * JT, j1 = min(w, j0 + JT);
@@ -169,20 +125,7 @@ __global__ __launch_bounds__(256) void softce_pass1_kernel(const float* __restri
         if (x0 >= j0) loss += l;          // the tile that owns x0 accounts for the pixel's loss
     }
     __syncthreads();
-    if (tmp) {
-        const int nj = j1 - j0;
-        for (int item = threadIdx.x; item < nj * K2; item += 256) {
-            const int jj = item / K2, k = item - jj * K2;
-            const int j = j0 + jj;
-            float s = 0.f;
-            // pixels with x0 == j-1 contribute lam (as x1), then pixels with x0 == j contribute 1-lam (+ lam at the clamped right edge)
-            const int p0 = max(pstart[jj], 0), p1 = min(max(pstart[jj + 1], 0), npx), p2 = min(pstart[jj + 2], npx);
-            for (int px = p0; px < p1; ++px) s += (0.f + lam[px]) * dbuf[(long)px * K2 + k];
-            const bool edge = j == w - 1;
-            for (int px = p1; px < p2; ++px) s += ((1.f - lam[px]) + (edge ? lam[px] : 0.f)) * dbuf[(long)px * K2 + k];
-            tmp[(((long)b * H + y) * w + j) * K2 + k] = s;
-        }
-    }
+    if (tmp) tile_gather_x(dbuf, lam, pstart, tmp + ((long)b * H + y) * w * K2, K2, j0, j1, w, npx);
     block_sum(loss, red);
     if (threadIdx.x == 0) partial[((long)b * H + y) * gridDim.x + jt] = loss;
 }
@@ -413,14 +356,6 @@ __global__ void adam_dev_kernel(float* __restrict__ p, float* __restrict__ g, fl
     }
 }
 
-inline unsigned nblk(long n, int bs) { return (unsigned)((n + bs - 1) / bs); }
-
-inline int npx_bound(const Axis& ax) {
-    if (ax.scale <= 0.f) return ax.n_out;
-    const long n = (long)((float)(JT + 1) / ax.scale) + 4;
-    return (int)(n < ax.n_out ? n : ax.n_out);
-}
-
 }  // namespace
 
 extern "C" size_t mi_upsample_softce_workspace(int B, int h, int w, int K, int H, int W) {
@@ -442,8 +377,8 @@ extern "C" int mi_upsample_softce(const float* seg_low, float inv_temperature, f
     float* partial = (float*)workspace;
     const size_t poff = (((size_t)B * H * tiles * sizeof(float)) + 255) & ~(size_t)255;
     float* tmp = dd_low ? (float*)((char*)workspace + poff) : nullptr;
-    const int npx_max = npx_bound(ax);
-    const size_t lds = ((size_t)npx_max * K2 + (size_t)npx_max * 2 + 256 + (JT + 4) + (size_t)(JT + 2) * (K + K2)) * 4;
+    const int npx_max = pass1_npx_max(ax, JT);
+    const size_t lds = ((size_t)npx_max * K2 + (size_t)npx_max + 256 + (JT + 4) + (size_t)(JT + 2) * (K + K2)) * 4;
     MI_REQUIRE(lds <= 160 * 1024, "mi_upsample_softce: upsample factor too large for one LDS tile (%zu B)", lds);
     static std::atomic<uint64_t> lds_set[2];
     mi_allow_dynamic_lds((const void*)softce_pass1_kernel<19>, MI_LDS_MAX, lds_set[0]);

@@ -1,0 +1,369 @@
+// What the bilinear-upsample sources (upsample_ce.hip, upsample_infer.hip, fada.hip) share: the source-index arithmetic, the fixed-order reductions,
+// the per-pixel softmax core, the prologue / pixel / epilogue helpers of the two kernel skeletons of the fused upsample + loss heads (x-tile and row-walk), the LDS layout of the first,
+// and the launch planning.  Everything is file-local to the source that includes it (anonymous namespace): kernel names do not change.
+#pragma once
+#include "mi_common.h"
+#include <cmath>
+#include <type_traits>
+
+namespace {
+
+constexpr int KMAX = 32;            // classes held in registers
+constexpr int JT = 32;              // low-res columns of the largest x-tile; the launcher narrows it for large upsample factors (pick_jt)
+constexpr int GDL_XT = 256;         // output pixels of one row per workgroup in the row-walk kernels: one per thread and row
+
+struct Axis {              // source index exactly as ATen computes it in fp32: align_corners (off = 0): scale * dst; otherwise (off = 0.5):
+    float scale, off;      // max(scale * (dst + 0.5) - 0.5, 0)  (adding / subtracting 0.0f is exact: the align_corners bits are unchanged)
+    int n_in, n_out;
+    __device__ __forceinline__ float srcf(int dst) const {
+        const float f = scale * ((float)dst + off) - off;
+        return f < 0.f ? 0.f : f;
+    }
+    __device__ __forceinline__ void src(int dst, int& i0, int& i1, float& lam) const {
+        const float f = srcf(dst);
+        i0 = (int)f;
+        if (i0 > n_in - 1) i0 = n_in - 1;
+        i1 = (i0 < n_in - 1) ? i0 + 1 : i0;
+        lam = f - (float)i0;
+    }
+    // first dst index whose i0 >= c  (n_out if none)
+    __device__ __forceinline__ int first_with_i0_ge(int c) const {
+        if (c <= 0) return 0;
+        if (scale <= 0.f) return n_out;
+        if (c > n_in - 1) return n_out;
+        int d = (int)((float)c / scale) - 2;
+        if (d < 0) d = 0;
+        if (d > n_out) d = n_out;
+        while (d < n_out) {
+            int i0 = (int)srcf(d);
+            if (i0 > n_in - 1) i0 = n_in - 1;
+            if (i0 >= c) break;
+            ++d;
+        }
+        return d;
+    }
+};
+
+inline Axis make_axis(int n_in, int n_out, int align_corners = 1) {
+    Axis a;
+    a.n_in = n_in;
+    a.n_out = n_out;
+    a.off = align_corners ? 0.f : 0.5f;
+    a.scale = align_corners ? ((n_out > 1) ? (float)(n_in - 1) / (float)(n_out - 1) : 0.f) : (float)n_in / (float)n_out;      // (a size was given: in / out)
+    return a;
+}
+
+__device__ __forceinline__ float lerp2(float v00, float v01, float v10, float v11, float lx, float ly) {
+    return (1.f - ly) * ((1.f - lx) * v00 + lx * v01) + ly * ((1.f - lx) * v10 + lx * v11);
+}
+
+__device__ __forceinline__ void block_sum2(float& a, float& b, float* red) {
+    // fixed-order tree over 256 threads
+    const int t = threadIdx.x;
+    red[t] = a;
+    red[256 + t] = b;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if (t < w) {
+            red[t] += red[t + w];
+            red[256 + t] += red[256 + t + w];
+        }
+        __syncthreads();
+    }
+    a = red[0];
+    b = red[256];
+    __syncthreads();
+}
+
+__device__ __forceinline__ float wave_sum(float v) {          // xor butterfly: both partners add the same two values, every lane ends with the same bits
+    for (int m = 32; m > 0; m >>= 1) v += __shfl_xor(v, m);
+    return v;
+}
+__device__ __forceinline__ unsigned wave_sum(unsigned v) {
+    for (int m = 32; m > 0; m >>= 1) v += (unsigned)__shfl_xor((int)v, m);
+    return v;
+}
+__device__ __forceinline__ double wave_sum(double v) {
+    for (int m = 32; m > 0; m >>= 1) v += __shfl_xor(v, m);
+    return v;
+}
+
+// ------------------------------------------------------------------------------------------------ the per-pixel softmax core
+// KT > 0: the class count is a compile-time constant (19 for Cityscapes: exact-length register loops instead of 32 predicated iterations);
+// KT == 0: K is read from the arguments.  kreg<KT>: the register array length.
+template <int KT>
+constexpr int kreg = KT > 0 ? KT : KMAX;
+
+struct NoTerm {
+    __device__ __forceinline__ void operator()(int, float) const {}
+};
+
+// v[k] = exp(v[k] - mx) for k < K; returns their sum.  PICK: *picked = v[lab] - mx taken BEFORE the exponential (exp() of it underflows to 0 for a
+// confidently wrong pixel, |logit| gap > 87, and log(0) would make a loss inf).  term(k, v[k] - mx) sees every class, before the exponential too.
+// kr is the length of the register array v (kreg<KT>).  It arrives as an argument, and v as a pointer, on purpose: as `float (&v)[KR]` with the length
+// a template parameter, or with v declared in a function below the kernel, the generic instantiations of the kernels (32 predicated iterations) compiled
+// to five times the instructions and spilled (measured; profiles/upsample_skeleton_resources.txt).  So v and the loops after the core stay in the kernel.
+template <bool PICK = false, class Term = NoTerm>
+__device__ __forceinline__ float exp_terms(float* v, int kr, float mx, int K, long lab = 0, float* picked = nullptr, Term term = Term()) {
+    float se = 0.f;
+    if constexpr (PICK) *picked = 0.f;
+#pragma unroll
+    for (int k = 0; k < kr; ++k) {
+        if (k < K) {
+            if constexpr (PICK) {
+                if (k == lab) *picked = v[k] - mx;
+            }
+            term(k, v[k] - mx);
+            v[k] = __expf(v[k] - mx);
+            se += v[k];
+        }
+    }
+    return se;
+}
+
+// The K logits of one output pixel interpolated from two staged columns (c0, c1: already interpolated along y), then exp_terms on them.
+template <bool PICK = false, class Term = NoTerm>
+__device__ __forceinline__ float softmax_terms(const float* c0, const float* c1, float lx, int K, float* v, int kr, long lab = 0, float* picked = nullptr,
+                                               Term term = Term()) {
+    float mx = -3.0e38f;
+#pragma unroll
+    for (int k = 0; k < kr; ++k) {
+        if (k < K) {
+            v[k] = (1.f - lx) * c0[k] + lx * c1[k];
+            mx = fmaxf(mx, v[k]);
+        }
+    }
+    return exp_terms<PICK>(v, kr, mx, K, lab, picked, term);
+}
+
+// ------------------------------------------------------------------------------------------------ the x-tile skeleton
+// One workgroup per (b, y, jt_cols low-res columns): it owns the low-res columns [j0, j1) of output row y of image b; its pixels are those with x0 in
+// [j0-1, j1-1], starting at xa.  Once per pixel the threads leave d[k] (the loss's derivative by the pixel's K interpolated logits) in LDS; then (j, k)
+// items gather the pixels of their column support in ascending x:  tmp[b][y][j][k] = sum_x wx(x,j) d[x][k].
+
+// The dynamic LDS of an x-tile kernel, in floats.  Each kernel has one function that returns its TileLds; the kernel takes its pointers from it
+// (xtile_begin) and the launcher its byte count.
+struct TileLds {
+    int lam, red, pstart, vrow, extra, floats;
+    __host__ __device__ TileLds(int npx_max, int K, bool with_red, int n_extra) {
+        lam = npx_max * K;                          // from 0: dbuf [npx_max][K]; here: [npx_max] lambda_x
+        red = lam + npx_max;                        // [512] for block_sum2, where the kernel reduces
+        pstart = red + (with_red ? 512 : 0);        // [JT+3] first pixel (relative to xa) whose x0 >= j0 - 1 + q
+        vrow = pstart + JT + 4;                     // [JT+2][K] low-res row already interpolated along y
+        extra = vrow + (JT + 2) * K;                // [n_extra] the kernel's own
+        floats = extra + n_extra;
+    }
+    size_t bytes() const { return (size_t)floats * sizeof(float); }
+};
+
+// tile_stage: pstart[q] = first pixel (relative to xa) whose x0 >= j0 - 1 + q, and the touched source columns (from cbase) interpolated along y into vrow.
+__device__ __forceinline__ void tile_stage(const float* __restrict__ low, int K, const Axis& ay, const Axis& ax, int b, int y, int j0, int j1, int xa,
+                                           int* pstart, float* vrow, int& cbase) {
+    const int h = ay.n_in, w = ax.n_in;
+    int y0, y1;
+    float ly;
+    ay.src(y, y0, y1, ly);
+    const float* row0 = low + ((long)b * h + y0) * w * K;
+    const float* row1 = low + ((long)b * h + y1) * w * K;
+    cbase = max(j0 - 1, 0);
+    const int ncol = min(j1, w - 1) - cbase + 1;          // source columns this tile touches
+    if (threadIdx.x < j1 - j0 + 2) pstart[threadIdx.x] = ax.first_with_i0_ge(j0 - 1 + (int)threadIdx.x) - xa;
+    for (int e = threadIdx.x; e < ncol * K; e += 256) {
+        const long o = (long)cbase * K + e;
+        vrow[e] = (1.f - ly) * row0[o] + ly * row1[o];
+    }
+}
+
+// tile_gather_x: trow[j][k] = sum_x wx(x,j) dbuf[x][k] for the tile's columns, (j,k) items over the threads, each in ascending x (trow: row (b, y) of tmp).
+__device__ __forceinline__ void tile_gather_x(const float* dbuf, const float* lam, const int* pstart, float* __restrict__ trow, int K, int j0, int j1,
+                                              int w, int npx) {
+    const int nj = j1 - j0;
+    for (int item = threadIdx.x; item < nj * K; item += 256) {
+        const int jj = item / K, k = item - jj * K;
+        const int j = j0 + jj;
+        float s = 0.f;
+        // pixels with x0 == j-1 contribute lam to j (as x1), then pixels with x0 == j contribute 1-lam (and lam too when x1 is
+        // clamped onto j at the right edge); same weights and the same ascending-x order as a per-pixel test of x0 / x1
+        const int p0 = max(pstart[jj], 0), p1 = min(max(pstart[jj + 1], 0), npx), p2 = min(pstart[jj + 2], npx);
+        for (int px = p0; px < p1; ++px) s += (0.f + lam[px]) * dbuf[(long)px * K + k];
+        const bool edge = j == w - 1;
+        for (int px = p1; px < p2; ++px) s += ((1.f - lam[px]) + (edge ? lam[px] : 0.f)) * dbuf[(long)px * K + k];
+        trow[(long)j * K + k] = s;
+    }
+}
+
+// What an x-tile kernel knows about its tile after xtile_begin, and about one pixel of it after xtile_pixel.
+struct XTile {
+    float *dbuf, *lam, *red, *vrow, *extra;      // the LDS regions of TileLds
+    int* pstart;
+    int j0, j1, xa, npx, cbase;
+    long row;                                    // (b * H + y): the output row, for labels (row * W + x), tmp (row * w * K) and partial (row * tiles + tile)
+};
+struct XPixel {
+    float* d;                  // [K] the pixel's slot in dbuf
+    const float *c0, *c1;      // its two staged source columns
+    float lx;
+    long pix;                  // index into a [B][H][W] plane
+    bool own;                  // this tile accounts for the pixel (x0 >= j0; a pixel with x0 == j0-1 belongs to the previous tile)
+};
+
+// The prologue: carves the LDS, decodes the grid and stages (tile_stage).  The caller's __syncthreads() publishes the staging.
+__device__ __forceinline__ XTile xtile_begin(const TileLds& L, const float* __restrict__ low, int K, const Axis& ay, const Axis& ax, int npx_max,
+                                             int jt_cols) {
+    extern __shared__ __attribute__((aligned(16))) float sh[];
+    XTile t;
+    t.dbuf = sh;
+    t.lam = sh + L.lam;
+    t.red = sh + L.red;
+    t.pstart = reinterpret_cast<int*>(sh + L.pstart);
+    t.vrow = sh + L.vrow;
+    t.extra = sh + L.extra;
+    const int w = ax.n_in, y = blockIdx.y, b = blockIdx.z;
+    t.j0 = blockIdx.x * jt_cols;
+    t.j1 = min(w, t.j0 + jt_cols);
+    t.xa = ax.first_with_i0_ge(t.j0 - 1);                                   // pixels with x0 in [j0-1, j1-1]
+    t.npx = min(ax.first_with_i0_ge(t.j1) - t.xa, npx_max);
+    t.row = (long)b * ay.n_out + y;
+    tile_stage(low, K, ay, ax, b, y, t.j0, t.j1, t.xa, t.pstart, t.vrow, t.cbase);
+    return t;
+}
+
+// Pixel px of the tile (the loop is `for (int px = threadIdx.x; px < t.npx; px += 256)`): stores its lambda_x for the gather.
+__device__ __forceinline__ XPixel xtile_pixel(const XTile& t, const Axis& ax, int K, int px) {
+    const int x = t.xa + px;
+    int x0, x1;
+    XPixel q;
+    ax.src(x, x0, x1, q.lx);
+    t.lam[px] = q.lx;
+    q.d = t.dbuf + (long)px * K;
+    q.c0 = t.vrow + (x0 - t.cbase) * K;
+    q.c1 = t.vrow + (x1 - t.cbase) * K;
+    q.pix = t.row * ax.n_out + x;
+    q.own = x0 >= t.j0;
+    return q;
+}
+
+// The epilogue, after the __syncthreads() that publishes dbuf: the gather into row (b, y) of tmp.
+__device__ __forceinline__ void xtile_gather(const XTile& t, float* __restrict__ tmp, int K, int w) {
+    tile_gather_x(t.dbuf, t.lam, t.pstart, tmp + t.row * w * K, K, t.j0, t.j1, w, t.npx);
+}
+
+// ------------------------------------------------------------------------------------------------ the row-walk skeleton
+// One workgroup per (b, `rows` output rows, GDL_XT output columns); a thread keeps one column and walks the rows, what it accumulates in registers:
+//   const RowWalk r = rowwalk_begin(ay, ax, rows, ncol_max);
+//   for (int y = r.ya; y < r.yb; ++y) {
+//       rowwalk_stage(r, low, vrow, K, ay, ax.n_in, y);      // the row's touched source columns interpolated along y into vrow ([ncol_max][K]), and a barrier
+//       if (r.live) { ... the pixel r.pix(ay, ax, y) from vrow + r.c0 * K and vrow + r.c1 * K with r.lx ... }
+//       __syncthreads();                                     // the next row overwrites vrow
+//   }
+// The epilogues (how a workgroup reduces what its threads hold) differ and stay with the kernels.
+struct RowWalk {
+    int b, ya, yb, x, cbase, ncol, c0, c1;      // c0, c1: the thread's two source columns relative to cbase
+    float lx;
+    bool live;                                  // the thread has a column (x < xb)
+    __device__ __forceinline__ long pix(const Axis& ay, const Axis& ax, int y) const { return ((long)b * ay.n_out + y) * ax.n_out + x; }
+};
+
+__device__ __forceinline__ RowWalk rowwalk_begin(const Axis& ay, const Axis& ax, int rows, int ncol_max) {
+    RowWalk r;
+    const int H = ay.n_out, W = ax.n_out;
+    r.b = blockIdx.z;
+    const int xa = blockIdx.x * GDL_XT, xb = min(W, xa + GDL_XT);
+    r.ya = blockIdx.y * rows;
+    r.yb = min(H, r.ya + rows);
+    int clast, unused;
+    r.lx = 0.f;
+    ax.src(xa, r.cbase, unused, r.lx);
+    ax.src(xb - 1, unused, clast, r.lx);
+    r.ncol = min(clast - r.cbase + 1, ncol_max);      // upsampling: x0 advances by at most one per pixel, so GDL_XT pixels touch at most GDL_XT + 1 columns
+    r.x = xa + threadIdx.x;
+    r.live = r.x < xb;
+    int x0 = r.cbase, x1 = r.cbase;
+    if (r.live) ax.src(r.x, x0, x1, r.lx);
+    r.c0 = x0 - r.cbase;
+    r.c1 = x1 - r.cbase;
+    return r;
+}
+
+__device__ __forceinline__ void rowwalk_stage(const RowWalk& r, const float* __restrict__ low, float* vrow, int K, const Axis& ay, int w, int y) {
+    int y0, y1;
+    float ly;
+    ay.src(y, y0, y1, ly);
+    const float* row0 = low + (((long)r.b * ay.n_in + y0) * w + r.cbase) * K;
+    const float* row1 = low + (((long)r.b * ay.n_in + y1) * w + r.cbase) * K;
+    for (int e = threadIdx.x; e < r.ncol * K; e += 256) vrow[e] = (1.f - ly) * row0[e] + ly * row1[e];
+    __syncthreads();
+}
+
+// pass 2: dlow[b][i][j][k] = grad_scale / n_valid * sum_y wy(y,i) tmp[b][y][j][k]   (ascending y)
+// ZERO_STAYS: a sum that is exactly 0 stays 0 whatever the divisor (torch leaves the gradient of ignored pixels at 0 when no pixel counts, S = 0;
+// 0 * (grad_scale / 0) would be nan).  Any other sum is scaled as before.
+template <bool ZERO_STAYS>
+__device__ __forceinline__ void pass2_body(const float* __restrict__ tmp, const float* __restrict__ loss_out, float* __restrict__ dlow, int B, int K,
+                                           const Axis& ay, int w, float grad_scale) {
+    const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    const int H = ay.n_out, h = ay.n_in;
+    const long per_row = (long)w * K;
+    if (idx >= (long)B * h * per_row) return;
+    const long jk = idx % per_row;
+    const int i = (int)((idx / per_row) % h), b = (int)(idx / (per_row * h));
+    const int ya = ay.first_with_i0_ge(i - 1), yb = ay.first_with_i0_ge(i + 1);
+    float s = 0.f;
+    for (int y = ya; y < yb; ++y) {
+        int y0, y1;
+        float ly;
+        ay.src(y, y0, y1, ly);
+        const float wy = (y0 == i ? 1.f - ly : 0.f) + (y1 == i ? ly : 0.f);
+        s += wy * tmp[((long)b * H + y) * per_row + jk];
+    }
+    const float r = s * (loss_out ? grad_scale / loss_out[1] : grad_scale);      // (no loss_out: the Dice gradient, whose coefficients carry its normalisation)
+    dlow[idx] = (ZERO_STAYS && s == 0.f) ? 0.f : r;
+}
+
+// ------------------------------------------------------------------------------------------------ launch planning
+inline unsigned nblk(long n, int bs) { return (unsigned)((n + bs - 1) / bs); }
+inline size_t up256(size_t n) { return (n + 255) & ~(size_t)255; }
+
+inline int pass1_npx_max(const Axis& ax, int jt_cols) {
+    // upper bound of pixels whose x0 falls in jt_cols+1 consecutive source columns
+    if (ax.scale <= 0.f) return ax.n_out;
+    const long n = (long)((float)(jt_cols + 1) / ax.scale) + 4;
+    return (int)(n < ax.n_out ? n : ax.n_out);
+}
+
+// Low-res columns per workgroup: 32 up to an 8x upsample, fewer above (a tile of 32 columns at 32x is 1 056 pixels x 19 classes = 80 KB of LDS: one
+// workgroup per CU - the 1/32 head of GALD took 788 us against 204 us for the 1/4 head with the same 5.5 M pixels); about 256 pixels per tile.
+inline int pick_jt(int w, int W) {
+    const int f = w > 0 ? (W + w - 1) / w : 1;
+    int jt = JT;
+    while (jt > 4 && jt * f > 256) jt >>= 1;
+    return jt;
+}
+
+// The row-walk grid: GDL_XT-column tiles, and as many rows per workgroup as keep the launch near 1024 workgroups (4 per CU, what the Dice reduction's
+// registers let a CU hold: one round; and the partial rows a one-workgroup finalize has to add stay a few hundred KB at 6 x 720 x 1280).
+struct GdlPlan {
+    int tiles_x, rows, row_groups;
+    size_t nwg;
+};
+inline GdlPlan gdl_plan(int B, int H, int W) {
+    GdlPlan p;
+    p.tiles_x = (W + GDL_XT - 1) / GDL_XT;
+    const long units = (long)B * H * p.tiles_x;
+    long rows = (units + 1023) / 1024;
+    p.rows = (int)(rows < 1 ? 1 : (rows > H ? H : rows));
+    p.row_groups = (H + p.rows - 1) / p.rows;
+    p.nwg = (size_t)B * p.row_groups * p.tiles_x;
+    return p;
+}
+
+// f(std::integral_constant<int, KT>) with KT = 19 when K is 19, else 0 (K read at run time): the two instantiations every K-templated kernel has.
+template <class F>
+inline void with_kt(int K, F&& f) {
+    if (K == 19)
+        f(std::integral_constant<int, 19>{});
+    else
+        f(std::integral_constant<int, 0>{});
+}
+
+}  // namespace

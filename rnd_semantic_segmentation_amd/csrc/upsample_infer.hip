@@ -1,0 +1,328 @@
+// The inference tails on bilinearly upsampled logits: softmax probabilities (one source, or multi-scale and flip-averaged), the evaluation tail
+// that reduces them to predictions, pseudo-labels and score counts, and the align_corners image resize.
+//   softmax over classes for inference                        reference core/utils/utility.py:186
+// All arithmetic fp32.  They share only the source-index arithmetic (Axis) and the exponential loop with the training heads of upsample_ce.hip.
+#include "upsample_common.h"
+
+namespace {
+
+// ------------------------------------------------------------------------------------------------ inference tails
+// The per-source arithmetic of both inference tails: the bilinear (align_corners) sample of the NHWC map `low` (one image) at output pixel
+// (y, x), then v[k] = exp(value - max); returns 1 / sum (the probabilities are v[k] * result) and the first arg max.
+// The interpolation is written out operation by operation - row0 = fma(lx, v01, (1-lx) v00), row1 = fma(1-lx, v10, lx v11),
+// value = (1-ly) row0 + ly row1 with both products rounded - because that is the order mi_upsample_softmax has always computed (what the
+// compiler's contraction made of lerp2 there) and two kernels have to agree on it bit for bit; contraction is off so that it stays put.
+template <int KR>
+__device__ __forceinline__ float interp_softmax_terms(const float* __restrict__ low, int K, const Axis& ay, const Axis& ax, int y, int x,
+                                                      float (&v)[KR], int& arg) {
+#pragma clang fp contract(off)
+    const int w = ax.n_in;
+    int y0, y1, x0, x1;
+    float ly, lx;
+    ay.src(y, y0, y1, ly);
+    ax.src(x, x0, x1, lx);
+    const float* p00 = low + ((long)y0 * w + x0) * K;
+    const float* p01 = low + ((long)y0 * w + x1) * K;
+    const float* p10 = low + ((long)y1 * w + x0) * K;
+    const float* p11 = low + ((long)y1 * w + x1) * K;
+    const float mlx = 1.f - lx, mly = 1.f - ly;
+    float mx = -3.0e38f;
+    arg = 0;
+#pragma unroll
+    for (int k = 0; k < KR; ++k) {
+        if (k < K) {
+            const float row0 = __builtin_fmaf(lx, p01[k], mlx * p00[k]);
+            const float row1 = __builtin_fmaf(mlx, p10[k], lx * p11[k]);
+            v[k] = mly * row0 + ly * row1;
+            if (v[k] > mx) {
+                mx = v[k];
+                arg = k;
+            }
+        }
+    }
+    return 1.f / exp_terms(v, KR, mx, K);
+}
+
+// probs NCHW + optional argmax
+__global__ void upsample_softmax_kernel(const float* __restrict__ low, float* __restrict__ probs, uint8_t* __restrict__ pred, int B, int K,
+                                        Axis ay, Axis ax) {
+    const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    const int H = ay.n_out, W = ax.n_out, h = ay.n_in, w = ax.n_in;
+    if (idx >= (long)B * H * W) return;
+    const int x = (int)(idx % W), y = (int)((idx / W) % H), b = (int)(idx / ((long)W * H));
+    float v[KMAX];
+    int arg;
+    const float rse = interp_softmax_terms<KMAX>(low + (long)b * h * w * K, K, ay, ax, y, x, v, arg);
+    float* o = probs + ((long)b * K * H + y) * W + x;
+#pragma unroll
+    for (int k = 0; k < KMAX; ++k) {
+        if (k < K) o[(long)k * H * W] = v[k] * rse;
+    }
+    if (pred) pred[idx] = (uint8_t)arg;
+}
+
+// Multi-scale, flip-averaged tail (reference core/utils/utility.py:193-209): probs = ((p_0 + ... + p_{n-1}) / div_a) / div_b with
+// p_i = softmax(bilinear(low_i -> H x W)), read at column W-1-x for a mirrored source.  The reference adds materialised fp32 tensors, so every
+// p_i[k] is a rounded product before it is added (no fma), the sum runs in source order and the divisions are true divisions.
+// One thread owns P consecutive pixels of a row (2 when W is even, else 1) and keeps their K sums in registers; each class plane is written once.
+struct ProbSrc {
+    const float* low;
+    Axis ay, ax;
+    int mirror;
+};
+constexpr int MAX_PROB_SRC = 16;
+struct ProbSrcs {
+    ProbSrc s[MAX_PROB_SRC];      // by value in the kernel arguments: no device table
+};
+
+__device__ __forceinline__ float add_rounded_product(float acc, float a, float b) {
+#pragma clang fp contract(off)
+    const float p = a * b;
+    return acc + p;
+}
+
+// The per-pixel arithmetic of the multi-scale tails, shared by the probability kernel and the predict-and-score kernel so that the two cannot
+// drift apart: acc[p][k] = ((p_0 + ... + p_{n-1}) / div_a) / div_b for the P pixels (y, xb .. xb+P-1), summed in source order from rounded
+// products, with true divisions (the second one skipped when div_b == 1).
+template <int KR, int P>
+__device__ __forceinline__ void multi_probs(const ProbSrcs& srcs, int n, int K, int W, int y, int xb, float div_a, float div_b, float (&acc)[P][KR]) {
+#pragma unroll
+    for (int p = 0; p < P; ++p)
+#pragma unroll
+        for (int k = 0; k < KR; ++k) acc[p][k] = 0.f;      // 0 + p_0 == p_0 exactly (p_0 >= +0)
+    for (int i = 0; i < n; ++i) {
+        const ProbSrc& s = srcs.s[i];
+#pragma unroll
+        for (int p = 0; p < P; ++p) {
+            const int x = xb + p;
+            float v[KR];
+            int arg;
+            const float rse = interp_softmax_terms<KR>(s.low, K, s.ay, s.ax, y, s.mirror ? W - 1 - x : x, v, arg);
+#pragma unroll
+            for (int k = 0; k < KR; ++k) {
+                if (k < K) acc[p][k] = add_rounded_product(acc[p][k], v[k], rse);
+            }
+            __builtin_amdgcn_sched_barrier(0);      // one pixel's loads at a time: interleaving the P pixels costs P times the registers
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < KR; ++k) {
+        if (k < K) {
+#pragma unroll
+            for (int p = 0; p < P; ++p) {
+                acc[p][k] = acc[p][k] / div_a;
+                if (div_b != 1.f) acc[p][k] = acc[p][k] / div_b;
+            }
+        }
+    }
+}
+
+// Waves per SIMD the register budget is held to.  A pixel has 4 x K corner loads in flight besides the P x K sums: one pixel per lane runs at
+// 4 waves, two pixels per lane (8-byte stores, 512 contiguous bytes per wave and class plane) at 2.  Four pixels per lane spill.  No variant here does.
+template <int KT, int P>
+__global__ __launch_bounds__(256, P == 1 ? 4 : 2) void upsample_softmax_multi_kernel(ProbSrcs srcs, int n, float* __restrict__ probs, int Krt, int H, int W,
+                                                                     float div_a, float div_b) {
+    const int K = KT > 0 ? KT : Krt;
+    constexpr int KR = KT > 0 ? KT : KMAX;
+    static_assert(P == 1 || P == 2, "one or two pixels per lane");
+    const int WP = W / P;                                  // P == 2 only when W is even
+    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= (long)H * WP) return;
+    const int xb = (int)(idx % WP) * P, y = (int)(idx / WP);
+    float acc[P][KR];
+    multi_probs<KR, P>(srcs, n, K, W, y, xb, div_a, div_b, acc);
+    float* o = probs + (long)y * W + xb;
+#pragma unroll
+    for (int k = 0; k < KR; ++k) {
+        if (k < K) {
+            float* ok = o + (long)k * H * W;
+            if constexpr (P == 2)
+                *reinterpret_cast<float2*>(ok) = make_float2(acc[0][k], acc[1][k]);        // W even and probs 8-byte aligned (the launcher checks)
+            else
+                ok[0] = acc[0][k];
+        }
+    }
+}
+
+// Evaluation tail without the probability map: the same K values per pixel as upsample_softmax_multi_kernel (multi_probs), reduced in registers to
+// pred = the LOWEST class index among their maxima (torch.max(dim) / numpy.argmax), pseudo = max >= threshold ? pred : 255, and - with labels -
+// the integers host/metrics.py derives from pred.  One LDS add per pixel: cell gt * K + pd where the label gt lies in [0, K) (confusion_matrix;
+// 255 and ignore_index lie outside [0, K)), cell K * K + pd where it does not and is not ignore_index.  From these, per class k:
+//   area_intersection = cmt[k][k], area_target = row sum k, area_output = column sum k + the extra cell k.
+// A workgroup sees at most 512 pixels, so its 32-bit LDS counters cannot overflow; it flushes one 64-bit global add per non-zero cell.  Integer sums
+// do not depend on arrival order: the counts are bit-reproducible.  counts: [K*K] cmt, [K] intersection, [K] output, [K] target; added to.
+template <int KT, int P>
+__global__ __launch_bounds__(256, P == 1 ? 4 : 2) void upsample_predict_score_kernel(ProbSrcs srcs, int n, int Krt, int H, int W, float div_a, float div_b,
+                                                                     const long long* __restrict__ labels, int ignore_index, float threshold,
+                                                                     uint8_t* __restrict__ pred, uint8_t* __restrict__ pseudo,
+                                                                     unsigned long long* __restrict__ counts) {
+    const int K = KT > 0 ? KT : Krt;
+    constexpr int KR = KT > 0 ? KT : KMAX;
+    static_assert(P == 1 || P == 2, "one or two pixels per lane");
+    __shared__ unsigned tab[KR * KR + KR];
+    const int tid = threadIdx.x;
+    if (counts) {                                          // uniform over the grid
+        for (int c = tid; c < K * K + K; c += 256) tab[c] = 0u;
+        __syncthreads();
+    }
+    const int WP = W / P;                                  // P == 2 only when W is even
+    const long idx = (long)blockIdx.x * 256 + tid;
+    if (idx < (long)H * WP) {
+        const int xb = (int)(idx % WP) * P, y = (int)(idx / WP);
+        float acc[P][KR];
+        multi_probs<KR, P>(srcs, n, K, W, y, xb, div_a, div_b, acc);
+        uint8_t pd[P], ps[P];
+#pragma unroll
+        for (int p = 0; p < P; ++p) {
+            float best = acc[p][0];
+            int arg = 0;
+#pragma unroll
+            for (int k = 1; k < KR; ++k) {
+                if (k < K && acc[p][k] > best) {           // strict: the first of equal maxima stays
+                    best = acc[p][k];
+                    arg = k;
+                }
+            }
+            pd[p] = (uint8_t)arg;
+            ps[p] = best >= threshold ? (uint8_t)arg : (uint8_t)255;
+        }
+        const long o = (long)y * W + xb;
+        if constexpr (P == 2) {                            // W even: o even; pred / pseudo 2-byte, labels 16-byte aligned (the launcher checks)
+            *reinterpret_cast<uchar2*>(pred + o) = make_uchar2(pd[0], pd[1]);
+            if (pseudo) *reinterpret_cast<uchar2*>(pseudo + o) = make_uchar2(ps[0], ps[1]);
+        } else {
+            pred[o] = pd[0];
+            if (pseudo) pseudo[o] = ps[0];
+        }
+        if (counts) {
+            long long gt[P];
+            if constexpr (P == 2) {
+                const longlong2 g = *reinterpret_cast<const longlong2*>(labels + o);
+                gt[0] = g.x;
+                gt[1] = g.y;
+            } else {
+                gt[0] = labels[o];
+            }
+#pragma unroll
+            for (int p = 0; p < P; ++p) {
+                if ((unsigned long long)gt[p] < (unsigned long long)K)
+                    atomicAdd(&tab[(int)gt[p] * K + pd[p]], 1u);
+                else if (gt[p] != (long long)ignore_index)
+                    atomicAdd(&tab[K * K + pd[p]], 1u);
+            }
+        }
+    }
+    if (counts) {
+        __syncthreads();
+        for (int c = tid; c < K * K; c += 256) {
+            const unsigned v = tab[c];
+            if (v) atomicAdd(&counts[c], (unsigned long long)v);
+        }
+        if (tid < K) {
+            unsigned row = 0u, col = 0u;
+            for (int j = 0; j < K; ++j) {
+                row += tab[tid * K + j];
+                col += tab[j * K + tid];
+            }
+            const unsigned diag = tab[tid * K + tid], out = col + tab[K * K + tid];
+            if (diag) atomicAdd(&counts[K * K + tid], (unsigned long long)diag);
+            if (out) atomicAdd(&counts[K * K + K + tid], (unsigned long long)out);
+            if (row) atomicAdd(&counts[K * K + 2 * K + tid], (unsigned long long)row);
+        }
+    }
+}
+
+// F.interpolate(x, (Ho, Wo), mode='bilinear', align_corners=True) on NCHW fp32 images; with_mirror: image b's horizontal mirror
+// (torch.flip(resized, [3])) is written as image B + b from the same registers, so the two halves are bit-equal mirrors.
+__global__ void image_resize_ac_kernel(const float* __restrict__ x, float* __restrict__ out, int B, int C, Axis ay, Axis ax, int with_mirror) {
+    const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    const int Ho = ay.n_out, Wo = ax.n_out, H = ay.n_in, W = ax.n_in;
+    if (idx >= (long)B * C * Ho * Wo) return;
+    const int xo = (int)(idx % Wo), yo = (int)((idx / Wo) % Ho);
+    const long bc = idx / ((long)Wo * Ho);
+    int y0, y1, x0, x1;
+    float ly, lx;
+    ay.src(yo, y0, y1, ly);
+    ax.src(xo, x0, x1, lx);
+    const float* p = x + bc * H * W;
+    const float v00 = p[(long)y0 * W + x0];
+    // on a grid point (every pixel when the size does not change) the value is the input's, bit for bit (-0 and non-finite neighbours included)
+    const float val = (lx == 0.f && ly == 0.f) ? v00 : lerp2(v00, p[(long)y0 * W + x1], p[(long)y1 * W + x0], p[(long)y1 * W + x1], lx, ly);
+    out[idx] = val;
+    if (with_mirror) out[((bc + (long)B * C) * Ho + yo) * Wo + (Wo - 1 - xo)] = val;
+}
+
+}  // namespace
+
+extern "C" int mi_upsample_softmax(const float* low, float* probs, uint8_t* pred, int B, int h, int w, int K, int H, int W, void* stream) {
+    MI_REQUIRE(low && probs && B > 0 && h > 0 && w > 0 && H > 0 && W > 0 && K > 0 && K <= KMAX, "mi_upsample_softmax: bad argument (K <= 32)");
+    hipLaunchKernelGGL(upsample_softmax_kernel, dim3(nblk((long)B * H * W, 256)), dim3(256), 0, (hipStream_t)stream, low, probs, pred, B, K,
+                       make_axis(h, H), make_axis(w, W));
+    MI_CHECK_LAUNCH("mi_upsample_softmax");
+    return MI_OK;
+}
+
+extern "C" int mi_upsample_softmax_multi(const MiProbSource* src, int n, float* probs, int K, int H, int W, float div_a, float div_b,
+                                         void* stream) {
+    MI_REQUIRE(src && probs, "mi_upsample_softmax_multi: null operand");
+    MI_REQUIRE(n >= 1 && n <= MAX_PROB_SRC, "mi_upsample_softmax_multi: 1 <= n <= 16 sources");
+    MI_REQUIRE(K > 0 && K <= KMAX && H > 0 && W > 0, "mi_upsample_softmax_multi: bad dimension (K <= 32)");
+    MI_REQUIRE(div_a != 0.f && div_b != 0.f, "mi_upsample_softmax_multi: zero divisor");
+    ProbSrcs srcs;
+    for (int i = 0; i < MAX_PROB_SRC; ++i) {
+        const MiProbSource& m = src[i < n ? i : 0];       // unused slots repeat source 0: never read, never uninitialised
+        MI_REQUIRE(m.low && m.h > 0 && m.w > 0, "mi_upsample_softmax_multi: bad source");
+        srcs.s[i] = ProbSrc{m.low, make_axis(m.h, H), make_axis(m.w, W), m.mirror != 0};
+    }
+    const bool wide = W % 2 == 0 && (reinterpret_cast<uintptr_t>(probs) & 7) == 0;
+    const unsigned nb = nblk((long)H * (wide ? W / 2 : W), 256);
+#define MI_LAUNCH_MULTI(KT, P) \
+    hipLaunchKernelGGL((upsample_softmax_multi_kernel<KT, P>), dim3(nb), dim3(256), 0, (hipStream_t)stream, srcs, n, probs, K, H, W, div_a, div_b)
+    if (K == 19) {
+        if (wide) MI_LAUNCH_MULTI(19, 2); else MI_LAUNCH_MULTI(19, 1);
+    } else {
+        if (wide) MI_LAUNCH_MULTI(0, 2); else MI_LAUNCH_MULTI(0, 1);
+    }
+#undef MI_LAUNCH_MULTI
+    MI_CHECK_LAUNCH("mi_upsample_softmax_multi");
+    return MI_OK;
+}
+
+extern "C" int mi_upsample_predict_score(const MiProbSource* src, int n, int K, int H, int W, float div_a, float div_b, const int64_t* labels,
+                                         int ignore_index, float threshold, uint8_t* pred, uint8_t* pseudo, int64_t* counts, void* stream) {
+    MI_REQUIRE(src && pred, "mi_upsample_predict_score: null operand");
+    MI_REQUIRE(n >= 1 && n <= MAX_PROB_SRC, "mi_upsample_predict_score: 1 <= n <= 16 sources");
+    MI_REQUIRE(K > 0 && K <= KMAX && H > 0 && W > 0, "mi_upsample_predict_score: bad dimension (K <= 32)");
+    MI_REQUIRE(div_a != 0.f && div_b != 0.f, "mi_upsample_predict_score: zero divisor");
+    MI_REQUIRE((labels != nullptr) == (counts != nullptr), "mi_upsample_predict_score: labels and counts go together");
+    MI_REQUIRE(ignore_index < 0 || ignore_index >= K, "mi_upsample_predict_score: ignore_index inside [0, K)");
+    MI_REQUIRE(threshold >= 0.f && threshold <= 1.f, "mi_upsample_predict_score: threshold outside [0, 1]");
+    ProbSrcs srcs;
+    for (int i = 0; i < MAX_PROB_SRC; ++i) {
+        const MiProbSource& m = src[i < n ? i : 0];       // unused slots repeat source 0: never read, never uninitialised
+        MI_REQUIRE(m.low && m.h > 0 && m.w > 0, "mi_upsample_predict_score: bad source");
+        srcs.s[i] = ProbSrc{m.low, make_axis(m.h, H), make_axis(m.w, W), m.mirror != 0};
+    }
+    const bool wide = W % 2 == 0 && (reinterpret_cast<uintptr_t>(pred) & 1) == 0 && (reinterpret_cast<uintptr_t>(pseudo) & 1) == 0 &&
+                      (reinterpret_cast<uintptr_t>(labels) & 15) == 0;
+    const unsigned nb = nblk((long)H * (wide ? W / 2 : W), 256);
+#define MI_LAUNCH_SCORE(KT, P)                                                                                                                 \
+    hipLaunchKernelGGL((upsample_predict_score_kernel<KT, P>), dim3(nb), dim3(256), 0, (hipStream_t)stream, srcs, n, K, H, W, div_a, div_b, \
+                       reinterpret_cast<const long long*>(labels), ignore_index, threshold, pred, pseudo, reinterpret_cast<unsigned long long*>(counts))
+    if (K == 19) {
+        if (wide) MI_LAUNCH_SCORE(19, 2); else MI_LAUNCH_SCORE(19, 1);
+    } else {
+        if (wide) MI_LAUNCH_SCORE(0, 2); else MI_LAUNCH_SCORE(0, 1);
+    }
+#undef MI_LAUNCH_SCORE
+    MI_CHECK_LAUNCH("mi_upsample_predict_score");
+    return MI_OK;
+}
+
+extern "C" int mi_image_resize_ac(const float* x, float* out, int B, int C, int H, int W, int Ho, int Wo, int with_mirror, void* stream) {
+    MI_REQUIRE(x && out && B > 0 && C > 0 && H > 0 && W > 0 && Ho > 0 && Wo > 0, "mi_image_resize_ac: bad argument");
+    hipLaunchKernelGGL(image_resize_ac_kernel, dim3(nblk((long)B * C * Ho * Wo, 256)), dim3(256), 0, (hipStream_t)stream, x, out, B, C,
+                       make_axis(H, Ho), make_axis(W, Wo), with_mirror != 0);
+    MI_CHECK_LAUNCH("mi_image_resize_ac");
+    return MI_OK;
+}

@@ -1,4 +1,4 @@
-"""GPU side of multi-scale, flip-averaged evaluation: mi_image_resize_ac, mi_upsample_softmax_multi (csrc/upsample_ce.hip) and
+"""GPU side of multi-scale, flip-averaged evaluation: mi_image_resize_ac, mi_upsample_softmax_multi (csrc/upsample_infer.hip) and
 multi_scale_inference / ASPPTester on the engine against the reference's own output (tests/golden/g14_*, written by
 tools/make_multiscale_golden.py).  Parity is claimed in fp32 precision; the mask / metric rule is tests/_multiscale.py's."""
 import logging

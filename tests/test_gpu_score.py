@@ -1,4 +1,4 @@
-"""GPU side of the fused evaluation tail: mi_upsample_predict_score (csrc/upsample_ce.hip) against the probability kernel it shares its arithmetic
+"""GPU side of the fused evaluation tail: mi_upsample_predict_score (csrc/upsample_infer.hip) against the probability kernel it shares its arithmetic
 with (zero differences allowed), its counts against host/metrics.py on the same mask, the reference's own masks and metrics (g14 / g6 fixtures, the
 rule of tests/_multiscale.py), ASPPTester with TEST.FUSED_SCORE True against False (same matrix, lines, JSON and PNG bytes) and the two scripts
 of the self-distillation stage on a tiny Cityscapes tree."""
