@@ -18,7 +18,7 @@
 // the widest access the view's alignment allows, and (optionally) emits per-tile column sums / sums of squares of the ROUNDED
 // outputs - the first level of the BatchNorm batch statistics (nn.BatchNorm2d in train(), PraNet_Res2Net.py:13,17-19) - so
 // that no separate pass over the conv output is needed for them.
-#include "mi_common.h"
+#include "wgrad_common.h"
 #include <type_traits>
 #include <atomic>
 #include <vector>
@@ -900,6 +900,33 @@ __device__ __forceinline__ s16x4 tr_read(const char* lds_generic) {
     return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(lds_generic));
 }
 
+// The main loop of gwgrad_body and gwgrad3_body: a register double buffer over an LDS double buffer.  load(kt, r): this thread's rows of K step kt from global
+// memory into register set r; stash(r): register set r into LDS buffer r; compute(buf): the MFMAs of LDS buffer buf.  Step kt + 2 is loaded while step kt is
+// multiplied.  (steps rounded up to two: a step past the split's last one multiplies zero-page operands - cheaper than a second loop exit; sched_barrier:
+//  left alone hipcc sinks a step's loads below its MFMAs, right in front of the wait for them)
+template <class Load, class Stash, class Compute>
+__device__ __forceinline__ void gw_pipeline(int nk, Load&& load, Stash&& stash, Compute&& compute) {
+    if (nk <= 0) return;
+    load(0, 0);
+    load(1, 1);
+    stash(0);
+    __syncthreads();
+    for (int kt = 0; kt < nk; kt += 2) {
+        load(kt + 2, 0);
+        __builtin_amdgcn_sched_barrier(0);
+        compute(0);
+        __builtin_amdgcn_sched_barrier(0);
+        stash(1);
+        __syncthreads();
+        load(kt + 3, 1);
+        __builtin_amdgcn_sched_barrier(0);
+        compute(1);
+        __builtin_amdgcn_sched_barrier(0);
+        stash(0);
+        __syncthreads();
+    }
+}
+
 // One workgroup = one (K split, tap, o tile, i tile).  Both operands have the contraction index (pixel) as their memory row, so the
 // tiles are staged pixel-major and the MFMA fragments come from ds_read_b64_tr_b16 (hardware transpose), as in igemm_tn.hip.
 // (the body is shared by the one-conv launch and by the table-driven launch that runs the weight gradients of many convs at once: `bid` of `nblk`
@@ -908,21 +935,15 @@ constexpr int GW_SMEM = 2 * 2 * WKP * WRS;                                 // [b
 template <int YVEC, int XVEC>
 __device__ __forceinline__ void gwgrad_body(const GWgP& p, int bid, int nblk, char* smem) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int tiles = p.o_tiles * p.i_tiles;
-    int id = p.remap ? mi_xcd_remap(bid, nblk) : bid;      // the (tile, tap) workgroups of a pixel split share its dy / x rows: keep them on one XCD's L2
-    const int tile = id % tiles;
-    id /= tiles;
-    const int t = id % p.T, split = id / p.T;
-    const int ot = tile / p.i_tiles, itile = tile - ot * p.i_tiles;
-    const int o0 = ot * WTO, i0 = itile * WTI;
+    // the (tile, tap) workgroups of a pixel split share its dy / x rows: MI_GCONV_REMAP keeps them on one XCD's L2
+    const WgDecode wg = wg_decode<WTO, WTI, WKP, true>(bid, nblk, p.o_tiles, p.i_tiles, p.T, p.M, p.rows_per_split, p.remap);
+    const int tiles = p.o_tiles * p.i_tiles, tile = wg.tile, t = wg.mid, split = wg.split, o0 = wg.o0, i0 = wg.i0, m_begin = wg.m_begin, m_end = wg.m_end;
     const int ky = t / p.kw, kx = t - ky * p.kw;
-    const int m_begin = split * p.rows_per_split;
-    const int m_end = min(p.M, m_begin + p.rows_per_split);
-    const int nk = MI_DBG_BIT(p, 1) ? 0 : (m_end > m_begin ? (m_end - m_begin + WKP - 1) / WKP : 0);
+    const int nk = MI_DBG_BIT(p, 1) ? 0 : wg.nk;
     const int lpx = tid >> 3, lch = tid & 7;          // loader: pixel rows lpx and lpx + 32 of the step, 8-channel chunk
     const int hw = p.Ho * p.Wo;
 
-    bf16x8 ry0[2], rx0[2], ry1[2], rx1[2];
+    bf16x8 ry[2][2], rx[2][2];              // [register set][pixel row]
     // load() is called for kt = 0, 1, 2, ... in order: the (image, row, column) of this thread's two pixel rows advance by 64 pixels per call instead of
     // being divided out of the pixel index every time (four integer divisions per step and thread in the first version)
     int cb[2], coh[2], cow[2];
@@ -938,34 +959,26 @@ __device__ __forceinline__ void gwgrad_body(const GWgP& p, int bid, int nblk, ch
     //  with step_rows < Ho, so every coordinate wraps at most once per step)
     const int step_imgs = WKP / hw, step_rem = WKP - step_imgs * hw;
     const int step_rows = step_rem / p.Wo, step_cols = step_rem - step_rows * p.Wo;
-    auto load = [&](int kt, bf16x8 (&ry)[2], bf16x8 (&rx)[2]) {
+    auto load = [&](int kt, int r) {
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
             const int m = m_begin + kt * WKP + lpx + 32 * h;
             const bool ok = m < m_end;                 // (a step past the last one has every row >= m_end: zero-page reads)
-            ry[h] = gload8<YVEC>(p.dY + (long)(ok ? m : 0) * p.ldy, o0 + lch * 8, p.O, ok);
+            ry[r][h] = gload8<YVEC>(p.dY + (long)(ok ? m : 0) * p.ldy, o0 + lch * 8, p.O, ok);
             const int b = cb[h], oh = coh[h], ow = cow[h];
-            {
-                const int w1 = cow[h] + step_cols;
-                const bool cw = w1 >= p.Wo;
-                cow[h] = cw ? w1 - p.Wo : w1;
-                const int h1 = coh[h] + step_rows + (cw ? 1 : 0);
-                const bool ch = h1 >= p.Ho;
-                coh[h] = ch ? h1 - p.Ho : h1;
-                cb[h] += step_imgs + (ch ? 1 : 0);
-            }
+            cb[h] += step_imgs + px_advance(coh[h], cow[h], step_rows, step_cols, p.Ho, p.Wo);
             const int ih = oh * p.sh + ky * p.dh - p.ph, iw = ow * p.sw + kx * p.dw - p.pw;
             const bool xok = ok & ((unsigned)ih < (unsigned)p.Ha) & ((unsigned)iw < (unsigned)p.Wa);
             const long pix = ((long)b * p.Ha + min(max(ih, 0), p.Ha - 1)) * p.Wa + min(max(iw, 0), p.Wa - 1);        // always a real pixel; !xok lanes read the zero page
-            rx[h] = gload8<XVEC>(p.X + (ok ? pix : 0) * p.ldx, i0 + lch * 8, p.I, xok);
+            rx[r][h] = gload8<XVEC>(p.X + (ok ? pix : 0) * p.ldx, i0 + lch * 8, p.I, xok);
         }
     };
-    auto stash = [&](int buf, const bf16x8 (&ry)[2], const bf16x8 (&rx)[2]) {
+    auto stash = [&](int r) {
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
-            char* sy = smem + buf * (2 * WKP * WRS) + (lpx + 32 * h) * WRS + lch * 16;
-            *reinterpret_cast<bf16x8*>(sy) = ry[h];
-            *reinterpret_cast<bf16x8*>(sy + WKP * WRS) = rx[h];
+            char* sy = smem + r * (2 * WKP * WRS) + (lpx + 32 * h) * WRS + lch * 16;
+            *reinterpret_cast<bf16x8*>(sy) = ry[r][h];
+            *reinterpret_cast<bf16x8*>(sy + WKP * WRS) = rx[r][h];
         }
     };
 
@@ -1005,49 +1018,11 @@ __device__ __forceinline__ void gwgrad_body(const GWgP& p, int bid, int nblk, ch
                 for (int b = 0; b < 2; ++b) acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xf[a].v, yf[b].v, acc[a][b], 0, 0, 0);
         }
     };
-    if (nk > 0) {
-        // (steps rounded up to two: a step past the split's last one multiplies zero-page operands - cheaper than a second loop exit; sched_barrier:
-        //  left alone hipcc sinks a step's loads below its MFMAs, right in front of the wait for them)
-        load(0, ry0, rx0);
-        load(1, ry1, rx1);
-        stash(0, ry0, rx0);
-        __syncthreads();
-        for (int kt = 0; kt < nk; kt += 2) {
-            load(kt + 2, ry0, rx0);
-            __builtin_amdgcn_sched_barrier(0);
-            compute(0);
-            __builtin_amdgcn_sched_barrier(0);
-            stash(1, ry1, rx1);
-            __syncthreads();
-            load(kt + 3, ry1, rx1);
-            __builtin_amdgcn_sched_barrier(0);
-            compute(1);
-            __builtin_amdgcn_sched_barrier(0);
-            stash(0, ry0, rx0);
-            __syncthreads();
-        }
-    }
-    // slab[split][t][o][i], o < O, i < roundup(I, 4) (i fastest): the lane owns o = column, four consecutive i = rows
+    gw_pipeline(nk, load, stash, compute);
+    // slab[split][t][o][i], o < O, i < roundup(I, 4) (i fastest): the lane owns o = column, four consecutive i = rows (with tickets the slab is handed to the
+    // tile's last workgroup: write-through)
     const int Ip = (p.I + 3) & ~3;
-    float* slab = p.slab + ((long)(split * p.T + t) * p.O) * Ip;
-    const int fcol = lane & 15, fq = lane >> 4;
-#pragma unroll
-    for (int b = 0; b < 2; ++b) {
-        const int o = o0 + wo * 32 + b * 16 + fcol;
-        if (o >= p.O) continue;
-#pragma unroll
-        for (int a = 0; a < 2; ++a) {
-            const int i = i0 + wi * 32 + a * 16 + fq * 4;
-            if (i < Ip) {
-                if (p.ticket) {                    // handed to the tile's last workgroup: write-through
-                    mi_st2_sc1(slab + (long)o * Ip + i, acc[a][b][0], acc[a][b][1]);
-                    mi_st2_sc1(slab + (long)o * Ip + i + 2, acc[a][b][2], acc[a][b][3]);
-                } else {
-                    *reinterpret_cast<f32x4*>(slab + (long)o * Ip + i) = acc[a][b];
-                }
-            }
-        }
-    }
+    slab_store(p.slab + ((long)(split * p.T + t) * p.O) * Ip, Ip, p.O, Ip, o0 + wo * 32, i0 + wi * 32, lane, acc, p.ticket != nullptr);
     if (p.ticket) {
         // few K splits: the (tap, tile)'s last workgroup adds the slabs itself - gwgrad_reduce_kernel's arithmetic in its order (lane l of 8 adds the
         // splits l, l + 8, ... ascending, the eight sums are combined as the butterfly does: ((0+1)+(2+3))+((4+5)+(6+7))) - the same bits, one launch
@@ -1126,17 +1101,10 @@ constexpr int GW3_SMEM = 2 * W3_STAGE + WRS;                               // tw
 template <int YVEC, int XVEC>
 __device__ __forceinline__ void gwgrad3_body(const GWgP& p, int bid, int nblk, char* smem) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int tiles = p.o_tiles * p.i_tiles;
-    const int kh = p.T / 3;
-    int id = p.remap ? mi_xcd_remap(bid, nblk) : bid;      // the (tile, tap) workgroups of a pixel split share its dy / x rows: keep them on one XCD's L2
-    const int tile = id % tiles;
-    id /= tiles;
-    const int ky = id % kh, split = id / kh;
-    const int ot = tile / p.i_tiles, itile = tile - ot * p.i_tiles;
-    const int o0 = ot * WTO, i0 = itile * WTI;
-    const int m_begin = split * p.rows_per_split;
-    const int m_end = min(p.M, m_begin + p.rows_per_split);
-    const int nk = MI_DBG_BIT(p, 1) ? 0 : (m_end > m_begin ? (m_end - m_begin + WKP - 1) / WKP : 0);
+    // the (tile, kernel row) workgroups of a pixel split share its dy / x rows: MI_GCONV_REMAP keeps them on one XCD's L2
+    const WgDecode wg = wg_decode<WTO, WTI, WKP, true>(bid, nblk, p.o_tiles, p.i_tiles, p.T / 3, p.M, p.rows_per_split, p.remap);
+    const int ky = wg.mid, split = wg.split, o0 = wg.o0, i0 = wg.i0, m_begin = wg.m_begin, m_end = wg.m_end;
+    const int nk = MI_DBG_BIT(p, 1) ? 0 : wg.nk;
     const int lpx = tid >> 3, lch = tid & 7;
     const int hw = p.Ha * p.Wa;
     const int dyoff = ky * p.dh - p.ph;                      // source row - output row
@@ -1165,47 +1133,40 @@ __device__ __forceinline__ void gwgrad3_body(const GWgP& p, int bid, int nblk, c
     //  (64 mod Ha*Wa) pixels = step_rows < Ha rows + step_cols columns and every coordinate wraps at most once)
     const int step_rem = WKP % hw;
     const int step_rows = step_rem / p.Wa, step_cols = step_rem - step_rows * p.Wa;
-    auto advance = [&](int& hh, int& ww) {
-        const int w1 = ww + step_cols;
-        const bool cw = w1 >= p.Wa;
-        ww = cw ? w1 - p.Wa : w1;
-        const int h1 = hh + step_rows + (cw ? 1 : 0);
-        hh = h1 >= p.Ha ? h1 - p.Ha : h1;
-    };
-    bf16x8 ry0[2], rx0[3], ry1[2], rx1[3];
-    uint32_t rf0 = 0, rf1 = 0;                               // validity bits of the two dy rows (byte h)
-    auto load = [&](int kt, bf16x8 (&ry)[2], bf16x8 (&rx)[3], uint32_t& rf) {
-        rf = 0;
+    bf16x8 ry[2][2], rx[2][3];                               // [register set][row]
+    uint32_t rf[2] = {0, 0};                                 // validity bits of the two dy rows (byte h)
+    auto load = [&](int kt, int r) {
+        rf[r] = 0;
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
             const int m = m_begin + kt * WKP + lpx + 32 * h;
             const bool ok = m < m_end;
-            ry[h] = gload8<YVEC>(p.dY + (long)(ok ? m : 0) * p.ldy, o0 + lch * 8, p.O, ok);
+            ry[r][h] = gload8<YVEC>(p.dY + (long)(ok ? m : 0) * p.ldy, o0 + lch * 8, p.O, ok);
             const uint32_t f = (yw[h] >= p.dw ? 1u : 0u) | (yw[h] + p.dw < p.Wa ? 2u : 0u);
-            rf |= f << (8 * h);
-            advance(yh[h], yw[h]);
+            rf[r] |= f << (8 * h);
+            px_advance(yh[h], yw[h], step_rows, step_cols, p.Ha, p.Wa);
         }
 #pragma unroll
         for (int h = 0; h < 3; ++h) {
             const bool in_window = lpx + 32 * h < xrows;
             const bool ok = in_window & (xq[h] >= 0) & (xq[h] < (long)p.M) & ((unsigned)(xh[h] - dyoff) < (unsigned)p.Ha) & (kt < nk);
-            rx[h] = gload8<XVEC>(p.X + (ok ? xq[h] : 0L) * p.ldx, i0 + lch * 8, p.I, ok);
+            rx[r][h] = gload8<XVEC>(p.X + (ok ? xq[h] : 0L) * p.ldx, i0 + lch * 8, p.I, ok);
             xq[h] += WKP;
-            advance(xh[h], xw[h]);
+            px_advance(xh[h], xw[h], step_rows, step_cols, p.Ha, p.Wa);
         }
     };
-    auto stash = [&](int buf, const bf16x8 (&ry)[2], const bf16x8 (&rx)[3], uint32_t rf) {
-        char* sx = smem + buf * W3_STAGE;
+    auto stash = [&](int r) {
+        char* sx = smem + r * W3_STAGE;
         char* sy = sx + W3_XROWS * WRS;
 #pragma unroll
         for (int h = 0; h < 3; ++h) {                        // (rows past the window go to the stage's dummy row: an unconditional write, no branch)
             const int row = lpx + 32 * h < W3_XROWS ? lpx + 32 * h : W3_DUMMY_ROW;
-            *reinterpret_cast<bf16x8*>(sx + row * WRS + lch * 16) = rx[h];
+            *reinterpret_cast<bf16x8*>(sx + row * WRS + lch * 16) = rx[r][h];
         }
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
-            *reinterpret_cast<bf16x8*>(sy + (lpx + 32 * h) * WRS + lch * 16) = ry[h];
-            sy[WKP * WRS + lpx + 32 * h] = (char)((rf >> (8 * h)) & 0xff);            // (the eight threads of a pixel row write the same byte)
+            *reinterpret_cast<bf16x8*>(sy + (lpx + 32 * h) * WRS + lch * 16) = ry[r][h];
+            sy[WKP * WRS + lpx + 32 * h] = (char)((rf[r] >> (8 * h)) & 0xff);            // (the eight threads of a pixel row write the same byte)
         }
     };
 
@@ -1254,42 +1215,10 @@ __device__ __forceinline__ void gwgrad3_body(const GWgP& p, int bid, int nblk, c
             }
         }
     };
-    if (nk > 0) {
-        load(0, ry0, rx0, rf0);
-        load(1, ry1, rx1, rf1);
-        stash(0, ry0, rx0, rf0);
-        __syncthreads();
-        for (int kt = 0; kt < nk; kt += 2) {                 // (steps rounded up to two, sched_barrier: see gwgrad_kernel)
-            load(kt + 2, ry0, rx0, rf0);
-            __builtin_amdgcn_sched_barrier(0);
-            compute(0);
-            __builtin_amdgcn_sched_barrier(0);
-            stash(1, ry1, rx1, rf1);
-            __syncthreads();
-            load(kt + 3, ry1, rx1, rf1);
-            __builtin_amdgcn_sched_barrier(0);
-            compute(1);
-            __builtin_amdgcn_sched_barrier(0);
-            stash(0, ry0, rx0, rf0);
-            __syncthreads();
-        }
-    }
+    gw_pipeline(nk, load, stash, compute);
     const int Ip = (p.I + 3) & ~3;
-    const int fcol = lane & 15, fq = lane >> 4;
 #pragma unroll
-    for (int t = 0; t < 3; ++t) {
-        float* slab = p.slab + ((long)(split * p.T + ky * 3 + t) * p.O) * Ip;
-#pragma unroll
-        for (int b = 0; b < 2; ++b) {
-            const int o = o0 + wo * 32 + b * 16 + fcol;
-            if (o >= p.O) continue;
-#pragma unroll
-            for (int a = 0; a < 2; ++a) {
-                const int i = i0 + wi * 32 + a * 16 + fq * 4;
-                if (i < Ip) *reinterpret_cast<f32x4*>(slab + (long)o * Ip + i) = acc[t][a][b];
-            }
-        }
-    }
+    for (int t = 0; t < 3; ++t) slab_store(p.slab + ((long)(split * p.T + ky * 3 + t) * p.O) * Ip, Ip, p.O, Ip, o0 + wo * 32, i0 + wi * 32, lane, acc[t]);
 }
 
 // dw[o][i][t] (+)= sum over the K splits (bitwise reproducible); 8 lanes per output element (t, o, i: i fastest): lane l adds the splits
@@ -1365,23 +1294,28 @@ __device__ __forceinline__ int gw_find(const GWgD* __restrict__ table, int first
     return lo;
 }
 
+// The prologue of the table-driven main kernels: this workgroup's conv (by value: scalar loads once, not re-read after the kernel's own stores), its
+// block id `b` among the conv's `nblk` workgroups; false for the padding up to the next multiple of 8.
+__device__ __forceinline__ bool gw_multi_begin(const GWgD* __restrict__ table, int first, int n, GWgP& p, int& b, int& nblk) {
+    const int at = gw_find(table, first, n, blockIdx.x, false);
+    p = table[at].p;
+    b = blockIdx.x - table[at].first_block;
+    nblk = table[at].nblk;
+    return b < nblk;
+}
 template <int YVEC, int XVEC>
 __global__ __launch_bounds__(256, 4) void gwgrad_multi_kernel(const GWgD* __restrict__ table, int first, int n) {
     __shared__ __attribute__((aligned(16))) char smem[GW_SMEM];
-    const int at = gw_find(table, first, n, blockIdx.x, false);
-    const GWgP p = table[at].p;                          // (by value: scalar loads once, not re-read after the kernel's own stores)
-    const int b = blockIdx.x - table[at].first_block;
-    if (b >= table[at].nblk) return;                     // (padding up to the next multiple of 8)
-    gwgrad_body<YVEC, XVEC>(p, b, table[at].nblk, smem);
+    GWgP p;
+    int b, nblk;
+    if (gw_multi_begin(table, first, n, p, b, nblk)) gwgrad_body<YVEC, XVEC>(p, b, nblk, smem);
 }
 template <int YVEC, int XVEC>
 __global__ __launch_bounds__(256, 2) void gwgrad3_multi_kernel(const GWgD* __restrict__ table, int first, int n) {
     __shared__ __attribute__((aligned(16))) char smem[GW3_SMEM];
-    const int at = gw_find(table, first, n, blockIdx.x, false);
-    const GWgP p = table[at].p;
-    const int b = blockIdx.x - table[at].first_block;
-    if (b >= table[at].nblk) return;
-    gwgrad3_body<YVEC, XVEC>(p, b, table[at].nblk, smem);
+    GWgP p;
+    int b, nblk;
+    if (gw_multi_begin(table, first, n, p, b, nblk)) gwgrad3_body<YVEC, XVEC>(p, b, nblk, smem);
 }
 
 // The reducer of the table-driven launch: a thread owns four consecutive i of one (t, o) - the lanes of a wave read 1 KiB runs of a slab - and adds the
@@ -1441,6 +1375,19 @@ void gwgrad_plan(int M, int O, int I, int T, int* S, int* rows, int* ot, int* it
     s = (M + r - 1) / r;
     *S = s;
     *rows = r;
+}
+
+// The operand vector widths (yv, xv) in {8, 4, 1} x {8, 4, 1} as compile-time constants: f(integral_constant<YVEC>, integral_constant<XVEC>)
+template <class F>
+void with_vec2(int yv, int xv, F&& f) {
+    auto with_x = [&](auto y) {
+        if (xv == 8) f(y, std::integral_constant<int, 8>{});
+        else if (xv == 4) f(y, std::integral_constant<int, 4>{});
+        else f(y, std::integral_constant<int, 1>{});
+    };
+    if (yv == 8) with_x(std::integral_constant<int, 8>{});
+    else if (yv == 4) with_x(std::integral_constant<int, 4>{});
+    else with_x(std::integral_constant<int, 1>{});
 }
 
 // ------------------------------------------------------------------------------------------------ weight pack (table driven)
@@ -1644,106 +1591,93 @@ struct GWRoute {
     int grid;               // workgroups of the main launch (a _multi job: its share of its class's launch)
 };
 
-// the argument checks of mi_gconv_wgrad (and mi_gconv_wgrad_route): nothing is dereferenced
-static int gwgrad_check(long ldy, long ldx, int B, int Ha, int Wa, int I, int Ho, int Wo, int O, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw_) {
-    MI_REQUIRE(B > 0 && Ha > 0 && Wa > 0 && Ho > 0 && Wo > 0 && I > 0 && O > 0, "mi_gconv_wgrad: empty shape");
-    MI_REQUIRE(ldy >= O && ldx >= I, "mi_gconv_wgrad: a view's row stride is smaller than its channel count");
-    MI_REQUIRE(kh > 0 && kw > 0 && sh > 0 && sw > 0 && dh > 0 && dw_ > 0 && ph >= 0 && pw >= 0, "mi_gconv_wgrad: bad conv geometry");
-    MI_REQUIRE((long)B * Ho * Wo < (1L << 31) && (long)B * Ha * Wa < (1L << 31), "mi_gconv_wgrad: more than 2^31 pixels");
-    MI_REQUIRE((Ha + 2 * ph - dh * (kh - 1) - 1) / sh + 1 == Ho && (Wa + 2 * pw - dw_ * (kw - 1) - 1) / sw + 1 == Wo,
-               "mi_gconv_wgrad: output %dx%d does not follow from input %dx%d", Ho, Wo, Ha, Wa);
+// the argument checks of mi_gconv_wgrad and mi_gconv_wgrad_route (job < 0) and of job `job` of mi_gconv_wgrad_multi: nothing is dereferenced
+static int gwgrad_check(const MiWgradJob& j, int job) {
+    char who[48];
+    if (job < 0) snprintf(who, sizeof(who), "mi_gconv_wgrad");
+    else snprintf(who, sizeof(who), "mi_gconv_wgrad_multi: job %d", job);
+    MI_REQUIRE(j.B > 0 && j.Ha > 0 && j.Wa > 0 && j.Ho > 0 && j.Wo > 0 && j.I > 0 && j.O > 0, "%s: empty shape", who);
+    MI_REQUIRE(j.ldy >= j.O && j.ldx >= j.I, "%s: a view's row stride is smaller than its channel count", who);
+    MI_REQUIRE(j.kh > 0 && j.kw > 0 && j.sh > 0 && j.sw > 0 && j.dh > 0 && j.dw_ > 0 && j.ph >= 0 && j.pw >= 0, "%s: bad conv geometry", who);
+    MI_REQUIRE((long)j.B * j.Ho * j.Wo < (1L << 31) && (long)j.B * j.Ha * j.Wa < (1L << 31), "%s: more than 2^31 pixels", who);
+    MI_REQUIRE((j.Ha + 2 * j.ph - j.dh * (j.kh - 1) - 1) / j.sh + 1 == j.Ho && (j.Wa + 2 * j.pw - j.dw_ * (j.kw - 1) - 1) / j.sw + 1 == j.Wo,
+               "%s: output %dx%d does not follow from input %dx%d", who, j.Ho, j.Wo, j.Ha, j.Wa);
     return MI_OK;
 }
 
+// A conv's kernel parameters without its plan: operands, geometry, switches, where the gradient goes.  The caller adds S, rows_per_split, the tile
+// counts, the slab and (one-conv launch) the tickets.
+static GWgP gwgp_make(const MiWgradJob& j, int dbg) {
+    GWgP p{};
+    p.remap = mi_sw().gconv_remap;
+    p.dbg = dbg;
+    p.dY = (const __bf16*)j.dy;
+    p.X = (const __bf16*)j.x;
+    p.ldy = j.ldy;
+    p.ldx = j.ldx;
+    p.M = j.B * j.Ho * j.Wo;
+    p.O = j.O; p.I = j.I; p.T = j.kh * j.kw;
+    p.Ho = j.Ho; p.Wo = j.Wo; p.Ha = j.Ha; p.Wa = j.Wa;
+    p.kw = j.kw; p.sh = j.sh; p.sw = j.sw; p.ph = j.ph; p.pw = j.pw; p.dh = j.dh; p.dw = j.dw_;
+    p.ticket = nullptr;
+    p.dwout = j.dw;
+    p.accumulate = j.accumulate;
+    return p;
+}
+
 // The one planning function of mi_gconv_wgrad (mi_gconv_wgrad_route reports it).
-static GWRoute gwgrad_route(const void* dy, long ldy, const void* x, long ldx, int B, int Ha, int Wa, int I, int Ho, int Wo, int O, int kh, int kw, int sh, int sw,
-                            int pw, int dw_, int* o_tiles, int* i_tiles) {
+static GWRoute gwgrad_route(const MiWgradJob& j, int* o_tiles, int* i_tiles) {
     GWRoute r{};
-    const int M = B * Ho * Wo;
+    const int M = j.B * j.Ho * j.Wo;
     // fused kernel row (gwgrad3_kernel): three-column kernels at stride 1 whose output has the input's height and width
     // (measured, bench.py --workload gald / pranet: GALD's weight gradients 9.96 -> 8.90 ms per step with every eligible conv fused, PraNet's 5.02 -> 5.23:
     //  on the small maps of the deep stages a third of the workgroups leaves the launch latency-bound on fewer CUs - fused from 65 536 pixels up, or when forced)
-    r.fused = kw == 3 && sh == 1 && sw == 1 && pw == dw_ && Ho == Ha && Wo == Wa && dw_ <= W3_MAXD && (mi_sw().gwgrad3 == 2 || (mi_sw().gwgrad3 == 1 && M >= 65536));
-    gwgrad_plan(M, O, I, r.fused ? kh : kh * kw, &r.S, &r.rows, o_tiles, i_tiles);
-    r.yvec = view_vec(dy, ldy, O);
-    r.xvec = view_vec(x, ldx, I);
-    r.grid = *o_tiles * *i_tiles * (r.fused ? kh : kh * kw) * r.S;
+    r.fused = j.kw == 3 && j.sh == 1 && j.sw == 1 && j.pw == j.dw_ && j.Ho == j.Ha && j.Wo == j.Wa && j.dw_ <= W3_MAXD &&
+              (mi_sw().gwgrad3 == 2 || (mi_sw().gwgrad3 == 1 && M >= 65536));
+    gwgrad_plan(M, j.O, j.I, r.fused ? j.kh : j.kh * j.kw, &r.S, &r.rows, o_tiles, i_tiles);
+    r.yvec = view_vec(j.dy, j.ldy, j.O);
+    r.xvec = view_vec(j.x, j.ldx, j.I);
+    r.grid = *o_tiles * *i_tiles * (r.fused ? j.kh : j.kh * j.kw) * r.S;
     return r;
+}
+
+// the one-conv reducer: 32 output elements (8 lanes each) per block
+static int gwgrad_reduce_launch(const GWgP& p, hipStream_t s) {
+    const long n = (long)p.O * p.I * p.T;
+    const int blocks = (int)((n + 31) / 32 < 4096 ? (n + 31) / 32 : 4096);
+    hipLaunchKernelGGL(gwgrad_reduce_kernel, dim3(blocks), dim3(256), 0, s, p.slab, p.dwout, p.O, p.I, p.T, p.S, p.accumulate);
+    MI_CHECK_LAUNCH("gwgrad_reduce_kernel");
+    return MI_OK;
 }
 
 int mi_gconv_wgrad(const void* dy, long ldy, const void* x, long ldx, float* dw, int B, int Ha, int Wa, int I, int Ho, int Wo, int O,
                    int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw_, int accumulate, void* workspace, size_t workspace_bytes,
                    unsigned* tickets, int n_tickets, void* stream) {
     MI_REQUIRE(dy && x && dw && workspace, "mi_gconv_wgrad: null operand");
-    const int rc = gwgrad_check(ldy, ldx, B, Ha, Wa, I, Ho, Wo, O, kh, kw, sh, sw, ph, pw, dh, dw_);
+    const MiWgradJob j{dy, ldy, x, ldx, dw, B, Ha, Wa, I, Ho, Wo, O, kh, kw, sh, sw, ph, pw, dh, dw_, accumulate};
+    const int rc = gwgrad_check(j, -1);
     if (rc != MI_OK) return rc;
     MI_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 15) == 0, "mi_gconv_wgrad: workspace must be 16-byte aligned");
-    GWgP p;
-    p.remap = mi_sw().gconv_remap;
-    p.dbg = mi_sw().gw_dbg;
-    p.dY = (const __bf16*)dy;
-    p.X = (const __bf16*)x;
+    GWgP p = gwgp_make(j, mi_sw().gw_dbg);
     p.slab = (float*)workspace;
-    p.ldy = ldy;
-    p.ldx = ldx;
-    p.M = B * Ho * Wo;
-    p.O = O; p.I = I; p.T = kh * kw;
-    p.Ho = Ho; p.Wo = Wo; p.Ha = Ha; p.Wa = Wa;
-    p.kw = kw; p.sh = sh; p.sw = sw; p.ph = ph; p.pw = pw; p.dh = dh; p.dw = dw_;
-    const GWRoute r = gwgrad_route(dy, ldy, x, ldx, B, Ha, Wa, I, Ho, Wo, O, kh, kw, sh, sw, pw, dw_, &p.o_tiles, &p.i_tiles);
+    const GWRoute r = gwgrad_route(j, &p.o_tiles, &p.i_tiles);
     p.S = r.S;
     p.rows_per_split = r.rows;
     const size_t need = (size_t)p.S * p.T * O * ((I + 3) & ~3) * sizeof(float);
     if (workspace_bytes < need) return mi_set_error(MI_ENOMEM, "mi_gconv_wgrad: workspace %zu < %zu bytes", workspace_bytes, need);
     hipStream_t s = (hipStream_t)stream;
-    const int yv = r.yvec, xv = r.xvec;
-    if (r.fused) {
-        p.ticket = nullptr;
-        p.dwout = dw;
-        p.accumulate = accumulate;
-        const dim3 grid3(r.grid);
-#define GW3(YV, XV) hipLaunchKernelGGL((gwgrad3_kernel<YV, XV>), grid3, dim3(256), 0, s, p)
-        if (yv == 8 && xv == 8) GW3(8, 8);
-        else if (yv == 8 && xv == 4) GW3(8, 4);
-        else if (yv == 8) GW3(8, 1);
-        else if (yv == 4 && xv == 8) GW3(4, 8);
-        else if (yv == 4 && xv == 4) GW3(4, 4);
-        else if (yv == 4) GW3(4, 1);
-        else if (xv == 8) GW3(1, 8);
-        else if (xv == 4) GW3(1, 4);
-        else GW3(1, 1);
-#undef GW3
-        MI_CHECK_LAUNCH("gwgrad3_kernel");
-        const long n3 = (long)O * I * p.T;
-        const int blocks3 = (int)((n3 + 31) / 32 < 4096 ? (n3 + 31) / 32 : 4096);
-        hipLaunchKernelGGL(gwgrad_reduce_kernel, dim3(blocks3), dim3(256), 0, s, p.slab, dw, O, I, p.T, p.S, accumulate);
-        MI_CHECK_LAUNCH("gwgrad_reduce_kernel");
-        return MI_OK;
-    }
-    // few K splits: the slabs are added by the last workgroup of each (tap, tile) inside this launch (needs one zeroed ticket word per (tap, tile))
-    const bool inlaunch = tickets && p.S <= GW_INLAUNCH_S && p.o_tiles * p.i_tiles * p.T <= n_tickets;
+    // few K splits (per-tap kernel only): the slabs are added by the last workgroup of each (tap, tile) inside this launch (needs one zeroed ticket word per
+    // (tap, tile))
+    const bool inlaunch = !r.fused && tickets && p.S <= GW_INLAUNCH_S && p.o_tiles * p.i_tiles * p.T <= n_tickets;
     p.ticket = inlaunch ? tickets : nullptr;
-    p.dwout = dw;
-    p.accumulate = accumulate;
     const dim3 grid(r.grid);
-#define GW(YV, XV) hipLaunchKernelGGL((gwgrad_kernel<YV, XV>), grid, dim3(256), 0, s, p)
-    if (yv == 8 && xv == 8) GW(8, 8);
-    else if (yv == 8 && xv == 4) GW(8, 4);
-    else if (yv == 8) GW(8, 1);
-    else if (yv == 4 && xv == 8) GW(4, 8);
-    else if (yv == 4 && xv == 4) GW(4, 4);
-    else if (yv == 4) GW(4, 1);
-    else if (xv == 8) GW(1, 8);
-    else if (xv == 4) GW(1, 4);
-    else GW(1, 1);
-#undef GW
-    MI_CHECK_LAUNCH("gwgrad_kernel");
-    if (inlaunch) return MI_OK;
-    const long n = (long)O * I * p.T;
-    const int blocks = (int)((n + 31) / 32 < 4096 ? (n + 31) / 32 : 4096);          // 32 output elements (8 lanes each) per block
-    hipLaunchKernelGGL(gwgrad_reduce_kernel, dim3(blocks), dim3(256), 0, s, p.slab, dw, O, I, p.T, p.S, accumulate);
-    MI_CHECK_LAUNCH("gwgrad_reduce_kernel");
-    return MI_OK;
+    with_vec2(r.yvec, r.xvec, [&](auto yv, auto xv) {
+        constexpr int YV = decltype(yv)::value, XV = decltype(xv)::value;
+        if (r.fused) hipLaunchKernelGGL((gwgrad3_kernel<YV, XV>), grid, dim3(256), 0, s, p);
+        else hipLaunchKernelGGL((gwgrad_kernel<YV, XV>), grid, dim3(256), 0, s, p);
+    });
+    MI_CHECK_LAUNCH(r.fused ? "gwgrad3_kernel" : "gwgrad_kernel");
+    return inlaunch ? MI_OK : gwgrad_reduce_launch(p, s);
 }
 
 
@@ -1758,16 +1692,7 @@ static bool gwm_fused(const MiWgradJob& j, long M) {
 static void gwm_plan(const MiWgradJob& j, GWgD& d) {
     const int steps = mi_sw().gwm_steps;
     GWgP& p = d.p;
-    p.remap = mi_sw().gconv_remap;
-    p.dbg = 0;
-    p.dY = (const __bf16*)j.dy;
-    p.X = (const __bf16*)j.x;
-    p.ldy = j.ldy;
-    p.ldx = j.ldx;
-    p.M = j.B * j.Ho * j.Wo;
-    p.O = j.O; p.I = j.I; p.T = j.kh * j.kw;
-    p.Ho = j.Ho; p.Wo = j.Wo; p.Ha = j.Ha; p.Wa = j.Wa;
-    p.kw = j.kw; p.sh = j.sh; p.sw = j.sw; p.ph = j.ph; p.pw = j.pw; p.dh = j.dh; p.dw = j.dw_;
+    p = gwgp_make(j, 0);
     p.o_tiles = (j.O + WTO - 1) / WTO;
     p.i_tiles = (j.I + WTI - 1) / WTI;
     int S = (p.M + WKP * (steps > 0 ? steps : 48) - 1) / (WKP * (steps > 0 ? steps : 48));
@@ -1775,9 +1700,6 @@ static void gwm_plan(const MiWgradJob& j, GWgD& d) {
     int r = rup((p.M + S - 1) / S, WKP);
     p.rows_per_split = r;
     p.S = (p.M + r - 1) / r;
-    p.ticket = nullptr;
-    p.dwout = j.dw;
-    p.accumulate = j.accumulate;
     const bool fused = gwm_fused(j, p.M);
     d.nblk = p.o_tiles * p.i_tiles * (fused ? j.kh : p.T) * p.S;
     const long n4 = (long)j.O * ((j.I + 3) / 4) * p.T;                  // the reducer's threads: four consecutive i each
@@ -1796,18 +1718,18 @@ size_t mi_gconv_wgrad_multi_table_bytes(int n) { return (size_t)(n > 0 ? n : 0) 
 int mi_gconv_wgrad_route(const void* dy, long ldy, const void* x, long ldx, int B, int Ha, int Wa, int I, int Ho, int Wo, int O, int kh, int kw, int sh, int sw,
                          int ph, int pw, int dh, int dw_, int multi, int* route) {
     MI_REQUIRE(route, "mi_gconv_wgrad_route: null route");
-    const int rc = gwgrad_check(ldy, ldx, B, Ha, Wa, I, Ho, Wo, O, kh, kw, sh, sw, ph, pw, dh, dw_);
+    const MiWgradJob j{dy, ldy, x, ldx, nullptr, B, Ha, Wa, I, Ho, Wo, O, kh, kw, sh, sw, ph, pw, dh, dw_, 0};
+    const int rc = gwgrad_check(j, -1);
     if (rc != MI_OK) return rc;
     GWRoute r{};
     if (multi) {
-        const MiWgradJob j{dy, ldy, x, ldx, nullptr, B, Ha, Wa, I, Ho, Wo, O, kh, kw, sh, sw, ph, pw, dh, dw_, 0};
         GWgD d;
         const int c = gwm_route(j, d);
         static const int vv[3] = {8, 4, 1};
         r = GWRoute{c >= 9, vv[(c % 9) / 3], vv[c % 3], d.p.S, d.p.rows_per_split, d.nblk};
     } else {
         int ot, it;
-        r = gwgrad_route(dy, ldy, x, ldx, B, Ha, Wa, I, Ho, Wo, O, kh, kw, sh, sw, pw, dw_, &ot, &it);
+        r = gwgrad_route(j, &ot, &it);
     }
     const int v[MI_GWROUTE_LEN] = {r.fused, r.yvec, r.xvec, r.S, r.rows, r.grid};
     for (int k = 0; k < MI_GWROUTE_LEN; ++k) route[k] = v[k];
@@ -1838,12 +1760,7 @@ int mi_gconv_wgrad_multi(const MiWgradJob* jobs, int n, void* table_dev, size_t 
     for (int k = 0; k < n; ++k) {
         const MiWgradJob& j = jobs[k];
         MI_REQUIRE(j.dy && j.x && j.dw, "mi_gconv_wgrad_multi: job %d: null operand", k);
-        MI_REQUIRE(j.B > 0 && j.Ha > 0 && j.Wa > 0 && j.Ho > 0 && j.Wo > 0 && j.I > 0 && j.O > 0, "mi_gconv_wgrad_multi: job %d: empty shape", k);
-        MI_REQUIRE(j.ldy >= j.O && j.ldx >= j.I, "mi_gconv_wgrad_multi: job %d: a view's row stride is smaller than its channel count", k);
-        MI_REQUIRE(j.kh > 0 && j.kw > 0 && j.sh > 0 && j.sw > 0 && j.dh > 0 && j.dw_ > 0 && j.ph >= 0 && j.pw >= 0, "mi_gconv_wgrad_multi: job %d: bad conv geometry", k);
-        MI_REQUIRE((long)j.B * j.Ho * j.Wo < (1L << 31) && (long)j.B * j.Ha * j.Wa < (1L << 31), "mi_gconv_wgrad_multi: job %d: more than 2^31 pixels", k);
-        MI_REQUIRE((j.Ha + 2 * j.ph - j.dh * (j.kh - 1) - 1) / j.sh + 1 == j.Ho && (j.Wa + 2 * j.pw - j.dw_ * (j.kw - 1) - 1) / j.sw + 1 == j.Wo,
-                   "mi_gconv_wgrad_multi: job %d: output %dx%d does not follow from input %dx%d", k, j.Ho, j.Wo, j.Ha, j.Wa);
+        if (const int rc = gwgrad_check(j, k)) return rc;
         for (int q = 0; q < k; ++q) MI_REQUIRE(jobs[q].dw != j.dw, "mi_gconv_wgrad_multi: jobs %d and %d write the same gradient", q, k);
         cls[k] = gwm_route(j, table[k]);
         need += gwm_slab_bytes(table[k]);
@@ -1885,22 +1802,12 @@ int mi_gconv_wgrad_multi(const MiWgradJob* jobs, int n, void* table_dev, size_t 
     static const int vv[3] = {8, 4, 1};
     for (int c = 0; c < 18; ++c) {
         if (!cls_n[c]) continue;
-        const int yv = vv[(c % 9) / 3], xv = vv[c % 3];
         const dim3 grid((unsigned)cls_blocks[c]);
-#define GWM(K, YV, XV) hipLaunchKernelGGL((K<YV, XV>), grid, dim3(256), 0, s, (const GWgD*)tdev, cls_first[c], cls_n[c])
-#define GWM_ALL(K)                                   \
-        if (yv == 8 && xv == 8) GWM(K, 8, 8);        \
-        else if (yv == 8 && xv == 4) GWM(K, 8, 4);   \
-        else if (yv == 8) GWM(K, 8, 1);              \
-        else if (yv == 4 && xv == 8) GWM(K, 4, 8);   \
-        else if (yv == 4 && xv == 4) GWM(K, 4, 4);   \
-        else if (yv == 4) GWM(K, 4, 1);              \
-        else if (xv == 8) GWM(K, 1, 8);              \
-        else if (xv == 4) GWM(K, 1, 4);              \
-        else GWM(K, 1, 1);
-        if (c < 9) { GWM_ALL(gwgrad_multi_kernel) } else { GWM_ALL(gwgrad3_multi_kernel) }
-#undef GWM_ALL
-#undef GWM
+        with_vec2(vv[(c % 9) / 3], vv[c % 3], [&](auto yv, auto xv) {
+            constexpr int YV = decltype(yv)::value, XV = decltype(xv)::value;
+            if (c < 9) hipLaunchKernelGGL((gwgrad_multi_kernel<YV, XV>), grid, dim3(256), 0, s, (const GWgD*)tdev, cls_first[c], cls_n[c]);
+            else hipLaunchKernelGGL((gwgrad3_multi_kernel<YV, XV>), grid, dim3(256), 0, s, (const GWgD*)tdev, cls_first[c], cls_n[c]);
+        });
     }
     MI_CHECK_LAUNCH("gwgrad_multi_kernel");
     hipLaunchKernelGGL(gwgrad_reduce_multi_kernel, dim3((unsigned)rblocks), dim3(256), 0, s, (const GWgD*)tdev, n);

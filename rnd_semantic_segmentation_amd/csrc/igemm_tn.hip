@@ -9,7 +9,7 @@
 // reproducible; no float atomics), applies the folded FrozenBN scale and scatters to torch's OIHW layout.
 // Replaces the weight half of convolution_backward for reference core/components/resnet.py:22-30 convs and
 // (out_map 1) for the four ASPP convs of core/models/classifiers/aspp/classifier.py:12-20.
-#include "mi_common.h"
+#include "wgrad_common.h"
 #include <stdlib.h>
 
 namespace {
@@ -61,6 +61,32 @@ __device__ __forceinline__ void blds16_tn(__amdgpu_buffer_rsrc_t rsrc, unsigned 
     __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void*)lds_wave_base, 16, voffset, 0, 0, 0);
 }
 
+// The fragment-read + MFMA block of the 128 x 128 kernels (wgrad_tn_kernel, wgrad_s4_kernel): 32 pixel rows of both tiles (sy / sx: LDS byte address of the
+// dy / x rows, the lane's row_off included), wave (wi, wo_) owns 64 (i) x 64 (o).
+// transposed-read addressing: 16-lane group g reads pixel rows half*16 + g*4 + q (q = (lane&15)>>2),
+// 4 columns (8 B) starting at column 4*(lane&3) of the 16-column subtile; same pixel<->k mapping on both operands.
+__device__ __forceinline__ void tn_frag_mfma(unsigned sy, unsigned sx, int wi, int wo_, int pc, int rsw, f32x4 (&acc)[4][4]) {
+    union { bf16x8 v; s16x4 h[2]; } xf[4], yf[4];
+#pragma unroll
+    for (int a = 0; a < 4; ++a) {
+        const unsigned base = sx + (((wi * 8 + a * 2 + (pc >> 1)) ^ rsw) << 4);
+        xf[a].h[0] = tr_read_lds<0>(base);
+        xf[a].h[1] = tr_read_lds<16 * ROWB>(base);
+    }
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+        const unsigned base = sy + (((wo_ * 8 + b * 2 + (pc >> 1)) ^ rsw) << 4);
+        yf[b].h[0] = tr_read_lds<0>(base);
+        yf[b].h[1] = tr_read_lds<16 * ROWB>(base);
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int a = 0; a < 4; ++a)
+#pragma unroll
+        for (int b = 0; b < 4; ++b) acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xf[a].v, yf[b].v, acc[a][b], 0, 0, 0);
+}
+
 // Staging: tiles go global -> LDS directly (global_load_lds, 1 KiB = 4 pixel rows x 256 B per wave-instruction).
 // The LDS image is lane-linear per DMA; 16-B chunk c of pixel row r sits at physical chunk c ^ ((r & 7) << 1), applied to
 // the per-lane SOURCE address and to the transposed-read address.  With that XOR the 32 lanes of a
@@ -74,16 +100,9 @@ __global__ __launch_bounds__(256, 2) void wgrad_tn_kernel(WgradParams p) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     // XCD-aware flattening: consecutive logical ids (= the output tiles of ONE K-split and tap, which all stream the same
     // pixel rows) land on the same XCD, so the rows are fetched into one L2 instead of eight.
-    const int tiles = p.o_tiles * p.i_tiles;
-    const int logical = mi_xcd_remap(blockIdx.x, tiles * p.T * p.S);
-    const int tile = logical % tiles, rest = logical / tiles;
-    const int t = rest % p.T, split = rest / p.T;
-    const int ot = tile / p.i_tiles, it = tile - ot * p.i_tiles;
-    const int o0 = ot * TO, i0 = it * TI;
+    const WgDecode wg = wg_decode<TO, TI, KP>(blockIdx.x, p.o_tiles * p.i_tiles * p.T * p.S, p.o_tiles, p.i_tiles, p.T, p.M, p.rows_per_split);
+    const int t = wg.mid, split = wg.split, o0 = wg.o0, i0 = wg.i0, m_begin = wg.m_begin, m_end = wg.m_end, nk = wg.nk;
     const int ky = t / p.ksz, kx = t - ky * p.ksz;
-    const int m_begin = split * p.rows_per_split;
-    const int m_end = min(p.M, m_begin + p.rows_per_split);
-    const int nk = (m_end - m_begin + KP - 1) / KP;
     const char* zero = reinterpret_cast<const char*>(g_zero_page_tn);
 
     // DMA assignment: wave w moves pieces 4w..4w+3 (4 rows each) of both tiles; lane -> (row, physical chunk)
@@ -187,8 +206,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_tn_kernel(WgradParams p) {
 #pragma unroll
         for (int b = 0; b < 4; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-    // transposed-read addressing: 16-lane group g reads pixel rows ks*32 + half*16 + g*4 + q (q = (lane&15)>>2),
-    // 4 columns (8 B) starting at column 4*(lane&3) of the 16-column subtile; same pixel<->k mapping on both operands.
+    // (transposed-read addressing: tn_frag_mfma; a 64-pixel stage is two blocks of 32 rows)
     const int g = lane >> 4, q = (lane & 15) >> 2, pc = lane & 3;
     const int rsw = (((g & 1) * 4 + q) << 1);                 // ((row & 7) << 1): ks*32 and half*16 are multiples of 8
     const int row_off = (g * 4 + q) * ROWB + (pc & 1) * 8;
@@ -197,27 +215,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_tn_kernel(WgradParams p) {
         const unsigned sy = lds0 + buf * STAGE_BYTES + row_off;
         const unsigned sx = sy + TILE_BYTES;
 #pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-            union { bf16x8 v; s16x4 h[2]; } xf[4], yf[4];
-#pragma unroll
-            for (int a = 0; a < 4; ++a) {
-                const unsigned base = sx + (ks * 32) * ROWB + (((wi * 8 + a * 2 + (pc >> 1)) ^ rsw) << 4);
-                xf[a].h[0] = tr_read_lds<0>(base);
-                xf[a].h[1] = tr_read_lds<16 * ROWB>(base);
-            }
-#pragma unroll
-            for (int b = 0; b < 4; ++b) {
-                const unsigned base = sy + (ks * 32) * ROWB + (((wo_ * 8 + b * 2 + (pc >> 1)) ^ rsw) << 4);
-                yf[b].h[0] = tr_read_lds<0>(base);
-                yf[b].h[1] = tr_read_lds<16 * ROWB>(base);
-            }
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int a = 0; a < 4; ++a)
-#pragma unroll
-                for (int b = 0; b < 4; ++b) acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xf[a].v, yf[b].v, acc[a][b], 0, 0, 0);
-        }
+        for (int ks = 0; ks < 2; ++ks) tn_frag_mfma(sy + (ks * 32) * ROWB, sx + (ks * 32) * ROWB, wi, wo_, pc, rsw, acc);
     };
 
     if (nk > 0) {
@@ -233,19 +231,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_tn_kernel(WgradParams p) {
         }
     }
     // slab[split][t][o][i], i fastest: lane owns o = col, i..i+3 = rows
-    float* slab = p.slab + ((long)(split * p.T + t) * p.O) * p.I;
-    const int fcol = lane & 15, fq = lane >> 4;
-#pragma unroll
-    for (int b = 0; b < 4; ++b) {
-        const int o = o0 + wo_ * 64 + b * 16 + fcol;
-        if (o >= p.O) continue;
-#pragma unroll
-        for (int a = 0; a < 4; ++a) {
-            const int i = i0 + wi * 64 + a * 16 + fq * 4;
-            if (i >= p.I) continue;
-            *reinterpret_cast<f32x4*>(slab + (long)o * p.I + i) = acc[a][b];
-        }
-    }
+    slab_store(p.slab + ((long)(split * p.T + t) * p.O) * p.I, p.I, p.O, p.I, o0 + wo_ * 64, i0 + wi * 64, lane, acc);
 }
 
 // ---- 1x1 / stride 1 weight gradient as a deeper stream: 32-pixel stages, 4-slot ring, three stages in flight ------------------
@@ -264,14 +250,8 @@ __global__ __launch_bounds__(256, 2) void wgrad_s4_kernel(WgradParams p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int tiles = p.o_tiles * p.i_tiles;
-    const int logical = mi_xcd_remap(blockIdx.x, tiles * p.S);
-    const int tile = logical % tiles, split = logical / tiles;
-    const int ot = tile / p.i_tiles, it = tile - ot * p.i_tiles;
-    const int o0 = ot * TO, i0 = it * TI;
-    const int m_begin = split * p.rows_per_split;
-    const int m_end = min(p.M, m_begin + p.rows_per_split);
-    const int nk = (m_end - m_begin + KP4 - 1) / KP4;
+    const WgDecode wg = wg_decode<TO, TI, KP4>(blockIdx.x, p.o_tiles * p.i_tiles * p.S, p.o_tiles, p.i_tiles, 1, p.M, p.rows_per_split);
+    const int split = wg.split, o0 = wg.o0, i0 = wg.i0, m_begin = wg.m_begin, m_end = wg.m_end, nk = wg.nk;
 
     // DMA: a stage is 8 + 8 pieces of 4 pixel rows x 256 B; wave w moves pieces 2w, 2w+1 of both tiles
     const int prow = lane >> 4, pch = lane & 15;
@@ -312,26 +292,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_s4_kernel(WgradParams p) {
     const unsigned lds0 = lds_address(smem);
     auto compute = [&](int slot) {
         const unsigned sy = lds0 + slot * SLOT4 + row_off;
-        const unsigned sx = sy + KP4 * ROWB;
-        union { bf16x8 v; s16x4 h[2]; } xf[4], yf[4];
-#pragma unroll
-        for (int a = 0; a < 4; ++a) {
-            const unsigned base = sx + (((wi * 8 + a * 2 + (pc >> 1)) ^ rsw) << 4);
-            xf[a].h[0] = tr_read_lds<0>(base);
-            xf[a].h[1] = tr_read_lds<16 * ROWB>(base);
-        }
-#pragma unroll
-        for (int b = 0; b < 4; ++b) {
-            const unsigned base = sy + (((wo_ * 8 + b * 2 + (pc >> 1)) ^ rsw) << 4);
-            yf[b].h[0] = tr_read_lds<0>(base);
-            yf[b].h[1] = tr_read_lds<16 * ROWB>(base);
-        }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int a = 0; a < 4; ++a)
-#pragma unroll
-            for (int b = 0; b < 4; ++b) acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xf[a].v, yf[b].v, acc[a][b], 0, 0, 0);
+        tn_frag_mfma(sy, sy + KP4 * ROWB, wi, wo_, pc, rsw, acc);
     };
 
     // stages 0..2 in flight; step s: my pieces of stage s landed (8 younger instructions may be pending), barrier (everyone's have,
@@ -345,19 +306,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_s4_kernel(WgradParams p) {
         stage((s + 3) & (NSLOT4 - 1));
         compute(s & (NSLOT4 - 1));
     }
-    float* slab = p.slab + ((long)split * p.O) * p.I;
-    const int fcol = lane & 15, fq = lane >> 4;
-#pragma unroll
-    for (int b = 0; b < 4; ++b) {
-        const int o = o0 + wo_ * 64 + b * 16 + fcol;
-        if (o >= p.O) continue;
-#pragma unroll
-        for (int a = 0; a < 4; ++a) {
-            const int i = i0 + wi * 64 + a * 16 + fq * 4;
-            if (i >= p.I) continue;
-            *reinterpret_cast<f32x4*>(slab + (long)o * p.I + i) = acc[a][b];
-        }
-    }
+    slab_store(p.slab + ((long)split * p.O) * p.I, p.I, p.O, p.I, o0 + wo_ * 64, i0 + wi * 64, lane, acc);
 }
 
 // ---- 128 (o) x 256 (i) tile, 32 pixels per K step --------------------------------------------------------------------------
@@ -377,16 +326,9 @@ __global__ __launch_bounds__(256, 2) void wgrad_tn256_kernel(WgradParams p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int tiles = p.o_tiles * p.i_tiles;
-    const int logical = mi_xcd_remap(blockIdx.x, tiles * p.T * p.S);
-    const int tile = logical % tiles, rest = logical / tiles;
-    const int t = rest % p.T, split = rest / p.T;
-    const int ot = tile / p.i_tiles, it = tile - ot * p.i_tiles;
-    const int o0 = ot * TO, i0 = it * TI2;
+    const WgDecode wg = wg_decode<TO, TI2, KP2>(blockIdx.x, p.o_tiles * p.i_tiles * p.T * p.S, p.o_tiles, p.i_tiles, p.T, p.M, p.rows_per_split);
+    const int t = wg.mid, split = wg.split, o0 = wg.o0, i0 = wg.i0, m_begin = wg.m_begin, m_end = wg.m_end, nk = wg.nk;
     const int ky = t / p.ksz, kx = t - ky * p.ksz;
-    const int m_begin = split * p.rows_per_split;
-    const int m_end = min(p.M, m_begin + p.rows_per_split);
-    const int nk = (m_end - m_begin + KP2 - 1) / KP2;
     const char* zero = reinterpret_cast<const char*>(g_zero_page_tn);
 
     // DMA: wave w moves dy pieces 2w, 2w+1 (4 rows x 256 B each) and x pieces 4w .. 4w+3 (2 rows x 512 B each)
@@ -503,60 +445,17 @@ __global__ __launch_bounds__(256, 2) void wgrad_tn256_kernel(WgradParams p) {
         }
     }
 
-    float* slab = p.slab + ((long)(split * p.T + t) * p.O) * p.I;
-    const int fcol = lane & 15, fq = lane >> 4;
-#pragma unroll
-    for (int b = 0; b < 4; ++b) {
-        const int o = o0 + wo_ * 64 + b * 16 + fcol;
-        if (o >= p.O) continue;
-#pragma unroll
-        for (int a = 0; a < 8; ++a) {
-            const int i = i0 + wi * 128 + a * 16 + fq * 4;
-            if (i >= p.I) continue;
-            *reinterpret_cast<f32x4*>(slab + (long)o * p.I + i) = acc[a][b];
-        }
-    }
+    slab_store(p.slab + ((long)(split * p.T + t) * p.O) * p.I, p.I, p.O, p.I, o0 + wo_ * 64, i0 + wi * 128, lane, acc);
 }
 
-int pick_splits256(long M, int tiles) {
-    // as pick_splits, for 32-pixel steps: 512 slots, ~12 steps of fixed cost per workgroup, never fewer than 16 steps per split
-    const long steps = (M + KP2 - 1) / KP2;
-    int best = 1;
-    double best_cost = 1e30;
-    for (int s = 1; s <= 128; ++s) {
-        const long per = (steps + s - 1) / s;
-        if (s > 1 && per < 16) break;
-        const long rounds = ((long)tiles * s + 511) / 512;
-        const double cost = (double)rounds * (double)(per + 12);
-        if (cost < best_cost - 1e-9) {
-            best_cost = cost;
-            best = s;
-        }
-    }
-    return best;
-}
+// as pick_splits, for 32-pixel steps: 512 slots, ~12 steps of fixed cost per workgroup, never fewer than 16 steps per split
+int pick_splits256(long M, int tiles) { return wgrad_pick_splits(M, tiles, KP2, 16, 12, 512, 128); }
 
 // Splits of the deep-stream 1x1 kernel.  MI_WGRAD_S4_SLOTS (default 512 = two workgroups per CU): workgroup slots the cost model fills.
 // With 256 (one workgroup per CU, twice the K steps, half the partial planes) the launches themselves are 7 % faster when timed alone
 // (256 <-> 1024: 64.7 vs 70.0 us; the class 3.72 vs 4.02 ms single-stream), but the two-stream step is not (278.9 vs 280.0 images/s): a
 // launch that fills every CU's slot leaves the data-gradient chain beside it nothing to overlap with.
-int pick_splits_s4(long M, int tiles) {
-    const int slots = mi_sw().wgrad_s4_slots;
-    const long steps = (M + 31) / 32;
-    int best = 1;
-    double best_cost = 1e30;
-    for (int s = 1; s <= 128; ++s) {
-        const long per = (steps + s - 1) / s;
-        if (s > 1 && per < 16) break;
-        const long rounds = ((long)tiles * s + slots - 1) / slots;
-        const double cost = (double)rounds * (double)(per + 12);
-        if (cost < best_cost - 1e-9) {
-            best_cost = cost;
-            best = s;
-        }
-    }
-    return best;
-}
+int pick_splits_s4(long M, int tiles) { return wgrad_pick_splits(M, tiles, KP4, 16, 12, mi_sw().wgrad_s4_slots, 128); }
 
 inline bool use_tn256(int O, int I, int ksize, int pad, int stride, int Ha, int Ho, int Wa, int Wo) {
     // MI_WGRAD_TI256: unset = by rule, 0 = never, 1 = every stride-1 conv with I >= 256 (tests).
@@ -575,12 +474,10 @@ inline bool use_tn256(int O, int I, int ksize, int pad, int stride, int Ha, int 
 // dw[o][i][t] = scale[o] * sum_s slab[s][t][o][i]   (fixed summation order -> reproducible).
 // One workgroup per (o, 64 consecutive i): threads (t-major) read slab rows coalesced over i, the T x 64 block is
 // transposed through LDS and written out as 64*T contiguous floats (OIHW keeps t fastest).
-__global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* __restrict__ slab, float* __restrict__ dw,
-                                                           const float* __restrict__ scale, int S, int T, int O, int I,
-                                                           int accumulate, int out_map, int ncls) {
-    __shared__ float tile[9 * 64];
+__device__ __forceinline__ void wgrad_reduce_body(const float* __restrict__ slab, float* __restrict__ dw, const float* __restrict__ scale, int S, int T, int O, int I,
+                                                  int accumulate, int out_map, int ncls, int bx, int o, float* tile) {
     const int IB = (T == 1) ? 256 : 64;            // i-columns per workgroup: T * IB <= 576 items
-    const int o = blockIdx.y, ib = blockIdx.x * IB;
+    const int ib = bx * IB;
     const long plane = (long)O * I;
     const float sc = scale ? scale[o] : 1.f;
     const int ni = min(IB, I - ib);
@@ -617,11 +514,17 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* __restri
         }
     }
 }
+__global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* __restrict__ slab, float* __restrict__ dw,
+                                                           const float* __restrict__ scale, int S, int T, int O, int I,
+                                                           int accumulate, int out_map, int ncls) {
+    __shared__ float tile[9 * 64];
+    wgrad_reduce_body(slab, dw, scale, S, T, O, I, accumulate, out_map, ncls, blockIdx.x, blockIdx.y, tile);
+}
 
 // The reducers of several weight gradients in ONE launch (mi_conv_wgrad_reduce: the three convs of a bottleneck, round 5).  Alone each reducer is a 10-us
 // launch of 33 MB that, on the weight-gradient stream beside the data-gradient chain, waits ~35 us for its turn on the CUs - three times per block, with the
 // next weight gradient queued behind it.  The jobs travel in the kernel arguments; a workgroup finds its job by the prefix sums of their grids and then runs
-// wgrad_reduce_kernel's body unchanged (same fixed order, same bits).
+// wgrad_reduce_body unchanged (same fixed order, same bits).
 constexpr int MI_REDUCE_MAX_JOBS = 8;
 struct WgradReduceJob {
     const float* slab;
@@ -634,44 +537,6 @@ struct WgradReduceTable {
     int first[MI_REDUCE_MAX_JOBS + 1];
     int n;
 };
-__device__ __forceinline__ void wgrad_reduce_body(const float* __restrict__ slab, float* __restrict__ dw, const float* __restrict__ scale, int S, int T, int O, int I,
-                                                  int accumulate, int out_map, int ncls, int bx, int o, float* tile) {
-    const int IB = (T == 1) ? 256 : 64;
-    const int ib = bx * IB;
-    const long plane = (long)O * I;
-    const float sc = scale ? scale[o] : 1.f;
-    const int ni = min(IB, I - ib);
-    for (int item = threadIdx.x; item < T * IB; item += 256) {
-        const int t = item / IB, ii = item - t * IB;
-        float s = 0.f;
-        if (ii < ni) {
-            const float* src = slab + (long)t * plane + (long)o * I + ib + ii;
-            const long sstride = (long)T * plane;
-            int k = 0;
-            for (; k + 8 <= S; k += 8) {
-                float v[8];
-#pragma unroll
-                for (int u = 0; u < 8; ++u) v[u] = src[(long)(k + u) * sstride];
-#pragma unroll
-                for (int u = 0; u < 8; ++u) s += v[u];
-            }
-            for (; k < S; ++k) s += src[(long)k * sstride];
-        }
-        tile[ii * T + t] = s * sc;
-    }
-    __syncthreads();
-    if (out_map == 0) {
-        float* dst = dw + ((long)o * I + ib) * T;
-        for (int e = threadIdx.x; e < ni * T; e += 256) dst[e] = accumulate ? dst[e] + tile[e] : tile[e];
-    } else {
-        const int grp = o / ncls, cls = o - grp * ncls;
-        const int r = grp / 9, tap = grp - r * 9;
-        for (int e = threadIdx.x; e < ni; e += 256) {
-            const long d = (((long)r * ncls + cls) * I + ib + e) * 9 + tap;
-            dw[d] = accumulate ? dw[d] + tile[e] : tile[e];
-        }
-    }
-}
 __global__ __launch_bounds__(256) void wgrad_reduce_multi_kernel(WgradReduceTable tab) {
     __shared__ float tile[9 * 64];
     int j = 0;
@@ -717,212 +582,8 @@ struct WgradP3Params {
 };
 
 #ifdef MI_EXPERIMENTS   // opt-in kernel that does not win: built by tools/experiments/build.sh only, not part of libmi355seg.so
-__global__ __launch_bounds__(512, 1) void wgrad_p3_kernel(WgradP3Params p) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int grp = wave >> 2, wq = wave & 3;
-    const int tiles = p.o_tiles * p.i_tiles;
-    const int logical = mi_xcd_remap(blockIdx.x, tiles * 3 * p.S);
-    const int tile = logical % tiles, rest = logical / tiles;
-    const int ky = rest % 3, split = rest / 3;
-    const int ot = tile / p.i_tiles, it = tile - ot * p.i_tiles;
-    const int o0 = ot * TO, i0 = it * TI;
-    const long q_begin = (p.dbg & 16) ? 0 : (long)split * p.slabs_per_split * P3_KS;      // dbg 16: every split streams the same (L2-hot) rows
-    long left = (p.Q - q_begin + P3_KS - 1) / P3_KS;
-    const int ns = (int)(left < 0 ? 0 : (left < p.slabs_per_split ? left : p.slabs_per_split));
-    // ---- DMA roles.  lane -> (row within the piece, physical 16-B chunk); it fetches logical chunk physical ^ ((row & 7) << 1).
-    const int prow = lane >> 4, pch = lane & 15;
-    // zero rows (pad slots, rows outside the image, tile tails): 16 lanes read the 256-B zero page as one contiguous row
-    const char* zero = reinterpret_cast<const char*>(g_zero_page_tn) + pch * 16;
-    // A wave stages a SPAN of consecutive padded coordinates per slab (16 dy rows or 20 window rows): piece j = rows 4j .. 4j+3.
-    // The span's first row is wave-uniform, so its coordinates (q, padded column wp, image row h, pixel index pix) live in
-    // scalar registers and advance with scalar arithmetic: 64 coordinates = n0 whole image rows + r0 columns (+ one carry).
-    // Fast path (3 of 4 slabs at W = 97): the whole span lies inside the real columns of one valid image row -> the rows are
-    // consecutive pixels, address = scalar base + a per-lane constant (2 vector ops per piece).  Otherwise every lane derives
-    // its row's coordinates from the scalars (one carry at most: the plan requires span <= WP).
-    constexpr int NPMAX = P3_NPX;
-    const int np = grp == 0 ? P3_NPY : P3_NPX;
-    const int span = np * 4;
-    const int dh = grp == 0 ? 0 : (ky - 1) * p.d;
-    const int n0 = P3_KS / p.WP, r0 = P3_KS - n0 * p.WP;
-    const int pix_step = n0 * p.W + r0;                 // minus 2d when the column wraps into the next image row
-    const int span0 = grp == 0 ? wq * (P3_NPY * 4) : wq * (P3_NPX * 4);
-    int s_q = (int)(q_begin + span0 - (grp == 0 ? 0 : p.d));                 // may be < 0 (first window rows of split 0)
-    int s_wp, s_h, s_pix;
-    {
-        const long qs = (long)s_q + p.WP;                                     // >= 0 (d <= WP)
-        const int bh = (int)(qs / p.WP) - 1;
-        s_wp = (int)(qs % p.WP);
-        s_h = bh < 0 ? p.H - 1 : bh % p.H;                                    // row -1 precedes row 0 of image 0
-        s_pix = (bh + dh) * p.W + s_wp - p.d;
-    }
-    // the lane's channel chunk depends on (row & 7), i.e. on the parity of the piece: two per-lane constants
-    const __bf16* opnd = grp == 0 ? p.dY : p.X;
-    const int c0 = grp == 0 ? o0 : i0, cmax = grp == 0 ? p.O : p.I;
-    const unsigned row_bytes = (unsigned)cmax * 2u;
-    const int lch_e = pch ^ (((span0 + prow) & 7) << 1), lch_o = pch ^ (((span0 + prow + 4) & 7) << 1);
-    const bool ok_e = c0 + lch_e * 8 < cmax, ok_o = c0 + lch_o * 8 < cmax;
-    const unsigned off_e = prow * row_bytes + (c0 + lch_e * 8) * 2, off_o = prow * row_bytes + (c0 + lch_o * 8) * 2;
-    const char* opnd_b = reinterpret_cast<const char*>(opnd);
-    const int Qi = (int)p.Q;
-    int ld_s = 0;
-    auto stage_next = [&]() {
-        char* dst = smem + (ld_s & 3) * P3_SLAB + (grp == 0 ? wq * (P3_NPY * 1024) : P3_DY_BYTES + wq * (P3_NPX * 1024));
-        const bool fast = s_q >= 0 && s_q + span <= Qi && s_wp >= p.d && s_wp + span <= p.W + p.d && (unsigned)(s_h + dh) < (unsigned)p.H;
-        if (fast) {
-            const char* P = opnd_b + (unsigned long)(unsigned)s_pix * row_bytes;              // scalar
-#pragma unroll
-            for (int j = 0; j < NPMAX; ++j)
-                if (j < np) {
-                    const char* src = P + (j * 4 * row_bytes + ((j & 1) ? off_o : off_e));
-                    glds16_tn(((j & 1) ? ok_o : ok_e) ? src : zero, dst + j * 1024);
-                }
-        } else {
-#pragma unroll
-            for (int j = 0; j < NPMAX; ++j)
-                if (j < np) {
-                    const int r = j * 4 + prow;
-                    int wp = s_wp + r;
-                    const bool c = wp >= p.WP;
-                    wp -= c ? p.WP : 0;
-                    int h = s_h + (c ? 1 : 0);
-                    h = h >= p.H ? h - p.H : h;
-                    const int pix = s_pix + r - (c ? 2 * p.d : 0);
-                    const bool ok = ((j & 1) ? ok_o : ok_e) && (unsigned)(s_q + r) < (unsigned)Qi && (unsigned)(wp - p.d) < (unsigned)p.W &&
-                                    (unsigned)(h + dh) < (unsigned)p.H;
-                    const char* src = opnd_b + (unsigned long)(unsigned)(ok ? pix : 0) * row_bytes + (((j & 1) ? off_o : off_e) - prow * row_bytes);
-                    glds16_tn(ok ? src : zero, dst + j * 1024);
-                }
-        }
-        // the span's first row in the next slab (scalar)
-        s_q += P3_KS;
-        s_wp += r0;
-        const int c = s_wp >= p.WP ? 1 : 0;
-        s_wp -= c ? p.WP : 0;
-        s_h += n0 + c;
-        s_h = s_h >= p.H ? s_h - p.H : s_h;
-        s_pix += pix_step - (c ? 2 * p.d : 0);
-        ++ld_s;
-    };
-
-    // ---- compute roles: wave (wi, wo) owns i in [wi*32, +32) x o in [wo*64, +64) for the three taps kx
-    const int wi = wq, wo = grp;
-    f32x4 acc[3][2][4];
-#pragma unroll
-    for (int kx = 0; kx < 3; ++kx)
-#pragma unroll
-        for (int a = 0; a < 2; ++a)
-#pragma unroll
-            for (int b = 0; b < 4; ++b) acc[kx][a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
-    const int g = lane >> 4, q4 = (lane & 15) >> 2, pc = lane & 3;
-    const int rk0 = g * 4 + q4;
-    const int y_off = rk0 * ROWB + (pc & 1) * 8, y_sw = (rk0 & 7) << 1;
-    int x_off[3], x_sw[3];
-#pragma unroll
-    for (int kx = 0; kx < 3; ++kx) {
-        const int rk = rk0 + kx * p.d;
-        x_off[kx] = P3_DY_BYTES + rk * ROWB + (pc & 1) * 8;
-        x_sw[kx] = (rk & 7) << 1;
-    }
-    union Frag { bf16x8 v; s16x4 h[2]; };
-    Frag yf[2][4], xf[2][3][2];
-    const unsigned lds0 = lds_address(smem);
-    auto read_frags = [&](int s) {
-        unsigned sb = lds0 + (s & 3) * P3_SLAB;
-        asm volatile("" : "+v"(sb));          // opaque: keeps the 10 fragment offsets, not 40 precomputed per-slot addresses, in registers
-#pragma unroll
-        for (int b = 0; b < 4; ++b) {
-            const unsigned base = sb + y_off + ((((wo * 4 + b) * 2 + (pc >> 1)) ^ y_sw) << 4);
-            yf[0][b].h[0] = tr_read_lds<0>(base);
-            yf[0][b].h[1] = tr_read_lds<16 * ROWB>(base);
-            yf[1][b].h[0] = tr_read_lds<32 * ROWB>(base);
-            yf[1][b].h[1] = tr_read_lds<48 * ROWB>(base);
-        }
-#pragma unroll
-        for (int kx = 0; kx < 3; ++kx)
-#pragma unroll
-            for (int a = 0; a < 2; ++a) {
-                const unsigned base = sb + x_off[kx] + ((((wi * 2 + a) * 2 + (pc >> 1)) ^ x_sw[kx]) << 4);
-                xf[0][kx][a].h[0] = tr_read_lds<0>(base);
-                xf[0][kx][a].h[1] = tr_read_lds<16 * ROWB>(base);
-                xf[1][kx][a].h[0] = tr_read_lds<32 * ROWB>(base);
-                xf[1][kx][a].h[1] = tr_read_lds<48 * ROWB>(base);
-            }
-    };
-    auto mfma_half = [&](int ks) {
-#pragma unroll
-        for (int kx = 0; kx < 3; ++kx)
-#pragma unroll
-            for (int a = 0; a < 2; ++a)
-#pragma unroll
-                for (int b = 0; b < 4; ++b)
-                    acc[kx][a][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xf[ks][kx][a].v, yf[ks][b].v, acc[kx][a][b], 0, 0, 0);
-    };
-
-    // ---- main loop (interval scheme of igemm_pp.hip) ----------------------------------------------------------------------------
-    for (int s = 0; s < 3 && s < ns; ++s) stage_next();
-    if (ns >= 3) {
-        if (grp == 0) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * P3_NPY) : "memory");
-        else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * P3_NPX) : "memory");
-    } else {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    __builtin_amdgcn_s_barrier();
-    if (grp == 1) __builtin_amdgcn_s_barrier();
-    const int dbg = p.dbg;
-    for (int s = 0; s < ns; ++s) {
-        if (s + 3 < ns && !(dbg & 1)) stage_next();
-        if (!(dbg & 2) || s == 0) read_frags(s);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_sched_barrier(0);
-        if (grp == 1) {
-            if (s + 3 < ns) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * P3_NPX) : "memory");
-            else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
-        __builtin_amdgcn_s_barrier();
-        __builtin_amdgcn_s_setprio(1);
-        if (!(dbg & 4)) {
-            mfma_half(0);
-            mfma_half(1);
-        }
-        __builtin_amdgcn_s_setprio(0);
-        if (grp == 0) {
-            if (s + 3 < ns) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * P3_NPY) : "memory");
-            else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
-        __builtin_amdgcn_s_barrier();
-    }
-    if (grp == 0) __builtin_amdgcn_s_barrier();
-
-    // ---- partial planes: slab[split][ky*3+kx][o][i], i fastest; lane owns o = column, i .. i+3 = rows
-    if (dbg & 8) {
-#pragma unroll
-        for (int kx = 0; kx < 3; ++kx)
-#pragma unroll
-            for (int a = 0; a < 2; ++a)
-#pragma unroll
-                for (int b = 0; b < 4; ++b) asm volatile("" ::"v"(acc[kx][a][b]));
-        return;
-    }
-    const int fcol = lane & 15, fq = lane >> 4;
-#pragma unroll
-    for (int kx = 0; kx < 3; ++kx) {
-        float* plane = p.slab + ((long)(split * 9 + ky * 3 + kx) * p.O) * p.I;
-#pragma unroll
-        for (int b = 0; b < 4; ++b) {
-            const int o = o0 + wo * 64 + b * 16 + fcol;
-            if (o >= p.O) continue;
-#pragma unroll
-            for (int a = 0; a < 2; ++a) {
-                const int i = i0 + wi * 32 + a * 16 + fq * 4;
-                if (i >= p.I) continue;
-                *reinterpret_cast<f32x4*>(plane + (long)o * p.I + i) = acc[kx][a][b];
-            }
-        }
-    }
-}
-#endif  // MI_EXPERIMENTS
+#include "../../tools/experiments/wgrad_p3.inc"
+#endif
 
 // ---------------------------------------------------------------------------------------------------------------------------
 // wgrad_q3_kernel: the fused-row idea in the structure that the per-tap kernel has proven - 4 waves, TWO workgroups per CU that
@@ -947,12 +608,8 @@ __global__ __launch_bounds__(256, 2) void wgrad_q3_kernel(WgradP3Params p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wq = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int tiles = p.o_tiles * p.i_tiles;
-    const int logical = mi_xcd_remap(blockIdx.x, tiles * 3 * p.S);
-    const int tile = logical % tiles, rest = logical / tiles;
-    const int ky = rest % 3, split = rest / 3;
-    const int ot = tile / p.i_tiles, it = tile - ot * p.i_tiles;
-    const int o0 = ot * Q3_TO, i0 = it * TI;
+    const WgDecode wg = wg_decode_tile<Q3_TO, TI>(blockIdx.x, p.o_tiles * p.i_tiles * 3 * p.S, p.o_tiles, p.i_tiles, 3);
+    const int ky = wg.mid, split = wg.split, o0 = wg.o0, i0 = wg.i0;
     const long q_begin = (long)split * p.slabs_per_split * P3_KS;
     long left = (p.Q - q_begin + P3_KS - 1) / P3_KS;
     const int ns = (int)(left < 0 ? 0 : (left < p.slabs_per_split ? left : p.slabs_per_split));
@@ -1143,7 +800,6 @@ __global__ __launch_bounds__(256, 2) void wgrad_q3_kernel(WgradP3Params p) {
         }
     }
 
-    const int fcol = lane & 15, fq = lane >> 4;
     if (Q3_DBG(8)) {
 #pragma unroll
         for (int kx = 0; kx < 3; ++kx)
@@ -1154,20 +810,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_q3_kernel(WgradP3Params p) {
         return;
     }
 #pragma unroll
-    for (int kx = 0; kx < 3; ++kx) {
-        float* plane = p.slab + ((long)(split * 9 + ky * 3 + kx) * p.O) * p.I;
-#pragma unroll
-        for (int b = 0; b < 4; ++b) {
-            const int o = o0 + b * 16 + fcol;
-            if (o >= p.O) continue;
-#pragma unroll
-            for (int a = 0; a < 2; ++a) {
-                const int i = i0 + wq * 32 + a * 16 + fq * 4;
-                if (i >= p.I) continue;
-                *reinterpret_cast<f32x4*>(plane + (long)o * p.I + i) = acc[kx][a][b];
-            }
-        }
-    }
+    for (int kx = 0; kx < 3; ++kx) slab_store(p.slab + ((long)(split * 9 + ky * 3 + kx) * p.O) * p.I, p.I, p.O, p.I, o0, i0 + wq * 32, lane, acc[kx]);
 }
 
 // Split / grid of the fused 3x3 kernel; returns false when the shape should stay on the per-tap kernel.
@@ -1199,25 +842,9 @@ bool p3_plan(int B, int H, int W, int O, int I, int dil, bool force, P3Plan& pl,
     return O >= 96 && I >= 96 && pl.slabs_per_split >= 8;
 }
 
-int pick_splits(long M, int tiles) {
-    // 512 workgroup slots (256 CUs x 2 resident).  Minimise rounds x (K-steps per split + ~6 steps of fixed cost per
-    // workgroup: prologue, pipeline fill, slab write); never fewer than 8 K-steps per split.
-    const long steps = (M + KP - 1) / KP;
-    int best = 1;
-    double best_cost = 1e30;
-    for (int s = 1; s <= 64; ++s) {
-        const long per = (steps + s - 1) / s;
-        if (s > 1 && per < 8) break;
-        const long blocks = (long)tiles * s;
-        const long rounds = (blocks + 511) / 512;
-        const double cost = (double)rounds * (double)(per + 6);
-        if (cost < best_cost - 1e-9) {
-            best_cost = cost;
-            best = s;
-        }
-    }
-    return best;
-}
+// 512 workgroup slots (256 CUs x 2 resident).  Minimise rounds x (K-steps per split + ~6 steps of fixed cost per
+// workgroup: prologue, pipeline fill, slab write); never fewer than 8 K-steps per split (the model: wgrad_pick_splits).
+int pick_splits(long M, int tiles) { return wgrad_pick_splits(M, tiles, KP, 8, 6, 512, 64); }
 
 }  // namespace
 
@@ -1248,6 +875,14 @@ extern "C" size_t mi_conv_wgrad_workspace(int B, int Ho, int Wo, int O, int I, i
     return need;
 }
 
+// "opt in to LDS bytes of dynamic LDS for this instantiation (once per device), launch it"
+template <auto KERN, int LDS, class P>
+static void launch_lds(unsigned grid, unsigned block, hipStream_t st, const P& p) {
+    static std::atomic<uint64_t> attr{0};
+    mi_allow_dynamic_lds((const void*)KERN, LDS, attr);
+    hipLaunchKernelGGL(KERN, dim3(grid), dim3(block), LDS, st, p);
+}
+
 static int launch_p3(const void* dy, const void* x, float* ws, int H, int W, int O, int I, int dil, const P3Plan& pl, int BH, hipStream_t st, bool q3 = false) {
     WgradP3Params q;
     q.dY = (const __bf16*)dy;
@@ -1266,16 +901,13 @@ static int launch_p3(const void* dy, const void* x, float* ws, int H, int W, int
     q.o_tiles = pl.o_tiles;
     q.i_tiles = pl.i_tiles;
     q.dbg = mi_sw().p3_dbg;
+    const unsigned nb = (unsigned)(pl.o_tiles * pl.i_tiles * 3 * pl.S);
     if (q3) {
-        static std::atomic<uint64_t> attrq{0};
-        mi_allow_dynamic_lds((const void*)wgrad_q3_kernel, Q3_LDS, attrq);
-        hipLaunchKernelGGL(wgrad_q3_kernel, dim3((unsigned)(pl.o_tiles * pl.i_tiles * 3 * pl.S)), dim3(256), Q3_LDS, st, q);
+        launch_lds<wgrad_q3_kernel, Q3_LDS>(nb, 256, st, q);
         return 0;
     }
 #ifdef MI_EXPERIMENTS
-    static std::atomic<uint64_t> attr{0};
-    mi_allow_dynamic_lds((const void*)wgrad_p3_kernel, P3_LDS, attr);
-    hipLaunchKernelGGL(wgrad_p3_kernel, dim3((unsigned)(pl.o_tiles * pl.i_tiles * 3 * pl.S)), dim3(512), P3_LDS, st, q);
+    launch_lds<wgrad_p3_kernel, P3_LDS>(nb, 512, st, q);
     return 0;
 #else
     return -1;
@@ -1441,33 +1073,18 @@ static int mi_conv_wgrad_impl(const void* dy, const void* x, float* dw, int B, i
     p.S = w.S;
     p.rows_per_split = w.steps * w.step_rows;
     const hipStream_t sq = (hipStream_t)stream;
+    const unsigned nb = (unsigned)(p.o_tiles * p.i_tiles * p.T * p.S);             // (the deep stream has T == 1)
     if (w.kernel == MI_WPLAN_TN256) {
-        static std::atomic<uint64_t> attr2[2];
-        mi_allow_dynamic_lds((const void*)wgrad_tn256_kernel<1>, LDS2_BYTES, attr2[0]);
-        mi_allow_dynamic_lds((const void*)wgrad_tn256_kernel<2>, LDS2_BYTES, attr2[1]);
-        const unsigned nb = (unsigned)(p.o_tiles * p.i_tiles * p.T * p.S);
-        if (w.mode == 2)
-            hipLaunchKernelGGL(wgrad_tn256_kernel<2>, dim3(nb), dim3(256), LDS2_BYTES, sq, p);
-        else
-            hipLaunchKernelGGL(wgrad_tn256_kernel<1>, dim3(nb), dim3(256), LDS2_BYTES, sq, p);
+        if (w.mode == 2) launch_lds<wgrad_tn256_kernel<2>, LDS2_BYTES>(nb, 256, sq, p);
+        else launch_lds<wgrad_tn256_kernel<1>, LDS2_BYTES>(nb, 256, sq, p);
         MI_CHECK_LAUNCH("mi_conv_wgrad (128 x 256 tile)");
     } else if (w.kernel == MI_WPLAN_S4) {
-        static std::atomic<uint64_t> attr4;
-        mi_allow_dynamic_lds((const void*)wgrad_s4_kernel, LDS4_BYTES, attr4);
-        hipLaunchKernelGGL(wgrad_s4_kernel, dim3((unsigned)(p.o_tiles * p.i_tiles * p.S)), dim3(256), LDS4_BYTES, sq, p);
+        launch_lds<wgrad_s4_kernel, LDS4_BYTES>(nb, 256, sq, p);
         MI_CHECK_LAUNCH("mi_conv_wgrad (1x1 deep stream)");
     } else {
-        static std::atomic<uint64_t> attr_set[3];
-        mi_allow_dynamic_lds((const void*)wgrad_tn_kernel<0>, LDS_BYTES, attr_set[0]);
-        mi_allow_dynamic_lds((const void*)wgrad_tn_kernel<1>, LDS_BYTES, attr_set[1]);
-        mi_allow_dynamic_lds((const void*)wgrad_tn_kernel<2>, LDS_BYTES, attr_set[2]);
-        const unsigned nblocks = (unsigned)(p.o_tiles * p.i_tiles * p.T * p.S);
-        if (w.mode == 2)
-            hipLaunchKernelGGL(wgrad_tn_kernel<2>, dim3(nblocks), dim3(256), LDS_BYTES, sq, p);
-        else if (w.mode == 1)
-            hipLaunchKernelGGL(wgrad_tn_kernel<1>, dim3(nblocks), dim3(256), LDS_BYTES, sq, p);
-        else
-            hipLaunchKernelGGL(wgrad_tn_kernel<0>, dim3(nblocks), dim3(256), LDS_BYTES, sq, p);
+        if (w.mode == 2) launch_lds<wgrad_tn_kernel<2>, LDS_BYTES>(nb, 256, sq, p);
+        else if (w.mode == 1) launch_lds<wgrad_tn_kernel<1>, LDS_BYTES>(nb, 256, sq, p);
+        else launch_lds<wgrad_tn_kernel<0>, LDS_BYTES>(nb, 256, sq, p);
         MI_CHECK_LAUNCH("mi_conv_wgrad");
     }
     int o_real = O;

@@ -117,6 +117,8 @@ CONV_CASES = [
 # for 448, so S differs.  d in {1, 2, 4}; 320 -> 256: a ragged i tile (128-wide); 256 -> 264: a ragged o tile (64-wide); 270 x 18, d = 1: WP = W + 2 d = 20,
 # the narrowest map the kernel takes - 270 x 17 (WP = 19) falls to tn.m1, with S = 14 and a ragged last split.
 # s4 / tn256 / tn: S = 1 on the 9 x 11 / 13 x 15 maps, S > 1 with a last split shorter than the others on the larger ones.
+# 72 -> 136 on 2 x 33 x 35 (tn.m1 and s4, the kernels that share the fragment block and, with every other one, the workgroup decode and the slab store of
+# csrc/wgrad_common.h): two o tiles of which the second holds 8 channels, a 72-channel i tile, S > 1 with a short last split whose last K step has 6 pixels.
 WGRAD_CASES = [
     WgradCase('q3', 'q3.deferred', 2, 67, 70, 256, 256, 3, 1, 1, 0),
     WgradCase('q3', 'q3.deferred', 2, 66, 69, 256, 256, 3, 1, 2, 0),
@@ -128,10 +130,12 @@ WGRAD_CASES = [
     WgradCase('tn.m1', 'tn.m1.deferred', 2, 270, 17, 256, 256, 3, 1, 1, 0),
     WgradCase('tn.m1', 'tn.m1.deferred', 2, 13, 15, 64, 64, 3, 1, 1, 0),
     WgradCase('tn.m1', 'tn.m1.deferred', 2, 45, 47, 64, 72, 3, 1, 1, 0),
+    WgradCase('tn.m1', 'tn.m1.deferred', 2, 33, 35, 72, 136, 3, 1, 1, 0),
     WgradCase('tn.m0', 'tn.m0.deferred', 2, 33, 35, 64, 128, 3, 2, 1, 0),
     WgradCase('tn.m0', 'tn.m0.deferred', 2, 65, 67, 64, 136, 1, 2, 1, 0),
     WgradCase('s4', 's4.deferred', 2, 9, 11, 64, 256, 1, 1, 1, 0),
     WgradCase('s4', 's4.deferred', 2, 45, 47, 64, 256, 1, 1, 1, 0),
+    WgradCase('s4', 's4.deferred', 2, 33, 35, 72, 136, 1, 1, 1, 0),
     WgradCase('tn256.m2', 'tn256.m2.deferred', 2, 9, 11, 512, 1024, 1, 1, 1, 0),
     WgradCase('tn256.m2', 'tn256.m2.deferred', 2, 45, 47, 512, 1024, 1, 1, 1, 0),
     WgradCase('tn256.m2.aspp', 'tn256.m2.aspp.deferred', 2, 33, 35, 768, 704, 1, 1, 1, 1),

@@ -97,6 +97,12 @@ def test_the_cases_hold_the_edges_they_claim(conv_plans, wgrad_plans):
         ss = {min(one.S, 2) for c, (one, de) in wg if one.kernel == 0 and one.mode == mode}
         assert ss == {1, 2}, "tn.m%d: S = 1 and S > 1" % mode
     assert any(one.kernel == 0 and one.mode == 1 and one.S > 1 and c.Cout % 128 for c, (one, de) in wg), "no tn.m1 case with several splits and a ragged o tile"
+    # the shared decode / slab store (csrc/wgrad_common.h) on the 128 x 128 tile: a partial LAST o tile behind a full one and a partial i tile in one launch,
+    # with several splits, a short last split and a partial last K step - for the per-tap kernel and for the deep stream
+    for kern, mode, name in ((0, 1, "tn.m1"), (4, 0, "s4")):
+        assert any(one.kernel == kern and one.mode == mode and one.o_tiles > 1 and c.Cout % 128 and c.Cin % 128 and one.S > 1
+                   and M % (one.steps * one.step_rows) and M % one.step_rows
+                   for c, (one, de) in wg for M in [c.B * out_hw(c)[0] * out_hw(c)[1]]), "no %s case with a ragged last o tile, a ragged i tile and a ragged last split" % name
     assert any(c.out_map == 1 for c in WGRAD_CASES), "no out_map 1 (.aspp) case"
 
 
