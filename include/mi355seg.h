@@ -700,6 +700,43 @@ typedef struct MiAugSample {
 int mi_augment_batch(void* table_dev, const void* table_host, int B, int out_h, int out_w, int lab_h, int lab_w, float* out_img, float* out_lab,
                      void* stream);
 
+/* ---- the `pra` input transform of a batch (csrc/augment_pra.hip) ---------------------------------------------------------------------------
+ * PraNet's polyp transform (the operations, probabilities and ranges of core/components/augment.py:55-85, the arithmetic defined on PIL; the
+ * contract is in DESIGN.md) for decoded uint8 images and grey masks; the results equal PIL's bit for bit.  Everything random or derived is
+ * decided by the host (host/pra_augment.py) and arrives as one MiPraSample per image; images of a batch may differ in size.  Four launches
+ * per batch whatever B is: gather + colour -> win, horizontal pass -> tmp, vertical pass + normalise, mask.
+ *
+ * Geometry: sym = 4 * transpose + 2 * flip_rows + flip_cols names one of the eight symmetries of the square; pixel (y, x) of the transformed
+ * frame (W x H when transposed, else H x W) is source pixel (fr(a), fc(b)), (a, b) = transpose ? (x, y) : (y, x), fr(a) = flip_rows ? H-1-a : a,
+ * fc(b) = flip_cols ? W-1-b : b.  The window [y0, y0 + wh) x [x0, x0 + ww) of the transformed frame is what is resized to out_h x out_w.
+ * Colour, per pixel of the window only: when hsv != 0, PIL rgb2hsv, H = (H + hue_shift) & 255, S = lut_s[S], V = lut_v[V], PIL hsv2rgb;
+ * then, when bc != 0, every channel through lut_bc.  (The HSV round trip is lossy: it is skipped, not run with zero shifts.)
+ * Resize: PIL BILINEAR - horizontal pass, then vertical, each rounding to uint8; a pass whose size does not change is skipped and its table
+ * pointers are NULL.  Tables as for mi_augment_batch: hcoef [hk][out_w], vcoef [vk][out_h], 22 fraction bits, tap-major; hbound [out_w][2],
+ * vbound [out_h][2] = {first index in the window, taps}; hk / vk must be 2 * ceil(max(in / out, 1)) + 1.
+ * Mask: output (y, x) shows window pixel (ny[y], nx[x]) (PIL NEAREST, computed by the host) through mask_table, as float.
+ * Byte buffers: 4-byte aligned, readable / writable up to their size rounded up to a multiple of 16.  win: wh * wstride bytes,
+ * wstride = 12 * ceil(ww / 4); tmp: wh * tstride bytes, tstride = 12 * ceil(out_w / 4) (only when ww != out_w). */
+typedef struct MiPraSample {
+    const uint8_t* img;       /* [H][W][3] decoded RGB */
+    const uint8_t* mask;      /* [H][W] grey levels, NULL: no mask */
+    uint8_t* win;
+    uint8_t* tmp;
+    const int32_t* hcoef;
+    const int32_t* hbound;
+    const int32_t* vcoef;
+    const int32_t* vbound;
+    const int32_t* ny;        /* [out_h] */
+    const int32_t* nx;        /* [out_w] */
+    int32_t H, W, sym, y0, x0, wh, ww, hk, vk, wstride, tstride;
+    int32_t hsv, hue_shift, bc;
+    float mean[3], std[3];
+    uint8_t lut_s[256], lut_v[256], lut_bc[256], mask_table[256];
+} MiPraSample;
+/* table_dev: the B records in device memory; table_host: the same records, read here to validate them and to size the launches.
+ * out_img [B][3][out_h][out_w] fp32, out_mask [B][out_h][out_w] fp32 (NULL when no sample has a mask). */
+int mi_augment_pra_batch(const void* table_dev, const void* table_host, int B, int out_h, int out_w, float* out_img, float* out_mask, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

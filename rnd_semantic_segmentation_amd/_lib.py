@@ -136,6 +136,7 @@ SIGNATURES = {
     "mi_gcca_f32": (I, [P, L, P, L, P, L, P, L] + [I] * 5 + [P]),
     "mi_gpoint_f32": (I, [I, P, L, P, L, P, P, I, P, L, L, I, P]),
     "mi_augment_batch": (I, [P, P, I, I, I, I, I, P, P, P]),
+    "mi_augment_pra_batch": (I, [P, P, I, I, I, P, P, P]),
 }
 
 class MiProbSource(ctypes.Structure):
@@ -153,6 +154,17 @@ class MiAugSample(ctypes.Structure):
                 ("tstride", c_int), ("lab_sh", c_int), ("lab_sw", c_int),
                 ("n_ops", c_int), ("op", c_int * 4), ("hue_shift", c_int), ("factor", c_float * 4),
                 ("to_bgr255", c_int), ("mean", c_float * 3), ("std", c_float * 3), ("lab_table", ctypes.c_uint8 * 256)]
+
+
+class MiPraSample(ctypes.Structure):
+    """One image of mi_augment_pra_batch (include/mi355seg.h): buffers, symmetry and window, resample and nearest tables, colour tables,
+    normalisation, mask table."""
+    _fields_ = [("img", c_void_p), ("mask", c_void_p), ("win", c_void_p), ("tmp", c_void_p), ("hcoef", c_void_p), ("hbound", c_void_p),
+                ("vcoef", c_void_p), ("vbound", c_void_p), ("ny", c_void_p), ("nx", c_void_p),
+                ("H", c_int), ("W", c_int), ("sym", c_int), ("y0", c_int), ("x0", c_int), ("wh", c_int), ("ww", c_int), ("hk", c_int), ("vk", c_int),
+                ("wstride", c_int), ("tstride", c_int), ("hsv", c_int), ("hue_shift", c_int), ("bc", c_int),
+                ("mean", c_float * 3), ("std", c_float * 3),
+                ("lut_s", ctypes.c_uint8 * 256), ("lut_v", ctypes.c_uint8 * 256), ("lut_bc", ctypes.c_uint8 * 256), ("mask_table", ctypes.c_uint8 * 256)]
 
 
 _lib = None

@@ -11,32 +11,13 @@
 // uint8 rows are read as aligned dwords (a byte span is covered by the dwords around it and shifted into place) and written as dwords;
 // single bytes only at image tails, padding borders and for the label gather.
 //
-// Arithmetic that decides bits is spelled with explicitly rounded operations and contraction is off: PIL's blend is fp32 without FMA, its
-// HSV conversion mixes fp32 and fp64 (see rgb_to_hsv), Normalize is four separate fp32 roundings.
-#include "mi_common.h"
+// Arithmetic that decides bits is spelled with explicitly rounded operations and contraction is off (augment_common.h, shared with the `pra`
+// transform of augment_pra.hip).
+#include "augment_common.h"
 
 #pragma clang fp contract(off)
 
 namespace {
-
-constexpr int AUG_THREADS = 256;
-constexpr int PRECISION_BITS = 22;      // PIL Resample.c
-
-// One rounding each, never contracted (the pragma above covers this file's own expressions; the __f*_rn helpers of the HIP headers are
-// plain operators compiled outside it, so they are not used here).
-__device__ __forceinline__ float f_add(float a, float b) { return a + b; }
-__device__ __forceinline__ float f_sub(float a, float b) { return a - b; }
-__device__ __forceinline__ float f_mul(float a, float b) { return a * b; }
-__device__ __forceinline__ float f_div(float a, float b) { return a / b; }      // correctly rounded: hipcc's default for fp32 division
-__device__ __forceinline__ double d_add(double a, double b) { return a + b; }
-__device__ __forceinline__ double d_sub(double a, double b) { return a - b; }
-__device__ __forceinline__ double d_mul(double a, double b) { return a * b; }
-
-struct Px {
-    int r, g, b;
-};
-
-__device__ __forceinline__ int clip8(int v) { return v < 0 ? 0 : (v > 255 ? 255 : v); }
 
 __device__ __forceinline__ int grey_of(const Px& p) { return (19595 * p.r + 38470 * p.g + 7471 * p.b + 0x8000) >> 16; }      // PIL L = ITU-R 601-2
 
@@ -44,57 +25,6 @@ __device__ __forceinline__ int grey_of(const Px& p) { return (19595 * p.r + 3847
 __device__ __forceinline__ int blend1(int deg, int v, float f) {
     const float t = f_add((float)deg, f_mul(f, (float)(v - deg)));
     return t <= 0.f ? 0 : (t >= 255.f ? 255 : (int)t);
-}
-
-// PIL Convert.c rgb2hsv: s, rc, gc, bc and the r == max branch in fp32; the other two branches and the wrap into [0, 1) are evaluated in
-// fp64 (the literals 2.0, 4.0, 6.0, 1.0 are doubles in C) and rounded to fp32; the scaling to uint8 in fp64.
-__device__ __forceinline__ void rgb_to_hsv(const Px& p, int& H, int& S, int& V) {
-    const int mx = max(p.r, max(p.g, p.b)), mn = min(p.r, min(p.g, p.b));
-    V = mx;
-    if (mx == mn) {
-        H = 0;
-        S = 0;
-        return;
-    }
-    const float cr = (float)(mx - mn);
-    const float s = f_div(cr, (float)mx);
-    const float rc = f_div((float)(mx - p.r), cr), gc = f_div((float)(mx - p.g), cr), bc = f_div((float)(mx - p.b), cr);
-    float h;
-    if (p.r == mx)
-        h = f_sub(bc, gc);
-    else if (p.g == mx)
-        h = (float)d_sub(d_add(2.0, (double)rc), (double)bc);
-    else
-        h = (float)d_sub(d_add(4.0, (double)gc), (double)rc);
-    h = (float)fmod(d_add((double)h / 6.0, 1.0), 1.0);
-    H = clip8((int)d_mul((double)h, 255.0));
-    S = clip8((int)d_mul((double)s, 255.0));
-}
-
-// PIL Convert.c hsv2rgb: fp64 throughout, round half to even
-__device__ __forceinline__ Px hsv_to_rgb(int H, int S, int V) {
-    Px o;
-    if (S == 0) {
-        o.r = o.g = o.b = V;
-        return o;
-    }
-    const double x = d_mul((double)H, 6.0) / 255.0;
-    const double fi = floor(x);
-    const double f = d_sub(x, fi);
-    const double fs = (double)S / 255.0;
-    const double v = (double)V;
-    const int p = clip8((int)rint(d_mul(v, d_sub(1.0, fs))));
-    const int q = clip8((int)rint(d_mul(v, d_sub(1.0, d_mul(fs, f)))));
-    const int t = clip8((int)rint(d_mul(v, d_sub(1.0, d_mul(fs, d_sub(1.0, f))))));
-    switch ((int)fi % 6) {
-    case 0: o.r = V, o.g = t, o.b = p; break;
-    case 1: o.r = q, o.g = V, o.b = p; break;
-    case 2: o.r = p, o.g = V, o.b = t; break;
-    case 3: o.r = p, o.g = q, o.b = V; break;
-    case 4: o.r = t, o.g = p, o.b = V; break;
-    default: o.r = V, o.g = p, o.b = q; break;
-    }
-    return o;
 }
 
 // ops [0, n) of the sample on one pixel; contrast_deg: int(mean(grey) + 0.5) of the image as it stood when the contrast op ran
@@ -125,40 +55,6 @@ __device__ __forceinline__ int contrast_pos(const MiAugSample& d) {
     for (int k = 0; k < d.n_ops; ++k)
         if (d.op[k] == 2) return k;
     return -1;
-}
-
-// four consecutive pixels (12 bytes, 4-byte aligned) <-> three dwords
-__device__ __forceinline__ void unpack4(const uint32_t w[3], Px px[4]) {
-    uint8_t b[12];
-#pragma unroll
-    for (int i = 0; i < 12; ++i) b[i] = (w[i >> 2] >> (8 * (i & 3))) & 255u;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) px[i].r = b[3 * i], px[i].g = b[3 * i + 1], px[i].b = b[3 * i + 2];
-}
-__device__ __forceinline__ void pack4(const Px px[4], uint32_t w[3]) {
-    uint32_t b[12];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) b[3 * i] = px[i].r, b[3 * i + 1] = px[i].g, b[3 * i + 2] = px[i].b;
-#pragma unroll
-    for (int i = 0; i < 3; ++i) w[i] = b[4 * i] | (b[4 * i + 1] << 8) | (b[4 * i + 2] << 16) | (b[4 * i + 3] << 24);
-}
-
-// 12 bytes from any address as three dwords: aligned loads of the dwords around them, shifted into place.  Reads at most up to the next
-// 4-byte boundary after p + 12 (the buffers are readable to their size rounded up, mi355seg.h).
-__device__ __forceinline__ void load_span12(const uint8_t* p, uint32_t w[3]) {
-    const uintptr_t a = reinterpret_cast<uintptr_t>(p);
-    const int s = (int)(a & 3);
-    const uint32_t* q = reinterpret_cast<const uint32_t*>(a - s);
-    const uint32_t d0 = q[0], d1 = q[1], d2 = q[2];
-    if (s == 0) {
-        w[0] = d0, w[1] = d1, w[2] = d2;
-        return;
-    }
-    const uint32_t d3 = q[3];
-    const int sh = 8 * s;
-    w[0] = (uint32_t)((((uint64_t)d1 << 32) | d0) >> sh);
-    w[1] = (uint32_t)((((uint64_t)d2 << 32) | d1) >> sh);
-    w[2] = (uint32_t)((((uint64_t)d3 << 32) | d2) >> sh);
 }
 
 __device__ __forceinline__ int contrast_degenerate(const MiAugSample& d) {
@@ -246,30 +142,7 @@ __global__ __launch_bounds__(AUG_THREADS) void aug_hpass_kernel(const MiAugSampl
             const int x = d.cx0 + gg * 4 + i;
             out[i].r = out[i].g = out[i].b = 0;
             if (x >= d.cx1) continue;
-            int x0 = d.hbound[2 * x], n = d.hbound[2 * x + 1];
-            x0 = min(max(x0, 0), d.W);                       // a table can never steer a read out of the row
-            n = min(min(n, d.hk), d.W - x0);
-            const uintptr_t a = reinterpret_cast<uintptr_t>(row + (long)x0 * 3);
-            const int s = (int)(a & 3), nb = 3 * n;
-            const uint32_t* q = reinterpret_cast<const uint32_t*>(a - s);
-            const int nd = (s + nb + 3) >> 2;
-            int acc[3] = {1 << (PRECISION_BITS - 1), 1 << (PRECISION_BITS - 1), 1 << (PRECISION_BITS - 1)};
-            int tap = 0, ch = 0, b = -s;
-            int c = n > 0 ? d.hcoef[x] : 0;
-            for (int w = 0; w < nd; ++w) {
-                const uint32_t v = q[w];
-#pragma unroll
-                for (int k = 0; k < 4; ++k, ++b) {
-                    if (b >= 0 && b < nb) {
-                        acc[ch] += c * (int)((v >> (8 * k)) & 255u);
-                        if (++ch == 3) {
-                            ch = 0;
-                            if (++tap < n) c = d.hcoef[(long)tap * d.sw + x];
-                        }
-                    }
-                }
-            }
-            out[i].r = clip8(acc[0] >> PRECISION_BITS), out[i].g = clip8(acc[1] >> PRECISION_BITS), out[i].b = clip8(acc[2] >> PRECISION_BITS);
+            out[i] = resample_row_px(row, d.W, d.hbound[2 * x], d.hbound[2 * x + 1], d.hk, d.hcoef, d.sw, x);
         }
         uint32_t w[3];
         pack4(out, w);
@@ -282,12 +155,7 @@ __global__ __launch_bounds__(AUG_THREADS) void aug_hpass_kernel(const MiAugSampl
 __global__ __launch_bounds__(AUG_THREADS) void aug_finish_kernel(const MiAugSample* table, float* out_img, int oh, int ow) {
     const MiAugSample& d = table[blockIdx.y];
     __shared__ float lut[3][256];
-    for (int i = threadIdx.x; i < 768; i += AUG_THREADS) {
-        const int c = i >> 8, u = i & 255;          // c: output channel; mean / std are indexed by the output channel (Normalize runs after the reorder)
-        const float x = d.to_bgr255 ? (float)u : f_div((float)u, 255.f);      // (u / 255) * 255 == u in fp32 for all 256 levels
-        lut[c][u] = f_div(f_sub(x, d.mean[c]), d.std[c]);
-    }
-    __syncthreads();
+    fill_normalise_table(lut, d.to_bgr255 != 0, d.mean, d.std);
     // where the vertical pass (or, without one, this kernel) reads: tmp, or the source itself when the horizontal pass is skipped
     const bool hp = d.hcoef != nullptr, vp = d.vcoef != nullptr;
     const uint8_t* src = hp ? d.tmp : (d.n_ops > 0 ? d.jit : d.img);
@@ -394,11 +262,6 @@ __global__ __launch_bounds__(AUG_THREADS) void aug_label_kernel(const MiAugSampl
             for (int i = 0; i < 4 && x4 + i < lw; ++i) o[i] = v[i];
         }
     }
-}
-
-int grid_x(long items) {
-    const long b = (items + AUG_THREADS - 1) / AUG_THREADS;
-    return (int)(b < 1 ? 1 : (b > 512 ? 512 : b));
 }
 
 }      // namespace

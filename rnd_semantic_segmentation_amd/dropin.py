@@ -45,7 +45,8 @@ ALIASES = {
     "core.datasets.dataset_path_catalog": _PKG + "datasets",          # core/datasets/dataset_path_catalog.py (DatasetCatalog)
     "core.datasets.gta5": _PKG + "datasets",                          # GTA5FoldDataSet
     "core.datasets.cityscapes": _PKG + "datasets",                    # cityscapesDataSet, cityscapesSelfDistillDataSet
-    "base.base_trainer": _PKG + "plugin",                             # base/base_trainer.py
+    "core.datasets.kvasir": _PKG + "datasets",                        # KvasirFoldDataset, KvasirDataSet
+    "base.base_trainer": _PKG + "plugin",                            # base/base_trainer.py
     "base.base_model": _PKG + "plugin",                               # base/base_model.py
 }
 PACKAGES = {"core.models", "core.models.classifiers", "core.models.classifiers.aspp", "core.models.classifiers.pranet", "core.models.classifiers.attn", "core.models.classifiers.gcpacc", "core.models.classifiers.gcpacc.encoders", "core.models.classifiers.gcpacc.contextagg", "core.components", "core.trainers", "core.adapters", "core.combos",

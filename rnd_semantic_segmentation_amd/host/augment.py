@@ -20,7 +20,7 @@ OP_NAMES = {OP_BRIGHTNESS: "brightness", OP_CONTRAST: "contrast", OP_SATURATION:
 PRECISION_BITS = 22          # PIL Resample.c: coefficients as fixed point with 22 fraction bits
 
 
-# ---- PIL's bicubic resampling coefficients (Resample.c precompute_coeffs + normalize_coeffs_8bpc) ------------------------------------------
+# ---- PIL's resampling coefficients (Resample.c precompute_coeffs + normalize_coeffs_8bpc) ------------------------------------------
 def _bicubic_kernel(x, a=-0.5):
     x = np.abs(x)
     near = ((a + 2.0) * x - (a + 3.0)) * x * x + 1
@@ -28,20 +28,35 @@ def _bicubic_kernel(x, a=-0.5):
     return np.where(x < 1.0, near, np.where(x < 2.0, far, 0.0))
 
 
-@functools.lru_cache(maxsize=64)
+def _triangle_kernel(x):
+    x = np.abs(x)
+    return np.where(x < 1.0, 1.0 - x, 0.0)
+
+
+FILTERS = {"bicubic": (_bicubic_kernel, 2.0), "bilinear": (_triangle_kernel, 1.0)}      # PIL Resample.c: (filter, support)
+
+
 def bicubic_tables(in_size, out_size):
-    """(coef int32 [k][out_size] tap-major, bound int32 [out_size][2] = {first source index, taps}, k) of one pass in_size -> out_size.
-    float64 throughout; the weights of an output are summed in tap order and divided by that sum, as PIL does."""
+    """resample_tables with the bicubic filter (the `aspp` transform's)."""
+    return resample_tables(in_size, out_size, "bicubic")
+
+
+@functools.lru_cache(maxsize=64)
+def resample_tables(in_size, out_size, filter="bicubic"):
+    """(coef int32 [k][out_size] tap-major, bound int32 [out_size][2] = {first source index, taps}, k) of one pass in_size -> out_size with
+    PIL's BICUBIC or BILINEAR filter.  float64 throughout; the weights of an output are summed in tap order and divided by that sum, as PIL
+    does."""
+    kernel, filter_support = FILTERS[filter]
     in_size, out_size = int(in_size), int(out_size)
     scale = in_size / out_size
     fs = max(scale, 1.0)
-    support = 2.0 * fs
+    support = filter_support * fs
     k = int(math.ceil(support)) * 2 + 1
     center = (np.arange(out_size, dtype=np.float64) + 0.5) * scale
     x0 = np.maximum((center - support + 0.5).astype(np.int64), 0)            # astype truncates toward zero like C's (int)
     n = np.minimum((center + support + 0.5).astype(np.int64), in_size) - x0
     j = np.arange(k, dtype=np.float64)[:, None]
-    w = _bicubic_kernel((j + x0[None, :] - center[None, :] + 0.5) * (1.0 / fs))
+    w = kernel((j + x0[None, :] - center[None, :] + 0.5) * (1.0 / fs))
     w = np.where(np.arange(k)[:, None] < n[None, :], w, 0.0)
     total = np.zeros(out_size, np.float64)
     for t in range(k):                                                       # in tap order: the sum's rounding is part of the result
@@ -237,8 +252,12 @@ class DeviceAugmenter:
     def __call__(self, images, labels, plans, stream=None):
         """images: uint8 [H,W,3] arrays / CPU tensors, labels: uint8 [H,W] or None per sample, plans: Plan per sample.  Returns
         (float32 [B,3,h,w], float32 [B,lh,lw] or None) on the device; with `stream`, the work is enqueued there and the caller orders its
-        own stream behind the returned tensors (see DeviceAugmentLoader)."""
+        own stream behind the returned tensors (see DeviceAugmentLoader).  A batch of host/pra_augment.PraPlan runs the `pra` transform
+        (mi_augment_pra_batch) through the same slots."""
         from .. import _lib, kernels
+        from . import pra_augment
+        if isinstance(plans[0], pra_augment.PraPlan):
+            return pra_augment.run_batch(self, images, labels, plans, stream)
         torch = self.torch
         B = len(plans)
         p0 = plans[0]

@@ -2,8 +2,10 @@
 signatures (core/datasets/build.py:5-30).
 
 GTA5 / Cityscapes are read from disk when DATASETS.DATASET_DIR holds them (host/datasets.py decodes, csrc/augment.hip runs the `aspp`
-transform on the batch).  Everything else - a synthetic dataset name, the polyp / kvasir names (their transforms need albumentations),
-a dataset directory that does not exist - is backed by a synthetic generator, on which BASELINE.json's configs are defined.
+transform on the batch).  So is Kvasir-SEG (DATASET_DIR/kvasir): the polyp_* names with AUG.NAME "pra" (PraNet; csrc/augment_pra.hip runs
+the `pra` transform), the kvasir_* names with AUG.NAME "aspp" (two-class DeepLab).  Everything else - a synthetic dataset name, a polyp /
+kvasir name under any other AUG.NAME, a dataset directory that does not exist - is backed by a synthetic generator, on which
+BASELINE.json's configs are defined.
 Both keep the TENSOR CONTRACT of the loader
 (core/datasets/transform.py:31-46, cityscapes.py:137-151, defaults.py:21-24):
     image  float32 [3,H,W], RGB/255 then (x-mean)/std   (here: unit-variance noise of that shape)
@@ -73,10 +75,16 @@ def build_collate_fn(cfg):
 
 
 def real_dataset_root(cfg, name):
-    """The directory a GTA5 / Cityscapes dataset name reads, when it exists; None for every name and configuration that gets the synthetic data."""
+    """The directory a dataset name reads, when it is read from disk; None for every name and configuration that gets the synthetic data.
+    GTA5 / Cityscapes: when the directory exists.  polyp_*: when it exists and AUG.NAME is "pra"; kvasir_*: when it exists and AUG.NAME is "aspp"."""
     from .datasets import DatasetCatalog
     name = str(name)
-    if "polyp" in name or "kvasir" in name or not ("gta5" in name or "cityscapes" in name) or not cfg.DATASETS.DATASET_DIR:
+    if not cfg.DATASETS.DATASET_DIR:
+        return None
+    if "polyp" in name or "kvasir" in name:
+        if cfg.AUG.NAME != ("pra" if "polyp" in name else "aspp"):
+            return None
+    elif not ("gta5" in name or "cityscapes" in name):
         return None
     root = DatasetCatalog.root(cfg, name)
     return root if root is not None and os.path.isdir(root) else None
@@ -85,15 +93,15 @@ def real_dataset_root(cfg, name):
 def build_dataset(cfg, mode="train", is_source=True):
     assert mode in ["train", "val", "test"]
     name = cfg.DATASETS.SOURCE_TRAIN if (mode == "train" and is_source) else (cfg.DATASETS.TARGET_TRAIN if mode == "train" else cfg.DATASETS.TEST)
-    if "polyp" in str(name) or "kvasir" in str(name):           # dataset_path_catalog.py:36-51,99-106
-        return SyntheticPolyp(cfg, mode)
+    polyp = "polyp" in str(name) or "kvasir" in str(name)       # dataset_path_catalog.py:36-51,99-106
     if real_dataset_root(cfg, name) is None:
-        return SyntheticSegmentation(cfg, mode, is_source)
-    if cfg.AUG.NAME != "aspp":
+        return SyntheticPolyp(cfg, mode) if polyp else SyntheticSegmentation(cfg, mode, is_source)
+    if not polyp and cfg.AUG.NAME != "aspp":
         raise ValueError("AUG.NAME %r: datasets read from disk are transformed by the 'aspp' transform only (the reference's other transforms need "
                          "albumentations); set AUG.NAME to 'aspp' or point DATASETS.DATASET_DIR away from %s" % (cfg.AUG.NAME, real_dataset_root(cfg, name)))
     from .augment import AugmentSpec
     from .datasets import DatasetCatalog
+    from .pra_augment import PraSpec
     split = mode if mode != "test" else str(cfg.DATASETS.TEST).split("_")[-1]          # build.py:28
-    return DatasetCatalog.get(cfg, name, split, num_classes=cfg.MODEL.NUM_CLASSES, transform=AugmentSpec.from_cfg(cfg, mode, is_source),
-                              cross_val=cfg.DATASETS.CROSS_VAL)
+    spec = PraSpec.from_cfg(cfg, mode) if "polyp" in str(name) else AugmentSpec.from_cfg(cfg, mode, is_source)
+    return DatasetCatalog.get(cfg, name, split, num_classes=cfg.MODEL.NUM_CLASSES, transform=spec, cross_val=cfg.DATASETS.CROSS_VAL)

@@ -5,6 +5,8 @@ The reference's __getitem__ runs the whole `aspp` transform on the CPU through P
 host/augment.AugmentSpec (what build_dataset passes) returns what the DEVICE transform consumes - the decoded uint8 [H,W,3] image, the raw
 uint8 [H,W] label ids and the name - and the DeviceAugmentLoader runs csrc/augment.hip on the batch.  A callable `transform` is still
 honoured as in the reference: it receives (PIL RGB image, PIL mode-F label with the ids already mapped) and its result is returned.
+Kvasir-SEG in folds (core/datasets/kvasir.py) is read the same way: KvasirFoldDataset with a host/pra_augment.PraSpec for PraNet (the `pra`
+transform, csrc/augment_pra.hip), KvasirDataSet as a two-class set for the `aspp` transform.
 PIL is imported when a dataset is constructed, not with this module.
 """
 import os
@@ -14,7 +16,7 @@ import numpy as np
 import torch
 from torch.utils.data import DataLoader, Dataset
 
-from . import augment
+from . import augment, pra_augment
 
 # label id -> train id (data of the Cityscapes label definition; every other id is IGNORE), and the class names
 TRAINID_19 = {7: 0, 8: 1, 11: 2, 12: 3, 13: 4, 17: 5, 19: 6, 20: 7, 21: 8, 22: 9, 23: 10, 24: 11, 25: 12, 26: 13, 27: 14, 28: 15, 31: 16, 32: 17, 33: 18}
@@ -44,7 +46,7 @@ class _DecodedSegmentation(Dataset):
 
     @property
     def device_transform(self):
-        return isinstance(self.transform, augment.AugmentSpec)
+        return isinstance(self.transform, (augment.AugmentSpec, pra_augment.PraSpec))
 
     def __len__(self):
         return len(self.image_paths)
@@ -148,6 +150,68 @@ class cityscapesSelfDistillDataSet(cityscapesDataSet):
         return path, os.path.join(self.label_dir, img_name), img_name[:-4]
 
 
+def _fold_images(data_root, mode, cross_val):
+    """<fold>/images/*.png of the folds a mode reads: train = folds whose name does not contain str(cross_val), every other mode = those
+    that do; sorted (see GTA5FoldDataSet)."""
+    paths = []
+    for fold in sorted(glob(data_root + "/*/")):
+        inside = str(cross_val) in os.path.basename(fold[:-1])
+        if inside != (mode == "train"):
+            paths += glob(os.path.join(fold, "images") + "/*.png")
+    return sorted(paths)
+
+
+class KvasirFoldDataset(_DecodedSegmentation):
+    """core/datasets/kvasir.py:11-64: Kvasir-SEG in folds, <fold>/images/*.png with <fold>/masks/<same name>, for PraNet.  With a
+    host/pra_augment.PraSpec as `transform` it returns the decoded uint8 [H,W,3] image, the uint8 [H,W] grey mask (convert("L")) and the
+    name, and the `pra` transform runs on the device; a callable transform receives (PIL RGB image, PIL L mask)."""
+
+    def __init__(self, cfg, data_root, mode="train", cross_val=0, transform=None, debug=False):
+        super().__init__()
+        self._setup(transform, None, debug)
+        self.cfg = cfg
+        self.data_root = data_root
+        self.mode = mode
+        self.image_paths = _fold_images(data_root, mode, cross_val)
+        self.id_table = pra_augment.MASK_TABLE                   # grey level -> {0, 1}: what the loader passes to the plans
+
+    def _paths(self, index):
+        path = self.image_paths[index]
+        img_name = os.path.basename(path)
+        return path, os.path.join(os.path.dirname(os.path.dirname(path)), "masks", img_name), img_name[:-4]
+
+    def __getitem__(self, index):
+        from PIL import Image
+        if self.debug:
+            index = 0
+        img_path, mask_path, name = self._paths(index)
+        image = Image.open(img_path).convert("RGB")
+        mask = Image.open(mask_path).convert("L")
+        if mask.size != image.size:
+            raise ValueError("%s: the mask is %dx%d, its image %dx%d" % (mask_path, mask.size[0], mask.size[1], image.size[0], image.size[1]))
+        if self.device_transform:
+            return torch.from_numpy(np.array(image, dtype=np.uint8)), torch.from_numpy(np.array(mask, dtype=np.uint8)), name
+        if self.transform is not None:
+            image, mask = self.transform(image, mask)
+        return image, mask, name
+
+
+class KvasirDataSet(_DecodedSegmentation):
+    """core/datasets/kvasir.py:66-117: the same tree as a two-class segmentation set for the `aspp` transform (the reference's two-class
+    DeepLab YAML): mask values 0 and 1 are the classes, everything else is ignore_label."""
+
+    def __init__(self, data_root, num_classes=2, mode="train", cross_val=0, transform=None, ignore_label=255, debug=False):
+        super().__init__()
+        self._setup(transform, ignore_label, debug)
+        self.data_root = data_root
+        self.mode = mode
+        self.image_paths = _fold_images(data_root, mode, cross_val)
+        self.id_to_trainid = {0: 0, 1: 1}
+        self.id_table = id_table(self.id_to_trainid, ignore_label)
+
+    _paths = KvasirFoldDataset._paths
+
+
 class DatasetCatalog(object):
     """core/datasets/dataset_path_catalog.py: dataset name -> directory under DATASETS.DATASET_DIR, routed by substring of the name."""
     DATASETS = {
@@ -183,9 +247,14 @@ class DatasetCatalog(object):
             if "distill" in name:
                 return cityscapesSelfDistillDataSet(root, os.path.join(data_dir, attrs["label_dir"]), num_classes=num_classes, mode=mode, transform=transform)
             return cityscapesDataSet(root, num_classes=num_classes, mode=mode, transform=transform)
-        if any(k in name for k in ("synthia", "kvasir", "polyp", "bli")):
-            raise RuntimeError("Dataset %r is not read from disk by this project (GTA5 and Cityscapes are; the reference's Synthia class does not "
-                               "exist and its Kvasir / BLI transforms need albumentations)" % name)
+        if "polyp" in name:
+            return KvasirFoldDataset(cfg, os.path.join(data_dir, DatasetCatalog.DATASETS[name]["data_dir"]), mode=mode, cross_val=cross_val, transform=transform)
+        if "kvasir" in name:
+            return KvasirDataSet(os.path.join(data_dir, DatasetCatalog.DATASETS[name]["data_dir"]), num_classes=num_classes, mode=mode, cross_val=cross_val,
+                                 transform=transform)
+        if any(k in name for k in ("synthia", "bli")):
+            raise RuntimeError("Dataset %r is not read from disk by this project (GTA5, Cityscapes and Kvasir are; the reference's Synthia class "
+                               "does not exist and its BLI transform needs albumentations)" % name)
         raise RuntimeError("Dataset not available: {}".format(name))
 
 
@@ -213,7 +282,8 @@ class _EpochBatches:
 
 class DeviceAugmentLoader:
     """A torch DataLoader whose workers decode, around the device transform.  Iterating yields the (image, label, names) batches of the loader
-    contract - float32 [B,3,h,w], float32 [B,lh,lw], list of str - as device tensors, produced by mi_augment_batch on a side stream, one
+    contract - float32 [B,3,h,w], float32 [B,lh,lw], list of str - as device tensors, produced by mi_augment_batch (an AugmentSpec) or
+    mi_augment_pra_batch (a PraSpec) on a side stream, one
     batch in flight ahead of the consumer.  The worker processes never touch HIP.
 
     The plan of a sample is seeded by (seed, epoch, dataset index); the epoch is `start_epoch` plus the number of __iter__ calls made so far,
@@ -222,7 +292,7 @@ class DeviceAugmentLoader:
     def __init__(self, dataset, batch_size=1, shuffle=False, sampler=None, num_workers=4, drop_last=False, device="cuda", seed=0, start_epoch=0,
                  prefetch_factor=2):
         if not has_device_transform(dataset):
-            raise ValueError("DeviceAugmentLoader needs a dataset built with the device transform (build_dataset with AUG.NAME 'aspp')")
+            raise ValueError("DeviceAugmentLoader needs a dataset built with a device transform (build_dataset with AUG.NAME 'aspp' or 'pra')")
         self.dataset = dataset
         self.base = base_dataset(dataset)
         self.spec = self.base.transform
@@ -250,7 +320,8 @@ class DeviceAugmentLoader:
         self.epoch = int(epoch)
 
     def plans_for(self, indices, sizes, epoch):
-        return [augment.sample_plan(self.spec, h, w, self.seed, epoch, i, self.base.id_table) for i, (h, w) in zip(indices, sizes)]
+        sample = pra_augment.sample_pra_plan if isinstance(self.spec, pra_augment.PraSpec) else augment.sample_plan
+        return [sample(self.spec, h, w, self.seed, epoch, i, self.base.id_table) for i, (h, w) in zip(indices, sizes)]
 
     def _launch(self, indices, samples, epoch):
         images = [s[0].numpy() for s in samples]
@@ -263,7 +334,7 @@ class DeviceAugmentLoader:
 
     def __iter__(self):
         if self.device.type != "cuda":
-            raise RuntimeError("the aspp transform runs on the GPU (csrc/augment.hip); there is no CPU path")
+            raise RuntimeError("the aspp / pra transforms run on the GPU (csrc/augment.hip, csrc/augment_pra.hip); there is no CPU path")
         if self._augmenter is None:
             self._augmenter = augment.DeviceAugmenter(self.device, slots=3)
             self._stream = torch.cuda.Stream(self.device)

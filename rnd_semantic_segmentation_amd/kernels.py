@@ -1015,3 +1015,22 @@ def augment_batch(table_dev, table_host, B, out_img, out_lab=None):
     check(_lib.lib().mi_augment_batch(_p(table_dev), _p(table_host), B, out_img.shape[2], out_img.shape[3], lh, lw, _p(out_img), _p(out_lab),
                                       _stream()), "mi_augment_batch")
     return out_img, out_lab
+
+
+def augment_pra_batch(table_dev, table_host, B, out_img, out_mask=None):
+    """The `pra` input transform of a batch (include/mi355seg.h, mi_augment_pra_batch): table_dev / table_host hold the same B MiPraSample
+    records at their start (host/pra_augment.py builds them), out_img [B,3,h,w] fp32 and out_mask [B,h,w] fp32 receive the loader
+    contract's tensors.  Enqueued on the current stream."""
+    _chk(out_img, torch.float32, "out_img")
+    if not table_dev.is_cuda or table_host.is_cuda or table_dev.dtype != torch.uint8 or table_host.dtype != torch.uint8:
+        raise _lib.MiError("augment_pra_batch: table_dev is a uint8 device tensor and table_host its uint8 host copy")
+    need = B * ctypes.sizeof(_lib.MiPraSample)
+    if table_dev.numel() < need or table_host.numel() < need or out_img.dim() != 4 or out_img.shape[0] != B or out_img.shape[1] != 3:
+        raise _lib.MiError("augment_pra_batch: %d records need %d bytes of table, out_img must be [%d,3,h,w]" % (B, need, B))
+    if out_mask is not None:
+        _chk(out_mask, torch.float32, "out_mask")
+        if tuple(out_mask.shape) != (B, out_img.shape[2], out_img.shape[3]):
+            raise _lib.MiError("augment_pra_batch: out_mask must be [%d,%d,%d]" % (B, out_img.shape[2], out_img.shape[3]))
+    check(_lib.lib().mi_augment_pra_batch(_p(table_dev), _p(table_host), B, out_img.shape[2], out_img.shape[3], _p(out_img), _p(out_mask), _stream()),
+          "mi_augment_pra_batch")
+    return out_img, out_mask
