@@ -338,6 +338,26 @@ int mi_upsample_softmax_multi(const MiProbSource* src, int n, float* probs, int 
 int mi_upsample_predict_score(const MiProbSource* src, int n, int K, int H, int W, float div_a, float div_b, const int64_t* labels,
                               int ignore_index, float threshold, uint8_t* pred, uint8_t* pseudo, int64_t* counts, void* stream);
 
+/* ---- the same tail with class-wise pseudo-label thresholds and the per-class confidence histogram they are taken from ---------
+ * One kernel body with mi_upsample_predict_score (the extras are compiled out of that entry): the per-pixel values, pred, counts, the vector
+ * paths and their alignment rules are those above.  What differs:
+ *   class_threshold  HOST array of K floats or NULL, copied by value into the kernel arguments (as src is; no device table, no extra copy);
+ *   pseudo [H][W] uint8 or NULL: max >= class_threshold[pred] ? pred : 255   (the same comparison; needs class_threshold);
+ *   hist   DEVICE int64 [K][bins] or NULL, ADDED to (zeroed by the caller once per data set; launches into one buffer add up):
+ *          hist[pred*bins + min(bins-1, int(max*bins))] += 1 for EVERY output pixel, whatever its label.  bins must be 1024: a power-of-two
+ *          scale and a truncation are exact in fp32, so the bin is a function of the fp32 maximum alone (host/metrics.py confidence_bin).
+ * From hist the host takes one threshold per class (host/metrics.py class_thresholds: the class's own confidence quantile, capped); a second
+ * launch with that table and hist = NULL writes the masks.  The thresholds are bin edges j/1024, so max >= t is bin >= j.
+ * Histogram in the kernel: two rounds of in-wave aggregation (the lanes holding the first waiting lane's cell retire, one lane carries their
+ * number), then a per-workgroup LDS table of 128 lines of 16 neighbouring bins (32-bit counters; a workgroup sees at most 512 pixels),
+ * open-addressed by line, flushed as 128-byte runs of 64-bit global atomic adds; a pixel that finds no line adds to hist directly.
+ * Integer sums: bit-reproducible.  hist should be 128-byte aligned for the runs to be whole lines (any alignment is correct).
+ * Refused before launch: everything mi_upsample_predict_score refuses (a threshold outside [0, 1] or NaN is any entry of the table), bins other
+ * than 1024 (0 is accepted with hist == NULL), hist with bins == 0, pseudo without class_threshold. */
+int mi_upsample_predict_score_cw(const MiProbSource* src, int n, int K, int H, int W, float div_a, float div_b, const int64_t* labels,
+                                 int ignore_index, const float* class_threshold, uint8_t* pred, uint8_t* pseudo, int64_t* counts, int bins,
+                                 int64_t* hist, void* stream);
+
 /* ---- input side of multi-scale evaluation: F.interpolate(x, (Ho, Wo), mode='bilinear', align_corners=True) (utility.py:197) ----
  * x [B][C][H][W] fp32 NCHW (the loader's layout, what mi_stem_f32 consumes) -> out [B*(1+with_mirror)][C][Ho][Wo].  with_mirror != 0:
  * image b's horizontally mirrored copy (torch.flip(resized, [3]), utility.py:204: the mirror of the RESIZED image) is written as image B + b

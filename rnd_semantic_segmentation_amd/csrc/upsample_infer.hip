@@ -151,20 +151,88 @@ __global__ __launch_bounds__(256, P == 1 ? 4 : 2) void upsample_softmax_multi_ke
 //   area_intersection = cmt[k][k], area_target = row sum k, area_output = column sum k + the extra cell k.
 // A workgroup sees at most 512 pixels, so its 32-bit LDS counters cannot overflow; it flushes one 64-bit global add per non-zero cell.  Integer sums
 // do not depend on arrival order: the counts are bit-reproducible.  counts: [K*K] cmt, [K] intersection, [K] output, [K] target; added to.
-template <int KT, int P>
+//
+// CW (mi_upsample_predict_score_cw) compiles in the two class-wise extras; without it they are gone and thr.t[0] is the one threshold:
+//   - the threshold of the WINNING class: thr.t[k] travels with the running maximum through the unrolled arg-max loop, so the table is read with
+//     compile-time indices (scalar registers straight from the kernel arguments), never with a per-lane index;
+//   - hist[pred * 1024 + bin] += 1, bin = min(1023, int(best * 1024)): the confidence histogram per predicted class (lds_hist_add below).
+struct ClassThr {
+    float t[KMAX];                // by value in the kernel arguments, as ProbSrcs is: no device table
+};
+constexpr int HIST_BINS = 1024;   // confidence bins per class: the cell of a pixel is pred * HIST_BINS + bin
+constexpr int HIST_LINE = 16;     // cells per line of the workgroup's table: 16 neighbouring bins of one class = 128 contiguous bytes of hist
+constexpr int HIST_LINES = 128;   // lines of the table (open-addressed by line number)
+constexpr int HIST_PROBES = 8;    // slots tried before a pixel goes to memory directly
+constexpr int HIST_PEEL = 2;      // in-wave aggregation rounds before the LDS adds
+constexpr unsigned HIST_EMPTY = 0xffffffffu;
+
+// One pixel's cell into the workgroup's table.  A dense K x 1024 table does not fit the occupancy (76 KB at K = 19), and one atomic per pixel on
+// the cell itself serialises where an image is saturated (road, sky: most of a wave in ONE cell).  So:
+//   1. HIST_PEEL rounds of in-wave aggregation: the lanes that hold the key of the first lane still waiting retire, their leader carries their
+//      number.  A saturated wave is one LDS add after round one; a spread wave loses two ballots.
+//   2. what is left goes into a table of HIST_LINES lines of HIST_LINE counters: atomicCAS claims a line for the line number cell / 16 (linear
+//      probing, at most HIST_PROBES slots), atomicAdd counts in the line's counter cell % 16.  Lines, not cells, because of the flush: measured,
+//      the LDS side is free and the global adds are everything - a table keyed by cell flushes one scattered 8-byte add per occupied cell,
+//      each a memory request of its own, and made the kernel 3 - 4 x slower on confidences that cluster in a few dozen cells per workgroup.
+//      A line flushes as 128 contiguous bytes, and the confidences of a class cluster in neighbouring bins.
+//   3. a pixel that finds no line within HIST_PROBES slots (more than ~100 distinct lines in one workgroup: noise, not a segmentation) adds to
+//      hist directly.  Correct for every input; only slow where nothing could be aggregated anyway.
+__device__ __forceinline__ void lds_hist_add(unsigned* hline, unsigned* hcnt, unsigned long long* __restrict__ hist, unsigned key, int lane) {
+    unsigned add = 1u;
+    bool waiting = true;
+#pragma unroll
+    for (int r = 0; r < HIST_PEEL; ++r) {
+        if (waiting) {
+            const unsigned k0 = (unsigned)__builtin_amdgcn_readfirstlane((int)key);
+            const bool same = key == k0;
+            const unsigned long long m = __ballot(same);   // among the lanes still waiting
+            if (same) {
+                waiting = false;
+                add = lane == __ffsll((long long)m) - 1 ? (unsigned)__popcll(m) : 0u;
+            }
+        }
+    }
+    if (add) {
+        const unsigned line = key / HIST_LINE;
+        unsigned s = (line * 2654435761u) >> 25;           // top 7 bits of the product: HIST_LINES == 1 << 7
+        bool placed = false;
+#pragma unroll 1
+        for (int probe = 0; probe < HIST_PROBES; ++probe) {
+            const unsigned prev = atomicCAS(&hline[s], HIST_EMPTY, line);
+            if (prev == HIST_EMPTY || prev == line) {
+                atomicAdd(&hcnt[s * HIST_LINE + key % HIST_LINE], add);
+                placed = true;
+                break;
+            }
+            s = (s + 1) & (HIST_LINES - 1);
+        }
+        if (!placed) atomicAdd(&hist[key], (unsigned long long)add);
+    }
+}
+
+template <int KT, int P, bool CW>
 __global__ __launch_bounds__(256, P == 1 ? 4 : 2) void upsample_predict_score_kernel(ProbSrcs srcs, int n, int Krt, int H, int W, float div_a, float div_b,
-                                                                     const long long* __restrict__ labels, int ignore_index, float threshold,
+                                                                     const long long* __restrict__ labels, int ignore_index, ClassThr thr,
                                                                      uint8_t* __restrict__ pred, uint8_t* __restrict__ pseudo,
-                                                                     unsigned long long* __restrict__ counts) {
+                                                                     unsigned long long* __restrict__ counts, unsigned long long* __restrict__ hist) {
     const int K = KT > 0 ? KT : Krt;
     constexpr int KR = KT > 0 ? KT : KMAX;
     static_assert(P == 1 || P == 2, "one or two pixels per lane");
+    static_assert(HIST_LINES == 128 && HIST_BINS % HIST_LINE == 0, "the hash takes 7 bits; a line never straddles two classes");
     __shared__ unsigned tab[KR * KR + KR];
+    __shared__ unsigned hline[CW ? HIST_LINES : 1], hcnt[CW ? HIST_LINES * HIST_LINE : 1];
     const int tid = threadIdx.x;
-    if (counts) {                                          // uniform over the grid
+    const bool with_hist = CW && hist != nullptr;          // uniform over the grid, as counts is
+    if (counts) {
         for (int c = tid; c < K * K + K; c += 256) tab[c] = 0u;
-        __syncthreads();
     }
+    if constexpr (CW) {
+        if (with_hist) {
+            if (tid < HIST_LINES) hline[tid] = HIST_EMPTY;
+            for (int c = tid; c < HIST_LINES * HIST_LINE; c += 256) hcnt[c] = 0u;
+        }
+    }
+    if (counts || with_hist) __syncthreads();
     const int WP = W / P;                                  // P == 2 only when W is even
     const long idx = (long)blockIdx.x * 256 + tid;
     if (idx < (long)H * WP) {
@@ -172,19 +240,22 @@ __global__ __launch_bounds__(256, P == 1 ? 4 : 2) void upsample_predict_score_ke
         float acc[P][KR];
         multi_probs<KR, P>(srcs, n, K, W, y, xb, div_a, div_b, acc);
         uint8_t pd[P], ps[P];
+        float bs[P];
 #pragma unroll
         for (int p = 0; p < P; ++p) {
-            float best = acc[p][0];
+            float best = acc[p][0], tb = thr.t[0];
             int arg = 0;
 #pragma unroll
             for (int k = 1; k < KR; ++k) {
                 if (k < K && acc[p][k] > best) {           // strict: the first of equal maxima stays
                     best = acc[p][k];
                     arg = k;
+                    if constexpr (CW) tb = thr.t[k];
                 }
             }
             pd[p] = (uint8_t)arg;
-            ps[p] = best >= threshold ? (uint8_t)arg : (uint8_t)255;
+            ps[p] = best >= tb ? (uint8_t)arg : (uint8_t)255;
+            bs[p] = best;
         }
         const long o = (long)y * W + xb;
         if constexpr (P == 2) {                            // W even: o even; pred / pseudo 2-byte, labels 16-byte aligned (the launcher checks)
@@ -211,9 +282,19 @@ __global__ __launch_bounds__(256, P == 1 ? 4 : 2) void upsample_predict_score_ke
                     atomicAdd(&tab[K * K + pd[p]], 1u);
             }
         }
+        if constexpr (CW) {
+            if (with_hist) {
+#pragma unroll
+                for (int p = 0; p < P; ++p) {
+                    // confidence_bin (host/metrics.py): a power-of-two scale and a truncation, both exact; the lower clamp only keeps a NaN in bounds
+                    const int bin = min(HIST_BINS - 1, max(0, (int)(bs[p] * (float)HIST_BINS)));
+                    lds_hist_add(hline, hcnt, hist, (unsigned)pd[p] * HIST_BINS + (unsigned)bin, tid & 63);
+                }
+            }
+        }
     }
+    if (counts || with_hist) __syncthreads();
     if (counts) {
-        __syncthreads();
         for (int c = tid; c < K * K; c += 256) {
             const unsigned v = tab[c];
             if (v) atomicAdd(&counts[c], (unsigned long long)v);
@@ -228,6 +309,14 @@ __global__ __launch_bounds__(256, P == 1 ? 4 : 2) void upsample_predict_score_ke
             if (diag) atomicAdd(&counts[K * K + tid], (unsigned long long)diag);
             if (out) atomicAdd(&counts[K * K + K + tid], (unsigned long long)out);
             if (row) atomicAdd(&counts[K * K + 2 * K + tid], (unsigned long long)row);
+        }
+    }
+    if constexpr (CW) {
+        if (with_hist) {                                   // a wave flushes 64 consecutive counters = 4 lines of 128 contiguous bytes each
+            for (int c = tid; c < HIST_LINES * HIST_LINE; c += 256) {
+                const unsigned v = hcnt[c];                // a counted line has its number: line * 16 + c % 16 < K * HIST_BINS by construction
+                if (v) atomicAdd(&hist[hline[c / HIST_LINE] * HIST_LINE + c % HIST_LINE], (unsigned long long)v);
+            }
         }
     }
 }
@@ -288,35 +377,70 @@ extern "C" int mi_upsample_softmax_multi(const MiProbSource* src, int n, float* 
     return MI_OK;
 }
 
-extern "C" int mi_upsample_predict_score(const MiProbSource* src, int n, int K, int H, int W, float div_a, float div_b, const int64_t* labels,
-                                         int ignore_index, float threshold, uint8_t* pred, uint8_t* pseudo, int64_t* counts, void* stream) {
-    MI_REQUIRE(src && pred, "mi_upsample_predict_score: null operand");
-    MI_REQUIRE(n >= 1 && n <= MAX_PROB_SRC, "mi_upsample_predict_score: 1 <= n <= 16 sources");
-    MI_REQUIRE(K > 0 && K <= KMAX && H > 0 && W > 0, "mi_upsample_predict_score: bad dimension (K <= 32)");
-    MI_REQUIRE(div_a != 0.f && div_b != 0.f, "mi_upsample_predict_score: zero divisor");
-    MI_REQUIRE((labels != nullptr) == (counts != nullptr), "mi_upsample_predict_score: labels and counts go together");
-    MI_REQUIRE(ignore_index < 0 || ignore_index >= K, "mi_upsample_predict_score: ignore_index inside [0, K)");
-    MI_REQUIRE(threshold >= 0.f && threshold <= 1.f, "mi_upsample_predict_score: threshold outside [0, 1]");
+// The one launcher of both evaluation-tail entries: the checks of mi_upsample_predict_score in their order (thr_ok is the caller's verdict on
+// its threshold(s)), then the core with or without the class-wise extras.
+static int launch_predict_score(const char* who, const MiProbSource* src, int n, int K, int H, int W, float div_a, float div_b, const int64_t* labels,
+                                int ignore_index, bool thr_ok, const ClassThr& thr, bool cw, uint8_t* pred, uint8_t* pseudo, int64_t* counts,
+                                int64_t* hist, void* stream) {
+    MI_REQUIRE(src && pred, "%s: null operand", who);
+    MI_REQUIRE(n >= 1 && n <= MAX_PROB_SRC, "%s: 1 <= n <= 16 sources", who);
+    MI_REQUIRE(K > 0 && K <= KMAX && H > 0 && W > 0, "%s: bad dimension (K <= 32)", who);
+    MI_REQUIRE(div_a != 0.f && div_b != 0.f, "%s: zero divisor", who);
+    MI_REQUIRE((labels != nullptr) == (counts != nullptr), "%s: labels and counts go together", who);
+    MI_REQUIRE(ignore_index < 0 || ignore_index >= K, "%s: ignore_index inside [0, K)", who);
+    MI_REQUIRE(thr_ok, "%s: threshold outside [0, 1]", who);
     ProbSrcs srcs;
     for (int i = 0; i < MAX_PROB_SRC; ++i) {
         const MiProbSource& m = src[i < n ? i : 0];       // unused slots repeat source 0: never read, never uninitialised
-        MI_REQUIRE(m.low && m.h > 0 && m.w > 0, "mi_upsample_predict_score: bad source");
+        MI_REQUIRE(m.low && m.h > 0 && m.w > 0, "%s: bad source", who);
         srcs.s[i] = ProbSrc{m.low, make_axis(m.h, H), make_axis(m.w, W), m.mirror != 0};
     }
     const bool wide = W % 2 == 0 && (reinterpret_cast<uintptr_t>(pred) & 1) == 0 && (reinterpret_cast<uintptr_t>(pseudo) & 1) == 0 &&
                       (reinterpret_cast<uintptr_t>(labels) & 15) == 0;
     const unsigned nb = nblk((long)H * (wide ? W / 2 : W), 256);
-#define MI_LAUNCH_SCORE(KT, P)                                                                                                                 \
-    hipLaunchKernelGGL((upsample_predict_score_kernel<KT, P>), dim3(nb), dim3(256), 0, (hipStream_t)stream, srcs, n, K, H, W, div_a, div_b, \
-                       reinterpret_cast<const long long*>(labels), ignore_index, threshold, pred, pseudo, reinterpret_cast<unsigned long long*>(counts))
+#define MI_LAUNCH_SCORE(KT, P, CW)                                                                                                                 \
+    hipLaunchKernelGGL((upsample_predict_score_kernel<KT, P, CW>), dim3(nb), dim3(256), 0, (hipStream_t)stream, srcs, n, K, H, W, div_a, div_b, \
+                       reinterpret_cast<const long long*>(labels), ignore_index, thr, pred, pseudo, reinterpret_cast<unsigned long long*>(counts), \
+                       reinterpret_cast<unsigned long long*>(hist))
+#define MI_LAUNCH_SCORE_P(KT, CW) \
+    do {                          \
+        if (wide) MI_LAUNCH_SCORE(KT, 2, CW); else MI_LAUNCH_SCORE(KT, 1, CW); \
+    } while (0)
     if (K == 19) {
-        if (wide) MI_LAUNCH_SCORE(19, 2); else MI_LAUNCH_SCORE(19, 1);
+        if (cw) MI_LAUNCH_SCORE_P(19, true); else MI_LAUNCH_SCORE_P(19, false);
     } else {
-        if (wide) MI_LAUNCH_SCORE(0, 2); else MI_LAUNCH_SCORE(0, 1);
+        if (cw) MI_LAUNCH_SCORE_P(0, true); else MI_LAUNCH_SCORE_P(0, false);
     }
+#undef MI_LAUNCH_SCORE_P
 #undef MI_LAUNCH_SCORE
-    MI_CHECK_LAUNCH("mi_upsample_predict_score");
+    MI_CHECK_LAUNCH(who);
     return MI_OK;
+}
+
+extern "C" int mi_upsample_predict_score(const MiProbSource* src, int n, int K, int H, int W, float div_a, float div_b, const int64_t* labels,
+                                         int ignore_index, float threshold, uint8_t* pred, uint8_t* pseudo, int64_t* counts, void* stream) {
+    ClassThr thr = {};
+    thr.t[0] = threshold;
+    return launch_predict_score("mi_upsample_predict_score", src, n, K, H, W, div_a, div_b, labels, ignore_index, threshold >= 0.f && threshold <= 1.f,
+                                thr, false, pred, pseudo, counts, nullptr, stream);
+}
+
+extern "C" int mi_upsample_predict_score_cw(const MiProbSource* src, int n, int K, int H, int W, float div_a, float div_b, const int64_t* labels,
+                                            int ignore_index, const float* class_threshold, uint8_t* pred, uint8_t* pseudo, int64_t* counts,
+                                            int bins, int64_t* hist, void* stream) {
+    static const char* who = "mi_upsample_predict_score_cw";
+    MI_REQUIRE(!(hist && bins == 0), "%s: hist without bins", who);
+    MI_REQUIRE(bins == HIST_BINS || (bins == 0 && !hist), "%s: bins must be 1024", who);
+    MI_REQUIRE(class_threshold || !pseudo, "%s: pseudo without class_threshold", who);
+    ClassThr thr = {};
+    bool ok = true;
+    if (class_threshold && K > 0 && K <= KMAX) {
+        for (int k = 0; k < K; ++k) {
+            thr.t[k] = class_threshold[k];
+            ok = ok && thr.t[k] >= 0.f && thr.t[k] <= 1.f;    // false for a NaN
+        }
+    }
+    return launch_predict_score(who, src, n, K, H, W, div_a, div_b, labels, ignore_index, ok, thr, true, pred, pseudo, counts, hist, stream);
 }
 
 extern "C" int mi_image_resize_ac(const float* x, float* out, int B, int C, int H, int W, int Ho, int Wo, int with_mirror, void* stream) {

@@ -13,7 +13,7 @@ from ast import literal_eval
 import yaml
 
 _VALID = (tuple, list, str, int, float, bool, type(None))
-_RANGES = {"TEST.PSEUDO_THRESHOLD": (0.0, 1.0), "SOLVER.TVERSKY_ALPHA": (0.0, 1.0), "SOLVER.LABEL_SMOOTHING": (0.0, 1.0),
+_RANGES = {"TEST.PSEUDO_THRESHOLD": (0.0, 1.0), "TEST.PSEUDO_PORTION": (0.0, 1.0), "SOLVER.TVERSKY_ALPHA": (0.0, 1.0), "SOLVER.LABEL_SMOOTHING": (0.0, 1.0),
            "SOLVER.OHEM_THRESH": (0.0, 1.0), "SOLVER.OHEM_MIN_KEPT": (1, float("inf"))}      # closed intervals a merged value has to lie in
 _CHOICES = {"SOLVER.LOSS": ("ce", "gdl", "tversky", "ohem"), "SOLVER.GDL_WEIGHT": ("square", "identity", "sqrt")}      # the only values a merged key may take
 
@@ -189,8 +189,13 @@ def default_tree():
         # not in the reference: PRECISION fp32 = exact evaluation path, bf16 = training engine; SCALES / FLIP other than these defaults make
         # ASPPTester call multi_scale_inference (utility.py:193-209) instead of inference(flip=False); FUSED_SCORE True = argmax, threshold and
         # metric counts in the evaluation tail's kernel (False = the probability map and torch ops: same numbers and files);
-        # PSEUDO_THRESHOLD in [0, 1]: saved masks hold 255 where the winning probability is below it (0 = the reference's plain argmax)
-        "TEST": {"BATCH_SIZE": 1, "PRECISION": "fp32", "SCALES": (1.0,), "FLIP": False, "FUSED_SCORE": True, "PSEUDO_THRESHOLD": 0.0},
+        # PSEUDO_THRESHOLD in [0, 1]: saved masks hold 255 where the winning probability is below it (0 = the reference's plain argmax);
+        # PSEUDO_CLASSWISE True = class-balanced pseudo-labels (CBST; the BDL / FADA self-distillation rule): one threshold per class, the
+        # PSEUDO_PORTION quantile (0.5 = the median) of the confidences of the pixels predicted as that class over the whole test set, capped at
+        # PSEUDO_THRESHOLD (0 = no cap); ASPPTester takes them from a histogram the evaluation tail accumulates, then writes the masks in a second
+        # pass (metrics.classwise_settings; PSEUDO_PORTION changed while PSEUDO_CLASSWISE is False is refused)
+        "TEST": {"BATCH_SIZE": 1, "PRECISION": "fp32", "SCALES": (1.0,), "FLIP": False, "FUSED_SCORE": True, "PSEUDO_THRESHOLD": 0.0,
+                 "PSEUDO_CLASSWISE": False, "PSEUDO_PORTION": 0.5},
         "OUTPUT_DIR": ".",
         "resume": "",
         "PSEUDO_DIR": "",

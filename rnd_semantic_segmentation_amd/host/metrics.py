@@ -14,9 +14,13 @@ Differences that are deliberate and documented:
    divides: the result is written once instead of being accumulated through full-size tensors.
  * predict_and_score() on the engine never builds the probability map: mi_upsample_predict_score takes the argmax of the same per-pixel values in
    registers, applies the pseudo-label threshold and counts the confusion matrix and the areas against the label in the same launch.
+ * class-wise pseudo-label thresholds (PSEUDO_BINS, confidence_bin, class_thresholds, classwise_settings; TEST.PSEUDO_CLASSWISE) are not in the
+   reference: the class-balanced rule of CBST / BDL / FADA self-distillation, stated in exact integers on a confidence histogram which the same
+   kernel accumulates (mi_upsample_predict_score_cw).
 """
 import json
 import logging
+import math
 import os
 import types
 from collections import OrderedDict, defaultdict, deque
@@ -260,9 +264,91 @@ def score_settings(cfg):
 def require_plain_argmax(cfg, who):
     """Pseudo-label thresholding is built into the DeepLab evaluation tail only: other testers refuse the key rather than ignore it."""
     _, threshold = score_settings(cfg)
+    if classwise_settings(cfg)[0]:
+        raise NotImplementedError("%s: TEST.PSEUDO_CLASSWISE - class-wise pseudo-label thresholds exist for the DeepLab (feature extractor, "
+                                  "classifier) pair only (ASPPTester); leave it False" % (who,))
     if threshold != 0.0:
         raise NotImplementedError("%s: TEST.PSEUDO_THRESHOLD %r - thresholded pseudo-labels exist for the DeepLab (feature extractor, "
                                   "classifier) pair only (ASPPTester); leave it at 0" % (who, threshold))
+
+
+# ----------------------------------------------------------------------------- class-wise pseudo-label thresholds
+PSEUDO_BINS = 1024                      # confidence bins per class; the kernel's histogram has this width and no other
+PSEUDO_PORTION_DEFAULT = 0.5            # TEST.PSEUDO_PORTION of host/config.py: the median rule
+
+
+def confidence_bin(best):
+    """min(PSEUDO_BINS - 1, int(best * 1024)) on the fp32 value(s) `best` (a number, an array or a tensor; same container back, int64).
+    Both steps are exact - a power-of-two scale and a truncation - so whoever sees the same fp32 winning probability gets the same bin: the
+    kernel and this line cannot round differently."""
+    if isinstance(best, torch.Tensor):
+        return (best.float() * float(PSEUDO_BINS)).long().clamp_(max=PSEUDO_BINS - 1)
+    out = np.minimum(PSEUDO_BINS - 1, (np.asarray(best, dtype=np.float32) * np.float32(PSEUDO_BINS)).astype(np.int64))
+    return int(out) if out.ndim == 0 else out
+
+
+def class_thresholds(hist, portion, cap):
+    """One pseudo-label threshold per class from hist int64 [K, PSEUDO_BINS], hist[c, j] = the number of pixels predicted as c whose winning
+    probability falls in bin j (confidence_bin).  float32 [K] (numpy).  Per class, in integers until the last line:
+        n = hist[c].sum();  n == 0: t = cap
+        r = min(n - 1, floor(portion * n))      the rank, ascending from 0, of the confidence at the `portion` quantile; `portion * n` is the
+                                                Python product float * int (one rounding to a double), math.floor of it an int
+        j = the smallest bin with cumsum(hist[c])[j] > r: the bin of the rank-r confidence
+        t = min(j / 1024, cap) as float32       j / 1024 is exact
+    A pixel keeps its label iff best >= t[pred]; t is a bin edge unless the cap bites, so that is bin >= j.  At least the share 1 - portion of
+    every class survives while the cap does not bite: rare, hard classes keep their most confident half instead of nothing."""
+    if isinstance(hist, torch.Tensor):
+        hist = hist.cpu().numpy()
+    hist = np.asarray(hist)
+    if hist.ndim != 2 or hist.shape[1] != PSEUDO_BINS or hist.dtype.kind not in "iu":
+        raise ValueError("class_thresholds: hist must be an integer [K, %d] array, got %s %s" % (PSEUDO_BINS, hist.dtype, hist.shape))
+    portion, cap = float(portion), float(cap)
+    if not 0.0 <= portion <= 1.0 or not 0.0 <= cap <= 1.0:          # (false for a NaN)
+        raise ValueError("class_thresholds: portion %r and cap %r must lie in [0, 1]" % (portion, cap))
+    hist = hist.astype(np.int64)
+    if (hist < 0).any():
+        raise ValueError("class_thresholds: negative count")
+    out = np.empty(hist.shape[0], dtype=np.float32)
+    for c in range(hist.shape[0]):
+        n = int(hist[c].sum())
+        if n == 0:
+            out[c] = np.float32(cap)
+            continue
+        r = min(n - 1, int(math.floor(portion * n)))
+        j = int(np.searchsorted(np.cumsum(hist[c]), r, side="right"))          # the first j with cumsum[j] > r
+        out[c] = min(np.float32(j / PSEUDO_BINS), np.float32(cap))
+    return out
+
+
+def threshold_table(hist, thresholds, names=None):
+    """What ASPPTester logs and writes as class_thresholds.json: per class its name, the pixels predicted as it, its threshold and the share of
+    those pixels in the bins at or above the threshold.  The share is the kept share exactly when the threshold is a bin edge (always, unless
+    a cap that is no multiple of 1/1024 bites: then the cap's own bin is left out and the share is a lower bound)."""
+    if isinstance(hist, torch.Tensor):
+        hist = hist.cpu().numpy()
+    hist = np.asarray(hist, dtype=np.int64)
+    K = hist.shape[0]
+    names = [str(c) for c in range(K)] if names is None else [str(v) for v in names]
+    pixels = [int(v) for v in hist.sum(1)]
+    first = [int(math.ceil(float(t) * PSEUDO_BINS)) for t in thresholds]          # float32 -> double and * 1024 are exact
+    kept = [int(hist[c, first[c]:].sum()) / pixels[c] if pixels[c] else 0.0 for c in range(K)]
+    return {"bins": PSEUDO_BINS, "classes": names, "pixels": pixels, "thresholds": [float(t) for t in thresholds], "kept": kept}
+
+
+def classwise_settings(cfg):
+    """(classwise, portion, cap) of cfg.TEST (PSEUDO_CLASSWISE / PSEUDO_PORTION are not reference keys; absent = False / 0.5).  The cap is
+    TEST.PSEUDO_THRESHOLD, where 0 means no cap (1.0) under PSEUDO_CLASSWISE.  PSEUDO_PORTION changed while PSEUDO_CLASSWISE is False is
+    refused instead of ignored."""
+    classwise = bool(cfg.TEST.PSEUDO_CLASSWISE) if "PSEUDO_CLASSWISE" in cfg.TEST else False
+    portion = cfg.TEST.PSEUDO_PORTION if "PSEUDO_PORTION" in cfg.TEST else PSEUDO_PORTION_DEFAULT
+    if isinstance(portion, bool) or not isinstance(portion, (int, float)) or not 0.0 <= portion <= 1.0:      # (a merged value was checked there)
+        raise ValueError("TEST.PSEUDO_PORTION %r lies outside [0, 1]" % (portion,))
+    _, threshold = score_settings(cfg)
+    if not classwise:
+        if float(portion) != PSEUDO_PORTION_DEFAULT:
+            raise NotImplementedError("TEST.PSEUDO_PORTION %r belongs to TEST.PSEUDO_CLASSWISE True" % (portion,))
+        return False, float(portion), threshold
+    return True, float(portion), threshold if threshold != 0.0 else 1.0
 
 
 class ScoreResult(object):
@@ -284,44 +370,97 @@ def scores_from_counts(counts, K, pred, pseudo):
     return ScoreResult(pred, pseudo, cmt, ai, ao + at - ai, at, ao)
 
 
-def predict_and_score(feature_extractor, classifier, image, label, flip=False, scales=(1.0,), *, num_classes, ignore_index=255, threshold=0.0):
+def _engine_masks(feature_extractor, classifier, image, size, flip, scales, **kw):
+    """(pred, pseudo, counts) of the engine's evaluation tail: the backbone passes of inference / multi_scale_inference, then ONE kernel."""
+    with torch.no_grad():
+        if tuple(scales) == (1.0,) and not flip:
+            return classifier.predict_mask(feature_extractor(image), size, **kw)
+        from .. import kernels
+        sizes, _, divisors = multi_scale_plan(image.shape[-2:], flip, scales)
+        x0 = image[:1].float().contiguous()
+        feats = [feature_extractor(kernels.image_resize_ac(x0, hw, with_mirror=flip)) for hw in sizes]
+        mirrors = [(False, True) if flip else (False,)] * len(sizes)
+        return classifier.predict_mask_multi(feats, mirrors, size, divisors, **kw)
+
+
+def _literal_output(feature_extractor, classifier, image, label, flip, scales):
+    if tuple(scales) == (1.0,) and not flip:
+        return inference(feature_extractor, classifier, image, label, flip=False)
+    return multi_scale_inference(feature_extractor, classifier, image, label, flip=flip, scales=list(scales))
+
+
+def _class_table(class_threshold, K, device):
+    t = torch.as_tensor(np.asarray(class_threshold, dtype=np.float32) if not isinstance(class_threshold, torch.Tensor) else class_threshold,
+                        dtype=torch.float32)
+    if t.shape != (K,) or not bool(((t >= 0) & (t <= 1)).all()):
+        raise ValueError("class_threshold must be %d values in [0, 1], got %r" % (K, t.tolist()))
+    return t.to(device)
+
+
+def literal_histogram(output, K):
+    """The confidence histogram of one [1,K,H,W] probability map with torch ops (int64 [K, PSEUDO_BINS] on its device): what the kernel adds
+    to `hist` for the same image."""
+    top = output[:1].max(1)
+    return torch.bincount((top[1] * PSEUDO_BINS + confidence_bin(top[0])).flatten(), minlength=K * PSEUDO_BINS).reshape(K, PSEUDO_BINS)
+
+
+def literal_pseudo(output, class_threshold):
+    """The class-wise pseudo-label mask of one [1,K,H,W] probability map with torch ops: uint8 [H,W], pred where max >= class_threshold[pred]."""
+    top = output[:1].max(1)
+    pred = top[1]
+    t = _class_table(class_threshold, output.shape[1], output.device)
+    return torch.where(top[0] >= t[pred], pred, torch.full_like(pred, 255))[0].to(torch.uint8)
+
+
+def predict_and_score(feature_extractor, classifier, image, label, flip=False, scales=(1.0,), *, num_classes, ignore_index=255, threshold=0.0,
+                      class_threshold=None, hist=None):
     """One image of ASPPTester.test(): inference(flip=False) (scales == (1.0,), no flip) or multi_scale_inference, then the argmax mask, the
     pseudo-label mask (argmax where the winning probability >= threshold, else 255; None for threshold 0), confusion_matrix and
     intersectionAndUnionGPU against label[:1].  On the engine (a classifier with predict_mask_multi, CUDA tensors) the backbone passes are
     those of inference / multi_scale_inference and everything after the logits is ONE kernel, which never writes the probability map; the
-    integers are the same.  A substituted / foreign classifier or CPU tensors run the literal composition."""
+    integers are the same.  A substituted / foreign classifier or CPU tensors run the literal composition.
+    Class-wise pseudo-labels: hist (the caller's int64 [K, PSEUDO_BINS] tensor, kept across images) receives this image's confidence histogram;
+    class_threshold (K values in [0, 1]) replaces threshold in the pseudo-label mask: argmax where the winning probability >= its class's."""
     K = int(num_classes)
     if not 0.0 <= float(threshold) <= 1.0:
         raise ValueError("threshold %r lies outside [0, 1]" % (threshold,))
+    if hist is not None and (hist.dtype != torch.int64 or tuple(hist.shape) != (K, PSEUDO_BINS)):
+        raise ValueError("hist must be int64 [%d, %d], got %s %s" % (K, PSEUDO_BINS, hist.dtype, tuple(hist.shape)))
     scales = tuple(scales)
-    single = scales == (1.0,) and not flip
     size = tuple(label.shape[-2:])
     y0 = label[:1]                                          # inference() keeps image 0 only (utility.py:190)
     if hasattr(classifier, "predict_mask_multi") and image.is_cuda:
         kw = dict(labels=y0[0].long().contiguous(), ignore_index=int(ignore_index), threshold=float(threshold), want_pseudo=threshold != 0)
-        with torch.no_grad():
-            if single:
-                pred, pseudo, counts = classifier.predict_mask(feature_extractor(image), size, **kw)
-            else:
-                from .. import kernels
-                sizes, _, divisors = multi_scale_plan(image.shape[-2:], flip, scales)
-                x0 = image[:1].float().contiguous()
-                feats = [feature_extractor(kernels.image_resize_ac(x0, hw, with_mirror=flip)) for hw in sizes]
-                mirrors = [(False, True) if flip else (False,)] * len(sizes)
-                pred, pseudo, counts = classifier.predict_mask_multi(feats, mirrors, size, divisors, **kw)
+        if class_threshold is not None:
+            kw.update(class_threshold=_class_table(class_threshold, K, "cpu"), want_pseudo=True)
+        if hist is not None:
+            kw.update(hist=hist, want_pseudo=class_threshold is not None)
+        pred, pseudo, counts = _engine_masks(feature_extractor, classifier, image, size, flip, scales, **kw)
         return scores_from_counts(counts, K, pred, pseudo)
-    if single:
-        output = inference(feature_extractor, classifier, image, label, flip=False)
-    else:
-        output = multi_scale_inference(feature_extractor, classifier, image, label, flip=flip, scales=list(scales))
+    output = _literal_output(feature_extractor, classifier, image, label, flip, scales)
     top = output.max(1)
     pred = top[1]
     pseudo = None
-    if threshold != 0:
+    if class_threshold is not None:
+        pseudo = literal_pseudo(output, class_threshold)
+    elif threshold != 0 and hist is None:
         pseudo = torch.where(top[0] >= threshold, pred, torch.full_like(pred, 255))[0].to(torch.uint8)
+    if hist is not None:
+        hist.add_(literal_histogram(output, K).to(hist.device))
     cmt = confusion_matrix(types.SimpleNamespace(MODEL=types.SimpleNamespace(NUM_CLASSES=K)), torch.flatten(pred), torch.flatten(y0))
     ai, union, at, ao = [t.cpu() for t in intersectionAndUnionGPU(pred.clone(), y0.long(), K, ignore_index)]
     return ScoreResult(pred[0].to(torch.uint8), pseudo, cmt, ai, union, at, ao)
+
+
+def classwise_pseudo_labels(feature_extractor, classifier, image, label, flip=False, scales=(1.0,), *, num_classes, class_threshold):
+    """The second pass of class-wise pseudo-labelling for one image: the uint8 [H,W] mask, argmax where the winning probability >= its class's
+    threshold, else 255.  No metric counting, no histogram.  Engine and literal composition as in predict_and_score."""
+    K = int(num_classes)
+    size = tuple(label.shape[-2:])
+    if hasattr(classifier, "predict_mask_multi") and image.is_cuda:
+        return _engine_masks(feature_extractor, classifier, image, size, flip, tuple(scales), class_threshold=_class_table(class_threshold, K, "cpu"),
+                             want_pseudo=True)[1]
+    return literal_pseudo(_literal_output(feature_extractor, classifier, image, label, flip, tuple(scales)), class_threshold)
 
 
 # ----------------------------------------------------------------------------- io / logging

@@ -289,17 +289,20 @@ class ASPP_Classifier_V2(nn.Module):
             lows, flags = self._lows_multi(feats, mirrors, "predict_probs_multi")
             return kernels.upsample_softmax_multi(lows, flags, tuple(int(s) for s in size), float(divisors[0]), float(divisors[1]))
 
-    def predict_mask_multi(self, feats, mirrors, size, divisors, labels=None, ignore_index=255, threshold=0.0, want_pseudo=False):
+    def predict_mask_multi(self, feats, mirrors, size, divisors, labels=None, ignore_index=255, threshold=0.0, want_pseudo=False, class_threshold=None,
+                           hist=None):
         """predict_probs_multi(feats, mirrors, size, divisors).max(1) without the probability map: (pred, pseudo, counts) of
         kernels.upsample_predict_score - the argmax mask, the thresholded pseudo-label mask and, with labels [H,W] int64, the confusion matrix
-        and intersection / output / target areas."""
+        and intersection / output / target areas.  class_threshold (K host floats, instead of threshold) and hist (the caller's int64
+        [K, PSEUDO_BINS] device tensor, added to) are the class-wise pseudo-label extras of that wrapper."""
         from .. import kernels
         with torch.no_grad():
             lows, flags = self._lows_multi(feats, mirrors, "predict_mask_multi")
             return kernels.upsample_predict_score(lows, flags, tuple(int(s) for s in size), float(divisors[0]), float(divisors[1]), labels=labels,
-                                                  ignore_index=ignore_index, threshold=threshold, want_pseudo=want_pseudo)
+                                                  ignore_index=ignore_index, threshold=threshold, want_pseudo=want_pseudo,
+                                                  class_threshold=class_threshold, hist=hist)
 
-    def predict_mask(self, x, size, labels=None, ignore_index=255, threshold=0.0, want_pseudo=False):
+    def predict_mask(self, x, size, labels=None, ignore_index=255, threshold=0.0, want_pseudo=False, class_threshold=None, hist=None):
         """predict_probs(x, size)[:1].max(1) without the probability map: the whole batch goes through the head as in predict_probs, image 0's
         logits are scored (inference() keeps image 0, utility.py:190)."""
         _require_gpu(x, "ASPP_Classifier_V2")
@@ -311,7 +314,8 @@ class ASPP_Classifier_V2(nn.Module):
                 self._engine.prepare(False)
                 low = self._engine.forward(self._nhwc(x))
             return kernels.upsample_predict_score([low[0]], [False], tuple(int(s) for s in size), 1.0, 1.0, labels=labels,
-                                                  ignore_index=ignore_index, threshold=threshold, want_pseudo=want_pseudo)
+                                                  ignore_index=ignore_index, threshold=threshold, want_pseudo=want_pseudo,
+                                                  class_threshold=class_threshold, hist=hist)
 
 
 class CrossEntropyLoss(nn.Module):

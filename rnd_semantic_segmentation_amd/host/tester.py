@@ -6,8 +6,9 @@ import os
 import numpy as np
 import torch
 
-from .metrics import (AverageMeter, confusion_matrix, dump_json, inference, intersectionAndUnionGPU, multi_scale_inference,
-                      predict_and_score, score_settings, strip_prefix_if_present, tta_settings)
+from .metrics import (PSEUDO_BINS, AverageMeter, class_thresholds, classwise_pseudo_labels, classwise_settings, confusion_matrix, dump_json, inference,
+                      intersectionAndUnionGPU, literal_histogram, literal_pseudo, multi_scale_inference, predict_and_score, score_settings,
+                      strip_prefix_if_present, threshold_table, tta_settings)
 from .modules import build_classifier, build_feature_extractor
 
 
@@ -23,6 +24,7 @@ class ASPPTester:
         self.palette = palette
         self.trainid2name = trainid2name
         self.saveres = saveres
+        classwise_settings(cfg)                            # a stray TEST.PSEUDO_PORTION is refused before anything is built
         self.feature_extractor = self.build_feature_extractor(cfg)
         self.feature_extractor.to(device)
         self.classifier = self.build_classifier(cfg)
@@ -55,6 +57,12 @@ class ASPPTester:
         mask.putpalette(list(self.palette))
         mask.save(os.path.join(folder, name[0] + ".png"))
 
+    def _literal_output(self, x, y, single, scales, flip):
+        if single:
+            return inference(self.feature_extractor, self.classifier, x, y, flip=False)     # [1,K,H,W]
+        # the call aspp_tester.py:61 keeps commented out
+        return multi_scale_inference(self.feature_extractor, self.classifier, x, y, flip=flip, scales=list(scales))
+
     def test(self):
         num_classes = self.cfg.MODEL.NUM_CLASSES
         self.feature_extractor.eval()
@@ -64,25 +72,27 @@ class ASPPTester:
         scales, flip = tta_settings(self.cfg)
         single = scales == (1.0,) and not flip
         fused, threshold = score_settings(self.cfg)
+        classwise, portion, cap = classwise_settings(self.cfg)
         # one kernel after the logits (argmax, threshold, counts) instead of the probability map and the torch-op metrics: same integers, same files
         fused = fused and self.device.type == "cuda" and hasattr(self.classifier, "predict_mask_multi")
+        # TEST.PSEUDO_CLASSWISE: this loop is pass 1 - the metrics as ever, no masks, and the confidence histogram of the whole set on the device
+        hist = torch.zeros(num_classes, PSEUDO_BINS, dtype=torch.int64, device=self.device) if classwise else None
         for x, y, name in self.test_loader:
             x = x.to(self.device, non_blocking=True)
             y = y.to(self.device, non_blocking=True).long()
             if fused:
                 r = predict_and_score(self.feature_extractor, self.classifier, x, y, flip=flip, scales=scales, num_classes=num_classes,
-                                      ignore_index=self.cfg.INPUT.IGNORE_LABEL, threshold=threshold)
-                if self.saveres:
+                                      ignore_index=self.cfg.INPUT.IGNORE_LABEL, threshold=0.0 if classwise else threshold, hist=hist)
+                if self.saveres and not classwise:
                     self.save_mask(r.pred if r.pseudo is None else r.pseudo, name)
                 cmt = cmt + r.cmt
                 self.meter.update(*[t.numpy() for t in (r.intersection, r.union, r.target, r.output)])
                 continue
-            if single:
-                output = inference(self.feature_extractor, self.classifier, x, y, flip=False)     # [1,K,H,W]
-            else:                                          # the call aspp_tester.py:61 keeps commented out
-                output = multi_scale_inference(self.feature_extractor, self.classifier, x, y, flip=flip, scales=list(scales))
+            output = self._literal_output(x, y, single, scales, flip)
             pred = output.max(1)[1]
-            if self.saveres and threshold == 0:
+            if classwise:
+                hist += literal_histogram(output, num_classes)
+            elif self.saveres and threshold == 0:
                 self.save_distill(output, name)
             elif self.saveres:
                 top = output.max(1)
@@ -95,4 +105,36 @@ class ASPPTester:
         os.makedirs(self.cfg.OUTPUT_DIR, exist_ok=True)
         dump_json(os.path.join(self.cfg.OUTPUT_DIR, "aspp_confusion_matrix.json"),
                   {"cmt": cmt.tolist(), "classes": list(self.trainid2name.values())})
+        if classwise:
+            self._classwise_masks(hist, portion, cap, fused, single, scales, flip)
         return cmt
+
+    def _classwise_masks(self, hist, portion, cap, fused, single, scales, flip):
+        """After pass 1 of TEST.PSEUDO_CLASSWISE: the thresholds from the histogram (one device-to-host copy), their table to the logger and to
+        PSEUDO_DIR/inference/<dataset>/class_thresholds.json, and - with --saveres - pass 2 over the loader, which writes the masks with the
+        table and does nothing else (the 1/8-resolution logits of pass 1 are not kept: a second backbone pass is cheap next to PNG encoding)."""
+        num_classes = self.cfg.MODEL.NUM_CLASSES
+        hist = hist.cpu()
+        self.class_hist = hist
+        self.class_thresholds = thresholds = class_thresholds(hist, portion, cap)
+        names = list(self.trainid2name.values())
+        names = names if len(names) == num_classes else None
+        table = threshold_table(hist, thresholds, names)
+        table.update(portion=portion, cap=cap)
+        for c in range(num_classes):
+            self.logger.info("Class-wise pseudo-labels, class {} ({}): {} pixels, threshold {:.6f}, kept {:.4f}.".format(
+                c, table["classes"][c], table["pixels"][c], table["thresholds"][c], table["kept"][c]))
+        folder = os.path.join(self.cfg.PSEUDO_DIR, "inference", self.cfg.DATASETS.TEST)
+        os.makedirs(folder, exist_ok=True)
+        dump_json(os.path.join(folder, "class_thresholds.json"), table)
+        if not self.saveres:
+            return
+        for x, y, name in self.test_loader:
+            x = x.to(self.device, non_blocking=True)
+            y = y.to(self.device, non_blocking=True).long()
+            if fused:
+                mask = classwise_pseudo_labels(self.feature_extractor, self.classifier, x, y, flip=flip, scales=scales, num_classes=num_classes,
+                                               class_threshold=thresholds)
+            else:
+                mask = literal_pseudo(self._literal_output(x, y, single, scales, flip), thresholds)
+            self.save_mask(mask, name)

@@ -612,11 +612,15 @@ def upsample_softmax_multi(lows, mirrors, size, div_a, div_b=1.0):
     return probs
 
 
-def upsample_predict_score(lows, mirrors, size, div_a, div_b=1.0, labels=None, ignore_index=255, threshold=0.0, want_pseudo=False):
+def upsample_predict_score(lows, mirrors, size, div_a, div_b=1.0, labels=None, ignore_index=255, threshold=0.0, want_pseudo=False, *, class_threshold=None,
+                           hist=None):
     """The evaluation tail without the probability map (mi_upsample_predict_score): the per-pixel values of upsample_softmax_multi(lows, mirrors,
     size, div_a, div_b), reduced in registers.  Returns (pred, pseudo, counts): pred uint8 [H,W] = the lowest class index among the maxima,
     pseudo uint8 [H,W] = pred where the maximum >= threshold else 255 (None unless want_pseudo), counts int64 [K*K + 3K] on the device = confusion
-    matrix, area_intersection, area_output, area_target of pred against labels [H,W] int64 (None without labels; split_counts names the parts)."""
+    matrix, area_intersection, area_output, area_target of pred against labels [H,W] int64 (None without labels; split_counts names the parts).
+    Class-wise pseudo-labels (mi_upsample_predict_score_cw, the same kernel body): class_threshold = K floats on the host (a sequence, an array or
+    a CPU tensor) replaces `threshold` in pseudo = pred where the maximum >= class_threshold[pred]; hist = the caller's int64 [K, PSEUDO_BINS]
+    device tensor, to which every pixel's (pred, metrics.confidence_bin(maximum)) cell is ADDED - it persists across images."""
     n = len(lows)
     if not 1 <= n <= 16 or len(mirrors) != n:
         raise _lib.MiError("upsample_predict_score: 1..16 sources with one mirror flag each (got %d / %d)" % (n, len(mirrors)))
@@ -637,9 +641,28 @@ def upsample_predict_score(lows, mirrors, size, div_a, div_b=1.0, labels=None, i
         counts = torch.zeros(K * K + 3 * K, dtype=torch.int64, device=dev)
     pred = torch.empty((H, W), dtype=torch.uint8, device=dev)
     pseudo = torch.empty((H, W), dtype=torch.uint8, device=dev) if want_pseudo else None
-    check(_lib.lib().mi_upsample_predict_score(ctypes.cast(src, ctypes.c_void_p), n, K, H, W, float(div_a), float(div_b), _p(labels),
-                                               int(ignore_index), float(threshold), _p(pred), _p(pseudo), _p(counts), _stream()),
-          "mi_upsample_predict_score")
+    if class_threshold is None and hist is None:
+        check(_lib.lib().mi_upsample_predict_score(ctypes.cast(src, ctypes.c_void_p), n, K, H, W, float(div_a), float(div_b), _p(labels),
+                                                   int(ignore_index), float(threshold), _p(pred), _p(pseudo), _p(counts), _stream()),
+              "mi_upsample_predict_score")
+        return pred, pseudo, counts
+    table = None
+    if class_threshold is not None:
+        values = [float(v) for v in (class_threshold.tolist() if hasattr(class_threshold, "tolist") else class_threshold)]
+        if len(values) != K:
+            raise _lib.MiError("class_threshold must hold %d values, got %d" % (K, len(values)))
+        table = (ctypes.c_float * K)(*values)
+    elif want_pseudo:
+        raise _lib.MiError("upsample_predict_score: want_pseudo with hist needs class_threshold (the scalar threshold is the plain entry's)")
+    bins = 0
+    if hist is not None:
+        _chk(hist, torch.int64, "hist")
+        if hist.dim() != 2 or hist.shape[0] != K or hist.device != dev:
+            raise _lib.MiError("hist must be [%d,bins] on %s, got %s on %s" % (K, dev, tuple(hist.shape), hist.device))
+        bins = int(hist.shape[1])
+    check(_lib.lib().mi_upsample_predict_score_cw(ctypes.cast(src, ctypes.c_void_p), n, K, H, W, float(div_a), float(div_b), _p(labels),
+                                                  int(ignore_index), ctypes.cast(table, ctypes.c_void_p) if table is not None else None, _p(pred),
+                                                  _p(pseudo), _p(counts), bins, _p(hist), _stream()), "mi_upsample_predict_score_cw")
     return pred, pseudo, counts
 
 

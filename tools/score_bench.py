@@ -15,6 +15,17 @@ The kernels' own times come from a separate `rocprofv3 --kernel-trace --stats` r
 mi_upsample_predict_score and mi_upsample_softmax_multi on the same sources per label size, and nothing else.
 
     python tools/score_bench.py [--iters 20] [--precision fp32|bf16] [--kernels N]
+
+--classwise measures the confidence histogram of class-wise pseudo-labels (TEST.PSEUDO_CLASSWISE) instead: per label size and source count,
+alternating in one process,
+  plain    mi_upsample_predict_score with labels (pass 1 without the feature)
+  hist     mi_upsample_predict_score_cw with labels and the histogram (pass 1 with it)
+  literal  the composition from torch ops: mi_upsample_softmax_multi (the map), max(1), confidence_bin, bincount
+on two inputs: the untrained net's logits (confidences spread over many cells) and saturated ones (one class leads by 100 everywhere: every pixel
+in ONE cell, the worst case for contention).  A figure is the time per call of --reps back-to-back calls between two device events; with
+--kernels N the three run N times each per case and nothing else, for a `rocprofv3 --kernel-trace` run (the kernels' own times).
+
+    python tools/score_bench.py --classwise [--iters 20] [--reps 20] [--precision bf16] [--kernels N]
 """
 import argparse
 import os
@@ -73,11 +84,75 @@ def peak_of(fn):
     return (torch.cuda.max_memory_allocated() - base) / 1e6
 
 
+def event_ms(fn, reps):
+    """Milliseconds per call of `reps` back-to-back calls, between two device events."""
+    start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    start.record()
+    for _ in range(reps):
+        fn()
+    end.record()
+    end.synchronize()
+    return start.elapsed_time(end) / reps
+
+
+def classwise(args, fe, cls, x):
+    K = NUM_CLASSES
+    for H, W in ((512, 1024), (1024, 2048)):
+        y = torch.from_numpy(synth.synth_label(1, H, W, K, seed=3)).cuda().long()
+        for multi in (False, True):
+            net, flags, (da, db) = low_sources(fe, cls, x, multi)
+            saturated = []
+            for low in net:
+                m = torch.zeros_like(low)
+                m[..., 0] = 100.0
+                saturated.append(m)
+            for what, lows in (("spread", net), ("saturated", saturated)):
+                hist = torch.zeros(K, metrics.PSEUDO_BINS, dtype=torch.int64, device="cuda")
+
+                def plain():
+                    return kernels.upsample_predict_score(lows, flags, (H, W), da, db, labels=y[0])
+
+                def with_hist():
+                    return kernels.upsample_predict_score(lows, flags, (H, W), da, db, labels=y[0], hist=hist)
+
+                def literal():
+                    top = kernels.upsample_softmax_multi(lows, flags, (H, W), da, db).max(1)
+                    return torch.bincount((top[1] * metrics.PSEUDO_BINS + metrics.confidence_bin(top[0])).flatten(),
+                                          minlength=K * metrics.PSEUDO_BINS).reshape(K, metrics.PSEUDO_BINS)
+
+                fns = (("plain", plain), ("hist", with_hist), ("literal", literal))
+                if args.kernels:
+                    for _ in range(args.kernels):
+                        for _, f in fns:
+                            f()
+                    torch.cuda.synchronize()
+                    continue
+                for _, f in fns:                                 # warm-up of every shape
+                    f()
+                hist.zero_()
+                with_hist()
+                want = literal()
+                same = torch.equal(hist, want)
+                cells = int((want > 0).sum())
+                times = {name: [] for name, _ in fns}
+                for _ in range(args.iters):                      # alternating: drift of the clocks hits all three alike
+                    for name, f in fns:
+                        times[name].append(event_ms(f, args.reps))
+                med = {name: statistics.median(v) for name, v in times.items()}
+                print("label %dx%d, %d source%s, %s, %s (%d occupied cells; histogram equals the literal one: %s; %d x %d calls):"
+                      % (H, W, len(lows), "s" if len(lows) > 1 else "", args.precision, what, cells, same, args.iters, args.reps))
+                for name, _ in fns:
+                    v = times[name]
+                    print("  %-7s median %8.4f ms per call (min %.4f, max %.4f)   / plain %.3f" % (name, med[name], min(v), max(v), med[name] / med["plain"]))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--precision", default="fp32", choices=("fp32", "bf16"))
     ap.add_argument("--kernels", type=int, default=0)
+    ap.add_argument("--classwise", action="store_true")
+    ap.add_argument("--reps", type=int, default=20)
     args = ap.parse_args()
     fe = modules.resnet_feature_extractor("resnet101", freeze_bn=True, pretrained_backbone=False)
     cls = modules.ASPP_Classifier_V2(2048, [6, 12, 18, 24], [6, 12, 18, 24], NUM_CLASSES)
@@ -85,6 +160,9 @@ def main():
     synth.load_formula_weights(cls)
     fe, cls = fe.cuda().eval().set_precision(args.precision), cls.cuda().eval().set_precision(args.precision)
     x = torch.from_numpy(synth.synth_image(1, 512, 1024, seed=3)).cuda()
+    if args.classwise:
+        classwise(args, fe, cls, x)
+        return
     for H, W in ((512, 1024), (1024, 2048)):
         y = torch.from_numpy(synth.synth_label(1, H, W, NUM_CLASSES, seed=3)).cuda().long()
         for multi in (False, True):
