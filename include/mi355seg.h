@@ -358,6 +358,32 @@ int mi_upsample_predict_score_cw(const MiProbSource* src, int n, int K, int H, i
                                  int ignore_index, const float* class_threshold, uint8_t* pred, uint8_t* pseudo, int64_t* counts, int bins,
                                  int64_t* hist, void* stream);
 
+/* ---- polyp evaluation tail: what Dice / IoU / F-beta / E-measure / S-measure / MAE need of PraNet's map, without the host ever seeing the map ----
+ * low [B][h][w] fp32 (the res2 logits), labels [B][H][W] int64 (ground truth in {0, 1}).  Per output pixel, all in fp32:
+ *   z = bilinear(low -> H x W), align_corners False, ATen's source index, each axis interpolated as a + lambda (b - a): a constant map stays constant
+ *       bit for bit and h == H / w == W is the identity; either axis may shrink or grow (two taps, no antialiasing, as F.interpolate);
+ *   p = 1 / (1 + exp(-z));   prob = (p - min) / (max - min + 1e-8), min / max of p over the WHOLE batch (pranet_tester.py:43);
+ *   q = int(prob * 255) truncated (0..255);   g = (label == 1).
+ * Outputs, all written (not added to) by every call:
+ *   hist   [B][2][256] int64: hist[b][g][q] = pixels of image b with ground truth g whose quantised probability is q;
+ *   sums   [B][MI_POLYP_SUMS] double: [quadrant LT, RT, LB, RB][sum prob, sum prob^2, sum prob g, sum prob^2 g, sum g] (20 values) over the
+ *          quadrants [0:cy, 0:cx], [0:cy, cx:W], [cy:H, 0:cx], [cy:H, cx:W], then cx, cy, and the batch's min and max of p.
+ *          cx = int(round_half_even(sum(col g) / G)) + 1, cy likewise with rows, in double; (0, 0) when G == 0;
+ *   counts [B][MI_POLYP_COUNTS] int64: G = sum g, sum(col g), sum(row g), the number of labels that are neither 0 nor 1 (counted as background);
+ *   prob   [B][H][W] fp32 or NULL;   pred [B][H][W] uint8 or NULL: prob > 1 - prob (PranetTester's mask; ties go to background).
+ * hist, sums, counts and pred come from exactly the fp32 values prob receives, and are the same bits whether prob / pred are requested or NULL.
+ * Bit-reproducible run to run: the histogram, the counts and min / max (on the bits of p >= 0) are integer atomics, which do not depend on
+ * arrival order; the floating-point sums use none - a thread adds at most 32 doubles, a wave adds in a xor butterfly, a workgroup writes one
+ * partial row into the workspace, and a last launch adds the rows of an image in a fixed order.  prob^2 is exact in double.
+ * Four launches on `stream` (init, scan, score, finalize); workspace: mi_polyp_score_workspace bytes, 8-byte aligned, no initialisation needed.
+ * Refused before any launch: a NULL low / labels / hist / sums / counts / workspace, a non-positive size, B > 65535, a side above 2^20 or more
+ * than 2^40 pixels, a workspace that is too small. */
+#define MI_POLYP_SUMS 24
+#define MI_POLYP_COUNTS 4
+size_t mi_polyp_score_workspace(int B, int h, int w, int H, int W);
+int mi_polyp_score(const float* low, const int64_t* labels, int B, int h, int w, int H, int W, int64_t* hist, double* sums, int64_t* counts,
+                   float* prob, uint8_t* pred, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- input side of multi-scale evaluation: F.interpolate(x, (Ho, Wo), mode='bilinear', align_corners=True) (utility.py:197) ----
  * x [B][C][H][W] fp32 NCHW (the loader's layout, what mi_stem_f32 consumes) -> out [B*(1+with_mirror)][C][Ho][Wo].  with_mirror != 0:
  * image b's horizontally mirrored copy (torch.flip(resized, [3]), utility.py:204: the mirror of the RESIZED image) is written as image B + b

@@ -59,6 +59,8 @@ SIGNATURES = {
     "mi_upsample_softmax_multi": (I, [P, I, P, I, I, I, F, F, P]),
     "mi_upsample_predict_score": (I, [P, I, I, I, I, F, F, P, I, F, P, P, P, P]),
     "mi_upsample_predict_score_cw": (I, [P, I, I, I, I, F, F, P, I, P, P, P, P, I, P, P]),
+    "mi_polyp_score_workspace": (Z, [I] * 5),
+    "mi_polyp_score": (I, [P, P] + [I] * 5 + [P, P, P, P, P, P, Z, P]),
     "mi_image_resize_ac": (I, [P, P] + [I] * 7 + [P]),
     "mi_stem_pool_fwd": (I, [P, P, P, P, P] + [I] * 6 + [P]),
     "mi_stem_pool_bwd": (I, [P, P, P, P] + [I] * 6 + [P]),

@@ -193,9 +193,12 @@ def default_tree():
         # PSEUDO_CLASSWISE True = class-balanced pseudo-labels (CBST; the BDL / FADA self-distillation rule): one threshold per class, the
         # PSEUDO_PORTION quantile (0.5 = the median) of the confidences of the pixels predicted as that class over the whole test set, capped at
         # PSEUDO_THRESHOLD (0 = no cap); ASPPTester takes them from a histogram the evaluation tail accumulates, then writes the masks in a second
-        # pass (metrics.classwise_settings; PSEUDO_PORTION changed while PSEUDO_CLASSWISE is False is refused)
+        # pass (metrics.classwise_settings; PSEUDO_PORTION changed while PSEUDO_CLASSWISE is False is refused);
+        # POLYP_METRICS True (PranetTester only; the other testers refuse it) = besides the intersection / union lines, the polyp-segmentation
+        # metrics PraNet is published with - mean Dice / IoU over 256 thresholds, F-beta, S-measure, E-measure, MAE - from one fused evaluation
+        # tail (mi_polyp_score), logged and written to OUTPUT_DIR/pranet_polyp_metrics.json; labels must be 0 / 1
         "TEST": {"BATCH_SIZE": 1, "PRECISION": "fp32", "SCALES": (1.0,), "FLIP": False, "FUSED_SCORE": True, "PSEUDO_THRESHOLD": 0.0,
-                 "PSEUDO_CLASSWISE": False, "PSEUDO_PORTION": 0.5},
+                 "PSEUDO_CLASSWISE": False, "PSEUDO_PORTION": 0.5, "POLYP_METRICS": False},
         "OUTPUT_DIR": ".",
         "resume": "",
         "PSEUDO_DIR": "",

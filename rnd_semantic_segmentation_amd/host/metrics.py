@@ -17,6 +17,9 @@ Differences that are deliberate and documented:
  * class-wise pseudo-label thresholds (PSEUDO_BINS, confidence_bin, class_thresholds, classwise_settings; TEST.PSEUDO_CLASSWISE) are not in the
    reference: the class-balanced rule of CBST / BDL / FADA self-distillation, stated in exact integers on a confidence histogram which the same
    kernel accumulates (mi_upsample_predict_score_cw).
+ * the polyp metrics (polyp_image_stats, PolypMeter, polyp_settings; TEST.POLYP_METRICS) are not in the reference either: mean Dice / IoU,
+   F-beta, E-measure, S-measure and MAE as PraNet and its successors report them on Kvasir, derived in float64 from the per-image histogram
+   and moment sums of mi_polyp_score - the host never sees the probability map.
 """
 import json
 import logging
@@ -461,6 +464,171 @@ def classwise_pseudo_labels(feature_extractor, classifier, image, label, flip=Fa
         return _engine_masks(feature_extractor, classifier, image, size, flip, tuple(scales), class_threshold=_class_table(class_threshold, K, "cpu"),
                              want_pseudo=True)[1]
     return literal_pseudo(_literal_output(feature_extractor, classifier, image, label, flip, tuple(scales)), class_threshold)
+
+
+# ----------------------------------------------------------------------------- polyp metrics (TEST.POLYP_METRICS)
+POLYP_EPS = 2.220446049250313e-16       # numpy's float64 eps, the constant of the published evaluation code
+POLYP_BINS = 256                        # thresholds 0..255 on q = int(float32(p) * 255)
+POLYP_KEYS = ("mDice", "mIoU", "meanF", "maxF", "S", "meanE", "maxE", "MAE")
+POLYP_QUADRANT_SUMS = 20                # sums[:20] = [LT, RT, LB, RB][sum p, sum p^2, sum p g, sum p^2 g, sum g]; sums[20:22] = cx, cy
+
+
+def polyp_settings(cfg):
+    """TEST.POLYP_METRICS of cfg.TEST (not a reference key; absent = False): PranetTester also reports the polyp-segmentation metrics."""
+    return bool(cfg.TEST.POLYP_METRICS) if "POLYP_METRICS" in cfg.TEST else False
+
+
+def require_no_polyp_metrics(cfg, who):
+    """The polyp metrics score PraNet's sigmoid map: testers of softmax models refuse the key rather than ignore it."""
+    if polyp_settings(cfg):
+        raise NotImplementedError("%s: TEST.POLYP_METRICS - the polyp metrics (Dice, IoU, F, S, E, MAE) exist for PranetTester only; leave it False"
+                                  % (who,))
+
+
+def _polyp_ratio(num, den, both_empty):
+    """num / den per threshold; where den == 0: 1 if prediction and ground truth are both empty, else 0."""
+    out = np.where(both_empty, 1.0, 0.0)
+    nz = den != 0
+    out[nz] = num[nz] / den[nz]
+    return out
+
+
+def _polyp_moments(n, s1, s2):
+    """(mean, variance with divisor n - 1, clamped at 0) of n values from their sum and sum of squares; fewer than 2 values: variance 0."""
+    mean = s1 / n
+    var = max(0.0, (s2 - n * mean * mean) / (n - 1)) if n > 1 else 0.0
+    return mean, var
+
+
+def _polyp_object(n, s1, s2):
+    """O(x) = 2 mean / (mean^2 + 1 + std(ddof=1) + eps) of n values from their sums; the std of fewer than 2 values is 0 (numpy: NaN)."""
+    if n == 0:
+        return 0.0
+    mean, var = _polyp_moments(n, s1, s2)
+    return 2.0 * mean / (mean * mean + 1.0 + math.sqrt(var) + POLYP_EPS)
+
+
+def _polyp_ssim(n, sp, sp2, spg, gq):
+    """The S-measure's region similarity of a quadrant of n pixels from sum p, sum p^2, sum p g, sum g (g^2 == g); fewer than 2 pixels: 0."""
+    if n < 2:
+        return 0.0
+    x, var_p = _polyp_moments(n, sp, sp2)
+    y, var_g = _polyp_moments(n, gq, gq)
+    cov = (spg - n * x * y) / (n - 1)
+    a = 4.0 * x * y * cov
+    b = (x * x + y * y) * (var_p + var_g)
+    if a != 0:
+        return a / (b + POLYP_EPS)
+    return 1.0 if b == 0 else 0.0
+
+
+def polyp_image_stats(hist, sums, H, W):
+    """One image's polyp metrics from what mi_polyp_score returns for it (or the same numbers computed elsewhere): hist int [2,256] (background,
+    foreground) of q = int(float32(p) * 255), sums float64 [>= 22] (POLYP_QUADRANT_SUMS quadrant sums, cx, cy).  float64 throughout.
+    Returns {"dice", "iou", "f", "e": float64 [256] curves over the thresholds q >= t, "S", "MAE": floats}.
+    Definitions: Dice 2TP/(TP+FP+G), IoU TP/(FP+G), F-beta with beta^2 = 0.3, the E-measure in the closed form of Fan et al. (IJCAI 2018) over
+    the four parts TP / FP / FN / TN, the S-measure of Fan et al. (ICCV 2017) with alpha = 0.5, MAE on the unquantised p.  Two deliberate
+    departures from the published code, which yields NaN there: a quadrant of fewer than 2 pixels contributes 0, and the std of fewer than 2
+    values is 0."""
+    hist = np.asarray(hist.cpu() if isinstance(hist, torch.Tensor) else hist).astype(np.int64)
+    sums = np.asarray(sums.cpu() if isinstance(sums, torch.Tensor) else sums, dtype=np.float64)
+    H, W = int(H), int(W)
+    N = H * W
+    if hist.shape != (2, POLYP_BINS) or sums.ndim != 1 or sums.shape[0] < POLYP_QUADRANT_SUMS + 2:
+        raise ValueError("polyp_image_stats: hist must be [2, %d] and sums hold at least %d values, got %s and %s"
+                         % (POLYP_BINS, POLYP_QUADRANT_SUMS + 2, hist.shape, sums.shape))
+    if int(hist.sum()) != N or (hist < 0).any():
+        raise ValueError("polyp_image_stats: the histogram holds %d pixels, the image %d" % (int(hist.sum()), N))
+    eps = POLYP_EPS
+    G = int(hist[1].sum())
+    tp = np.cumsum(hist[1][::-1])[::-1].astype(np.float64)          # TP_t = foreground pixels with q >= t
+    fp = np.cumsum(hist[0][::-1])[::-1].astype(np.float64)
+    empty = (tp + fp == 0) & (G == 0)
+    dice = _polyp_ratio(2.0 * tp, tp + fp + G, empty)
+    iou = _polyp_ratio(tp, fp + G, empty)
+    prec = _polyp_ratio(tp, tp + fp, empty)
+    rec = _polyp_ratio(tp, np.full(POLYP_BINS, float(G)), empty)
+    f = _polyp_ratio(1.3 * prec * rec, 0.3 * prec + rec, empty)
+    if G == 0:
+        e = (N - tp - fp) / (N - 1 + eps)
+    elif G == N:
+        e = (tp + fp) / (N - 1 + eps)
+    else:
+        mu_b, mu_g = (tp + fp) / N, G / N
+        e = np.zeros(POLYP_BINS)
+        for a, b, part in ((1 - mu_b, 1 - mu_g, tp), (1 - mu_b, -mu_g, fp), (-mu_b, 1 - mu_g, G - tp), (-mu_b, -mu_g, N - G - fp)):
+            align = 2.0 * a * b / (a * a + b * b + eps)
+            e = e + (align + 1.0) ** 2 / 4.0 * part
+        e = e / (N - 1 + eps)
+    quad = sums[:POLYP_QUADRANT_SUMS].reshape(4, 5)
+    sp, sp2, spg, sp2g = [float(v) for v in quad.sum(0)[:4]]
+    mae = ((G - spg) + (sp - spg)) / N                              # sum over foreground of (1 - p) + sum over background of p
+    yfrac = G / N
+    if G == 0:
+        s = 1.0 - sp / N
+    elif G == N:
+        s = sp / N
+    else:
+        # foreground: p over g == 1; background: 1 - p over g == 0, whose sums are n - sum p and n - 2 sum p + sum p^2
+        nb, spb, sp2b = N - G, sp - spg, sp2 - sp2g
+        s_obj = yfrac * _polyp_object(G, spg, sp2g) + (1.0 - yfrac) * _polyp_object(nb, nb - spb, nb - 2.0 * spb + sp2b)
+        cx, cy = int(sums[POLYP_QUADRANT_SUMS]), int(sums[POLYP_QUADRANT_SUMS + 1])
+        if not (0 <= cx <= W and 0 <= cy <= H):
+            raise ValueError("polyp_image_stats: split point (%d, %d) outside the %d x %d image" % (cx, cy, H, W))
+        sizes = (cx * cy, cy * (W - cx), (H - cy) * cx, (H - cy) * (W - cx))
+        w1, w2, w3 = cx * cy / N, cy * (W - cx) / N, (H - cy) * cx / N
+        weights = (w1, w2, w3, 1.0 - w1 - w2 - w3)
+        s_reg = 0.0
+        for n, wt, (qp, qp2, qpg, _, qg) in zip(sizes, weights, quad):
+            s_reg += wt * _polyp_ssim(n, float(qp), float(qp2), float(qpg), float(qg))
+        s = max(0.0, 0.5 * s_obj + 0.5 * s_reg)
+    return {"dice": dice, "iou": iou, "f": f, "e": e, "S": float(s), "MAE": float(mae)}
+
+
+def polyp_centre(G, col_sum, row_sum):
+    """(cx, cy) of the S-measure's split from the integers G = sum g, sum(col g), sum(row g): int(round_half_even(sum / G)) + 1 in float64
+    (Python's round is half-even), as mi_polyp_score computes it; (0, 0) when G == 0."""
+    G = int(G)
+    if G == 0:
+        return 0, 0
+    return int(round(int(col_sum) / G)) + 1, int(round(int(row_sum) / G)) + 1
+
+
+class PolypMeter(object):
+    """Dataset aggregation of polyp_image_stats: every curve is averaged over images, mean* is the mean of that curve over the 256 thresholds and
+    max* its maximum; S and MAE are means over images."""
+
+    def __init__(self):
+        self.reset()
+
+    def reset(self):
+        self.curves = {k: np.zeros(POLYP_BINS) for k in ("dice", "iou", "f", "e")}
+        self.s_sum = 0.0
+        self.mae_sum = 0.0
+        self.count = 0
+
+    def update(self, stats):
+        for k in self.curves:
+            self.curves[k] = self.curves[k] + np.asarray(stats[k], dtype=np.float64)
+        self.s_sum += float(stats["S"])
+        self.mae_sum += float(stats["MAE"])
+        self.count += 1
+
+    def mean_curves(self):
+        n = float(max(self.count, 1))
+        return {k: v / n for k, v in self.curves.items()}
+
+    def as_dict(self):
+        c = self.mean_curves()
+        n = float(max(self.count, 1))
+        return {"mDice": float(c["dice"].mean()), "mIoU": float(c["iou"].mean()), "meanF": float(c["f"].mean()), "maxF": float(c["f"].max()),
+                "S": self.s_sum / n, "meanE": float(c["e"].mean()), "maxE": float(c["e"].max()), "MAE": self.mae_sum / n, "images": self.count}
+
+    def summary(self, logger):
+        r = self.as_dict()
+        logger.info("Polyp metric, val result over {} images: mDice/mIoU {:.4f}/{:.4f}.".format(r["images"], r["mDice"], r["mIoU"]))
+        logger.info("Polyp metric, val result: meanF/maxF {:.4f}/{:.4f}, S-measure {:.4f}.".format(r["meanF"], r["maxF"], r["S"]))
+        logger.info("Polyp metric, val result: meanE/maxE {:.4f}/{:.4f}, MAE {:.4f}.".format(r["meanE"], r["maxE"], r["MAE"]))
 
 
 # ----------------------------------------------------------------------------- io / logging

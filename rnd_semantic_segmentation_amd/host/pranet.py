@@ -572,13 +572,16 @@ class PraNetTrainer(BaseTrainer):
 
 class PranetTester:
     """pranet_tester.py:10-53: res2 -> resize to the label size (align_corners False) -> sigmoid -> min-max normalise over the batch ->
-    {background, polyp} by which of (1 - p, p) is larger -> intersection / union meters."""
+    {background, polyp} by which of (1 - p, p) is larger -> intersection / union meters.  TEST.POLYP_METRICS True (not in the reference) adds
+    the polyp-segmentation metrics - mean Dice / IoU, F-beta, S-measure, E-measure, MAE - from one fused tail (score) and writes
+    OUTPUT_DIR/pranet_polyp_metrics.json; the intersection / union meters are then fed from that tail's mask."""
 
     def __init__(self, cfg, device, test_loader, logger):
-        from .metrics import require_plain_argmax, require_single_scale
+        from .metrics import polyp_settings, require_plain_argmax, require_single_scale
         require_single_scale(cfg, "PranetTester")
         require_plain_argmax(cfg, "PranetTester")
         self.cfg, self.logger, self.test_loader, self.device = cfg, logger, test_loader, device
+        self.polyp_metrics = polyp_settings(cfg)                      # TEST.POLYP_METRICS: test() scores through kernels.polyp_score
         self.model = PraNet()
         self.model.to(device)
         # The reference thresholds an fp32 forward (pranet_tester.py:36-46): TEST.PRECISION 'fp32' (default) evaluates in the reference's precision
@@ -598,16 +601,44 @@ class PranetTester:
             p = (p - p.min()) / (p.max() - p.min() + 1e-8)
             return (p > 1 - p).long()                                  # np.stack([1 - p, p]).max(1)[1]: ties go to background
 
+    def score(self, x, y, names=None):
+        """TEST.POLYP_METRICS: one batch through the fused tail (kernels.polyp_score: resize, sigmoid, batch min-max, histogram, moment sums and
+        the mask of predict in four small launches).  Returns (pred int64 [B,H,W], [polyp_image_stats per image]); a label outside {0, 1} raises
+        ValueError naming the image - the S-measure's geometry has no meaning with holes."""
+        from .. import kernels
+        from .metrics import polyp_image_stats
+        with torch.no_grad():
+            res2 = self.model(x)[3].float()
+        r = kernels.polyp_score(res2.reshape(res2.shape[0], res2.shape[2], res2.shape[3]).contiguous(), y.contiguous(), want_prob=False, want_pred=True)
+        hist, sums, counts = r.hist.cpu().numpy(), r.sums.cpu().numpy(), r.counts.cpu().numpy()
+        for b in range(y.shape[0]):
+            if counts[b, 3]:
+                name = names[b] if names is not None and len(names) > b else "#%d of the batch" % b
+                raise ValueError("PranetTester: TEST.POLYP_METRICS needs labels in {0, 1}; image %s has %d others" % (name, int(counts[b, 3])))
+        return r.pred.long(), [polyp_image_stats(hist[b], sums[b], y.shape[1], y.shape[2]) for b in range(y.shape[0])]
+
     def test(self):
-        from .metrics import AverageMeter, intersectionAndUnionGPU
+        from .metrics import AverageMeter, PolypMeter, dump_json, intersectionAndUnionGPU
         self.model.eval()
         self.meter = AverageMeter()
-        for x, y, _ in self.test_loader:
+        self.polyp_meter = PolypMeter() if self.polyp_metrics else None
+        for x, y, names in self.test_loader:
             x = x.to(self.device, non_blocking=True)
             y = y.to(self.device, non_blocking=True)
             h, w = y.shape[-2:]
             y = y.reshape(y.shape[0], h, w).long()
-            pred = self.predict(x, (h, w))
+            if self.polyp_metrics:
+                pred, stats = self.score(x, y, names)
+                for s in stats:
+                    self.polyp_meter.update(s)
+            else:
+                pred = self.predict(x, (h, w))
             inter, union, target, res = intersectionAndUnionGPU(pred, y, self.cfg.MODEL.NUM_CLASSES, self.cfg.INPUT.IGNORE_LABEL)
             self.meter.update(inter.cpu().numpy(), union.cpu().numpy(), target.cpu().numpy(), res.cpu().numpy())
         self.meter.summary(self.logger, self.cfg.MODEL.NUM_CLASSES)
+        if self.polyp_metrics:
+            self.polyp_meter.summary(self.logger)
+            os.makedirs(self.cfg.OUTPUT_DIR, exist_ok=True)
+            curves = self.polyp_meter.mean_curves()
+            dump_json(os.path.join(self.cfg.OUTPUT_DIR, "pranet_polyp_metrics.json"),
+                      dict(self.polyp_meter.as_dict(), dice_curve=curves["dice"].tolist(), iou_curve=curves["iou"].tolist()))

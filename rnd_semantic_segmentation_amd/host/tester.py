@@ -7,8 +7,8 @@ import numpy as np
 import torch
 
 from .metrics import (PSEUDO_BINS, AverageMeter, class_thresholds, classwise_pseudo_labels, classwise_settings, confusion_matrix, dump_json, inference,
-                      intersectionAndUnionGPU, literal_histogram, literal_pseudo, multi_scale_inference, predict_and_score, score_settings,
-                      strip_prefix_if_present, threshold_table, tta_settings)
+                      intersectionAndUnionGPU, literal_histogram, literal_pseudo, multi_scale_inference, predict_and_score, require_no_polyp_metrics,
+                      score_settings, strip_prefix_if_present, threshold_table, tta_settings)
 from .modules import build_classifier, build_feature_extractor
 
 
@@ -25,6 +25,7 @@ class ASPPTester:
         self.trainid2name = trainid2name
         self.saveres = saveres
         classwise_settings(cfg)                            # a stray TEST.PSEUDO_PORTION is refused before anything is built
+        require_no_polyp_metrics(cfg, "ASPPTester")
         self.feature_extractor = self.build_feature_extractor(cfg)
         self.feature_extractor.to(device)
         self.classifier = self.build_classifier(cfg)

@@ -671,6 +671,35 @@ def split_counts(counts, K):
     return counts[:K * K].reshape(K, K), counts[K * K:K * K + K], counts[K * K + K:K * K + 2 * K], counts[K * K + 2 * K:K * K + 3 * K]
 
 
+POLYP_SUMS, POLYP_COUNTS = 24, 4            # MI_POLYP_SUMS, MI_POLYP_COUNTS
+PolypScore = collections.namedtuple("PolypScore", "hist sums counts prob pred")
+
+
+def polyp_score(low, labels, want_prob=False, want_pred=True):
+    """The polyp evaluation tail (mi_polyp_score): low [B,h,w] fp32 (PraNet's res2 logits), labels [B,H,W] int64 -> PolypScore of device tensors:
+    hist int64 [B,2,256] (ground truth x quantised probability), sums float64 [B,24] (the S-measure's quadrant moments, cx, cy, the batch's min /
+    max of the sigmoid), counts int64 [B,4] (G, label column / row sums, labels outside {0, 1}), prob fp32 [B,H,W] (the normalised map
+    PranetTester.predict thresholds; None unless want_prob) and pred uint8 [B,H,W] (prob > 1 - prob; None unless want_pred).  The statistics are
+    the same bits whichever side outputs are asked for.  host/metrics.py polyp_image_stats turns (hist, sums) into the metrics."""
+    _chk(low, torch.float32, "low")
+    _chk(labels, torch.int64, "labels")
+    if low.dim() != 3 or labels.dim() != 3 or labels.shape[0] != low.shape[0] or labels.device != low.device:
+        raise _lib.MiError("polyp_score: low [B,h,w] and labels [B,H,W] on one device, got %s on %s and %s on %s"
+                           % (tuple(low.shape), low.device, tuple(labels.shape), labels.device))
+    (B, h, w), (H, W) = low.shape, labels.shape[1:]
+    dev = low.device
+    hist = torch.empty((B, 2, 256), dtype=torch.int64, device=dev)
+    sums = torch.empty((B, POLYP_SUMS), dtype=torch.float64, device=dev)
+    counts = torch.empty((B, POLYP_COUNTS), dtype=torch.int64, device=dev)
+    prob = torch.empty((B, H, W), dtype=torch.float32, device=dev) if want_prob else None
+    pred = torch.empty((B, H, W), dtype=torch.uint8, device=dev) if want_pred else None
+    nbytes = _lib.lib().mi_polyp_score_workspace(B, h, w, H, W)
+    ws = torch.empty(max(nbytes, 8) // 8 + 1, dtype=torch.float64, device=dev)
+    check(_lib.lib().mi_polyp_score(_p(low), _p(labels), B, h, w, H, W, _p(hist), _p(sums), _p(counts), _p(prob), _p(pred), _p(ws), ws.numel() * 8,
+                                    _stream()), "mi_polyp_score")
+    return PolypScore(hist, sums, counts, prob, pred)
+
+
 def image_resize_ac(x, size, with_mirror=False):
     """F.interpolate(x, size, mode='bilinear', align_corners=True) on [B,C,H,W] fp32 NCHW; with_mirror appends torch.flip(resized, [3]) of
     image b as image B + b (one launch)."""
