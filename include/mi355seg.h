@@ -409,6 +409,23 @@ int mi_stem_pool_bwd(const void* dpool, const uint8_t* idx, const float* scale, 
  * k < 147, zero above (ncols a multiple of 8; 192 when the matrix also feeds the forward as a 1x1 mi_conv_gemm, 160 for the weight gradient
  * alone).  With it the stem conv is a plain GEMM and its weight gradient a 1x1 mi_conv_wgrad (deterministic), not the library's atomics. */
 int mi_stem_im2col(const void* x_bf16_nhwc, void* col_bf16, int B, int H, int W, int Ho, int Wo, int ncols, void* stream);
+/* The stem conv on raw image rows (csrc/stem_direct.hip): no patch matrix in forward or backward.
+ * mi_stem_pack_image: x fp32 NCHW [B][3][H][W] (x_is_bf16_nhwc 0) or bf16 NHWC [B][H][W][3] (1) -> x4 bf16 [B][H][W][4], channel 3 = 0, in one pass
+ *   (channels 0..2 are x rounded to nearest even, like x.to(bf16)).  x4 8-byte aligned.
+ * mi_stem_conv_fwd: x4 and w fp32 [64][3][7][7] -> y [B][Ho][Wo][64] bf16 NHWC, the raw conv output.  The contraction runs in the order of
+ *   mi_stem_im2col (192 columns) + mi_conv_gemm, which it replaces: y has the same bits.  wpack: 6*64*32 bf16 (24 KiB, 16-byte aligned) of scratch,
+ *   rewritten by every call (the weights as [k / 32][o][k % 32], k the OIHW order).  O must be 64, (Ho, Wo) the 7x7/2/3 output size, every tensor
+ *   within 2^31 elements; refused before any launch otherwise.
+ * mi_stem_conv_wgrad: dy [B][Ho][Wo][64] bf16 NHWC and x4 -> dw fp32 [64][3][7][7].  Pixels are split over workgroups, each writes an fp32
+ *   partial into `workspace` (mi_stem_conv_wgrad_workspace bytes, 16-byte aligned), and a reducer sums the partials in ascending split order: no
+ *   float atomics, bit-reproducible.
+ * mi_stem_direct_enabled: the MI_STEM_DIRECT switch (default 1; 0: the host engine takes the patch-matrix route, mi_stem_im2col + GEMM). */
+int mi_stem_direct_enabled(void);
+int mi_stem_pack_image(const void* x, int x_is_bf16_nhwc, void* x4, int B, int H, int W, void* stream);
+int mi_stem_conv_fwd(const void* x4, const float* w, void* wpack, void* y, int B, int H, int W, int O, int Ho, int Wo, void* stream);
+size_t mi_stem_conv_wgrad_workspace(int B, int Ho, int Wo);
+int mi_stem_conv_wgrad(const void* dy, const void* x4, float* dw, int B, int H, int W, int O, int Ho, int Wo, void* workspace,
+                       size_t workspace_bytes, void* stream);
 
 /* ---- FADA adversarial step (reference core/combos/aspp_fada.py:80-127) ---------------------------
  * db[n] (+)= sum_m dy[m][n]  (conv bias gradient; dy bf16 [M][N], N % 8 == 0; fixed summation order) */

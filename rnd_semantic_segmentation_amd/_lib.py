@@ -65,6 +65,11 @@ SIGNATURES = {
     "mi_stem_pool_fwd": (I, [P, P, P, P, P] + [I] * 6 + [P]),
     "mi_stem_pool_bwd": (I, [P, P, P, P] + [I] * 6 + [P]),
     "mi_stem_im2col": (I, [P, P] + [I] * 6 + [P]),
+    "mi_stem_direct_enabled": (I, []),
+    "mi_stem_pack_image": (I, [P, I, P, I, I, I, P]),
+    "mi_stem_conv_fwd": (I, [P, P, P, P] + [I] * 6 + [P]),
+    "mi_stem_conv_wgrad_workspace": (Z, [I] * 3),
+    "mi_stem_conv_wgrad": (I, [P, P, P] + [I] * 6 + [P, Z, P]),
     "mi_bias_grad_bf16": (I, [P, P, I, I, I, P, Z, P]),
     "mi_upsample_softce_workspace": (Z, [I] * 6),
     "mi_upsample_softce": (I, [P, F, F, P, I, I, P, P] + [I] * 6 + [F, P, Z, P]),

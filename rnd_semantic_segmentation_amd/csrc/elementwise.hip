@@ -69,6 +69,9 @@ const MiSwitches& mi_sw() {
         sw.p3_dbg = 0;
 #endif
         sw.pp_trace_wg = env("MI_PP_TRACE_WG", 0);
+        sw.stem_direct = env("MI_STEM_DIRECT", 1);
+        sw.stem_wgrad_splits = env("MI_STEM_WGRAD_SPLITS", 512);
+        if (sw.stem_wgrad_splits < 1 || sw.stem_wgrad_splits > 4096) sw.stem_wgrad_splits = 512;
     });
     return sw;
 }

@@ -54,6 +54,8 @@ struct MiSwitches {
     int gwgrad3;           // MI_GWGRAD3          1: general weight gradient of three-column kernels as one fused kernel row per workgroup from 65 536 pixels up (0: per tap, 2: always)
     int p3_dbg;            // MI_P3_DBG           0 (-DMI_EXPERIMENTS builds only)
     int pp_trace_wg;       // MI_PP_TRACE_WG      0 (-DMI_PP_TRACE builds only)
+    int stem_wgrad_splits; // MI_STEM_WGRAD_SPLITS 512: workgroups (= fp32 partials of 56 KiB) the direct stem weight gradient splits the pixels over (two per CU)
+    int stem_direct;       // MI_STEM_DIRECT      1: the stem conv and its weight gradient on raw image rows (stem_direct.hip); 0: patch matrix + GEMM
 };
 const MiSwitches& mi_sw();
 

@@ -591,7 +591,7 @@ def bn_backward(g, y, fin, count, bn, bits=None):
 
 
 class BnStemFn(torch.autograd.Function):
-    """Stem with a trainable BatchNorm2d in train(): 7x7/2 conv (patch matrix + GEMM) -> batch statistics -> normalise + ReLU + 3x3/2 max-pool in ONE
+    """Stem with a trainable BatchNorm2d in train(): 7x7/2 conv (stem_conv_forward) -> batch statistics -> normalise + ReLU + 3x3/2 max-pool in ONE
     pass (the fused FrozenBN stem kernel with the batch affine).  Backward: pooled gradient routed by the stored argmax (already ReLU-masked), the
     BatchNorm backward, the stem weight gradient.  resnet.py:137-140, 177-180 with feature_extractor.py:37."""
 
@@ -708,20 +708,28 @@ class Fp32Aspp:
 
 
 def stem_conv_forward(x, weight):
-    """x [B,3,H,W] bf16 channels_last, weight fp32 [64,3,7,7] -> (y [B,Hc,Wc,64] bf16 NHWC, what the weight gradient needs): patch matrix + plain
-    GEMM on the implicit-GEMM kernel - no library convolution anywhere in the step (rounds 1-4 kept an MIOpen branch behind MI_STEM_CONV; removed)."""
-    y, col = K.stem_conv_fwd(x, weight)
+    """x [B,3,H,W] (fp32 NCHW as the loader hands it over, or bf16 channels_last), weight fp32 [64,3,7,7] -> (y [B,Hc,Wc,64] bf16 NHWC, what the
+    weight gradient needs).  The image is packed once as bf16 [B,H,W,4] and the conv runs on raw image rows staged in LDS (csrc/stem_direct.hip): no
+    patch matrix, and what is kept for backward is the packed image.  MI_STEM_DIRECT=0: patch matrix + plain GEMM on the implicit-GEMM kernel, the
+    matrix kept for backward.  No library convolution anywhere in the step (rounds 1-4 kept an MIOpen branch behind MI_STEM_CONV; removed)."""
+    if K.stem_direct_enabled():
+        x4 = K.stem_pack_image(x)
+        return K.stem_conv_direct(x4, weight), (x4,)
+    y, col = K.stem_conv_fwd(x.to(dtype=torch.bfloat16).contiguous(memory_format=torch.channels_last), weight)
     return y, (col,)
 
 
 def stem_conv_wgrad(dy_nhwc, saved):
-    """d loss / d conv1.weight: the 1x1 weight-gradient kernel on the forward's patch matrix (bit-reproducible)."""
+    """d loss / d conv1.weight from what stem_conv_forward saved (bit-reproducible on both routes): the packed image [B,H,W,4] -> the direct weight
+    gradient; the patch matrix -> the 1x1 weight-gradient kernel."""
+    if K.stem_direct_enabled():          # the switch is read once per process: the same answer as in stem_conv_forward
+        return K.stem_wgrad_direct(dy_nhwc, saved[0])
     return K.stem_wgrad(dy_nhwc, col=saved[0])
 
 
 class StemConvFn(torch.autograd.Function):
     """The 7x7/2 stem conv alone (the trainable-BatchNorm stem); the input image needs no gradient.
-    x [B,3,H,W] bf16 channels_last, weight fp32 -> [B,Hc,Wc,64] bf16 NHWC."""
+    x [B,3,H,W] fp32 NCHW or bf16 channels_last, weight fp32 -> [B,Hc,Wc,64] bf16 NHWC."""
 
     @staticmethod
     def forward(ctx, x, weight):
@@ -735,8 +743,8 @@ class StemConvFn(torch.autograd.Function):
 
 
 class StemFn(torch.autograd.Function):
-    """Stem: 7x7/2 conv (patch matrix + GEMM) + fused FrozenBN/ReLU/max-pool HIP kernel.
-    x [B,3,H,W] bf16 channels_last, weight fp32 [64,3,7,7] -> pooled [B,Hp,Wp,64] bf16 NHWC."""
+    """Stem: 7x7/2 conv (stem_conv_forward) + fused FrozenBN/ReLU/max-pool HIP kernel.
+    x [B,3,H,W] fp32 NCHW or bf16 channels_last, weight fp32 [64,3,7,7] -> pooled [B,Hp,Wp,64] bf16 NHWC."""
 
     @staticmethod
     def forward(ctx, x, weight, scale, shift):

@@ -146,7 +146,7 @@ class resnet_feature_extractor(nn.Module):
             return self._fp32.forward(x.float()).permute(0, 3, 1, 2)        # NCHW-shaped view of NHWC fp32 memory
         self.ensure_flat()
         bb = self.backbone
-        xb = x.to(dtype=torch.bfloat16).contiguous(memory_format=torch.channels_last)
+        xb = x          # engine.stem_conv_forward packs the image for the stem conv (fp32 NCHW or bf16 channels_last) in one pass
         self._engine.batch_stats = (not self.freeze_bn) and self.training
         if self._engine.batch_stats:
             # trainable BatchNorm2d in train(): batch statistics between each conv and its normalise pass, two autograd nodes with hand-written
@@ -154,7 +154,7 @@ class resnet_feature_extractor(nn.Module):
             y = engine.BnStemFn.apply(xb, bb.conv1.weight, bb.bn1.weight, bb.bn1.bias, bb.bn1)
             params = [p for rt in self._engine.convs for p in (rt.weight, rt.bn.weight, rt.bn.bias)]
             return engine.BnStagesFn.apply(y, self._engine, *params).permute(0, 3, 1, 2)
-        # stem: 7x7/2 conv as patch matrix + GEMM (engine.stem_conv_forward), then FrozenBN + ReLU + 3x3/2 max-pool in one HIP kernel
+        # stem: 7x7/2 conv on raw image rows (engine.stem_conv_forward), then FrozenBN + ReLU + 3x3/2 max-pool in one HIP kernel
         scale, shift = self._stem_fold()
         y = engine.StemFn.apply(xb, bb.conv1.weight, scale, shift)                       # [B,Hp,Wp,64] bf16 NHWC
         weights = [rt.weight for rt in self._engine.convs]

@@ -770,6 +770,70 @@ def stem_wgrad(dy, x=None, col=None):
     return dw.view(O, n)[:, :147].reshape(O, 3, 7, 7)
 
 
+def stem_direct_enabled():
+    """MI_STEM_DIRECT (default 1): the stem conv runs on raw image rows (csrc/stem_direct.hip); 0 restores patch matrix + GEMM."""
+    return bool(_lib.lib().mi_stem_direct_enabled())
+
+
+def _stem_out_hw(H, W):
+    return (H + 6 - 7) // 2 + 1, (W + 6 - 7) // 2 + 1
+
+
+def stem_pack_image(x):
+    """x [B,3,H,W] -> bf16 [B,H,W,4] with channel 3 = 0, in one pass: fp32 NCHW-contiguous (the loader's layout) or bf16 channels_last; any other
+    dtype / layout is first brought to bf16 channels_last by torch."""
+    if not x.is_cuda:
+        raise _lib.MiError("stem_pack_image: x must live on the GPU (no CPU path exists)")
+    if x.dim() != 4 or x.shape[1] != 3:
+        raise _lib.MiError("stem_pack_image: x must be [B,3,H,W], got %s" % (tuple(x.shape),))
+    B, _, H, W = x.shape
+    if x.dtype == torch.float32 and x.is_contiguous():
+        src, nhwc = x, 0
+    else:
+        src = x.to(dtype=torch.bfloat16).permute(0, 2, 3, 1)
+        if not src.is_contiguous():
+            src = src.contiguous()
+        nhwc = 1
+    x4 = torch.empty((B, H, W, 4), dtype=torch.bfloat16, device=x.device)
+    check(_lib.lib().mi_stem_pack_image(_p(src), nhwc, _p(x4), B, H, W, _stream()), "mi_stem_pack_image")
+    return x4
+
+
+def stem_conv_direct(x4, weight):
+    """The stem conv on the packed image: x4 [B,H,W,4] bf16 (stem_pack_image), weight fp32 [64,3,7,7] -> y [B,Ho,Wo,64] bf16 NHWC (raw conv
+    output, bit-equal to stem_conv_fwd's).  No patch matrix: a workgroup stages raw image rows in LDS."""
+    _chk(x4, torch.bfloat16, "x4")
+    w = _chk(weight.detach(), torch.float32, "weight")
+    B, H, W, C4 = x4.shape
+    if C4 != 4 or tuple(w.shape[1:]) != (3, 7, 7):
+        raise _lib.MiError("stem_conv_direct: x4 %s, weight %s" % (tuple(x4.shape), tuple(w.shape)))
+    O = w.shape[0]
+    Ho, Wo = _stem_out_hw(H, W)
+    y = torch.empty((B, Ho, Wo, O), dtype=torch.bfloat16, device=x4.device)
+    wpack = _workspace(6 * 64 * 32 * 2, x4.device, "stem_wpack")
+    check(_timed("stem_direct_fwd_kernel", 2.0 * B * Ho * Wo * O * 147, lambda: _lib.lib().mi_stem_conv_fwd(
+        _p(x4), _p(w), _p(wpack), _p(y), B, H, W, O, Ho, Wo, _stream()), tag=("fwd", 7, 4, O, B * Ho * Wo, 0, 1)), "mi_stem_conv_fwd")
+    return y
+
+
+def stem_wgrad_direct(dy, x4):
+    """Weight gradient of the stem conv on the packed image: dy [B,Ho,Wo,64] bf16 NHWC, x4 [B,H,W,4] bf16 -> fp32 [64,3,7,7]; fixed-order
+    partial sums, bit-reproducible."""
+    _chk(dy, torch.bfloat16, "dy")
+    _chk(x4, torch.bfloat16, "x4")
+    B, H, W, C4 = x4.shape
+    Ho, Wo = _stem_out_hw(H, W)
+    O = dy.shape[-1]
+    if C4 != 4 or tuple(dy.shape[:3]) != (B, Ho, Wo):
+        raise _lib.MiError("stem_wgrad_direct: dy %s does not belong to x4 %s" % (tuple(dy.shape), tuple(x4.shape)))
+    L = _lib.lib()
+    dw = torch.empty((O, 3, 7, 7), dtype=torch.float32, device=dy.device)
+    ws = _workspace(L.mi_stem_conv_wgrad_workspace(B, Ho, Wo), dy.device, "stem_wgrad")
+    check(_timed("stem_direct_wgrad_kernel+reduce", 2.0 * B * Ho * Wo * O * 147, lambda: L.mi_stem_conv_wgrad(
+        _p(dy), _p(x4), _p(dw), B, H, W, O, Ho, Wo, _p(ws), ws.numel(), _stream()), tag=("wgrad", 7, 4, O, B * Ho * Wo, 0, 1)), "mi_stem_conv_wgrad")
+    return dw
+
+
 def bias_grad_bf16(dy, db, accumulate=False):
     """db[n] (+)= sum over pixels of dy[..., n];  dy bf16 [B,H,W,N]"""
     _chk(dy, torch.bfloat16, "dy")
