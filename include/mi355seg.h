@@ -242,6 +242,21 @@ int mi_upsample_ce_w(const float* low, const int64_t* labels, const float* class
                      int B, int h, int w, int K, int H, int W, int ignore_index, float label_smoothing, float grad_scale, int align_corners,
                      void* workspace, size_t workspace_bytes, void* stream);
 
+/* Focal loss (Lin et al., 2017) in the same head: FL = -w_y (1 - p_y)^gamma log p_y, the smooth counterpart of OHEM.  Operands, restrictions,
+ * workspace (mi_upsample_ce_workspace), launch count and determinism as mi_upsample_ce_w.  With q = p_y, u = 1 - q, nll = -log q:
+ *   S    = sum_valid w_y
+ *   loss = sum_valid w_y u^gamma nll / S                                   (S == 0: nan)
+ *   m    = u^gamma (1 + gamma q nll / u)                                   (nll / u taken as 1 where u == 0)
+ *   d loss / d z_k = valid w_y m (p_k - [k==y]) / S
+ * u is formed as the sum of the other classes' exponentials over the sum of all, so it keeps its relative precision on confident pixels, and the
+ * gradient never forms u^(gamma-1): it is finite for every gamma in range.  0 <= gamma <= 8, finite.  gamma == 0 runs what mi_upsample_ce_w runs
+ * at label_smoothing 0 and gives its bits (with class_weights == NULL those of mi_upsample_ce_ex).  There is no label smoothing here.
+ * class_weights: [K] fp32 in DEVICE memory, read on every call, or NULL = all 1.  loss_out: [0] = loss, [1] = S, [2] = out-of-range labels,
+ * [3] = scratch.  dlow may be NULL (loss only, same loss bits); an entry of dlow that no valid pixel touches is exactly 0, also when S == 0. */
+int mi_upsample_ce_focal(const float* low, const int64_t* labels, const float* class_weights /*[K]*/, float* loss_out /*[4]*/, float* dlow,
+                         int B, int h, int w, int K, int H, int W, int ignore_index, float gamma, float grad_scale, int align_corners,
+                         void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- fused upsample + cross-entropy with online hard example mining (OHEM: the OhemCrossEntropy2d criterion GALDNet, CCNet, OCNet and HRNet-Seg
  * were published with) ----
  * Operands and restrictions as mi_upsample_ce_ex, and B H W < 2^24.  With z = bilinear(low) in either convention, p = softmax(z), y = label,

@@ -49,6 +49,7 @@ SIGNATURES = {
     "mi_upsample_ce": (I, [P, P, P, P] + [I] * 7 + [F, P, Z, P]),
     "mi_upsample_ce_ex": (I, [P, P, P, P] + [I] * 7 + [F, I, P, Z, P]),
     "mi_upsample_ce_w": (I, [P, P, P, P, P] + [I] * 7 + [F, F, I, P, Z, P]),
+    "mi_upsample_ce_focal": (I, [P, P, P, P, P] + [I] * 7 + [F, F, I, P, Z, P]),
     "mi_upsample_ce_ohem_workspace": (Z, [I] * 6),
     "mi_upsample_ce_ohem": (I, [P, P, P, P, P] + [I] * 7 + [F, L, F, I, P, Z, P]),
     "mi_upsample_gdl_workspace": (Z, [I] * 6),

@@ -134,10 +134,16 @@ __global__ void ce_bwd_kernel(const float* __restrict__ logits, const int64_t* _
 // finalize divides by S = sum_valid w_y and pass 2 by loss_out[1] as ever).  wce.cw (NULL: all 1) is read from device memory by every workgroup into
 // LDS - K floats, a label-indexed ds_read per pixel instead of a global load - with Wsum behind them, added in class order.
 // MODE == UPCE_PLAIN compiles none of it: wce is an unused kernel argument.
-enum { UPCE_PLAIN = 0, UPCE_WEIGHTED = 1 };
+// MODE == UPCE_FOCAL (mi_upsample_ce_focal, gamma > 0): FL = -w_y (1 - p_y)^gamma log p_y.  Per valid pixel, with q = p_y, u = 1 - q, nll = -log q:
+//   loss term = w_y u^gamma nll,  d_k = w_y m (p_k - [k==y]) with m = u^gamma (1 + gamma q nll / u),  "count" = w_y.
+// u is the sum of the OTHER classes' v_k (class order) over the sum of all - not 1 - q, which has no relative precision left on a confident pixel - and
+// nll is -log1p(-u) where u < 1/2 (log(sum) - picked rounds the sum to 1 + 6e-8 there).  m never forms u^(gamma-1) (infinite at u = 0 for gamma < 1):
+// nll / u tends to 1 as u tends to 0 and is taken as 1 there, so u == 0 gives m = 0 and d = 0 exactly.  d_y is -u itself.  The LDS extras are the K
+// class weights alone (no Wsum); wce.keep carries gamma.
+enum { UPCE_PLAIN = 0, UPCE_WEIGHTED = 1, UPCE_FOCAL = 2 };
 struct WceArgs {
     const float* cw;      // [K] class weights on the device, or NULL
-    float keep;           // 1 - s
+    float keep;           // 1 - s          (UPCE_FOCAL: gamma)
     float smooth;         // s / K
 };
 
@@ -147,8 +153,15 @@ struct WeightedSum {      // s += w_c (z_c - max), before the exponential for th
     __device__ __forceinline__ void operator()(int k, float zk) const { s += w[k] * zk; }
 };
 
-__host__ __device__ inline TileLds upce_lds(int npx_max, int K, int mode) {      // UPCE_WEIGHTED: [K] class weights, then Wsum
-    return TileLds(npx_max, K, true, mode == UPCE_WEIGHTED ? K + 1 : 0);
+__host__ __device__ inline TileLds upce_lds(int npx_max, int K, int mode) {      // UPCE_WEIGHTED: [K] class weights, then Wsum; UPCE_FOCAL: the weights
+    return TileLds(npx_max, K, true, mode == UPCE_WEIGHTED ? K + 1 : mode == UPCE_FOCAL ? K : 0);
+}
+
+// u^gamma and m = u^gamma (1 + gamma q nll / u) of the focal loss for gamma > 0, 0 <= u <= 1; both 0 at u == 0.
+__device__ __forceinline__ void focal_factors(float gamma, float u, float q, float nll, float& ug, float& m) {
+    ug = u > 0.f ? exp2f(gamma * log2f(u)) : 0.f;
+    const float ratio = u > 1e-30f ? nll / u : 1.f;
+    m = ug * (1.f + gamma * (q * ratio));
 }
 __host__ __device__ inline TileLds grad_lds(int npx_max, int K) {      // the x-tile kernels that only write a gradient
     return TileLds(npx_max, K, false, 0);
@@ -162,6 +175,9 @@ __global__ __launch_bounds__(256) void upce_pass1_kernel(const float* __restrict
     constexpr int KR = kreg<KT>;
     const XTile t = xtile_begin(upce_lds(npx_max, K, MODE), low, K, ay, ax, npx_max, jt_cols);
     float* wsh = t.extra;
+    if constexpr (MODE == UPCE_FOCAL) {
+        if (threadIdx.x < K) wsh[threadIdx.x] = wce.cw ? wce.cw[threadIdx.x] : 1.f;
+    }
     if constexpr (MODE == UPCE_WEIGHTED) {
         if (threadIdx.x < K) wsh[threadIdx.x] = wce.cw ? wce.cw[threadIdx.x] : 1.f;
         __syncthreads();
@@ -190,6 +206,32 @@ __global__ __launch_bounds__(256) void upce_pass1_kernel(const float* __restrict
         else
             se = softmax_terms<true>(q.c0, q.c1, q.lx, K, v, KR, lab, &picked);
         const float rse = 1.f / se;
+        if constexpr (MODE == UPCE_FOCAL) {
+            float other = 0.f, ey = 0.f;
+#pragma unroll
+            for (int k = 0; k < KR; ++k) {
+                if (k < K) {
+                    if (k == lab)
+                        ey = v[k];
+                    else
+                        other += v[k];
+                }
+            }
+            const float u = fminf(other * rse, 1.f), qy = ey * rse;
+            const float nll = u < 0.5f ? -log1pf(-u) : __logf(se) - picked;
+            float ug, m;
+            focal_factors(wce.keep, u, qy, nll, ug, m);
+            const float wy = wsh[lab], hard = wy * m;
+#pragma unroll
+            for (int k = 0; k < KR; ++k) {
+                if (k < K) d[k] = hard * (k == lab ? -u : v[k] * rse);
+            }
+            if (q.own) {
+                loss += (wy * ug) * nll;
+                cnt += wy;
+            }
+            continue;
+        }
         if constexpr (MODE == UPCE_WEIGHTED) {
             const float wy = wsh[lab], wsum = wsh[K];
             const float hard = wce.keep * wy;
@@ -875,23 +917,27 @@ namespace {
 // PLAIN instantiation whichever entry was called: the compiler contracts the two instantiations differently (the plain <19> interpolates with two
 // rounded products, the weighted one with an fma), so only the same code object makes "the defaults of mi_upsample_ce_w give mi_upsample_ce_ex's bits"
 // hold whatever a later compiler does.  The weights travel as a device pointer, so a captured graph sees later values.
-// zero_stays: the pass 2 that keeps exact zeros (wce_pass2_kernel).
+// zero_stays: the pass 2 that keeps exact zeros (wce_pass2_kernel).  focal_gamma > 0 (mi_upsample_ce_focal, without smoothing): the FOCAL instantiation;
+// 0 is everything above, untouched.
 int launch_upce(const char* who, const float* low, const int64_t* labels, const float* class_weights, float* loss_out, float* dlow, int B, int h, int w, int K,
                 int H, int W, int ignore_index, float label_smoothing, float grad_scale, int align_corners, bool zero_stays, void* workspace,
-                size_t workspace_bytes, hipStream_t st) {
+                size_t workspace_bytes, hipStream_t st, float focal_gamma = 0.f) {
     if (workspace_bytes < mi_upsample_ce_workspace(B, h, w, K, H, W)) return mi_set_error(MI_ENOMEM, "%s: workspace too small", who);
     const HeadPlan p = head_plan(h, w, H, W, align_corners);
     float* partial = (float*)workspace;
     float* tmp = dlow ? (float*)((char*)workspace + up256((size_t)B * H * p.tiles * 2 * sizeof(float))) : nullptr;
-    const bool plain = !class_weights && label_smoothing == 0.f;
-    const size_t lds = upce_lds(p.npx_max, K, plain ? UPCE_PLAIN : UPCE_WEIGHTED).bytes();
+    const bool focal = focal_gamma > 0.f, plain = !focal && !class_weights && label_smoothing == 0.f;
+    const size_t lds = upce_lds(p.npx_max, K, focal ? UPCE_FOCAL : plain ? UPCE_PLAIN : UPCE_WEIGHTED).bytes();
     MI_REQUIRE(lds <= MI_LDS_MAX, "%s: upsample factor too large for one LDS tile (%zu B)", who, lds);
-    const WceArgs wce{class_weights, 1.f - label_smoothing, label_smoothing / (float)K};
+    const WceArgs wce{class_weights, focal ? focal_gamma : 1.f - label_smoothing, label_smoothing / (float)K};
     unsigned* bad = reinterpret_cast<unsigned*>(loss_out + 3);
     if (hipMemsetAsync(bad, 0, sizeof(unsigned), st) != hipSuccess) return mi_set_error(MI_EHIP, "%s: memset", who);
     with_kt(K, [&](auto kt) {
         constexpr int KT = decltype(kt)::value;
-        if (plain)
+        if (focal)
+            launch_xtile<upce_pass1_kernel<KT, UPCE_FOCAL>>(p, H, B, lds, st, low, labels, partial, tmp, B, K, p.ay, p.ax, ignore_index, p.npx_max, bad,
+                                                            p.jt_cols, wce);
+        else if (plain)
             launch_xtile<upce_pass1_kernel<KT, UPCE_PLAIN>>(p, H, B, lds, st, low, labels, partial, tmp, B, K, p.ay, p.ax, ignore_index, p.npx_max, bad,
                                                             p.jt_cols, wce);
         else
@@ -935,6 +981,20 @@ extern "C" int mi_upsample_ce_w(const float* low, const int64_t* labels, const f
     MI_REQUIRE(std::isfinite(grad_scale), "mi_upsample_ce_w: grad_scale is not finite");
     return launch_upce("mi_upsample_ce_w", low, labels, class_weights, loss_out, dlow, B, h, w, K, H, W, ignore_index, label_smoothing, grad_scale,
                        align_corners, true, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+// Focal loss FL = -w_y (1 - p_y)^gamma log p_y on the upsampled logits, normalised by the weight sum of the valid pixels.  gamma == 0 is
+// mi_upsample_ce_w at label_smoothing 0: the same launches, the same bits.
+extern "C" int mi_upsample_ce_focal(const float* low, const int64_t* labels, const float* class_weights, float* loss_out, float* dlow, int B, int h, int w,
+                                    int K, int H, int W, int ignore_index, float gamma, float grad_scale, int align_corners, void* workspace,
+                                    size_t workspace_bytes, void* stream) {
+    MI_REQUIRE(low && labels && loss_out && workspace, "mi_upsample_ce_focal: null operand");
+    if (int rc = head_check("mi_upsample_ce_focal", B, h, w, K, H, W)) return rc;
+    MI_REQUIRE(std::isfinite(gamma), "mi_upsample_ce_focal: gamma is not finite");
+    MI_REQUIRE(gamma >= 0.f && gamma <= 8.f, "mi_upsample_ce_focal: gamma outside [0, 8]");
+    MI_REQUIRE(std::isfinite(grad_scale), "mi_upsample_ce_focal: grad_scale is not finite");
+    return launch_upce("mi_upsample_ce_focal", low, labels, class_weights, loss_out, dlow, B, h, w, K, H, W, ignore_index, 0.f, grad_scale, align_corners,
+                       true, workspace, workspace_bytes, (hipStream_t)stream, gamma);
 }
 
 extern "C" size_t mi_upsample_gdl_workspace(int B, int h, int w, int K, int H, int W) {

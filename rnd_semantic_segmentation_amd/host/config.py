@@ -14,7 +14,7 @@ import yaml
 
 _VALID = (tuple, list, str, int, float, bool, type(None))
 _RANGES = {"TEST.PSEUDO_THRESHOLD": (0.0, 1.0), "TEST.PSEUDO_PORTION": (0.0, 1.0), "SOLVER.TVERSKY_ALPHA": (0.0, 1.0), "SOLVER.LABEL_SMOOTHING": (0.0, 1.0),
-           "SOLVER.OHEM_THRESH": (0.0, 1.0), "SOLVER.OHEM_MIN_KEPT": (1, float("inf"))}      # closed intervals a merged value has to lie in
+           "SOLVER.OHEM_THRESH": (0.0, 1.0), "SOLVER.OHEM_MIN_KEPT": (1, float("inf")), "SOLVER.FOCAL_GAMMA": (0.0, 8.0)}      # closed intervals a merged value has to lie in
 _CHOICES = {"SOLVER.LOSS": ("ce", "gdl", "tversky", "ohem"), "SOLVER.GDL_WEIGHT": ("square", "identity", "sqrt")}      # the only values a merged key may take
 
 
@@ -185,6 +185,10 @@ def default_tree():
             # inside the fused heads (mi_upsample_ce_ohem).  OHEM_MIN_KEPT counts full-resolution pixels of one head, one batch, one rank.  The two keys
             # changed under any other LOSS are refused (plugin.ohem_options), as is "ohem" together with CLASS_WEIGHTS / LABEL_SMOOTHING.
             "OHEM_THRESH": 0.7, "OHEM_MIN_KEPT": 100000,
+            # not in the reference either: FOCAL_GAMMA in [0, 8] (0 = off) turns LOSS "ce" of ASPPTrainer, GALDTrainer and both FADA combos into the
+            # focal loss -w_y (1 - p_y)^FOCAL_GAMMA log p_y inside the fused heads (mi_upsample_ce_focal): OHEM's smooth counterpart.  It composes with
+            # CLASS_WEIGHTS; any other LOSS ("ohem" included), LABEL_SMOOTHING > 0 and PraNetTrainer refuse it (plugin.focal_options)
+            "FOCAL_GAMMA": 0.0,
         },
         # not in the reference: PRECISION fp32 = exact evaluation path, bf16 = training engine; SCALES / FLIP other than these defaults make
         # ASPPTester call multi_scale_inference (utility.py:193-209) instead of inference(flip=False); FUSED_SCORE True = argmax, threshold and

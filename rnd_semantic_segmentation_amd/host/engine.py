@@ -946,6 +946,27 @@ class AsppOhemLossFn(AsppLossFn):
         return loss_out[0].clone()
 
 
+class AsppFocalLossFn(AsppLossFn):
+    """AsppLossFn with the focal loss -w_y (1 - p_y)^gamma log p_y (K.upsample_ce_focal, gamma > 0); the backward is AsppLossFn's."""
+
+    @staticmethod
+    def forward(ctx, x, labels, eng, ignore_index, temperature, class_weights, gamma, *params):
+        train = any(ctx.needs_input_grad)
+        eng.prepare(train)
+        low = eng.forward(x)
+        eng.last_low = low
+        inv_t = 1.0 / temperature             # criterion(pred.div(T), label): the modulation sees the scaled logits
+        loss_out, dlow = K.upsample_ce_focal(low if temperature == 1.0 else low * inv_t, labels, gamma, want_grad=train,
+                                             grad_scale=1.0 if temperature == 1.0 else inv_t, ignore_index=ignore_index, class_weights=class_weights)
+        ctx.eng, ctx.x, ctx.dlow = eng, (x if train else None), dlow
+        ctx.loss_out = eng.last_loss_out = loss_out          # [loss, weight sum of the valid pixels, out-of-range labels, -]
+        bad = getattr(eng, "bad_labels", None)
+        if bad is None or bad.device != loss_out.device:
+            bad = eng.bad_labels = torch.zeros(1, dtype=torch.float32, device=loss_out.device)
+        bad.add_(loss_out[2:3])
+        return loss_out[0].clone()
+
+
 class UpsampleFn(torch.autograd.Function):
     """low [B,h,w,K] fp32 NHWC -> [B,K,H,W] fp32 NCHW, bilinear align_corners=True (classifier.py:31)."""
 

@@ -455,6 +455,8 @@ class AsppFada:
             self._reduce(f)
             f.optimizer_D.step()
         else:                                                   # literal order of operations for foreign modules
+            if getattr(a, "focal_gamma", 0.0) > 0.0:
+                raise NotImplementedError("SOLVER.FOCAL_GAMMA runs inside the fused head (classifier.loss); the literal path does not know it")
             src_fea = a.feature_extractor(src_input)
             src_pred = a.classifier(src_fea, src_size).div(T)
             loss_seg = F.cross_entropy(src_pred, src_label, ignore_index=self.cfg.INPUT.IGNORE_LABEL, weight=a.ce_weights, label_smoothing=a.ce_smoothing)

@@ -86,13 +86,19 @@ class _GaldRun(Run):
             acc(b, gk.gbinary(gk.OP_MUL, gm, a.t), True)
         return self.node(o, back)
 
-    def ce_head(self, low, labels, ignore_index, inv_t=None, class_weights=None, label_smoothing=0.0, ohem=None):
+    def ce_head(self, low, labels, ignore_index, inv_t=None, class_weights=None, label_smoothing=0.0, ohem=None, focal_gamma=0.0):
         """criterion(F.interpolate(low, size=labels.shape[-2:], mode="bilinear"), labels) (gcpa_cc2.py:78-81 + gald_trainer.py:76-79) fused: the
         full-resolution logits are never written; d loss / d low comes out of the same pass.  inv_t: criterion(out.div(T), labels) of
         gald_fada.py:85-88 as the same kernel on low * (1 / T) - bilinear upsampling is linear, so scaling before it is scaling after it.
         class_weights / label_smoothing: the criterion's weight= and label_smoothing= (mi_upsample_ce_w).  ohem = (thresh, min_kept): the
-        cross-entropy over this head's hard pixels only (mi_upsample_ce_ohem), mined on the logits after the scaling."""
+        cross-entropy over this head's hard pixels only (mi_upsample_ce_ohem), mined on the logits after the scaling.  focal_gamma > 0: the focal
+        loss -w_y (1 - p_y)^gamma log p_y (mi_upsample_ce_focal) on the logits after the scaling, with class_weights if given."""
         src = low.t if inv_t is None else low.t * inv_t
+        if focal_gamma > 0.0:
+            loss_out, dlow = K.upsample_ce_focal(src, labels, focal_gamma, want_grad=self.rec, ignore_index=ignore_index, align_corners=False,
+                                                 class_weights=class_weights)
+            _count_bad_labels(self.net, loss_out)
+            return self.node(loss_out[0].clone(), lambda g: acc(low, dlow * (g if inv_t is None else g * inv_t), True))
         if ohem is not None:
             loss_out, dlow, _ = K.upsample_ce_ohem(src, labels, ohem[0], ohem[1], want_grad=self.rec, ignore_index=ignore_index, align_corners=False)
             _count_bad_labels(self.net, loss_out)
@@ -395,50 +401,57 @@ class GCPADecoder(Engine):
         return super().forward(x, *feats)
 
     def _ce_extra(self):
-        """The cross-entropy's weight= / label_smoothing= of the running losses() / loss() call, as ce_head's keywords."""
+        """The cross-entropy's weight= / label_smoothing= / mining / focal exponent of the running losses() / loss() call, as ce_head's keywords."""
         return {"class_weights": self.__dict__.get("_ce_weights"), "label_smoothing": self.__dict__.get("_ce_smoothing") or 0.0,
-                "ohem": self.__dict__.get("_ce_ohem")}
+                "ohem": self.__dict__.get("_ce_ohem"), "focal_gamma": self.__dict__.get("_ce_focal") or 0.0}
 
-    def losses(self, x, feats, labels, ignore_index=255, criterion="ce", weight_type="square", class_weights=None, label_smoothing=0.0, ohem=None):
+    def losses(self, x, feats, labels, ignore_index=255, criterion="ce", weight_type="square", class_weights=None, label_smoothing=0.0, ohem=None,
+               focal_gamma=0.0):
         """(loss5, loss4, loss3, loss2) = criterion(out_i, labels) of gald_trainer.py:76-79 without materialising the four [B,19,H,W] logit tensors:
         what GALDTrainer.train_step calls.  criterion "ce": upsample + cross-entropy fused (mi_upsample_ce_ex; with class_weights [K] fp32 on the
         device or label_smoothing, CrossEntropyLoss(weight=, label_smoothing=): mi_upsample_ce_w); "gdl": upsample +
         GeneralizedDiceLoss(weight_type) fused (mi_upsample_gdl; gald_trainer.py:70-73); "ohem" with ohem = (thresh, min_kept): upsample +
-        cross-entropy over the hard pixels only (mi_upsample_ce_ohem), each of the four heads mining on its own logits."""
+        cross-entropy over the hard pixels only (mi_upsample_ce_ohem), each of the four heads mining on its own logits.  focal_gamma > 0 with
+        criterion "ce": the focal loss -w_y (1 - p_y)^gamma log p_y on every head (mi_upsample_ce_focal), with class_weights if given."""
         if criterion not in ("ce", "gdl", "ohem"):
             raise ValueError("criterion must be 'ce', 'gdl' or 'ohem', got %r" % (criterion,))
         if (criterion == "ohem") != (ohem is not None):
             raise ValueError("criterion 'ohem' and ohem=(thresh, min_kept) go together, got criterion %r with ohem %r" % (criterion, ohem))
         K.refuse_ohem_with_weights(ohem, class_weights, label_smoothing)
+        focal_gamma = K.refuse_focal_with(focal_gamma, ohem, label_smoothing)
         if ohem is not None:
             ohem = K.check_ohem(ohem)
             criterion = "ce"          # the cross-entropy head, with the mining entry
+        if criterion != "ce" and focal_gamma > 0.0:
+            raise ValueError("focal_gamma belongs to criterion 'ce', got %r" % (criterion,))
         if criterion != "ce" and (class_weights is not None or float(label_smoothing) != 0.0):
             raise ValueError("class_weights / label_smoothing belong to criterion 'ce', got %r" % (criterion,))
         if criterion == "gdl" and weight_type not in K.GDL_WEIGHT_TYPES:
             raise ValueError("Check out the weight_type: %r (one of %s)" % (weight_type, ", ".join(K.GDL_WEIGHT_TYPES)))
         self._ce_labels, self._ce_ignore = labels.long().contiguous(), int(ignore_index)
         self._gdl_weight = weight_type if criterion == "gdl" else None
-        self._ce_weights, self._ce_smoothing, self._ce_ohem = class_weights, float(label_smoothing), ohem
+        self._ce_weights, self._ce_smoothing, self._ce_ohem, self._ce_focal = class_weights, float(label_smoothing), ohem, focal_gamma
         try:
             return super().forward(x, *feats)
         finally:
-            self._ce_labels = self._gdl_weight = self._ce_weights = self._ce_smoothing = self._ce_ohem = None
+            self._ce_labels = self._gdl_weight = self._ce_weights = self._ce_smoothing = self._ce_ohem = self._ce_focal = None
 
-    def loss(self, x, feats, label, ignore_index=255, temperature=1.0, class_weights=None, label_smoothing=0.0, ohem=None):
+    def loss(self, x, feats, label, ignore_index=255, temperature=1.0, class_weights=None, label_smoothing=0.0, ohem=None, focal_gamma=0.0):
         """criterion(self(x, feats)[-1].div(temperature), label) of gald_fada.py:80-88 fused: out2 alone (linear5/4/3 are not run and get no
         gradient), upsampled with align_corners=False and cross-entropy in one pass on linear2 * (1 / temperature) - the same kernel as losses():
         bilinear upsampling is linear, so dividing the low-resolution logits divides the upsampled ones.  Leaves the 1/4-resolution linear2 logits
-        [B,K,h,w] fp32 (detached, before the division) in `self.last_low`.  ohem = (thresh, min_kept): the hard pixels only, as losses()."""
+        [B,K,h,w] fp32 (detached, before the division) in `self.last_low`.  ohem = (thresh, min_kept): the hard pixels only, as losses();
+        focal_gamma > 0: the focal loss, as losses()."""
         K.refuse_ohem_with_weights(ohem, class_weights, label_smoothing)
-        self._ce_labels, self._ce_ignore = label.long().contiguous(), int(ignore_index)
+        focal_gamma = K.refuse_focal_with(focal_gamma, ohem, label_smoothing)
+        self._ce_labels, self._ce_ignore, self._ce_focal = label.long().contiguous(), int(ignore_index), focal_gamma
         self._out2 = 1.0 / float(temperature)
         self._ce_weights, self._ce_smoothing = class_weights, float(label_smoothing)
         self._ce_ohem = None if ohem is None else K.check_ohem(ohem)
         try:
             return super().forward(x, *feats)
         finally:
-            self._ce_labels = self._out2 = self._ce_weights = self._ce_smoothing = self._ce_ohem = None
+            self._ce_labels = self._out2 = self._ce_weights = self._ce_smoothing = self._ce_ohem = self._ce_focal = None
 
     def low2(self, x, feats):
         """The 1/4-resolution linear2 logits [B,K,h,w] fp32 (NCHW-shaped view of NHWC memory) without a tape, in the module's mode: in train() the

@@ -111,6 +111,8 @@ class GaldFada:
             self._reduce(f)
             f.optimizer_D.step()
         else:                                                   # gald_fada.py:79-127 as written
+            if getattr(g, "focal_gamma", 0.0) > 0.0:
+                raise NotImplementedError("SOLVER.FOCAL_GAMMA runs inside the fused head (decoder.loss); the literal path does not know it")
             src_feats = enc(src_input)
             src_output = dec(src_input, src_feats)[-1].div(T)
             loss_seg = F.cross_entropy(src_output, src_label, ignore_index=ignore, weight=g.ce_weights, label_smoothing=g.ce_smoothing)

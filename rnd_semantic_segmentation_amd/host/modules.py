@@ -231,14 +231,21 @@ class ASPP_Classifier_V2(nn.Module):
             return engine.UpsampleFn.apply(low, tuple(int(s) for s in size))           # [B,K,H,W] fp32
         return low.permute(0, 3, 1, 2)
 
-    def loss(self, x, label, ignore_index=255, temperature=1.0, class_weights=None, label_smoothing=0.0, ohem=None):
+    def loss(self, x, label, ignore_index=255, temperature=1.0, class_weights=None, label_smoothing=0.0, ohem=None, focal_gamma=0.0):
         """criterion(self(x, label.shape[-2:]).div(temperature), label) fused (never writes the upsampled logits); class_weights ([K] fp32 on the
         device) and label_smoothing are the criterion's weight= and label_smoothing= (not used by the reference: host/config.py).
         ohem = (thresh, min_kept): the cross-entropy over the hard pixels only (mi_upsample_ce_ohem), mined on the logits after the division.
+        focal_gamma > 0: the focal loss -w_y (1 - p_y)^gamma log p_y (mi_upsample_ce_focal), with class_weights if given, on the logits after the division.
         Leaves the 1/8-resolution logits [B,K,h,w] (detached) in `self.last_low`."""
         engine.K.refuse_ohem_with_weights(ohem, class_weights, label_smoothing)
+        focal_gamma = engine.K.refuse_focal_with(focal_gamma, ohem, label_smoothing)
         _require_gpu(x, "ASPP_Classifier_V2")
         self.ensure_flat()
+        if focal_gamma > 0.0:
+            out = engine.AsppFocalLossFn.apply(self._nhwc(x), label.long().contiguous(), self._engine, int(ignore_index), float(temperature),
+                                               class_weights, focal_gamma, *self._params())
+            self.last_low = self._engine.last_low.detach().permute(0, 3, 1, 2)
+            return out
         if ohem is not None:
             thresh, min_kept = engine.K.check_ohem(ohem)
             out = engine.AsppOhemLossFn.apply(self._nhwc(x), label.long().contiguous(), self._engine, int(ignore_index), float(temperature),

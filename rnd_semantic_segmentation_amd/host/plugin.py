@@ -78,6 +78,34 @@ def ohem_options(cfg, who):
     return float(thresh), int(min_kept)
 
 
+FOCAL_GAMMA_MAX = 8.0          # SOLVER.FOCAL_GAMMA's range in host/config.py, mi_upsample_ce_focal's too
+
+
+def focal_options(cfg, who):
+    """SOLVER.FOCAL_GAMMA (not in the reference) as a float for the trainer `who`: 0 = off, > 0 = the focal loss -w_y (1 - p_y)^gamma log p_y in place of
+    SOLVER.LOSS "ce" inside the fused heads.  It composes with SOLVER.CLASS_WEIGHTS; whatever else it cannot modulate refuses it instead of ignoring it."""
+    solver = getattr(cfg, "SOLVER", None)
+    gamma = getattr(solver, "FOCAL_GAMMA", 0.0)
+    if isinstance(gamma, bool) or not isinstance(gamma, (int, float)) or not 0.0 <= gamma <= FOCAL_GAMMA_MAX:      # (a merged value was checked there; this one was assigned)
+        raise ValueError("SOLVER.FOCAL_GAMMA {!r} lies outside [0, {:g}]".format(gamma, FOCAL_GAMMA_MAX))
+    gamma = float(gamma)
+    if gamma == 0.0:
+        return 0.0
+    loss = getattr(solver, "LOSS", "ce")
+    if loss == "ohem":
+        raise NotImplementedError("SOLVER.FOCAL_GAMMA cannot be combined with SOLVER.LOSS 'ohem' ({}): the mining entry runs the plain cross-entropy; "
+                                  "focal loss is its smooth counterpart under SOLVER.LOSS 'ce'".format(who))
+    if loss != "ce":
+        raise NotImplementedError("SOLVER.FOCAL_GAMMA belongs to SOLVER.LOSS 'ce' (got {!r} for {})".format(loss, who))
+    if float(getattr(solver, "LABEL_SMOOTHING", 0.0)) > 0.0:
+        raise NotImplementedError("SOLVER.FOCAL_GAMMA cannot be combined with SOLVER.LABEL_SMOOTHING ({}): the focal entry modulates the cross-entropy "
+                                  "of the hard labels (SOLVER.CLASS_WEIGHTS are fine)".format(who))
+    if who == "PraNetTrainer":
+        raise NotImplementedError("PraNetTrainer's SOLVER.LOSS 'ce' is its structure loss (weighted BCE + IoU), which SOLVER.FOCAL_GAMMA does not modulate; "
+                                  "the key is for ASPPTrainer, GALDTrainer and the FADA combos")
+    return gamma
+
+
 class BaseTrainer:
     LOSSES = ("ce",)          # the criteria the trainer implements, as SOLVER.LOSS values
     MINED = ()                # SOLVER.LOSS values that are a LOSSES entry over mined pixels ("ohem" = "ce" over the hard pixels): accepted like LOSSES
@@ -87,6 +115,7 @@ class BaseTrainer:
         who = "PraNetTrainer" if any(c.__name__ == "PraNetTrainer" for c in type(self).__mro__) else type(self).__name__
         weights, self.ce_smoothing = ce_options(cfg, who)          # CrossEntropyLoss(weight=, label_smoothing=): refused early where they do not apply
         self.ohem = ohem_options(cfg, who)                          # (thresh, min_kept) under SOLVER.LOSS "ohem", else None
+        self.focal_gamma = focal_options(cfg, who)                  # SOLVER.FOCAL_GAMMA: > 0 = the focal loss in place of "ce", 0 = off
         self.cfg = cfg
         self.logger = setup_logger(name + "_train", cfg.OUTPUT_DIR, local_rank) if logger is None else logger
         self.train_loader = train_loader
@@ -111,6 +140,10 @@ class BaseTrainer:
         self.ce_kwargs = {"class_weights": self.ce_weights, "label_smoothing": self.ce_smoothing} if (weights is not None or self.ce_smoothing) else {}
         if self.ohem is not None:
             self.ce_kwargs = {"ohem": self.ohem}
+        if self.focal_gamma > 0.0:          # (focal_options refused smoothing and "ohem"): the weights, if any, without label_smoothing
+            self.ce_kwargs = {"focal_gamma": self.focal_gamma}
+            if self.ce_weights is not None:
+                self.ce_kwargs["class_weights"] = self.ce_weights
         self.init_params()
         if cfg.resume:
             self.logger.info("Loading checkpoint from {}".format(self.cfg.resume))

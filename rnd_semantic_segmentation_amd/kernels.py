@@ -508,6 +508,53 @@ def refuse_ohem_with_weights(ohem, class_weights, label_smoothing):
                                   "mi_upsample_ce_ohem mines on the plain cross-entropy")
 
 
+FOCAL_GAMMA_MAX = 8.0          # mi_upsample_ce_focal's range, SOLVER.FOCAL_GAMMA's too
+
+
+def check_focal_gamma(gamma):
+    """The focal exponent as a float in [0, FOCAL_GAMMA_MAX]; 0 = off."""
+    try:
+        g = float(gamma)
+    except (TypeError, ValueError):
+        raise ValueError("focal_gamma must be a number in [0, %g], got %r" % (FOCAL_GAMMA_MAX, gamma))
+    if not 0.0 <= g <= FOCAL_GAMMA_MAX:          # (a nan fails both comparisons)
+        raise ValueError("focal_gamma %r lies outside [0, %g]" % (gamma, FOCAL_GAMMA_MAX))
+    return g
+
+
+def refuse_focal_with(focal_gamma, ohem, label_smoothing):
+    """Focal loss (focal_gamma > 0) modulates the hard-label cross-entropy over every valid pixel: every layer refuses it together with OHEM
+    or label smoothing with this message.  Returns the checked exponent."""
+    g = check_focal_gamma(focal_gamma)
+    if g > 0.0 and (ohem is not None or float(label_smoothing) != 0.0):
+        raise NotImplementedError("focal_gamma (focal loss) cannot be combined with ohem / label_smoothing: mi_upsample_ce_focal modulates the "
+                                  "cross-entropy of the hard labels over every valid pixel (class_weights are fine)")
+    return g
+
+
+def upsample_ce_focal(low, labels, gamma, want_grad=True, grad_scale=1.0, ignore_index=255, align_corners=True, class_weights=None):
+    """Fused upsample + focal loss -w_y (1 - p_y)^gamma log p_y over the valid pixels, divided by their weight sum (mi_upsample_ce_focal).
+    Returns (loss_out[4] = loss, S, bad labels, scratch; dlow or None).  class_weights: [K] fp32 on low's device, or None; gamma in [0, 8],
+    0 = the weighted cross-entropy's launches and bits."""
+    _chk(low, torch.float32, "low")
+    _chk(labels, torch.int64, "labels")
+    gamma = check_focal_gamma(gamma)
+    B, h, w, K = low.shape
+    _, H, W = labels.shape
+    if class_weights is not None:
+        _chk(class_weights, torch.float32, "class_weights")
+        if tuple(class_weights.shape) != (K,) or class_weights.device != low.device:
+            raise _lib.MiError("upsample_ce_focal: class_weights must be [%d] on %s, got %s on %s" % (K, low.device, tuple(class_weights.shape),
+                                                                                                      class_weights.device))
+    L = _lib.lib()
+    ws = _workspace(L.mi_upsample_ce_workspace(B, h, w, K, H, W), low.device, "upce")
+    out = torch.empty(4, dtype=torch.float32, device=low.device)
+    dlow = torch.empty_like(low) if want_grad else None
+    check(L.mi_upsample_ce_focal(_p(low), _p(labels), _p(class_weights), _p(out), _p(dlow), B, h, w, K, H, W, ignore_index, gamma, float(grad_scale),
+                                 int(bool(align_corners)), _p(ws), ws.numel(), _stream()), "mi_upsample_ce_focal")
+    return out, dlow
+
+
 def upsample_ce_ohem(low, labels, thresh, min_kept, want_grad=True, grad_scale=1.0, ignore_index=255, align_corners=True, want_prob=False):
     """Fused upsample + cross-entropy over the hard pixels only (OHEM, mi_upsample_ce_ohem): kept = valid and softmax[label] <= t,
     t = max(thresh, min(min_kept, n valid)-th smallest softmax[label]).  Returns (loss_out[4] = loss, n_kept, bad labels, t; dlow or None;

@@ -2,7 +2,7 @@
 four head losses, backward, both Adam steps.
 
     python tools/gald_bench.py [--batch 6] [--height 720] [--width 1280] [--steps 10] [--loss ce|gdl|ohem] [--literal] [--alternate ROUNDS]
-                               [--class-weights median] [--label-smoothing S] [--ohem-thresh T] [--ohem-min-kept M]
+                               [--class-weights median] [--label-smoothing S] [--ohem-thresh T] [--ohem-min-kept M] [--focal-gamma G]
 
 --loss ce: the four fused upsample + cross-entropy heads (the default); --loss gdl: the four fused upsample + generalized Dice heads
 (configs/gald_src_dice.yaml).  --literal (with gdl): the composition without the fused kernel - decoder(x, feats) materialises the four [B,19,H,W]
@@ -14,6 +14,9 @@ F.cross_entropy(weight=, label_smoothing=) with autograd.
 keeping the pixels whose probability of the true class is at most max(T, the M-th smallest of the head); with --literal: the four materialised outputs
 through a torch-op OHEM (softmax, gather, torch.kthvalue, masked F.cross_entropy) with autograd.  With --alternate the variants are ce, ohem and
 ohem --literal.
+--focal-gamma G (with ce, combinable with --class-weights): the focal loss -w_y (1 - p_y)^G log p_y inside the fused heads (mi_upsample_ce_focal;
+configs/gald_src_focal.yaml); with --literal: the four materialised outputs through a focal loss written with F.log_softmax / gather / pow and
+autograd.  With --alternate the variants are ce, ce-focal and ce-focal --literal.
 --alternate N: ce, gdl and gdl --literal - and, when weights or smoothing are given, ce weighted fused and ce weighted literal - one after the other, N
 times over, in this one process (one JSON line per variant and round), so that they are compared on one box under the same conditions; the peak of
 allocated memory is reset before every variant."""
@@ -61,6 +64,16 @@ def torch_ohem(output, target, thresh, min_kept, ignore_label=255):
     return F.cross_entropy(output, torch.where(kept, target, torch.full_like(target, ignore_label)), ignore_index=ignore_label)
 
 
+def torch_focal(output, target, gamma, weight=None, ignore_label=255):
+    """Focal loss -w_y (1 - p_y)^gamma log p_y over the valid pixels, divided by their weight sum, with torch ops on a materialised [N,C,H,W] tensor."""
+    valid = target != ignore_label
+    y = torch.where(valid, target, torch.zeros_like(target))
+    logq = F.log_softmax(output, 1).gather(1, y.unsqueeze(1)).squeeze(1)
+    wy = valid.to(output.dtype) if weight is None else weight[y] * valid
+    u = (1.0 - logq.exp()).clamp_min(torch.finfo(output.dtype).tiny)
+    return -(wy * torch.pow(u, gamma) * logq).sum() / wy.sum()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=6)
@@ -75,8 +88,12 @@ def main():
     ap.add_argument("--label-smoothing", type=float, default=0.0, metavar="S", help="with ce: CrossEntropyLoss's label_smoothing")
     ap.add_argument("--ohem-thresh", type=float, default=0.7, metavar="T", help="with ohem: SOLVER.OHEM_THRESH")
     ap.add_argument("--ohem-min-kept", type=int, default=100000, metavar="M", help="with ohem: SOLVER.OHEM_MIN_KEPT")
+    ap.add_argument("--focal-gamma", type=float, default=0.0, metavar="G", help="with ce: SOLVER.FOCAL_GAMMA (combinable with --class-weights)")
     a = ap.parse_args()
-    weighted = a.class_weights is not None or a.label_smoothing != 0.0
+    focal = a.focal_gamma > 0.0
+    if focal and (a.loss != "ce" or a.label_smoothing != 0.0):
+        ap.error("--focal-gamma goes with --loss ce and without --label-smoothing")
+    weighted = (a.class_weights is not None or a.label_smoothing != 0.0) and not focal
     if weighted and a.loss != "ce" and not a.alternate:
         ap.error("--class-weights / --label-smoothing go with --loss ce")
     torch.manual_seed(0)
@@ -95,7 +112,11 @@ def main():
         oe.zero_grad()
         od.zero_grad()
         extra = {"class_weights": weights, "label_smoothing": a.label_smoothing} if loss_name == "ce-weighted" else {}
-        if literal and loss_name == "gdl":
+        if loss_name == "ce-focal":
+            extra = {"class_weights": weights, "focal_gamma": a.focal_gamma}
+        if literal and loss_name == "ce-focal":
+            l5, l4, l3, l2 = [torch_focal(o.float().contiguous(), lab, a.focal_gamma, weights) for o in dec(x, enc(x))]
+        elif literal and loss_name == "gdl":
             l5, l4, l3, l2 = [torch_gdl(o.float().contiguous(), lab) for o in dec(x, enc(x))]
         elif literal and loss_name == "ohem":
             l5, l4, l3, l2 = [torch_ohem(o.float().contiguous(), lab, a.ohem_thresh, a.ohem_min_kept) for o in dec(x, enc(x))]
@@ -132,10 +153,12 @@ def main():
             variants = (("ce", False), ("gdl", False), ("gdl", True)) + ((("ce-weighted", False), ("ce-weighted", True)) if weighted else ())
             if a.loss == "ohem":
                 variants = (("ce", False), ("ohem", False), ("ohem", True))
+            if focal:
+                variants = (("ce", False), ("ce-focal", False), ("ce-focal", True))
             for loss_name, literal in variants:
                 measure(loss_name, literal, a.warmup if r == 0 else 1)
     else:
-        measure("ce-weighted" if weighted else a.loss, a.literal, a.warmup)
+        measure("ce-focal" if focal else "ce-weighted" if weighted else a.loss, a.literal, a.warmup)
 
 
 if __name__ == "__main__":
