@@ -411,6 +411,16 @@ int mi_sgd_step(float* p, const float* g, float* buf, size_t n, float lr, float 
 /* the same update with hyper = {lr, momentum, weight_decay} read from DEVICE memory at run time: under HIP graph capture a
  * by-value argument is frozen into the graph, a pointer is not - the poly learning rate changes every step. */
 int mi_sgd_step_dev(float* p, const float* g, float* buf, size_t n, const float* hyper /*[3], device*/, void* stream);
+/* mi_sgd_step (mi_sgd_step_dev) over the whole flat store AND mi_pack_weights_multi of the updated weights, in one pass: every conv weight a row of
+ * `table_dev` describes (mi_pack_weights_multi's table, n_desc, total_blocks) is updated tile by tile and both bf16 operands are written from the
+ * registers / LDS that hold the new values; `gaps_dev` = n_gaps pairs [lo, hi) of element indices: what no row covers (other parameters, padding,
+ * a tail), updated in the same launch.  Rows and gaps must partition [0, n).  p and buf get mi_sgd_step's bits, wp / wpt the bits
+ * mi_pack_weights_multi writes from the stored p.  Buffers 16-byte aligned.  mi_sgd_pack_enabled: the MI_SGD_PACK switch (default 1). */
+int mi_sgd_pack_enabled(void);
+int mi_sgd_step_pack(float* p, const float* g, float* buf, size_t n, float lr, float momentum, float weight_decay, const float* sflat, void* wp,
+                     void* wpt, const int64_t* table_dev, int n_desc, int total_blocks, const int64_t* gaps_dev, int n_gaps, void* stream);
+int mi_sgd_step_pack_dev(float* p, const float* g, float* buf, size_t n, const float* hyper /*[3], device*/, const float* sflat, void* wp, void* wpt,
+                         const int64_t* table_dev, int n_desc, int total_blocks, const int64_t* gaps_dev, int n_gaps, void* stream);
 
 /* ---- stem tail: FrozenBN + ReLU + 3x3/stride 2/pad 1 max-pool fused (resnet.py:138-141) ----------------------
  * y: conv1 output [B][Hc][Wc][C] bf16 NHWC; pool [B][Hp][Wp][C] bf16; idx one byte per pooled element: the winning
@@ -434,6 +444,10 @@ int mi_stem_im2col(const void* x_bf16_nhwc, void* col_bf16, int B, int H, int W,
  * mi_stem_conv_wgrad: dy [B][Ho][Wo][64] bf16 NHWC and x4 -> dw fp32 [64][3][7][7].  Pixels are split over workgroups, each writes an fp32
  *   partial into `workspace` (mi_stem_conv_wgrad_workspace bytes, 16-byte aligned), and a reducer sums the partials in ascending split order: no
  *   float atomics, bit-reproducible.
+ * mi_stem_conv_wgrad_pool: the same weight gradient from the POOLED gradient: dpool [B][Hp][Wp][64] bf16 NHWC, idx (the argmax bytes of
+ *   mi_stem_pool_fwd, one per pooled element, 8-byte aligned) and the BatchNorm scale [64].  The launch builds each tile's dy in its staging exactly as
+ *   mi_stem_pool_bwd computes it, so dw has the bits of mi_stem_pool_bwd + mi_stem_conv_wgrad, and dy is never written.  Same workspace.
+ * mi_stem_pool_wgrad_enabled: the MI_STEM_POOL_WGRAD switch (default 1; 0: the host engine calls mi_stem_pool_bwd, then mi_stem_conv_wgrad).
  * mi_stem_direct_enabled: the MI_STEM_DIRECT switch (default 1; 0: the host engine takes the patch-matrix route, mi_stem_im2col + GEMM). */
 int mi_stem_direct_enabled(void);
 int mi_stem_pack_image(const void* x, int x_is_bf16_nhwc, void* x4, int B, int H, int W, void* stream);
@@ -441,6 +455,9 @@ int mi_stem_conv_fwd(const void* x4, const float* w, void* wpack, void* y, int B
 size_t mi_stem_conv_wgrad_workspace(int B, int Ho, int Wo);
 int mi_stem_conv_wgrad(const void* dy, const void* x4, float* dw, int B, int H, int W, int O, int Ho, int Wo, void* workspace,
                        size_t workspace_bytes, void* stream);
+int mi_stem_pool_wgrad_enabled(void);
+int mi_stem_conv_wgrad_pool(const void* dpool, const uint8_t* idx, const float* scale, const void* x4, float* dw, int B, int H, int W, int O,
+                            int Ho, int Wo, int Hp, int Wp, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- FADA adversarial step (reference core/combos/aspp_fada.py:80-127) ---------------------------
  * db[n] (+)= sum_m dy[m][n]  (conv bias gradient; dy bf16 [M][N], N % 8 == 0; fixed summation order) */
@@ -512,6 +529,9 @@ int mi_allreduce_bucket(void* ptr, size_t count, int dtype, int average, void* c
 /* y = msk > 0 ? x : 0 (bf16, n % 8 == 0): ReLU backward across an autograd boundary.  bits != 0: `msk` is the packed
  * sign-bit tensor written by MI_EPI_WRITE_MASK (same element order). */
 int mi_relu_mask(const void* x_bf16, const void* msk, void* y_bf16, size_t n, int bits, void* stream);
+/* The MI_HEAD_MASK switch (default 1): where the fused loss is the backbone output's only consumer (the source-only step), the host engine hands
+ * the output's sign bits to the head's data gradient (MI_EPI_BITMASK epilogue) and skips the stand-alone mi_relu_mask pass over that gradient. */
+int mi_head_mask_enabled(void);
 /* FrozenBN fold: scale = w*rsqrt(var) (no eps), shift = b - mean*scale (layers.py:18-20) */
 int mi_frozen_bn_fold(const float* w, const float* b, const float* mean, const float* var, float* scale, float* shift, int n, void* stream);
 

@@ -71,6 +71,9 @@ SIGNATURES = {
     "mi_stem_conv_fwd": (I, [P, P, P, P] + [I] * 6 + [P]),
     "mi_stem_conv_wgrad_workspace": (Z, [I] * 3),
     "mi_stem_conv_wgrad": (I, [P, P, P] + [I] * 6 + [P, Z, P]),
+    "mi_stem_pool_wgrad_enabled": (I, []),
+    "mi_stem_conv_wgrad_pool": (I, [P, P, P, P, P] + [I] * 8 + [P, Z, P]),
+    "mi_head_mask_enabled": (I, []),
     "mi_bias_grad_bf16": (I, [P, P, I, I, I, P, Z, P]),
     "mi_upsample_softce_workspace": (Z, [I] * 6),
     "mi_upsample_softce": (I, [P, F, F, P, I, I, P, P] + [I] * 6 + [F, P, Z, P]),
@@ -81,6 +84,9 @@ SIGNATURES = {
     "mi_adam_step_dev": (I, [P, P, P, P, Z, P, P]),
     "mi_sgd_step": (I, [P, P, P, Z, F, F, F, P]),
     "mi_sgd_step_dev": (I, [P, P, P, Z, P, P]),
+    "mi_sgd_pack_enabled": (I, []),
+    "mi_sgd_step_pack": (I, [P, P, P, Z, F, F, F, P, P, P, P, I, I, P, I, P]),
+    "mi_sgd_step_pack_dev": (I, [P, P, P, Z, P, P, P, P, P, I, I, P, I, P]),
     "mi_pack_weight_f32": (I, [P, P, I, I, I, P]),
     "mi_conv_f32": (I, [P, P, P] + [I] * 11 + [P, P, P, I, P]),
     "mi_stem_f32": (I, [P, P, P, P, P, I, I, I, P]),

@@ -70,6 +70,9 @@ const MiSwitches& mi_sw() {
 #endif
         sw.pp_trace_wg = env("MI_PP_TRACE_WG", 0);
         sw.stem_direct = env("MI_STEM_DIRECT", 1);
+        sw.stem_pool_wgrad = env("MI_STEM_POOL_WGRAD", 1);
+        sw.head_mask = env("MI_HEAD_MASK", 1);
+        sw.sgd_pack = env("MI_SGD_PACK", 1);
         sw.stem_wgrad_splits = env("MI_STEM_WGRAD_SPLITS", 512);
         if (sw.stem_wgrad_splits < 1 || sw.stem_wgrad_splits > 4096) sw.stem_wgrad_splits = 512;
     });
@@ -136,6 +139,173 @@ __global__ void sgd_dev_kernel(float* __restrict__ p, const float* __restrict__ 
     }
 }
 
+// ---- the SGD update and the bf16 repack of every conv weight in ONE pass (mi_sgd_step_pack) -------------------------------------------------
+// pack_multi_kernel (pack_aspp.hip) re-reads every fp32 weight a moment after sgd_kernel wrote it.  Here a workgroup owns the same 32 (o) x 128 (i)
+// group of one table row as there (same table, same first_block column), updates p / buf of each 32 x 32 tile with 16-byte accesses, keeps the new
+// weights in LDS and writes both packed operands from there with 16-byte stores.  Workgroups past the table's walk the `gaps`: the elements of the
+// flat store that no row covers (the stem weight, padding, a tail).  Every element is updated exactly once.
+// Bits: p and buf are sgd_kernel's, wp / wpt are pack_multi_kernel's of the stored p.  hipcc contracts sgd_kernel's vector loop into three FMAs and
+// its n % 4 tail into mul, add, mul, add, FMA; both forms are written out here, chosen by the element's index, so that no second contraction
+// decision is involved.
+__device__ __forceinline__ void sgd_update(float& p, float g, float& b, float lr, float mu, float wd) {
+    const float gg = __builtin_fmaf(wd, p, g);
+    b = __builtin_fmaf(mu, b, gg);
+    p = __builtin_fmaf(-lr, b, p);
+}
+__device__ __forceinline__ void sgd_update_tail(float& p, float g, float& b, float lr, float mu, float wd) {
+    const float gg = __fadd_rn(g, __fmul_rn(wd, p));
+    b = __fadd_rn(__fmul_rn(mu, b), gg);
+    p = __builtin_fmaf(-lr, b, p);
+}
+
+struct SgdPackArgs {
+    float* p;
+    const float* g;
+    float* buf;
+    size_t n;
+    const float* sflat;
+    __bf16* wp;
+    __bf16* wpt;
+    const long* table;         // [n_desc][8]: mi_pack_weights_multi's
+    const long* gaps;          // [n_gaps][2]: [lo, hi) element ranges outside every row
+    int n_desc, pack_blocks, n_gaps;
+    float lr, mu, wd;
+    const float* hyper;        // DEV: (lr, mu, wd) in device memory
+};
+
+constexpr int SP_TILES = 4;    // = PACK_TILES of pack_aspp.hip (the table's first_block column counts groups of that many tiles)
+constexpr int SP_BATCH = 3;    // 16-byte items of p, g and buf a thread has in flight
+
+template <bool DEV>
+__global__ __launch_bounds__(256) void sgd_pack_kernel(SgdPackArgs a) {
+    __shared__ float tile[32][32 * 9 + 1];
+    __shared__ float ssc[32];
+    const float lr = DEV ? a.hyper[0] : a.lr, mu = DEV ? a.hyper[1] : a.mu, wd = DEV ? a.hyper[2] : a.wd;
+    const int tid = threadIdx.x;
+    const size_t n_vec = a.n & ~(size_t)3;               // below: sgd_kernel's vector loop; from here on: its tail
+    if ((int)blockIdx.x >= a.pack_blocks) {
+        const long first = ((long)blockIdx.x - a.pack_blocks) * 256 + tid, stride = ((long)gridDim.x - a.pack_blocks) * 256;
+        for (int k = 0; k < a.n_gaps; ++k) {
+            const long lo = a.gaps[2 * k], hi = a.gaps[2 * k + 1];
+            for (long i = lo + first; i < hi; i += stride) {
+                float pv = a.p[i], bv = a.buf[i];
+                if ((size_t)i < n_vec) sgd_update(pv, a.g[i], bv, lr, mu, wd); else sgd_update_tail(pv, a.g[i], bv, lr, mu, wd);
+                a.buf[i] = bv;
+                a.p[i] = pv;
+            }
+        }
+        return;
+    }
+    int lo = 0, hi = a.n_desc - 1;                       // last row whose first_block <= blockIdx.x
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (a.table[mid * 8 + 7] <= (long)blockIdx.x) lo = mid; else hi = mid - 1;
+    }
+    const long* d = a.table + lo * 8;
+    const int O = (int)d[4], I = (int)d[5], T = (int)d[6];
+    const int tiles_i = (I + 31) >> 5, groups_i = (tiles_i + SP_TILES - 1) / SP_TILES;
+    const int local = (int)((long)blockIdx.x - d[7]);
+    const int ot = local / groups_i;
+    const int o0 = ot * 32, it0 = (local - ot * groups_i) * SP_TILES;
+    if (o0 >= O) return;
+    const int no = min(32, O - o0);
+    const long plane = (long)O * I;
+    const bool have_t = d[3] >= 0;
+    // 16-byte accesses wherever the row geometry keeps them aligned (every tile starts at a multiple of 32 input channels); element-wise otherwise
+    const bool vec_ld = ((d[0] | ((long)I * T)) & 3) == 0;
+    const bool vec_wp = ((d[2] | (long)I) & 7) == 0;
+    const bool vec_wpt = have_t && ((d[3] | (long)O) & 7) == 0;
+    if (tid < 32) ssc[tid] = (have_t && d[1] >= 0 && tid < no) ? a.sflat[d[1] + o0 + tid] : 1.f;
+    for (int it = it0; it < it0 + SP_TILES && it < tiles_i; ++it) {
+        const int i0 = it * 32;
+        const int ni = min(32, I - i0);
+        const int rowlen = ni * T;
+        if (it != it0) __syncthreads();                  // the previous tile's pack reads are done
+        if (vec_ld) {
+            const int r4 = rowlen >> 2, items = no * r4;
+            for (int base = tid; base < items; base += 256 * SP_BATCH) {
+                f32x4 pv[SP_BATCH], gv[SP_BATCH], bv[SP_BATCH];
+                long idx[SP_BATCH];
+                int oo[SP_BATCH], ee[SP_BATCH];
+#pragma unroll
+                for (int j = 0; j < SP_BATCH; ++j) {
+                    const int item = base + j * 256;
+                    oo[j] = item / r4;
+                    ee[j] = (item - oo[j] * r4) << 2;
+                    idx[j] = d[0] + ((long)(o0 + oo[j]) * I + i0) * T + ee[j];
+                    if (item < items) {
+                        pv[j] = *reinterpret_cast<const f32x4*>(a.p + idx[j]);
+                        gv[j] = *reinterpret_cast<const f32x4*>(a.g + idx[j]);
+                        bv[j] = *reinterpret_cast<const f32x4*>(a.buf + idx[j]);
+                    }
+                }
+#pragma unroll
+                for (int j = 0; j < SP_BATCH; ++j) {
+                    if (base + j * 256 < items) {
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) {
+                            float pe = pv[j][e], be = bv[j][e];
+                            sgd_update(pe, gv[j][e], be, lr, mu, wd);                   // a whole group of 4 below n lies below n_vec
+                            pv[j][e] = pe;
+                            bv[j][e] = be;
+                            tile[oo[j]][ee[j] + e] = pe;
+                        }
+                        *reinterpret_cast<f32x4*>(a.buf + idx[j]) = bv[j];
+                        *reinterpret_cast<f32x4*>(a.p + idx[j]) = pv[j];
+                    }
+                }
+            }
+        } else {
+            for (int item = tid; item < no * rowlen; item += 256) {
+                const int o = item / rowlen, e = item - o * rowlen;
+                const long idx = d[0] + ((long)(o0 + o) * I + i0) * T + e;
+                float pv = a.p[idx], bv = a.buf[idx];
+                if ((size_t)idx < n_vec) sgd_update(pv, a.g[idx], bv, lr, mu, wd); else sgd_update_tail(pv, a.g[idx], bv, lr, mu, wd);
+                a.buf[idx] = bv;
+                a.p[idx] = pv;
+                tile[o][e] = pv;
+            }
+        }
+        __syncthreads();
+        // forward operand wp[t][o][i]: 8 consecutive i per item
+        if (vec_wp) {
+            const int c8n = ni >> 3, per_t = no * c8n;
+            for (int item = tid; item < T * per_t; item += 256) {
+                const int t = item / per_t, rem = item - t * per_t;
+                const int o = rem / c8n, c = (rem - o * c8n) << 3;
+                bf16x8 v;
+#pragma unroll
+                for (int k = 0; k < 8; ++k) v[k] = (__bf16)tile[o][(c + k) * T + t];
+                *reinterpret_cast<bf16x8*>(a.wp + d[2] + t * plane + (long)(o0 + o) * I + i0 + c) = v;
+            }
+        } else {
+            for (int item = tid; item < T * no * ni; item += 256) {
+                const int t = item / (no * ni), rem = item - t * (no * ni);
+                const int o = rem / ni, c = rem - o * ni;
+                a.wp[d[2] + t * plane + (long)(o0 + o) * I + i0 + c] = (__bf16)tile[o][c * T + t];
+            }
+        }
+        // data-gradient operand wpt[t][i][o], the FrozenBN scale of output channel o folded in: 8 consecutive o per item
+        if (vec_wpt) {
+            const int o8n = no >> 3, per_t = ni * o8n;
+            for (int item = tid; item < T * per_t; item += 256) {
+                const int t = item / per_t, rem = item - t * per_t;
+                const int i = rem / o8n, o = (rem - i * o8n) << 3;
+                bf16x8 v;
+#pragma unroll
+                for (int k = 0; k < 8; ++k) v[k] = (__bf16)__fmul_rn(tile[o + k][i * T + t], ssc[o + k]);
+                *reinterpret_cast<bf16x8*>(a.wpt + d[3] + t * plane + (long)(i0 + i) * O + o0 + o) = v;
+            }
+        } else if (have_t) {
+            for (int item = tid; item < T * ni * no; item += 256) {
+                const int t = item / (ni * no), rem = item - t * (ni * no);
+                const int i = rem / no, o = rem - i * no;
+                a.wpt[d[3] + t * plane + (long)(i0 + i) * O + o0 + o] = (__bf16)__fmul_rn(tile[o][i * T + t], ssc[o]);
+            }
+        }
+    }
+}
+
 __global__ void relu_mask_kernel(const bf16x8* __restrict__ x, const bf16x8* __restrict__ m, bf16x8* __restrict__ y, size_t n8) {
     const size_t stride = (size_t)gridDim.x * blockDim.x;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n8; i += stride) {
@@ -181,6 +351,41 @@ extern "C" int mi_sgd_step_dev(float* p, const float* g, float* buf, size_t n, c
     return MI_OK;
 }
 
+int sgd_pack_launch(const char* who, float* p, const float* g, float* buf, size_t n, float lr, float mu, float wd, const float* hyper, bool dev,
+                    const float* sflat, void* wp, void* wpt, const int64_t* table_dev, int n_desc, int total_blocks, const int64_t* gaps_dev, int n_gaps,
+                    void* stream) {
+    MI_REQUIRE(p && g && buf && n > 0 && wp && table_dev && n_desc > 0 && total_blocks > 0 && (!dev || hyper), "%s: bad argument", who);
+    MI_REQUIRE(n_gaps >= 0 && (n_gaps == 0 || gaps_dev), "%s: n_gaps=%d without a gap table", who, n_gaps);
+    MI_REQUIRE(mi_aligned16(p) && mi_aligned16(g) && mi_aligned16(buf) && mi_aligned16(wp) && mi_aligned16(wpt), "%s: buffers must be 16-byte aligned", who);
+    SgdPackArgs a;
+    a.p = p, a.g = g, a.buf = buf, a.n = n;
+    a.sflat = sflat, a.wp = (__bf16*)wp, a.wpt = (__bf16*)wpt;
+    a.table = (const long*)table_dev, a.gaps = (const long*)gaps_dev;
+    a.n_desc = n_desc, a.pack_blocks = total_blocks, a.n_gaps = n_gaps;
+    a.lr = lr, a.mu = mu, a.wd = wd, a.hyper = hyper;
+    const unsigned grid = (unsigned)total_blocks + (n_gaps > 0 ? 64u : 0u);          // 64 workgroups walk the gaps (a few thousand elements)
+    if (dev)
+        hipLaunchKernelGGL(sgd_pack_kernel<true>, dim3(grid), dim3(256), 0, (hipStream_t)stream, a);
+    else
+        hipLaunchKernelGGL(sgd_pack_kernel<false>, dim3(grid), dim3(256), 0, (hipStream_t)stream, a);
+    MI_CHECK_LAUNCH(who);
+    return MI_OK;
+}
+
+extern "C" int mi_sgd_pack_enabled(void) { return mi_sw().sgd_pack != 0; }
+
+extern "C" int mi_sgd_step_pack(float* p, const float* g, float* buf, size_t n, float lr, float momentum, float weight_decay, const float* sflat, void* wp,
+                                void* wpt, const int64_t* table_dev, int n_desc, int total_blocks, const int64_t* gaps_dev, int n_gaps, void* stream) {
+    return sgd_pack_launch("mi_sgd_step_pack", p, g, buf, n, lr, momentum, weight_decay, nullptr, false, sflat, wp, wpt, table_dev, n_desc, total_blocks,
+                           gaps_dev, n_gaps, stream);
+}
+
+extern "C" int mi_sgd_step_pack_dev(float* p, const float* g, float* buf, size_t n, const float* hyper, const float* sflat, void* wp, void* wpt,
+                                    const int64_t* table_dev, int n_desc, int total_blocks, const int64_t* gaps_dev, int n_gaps, void* stream) {
+    return sgd_pack_launch("mi_sgd_step_pack_dev", p, g, buf, n, 0.f, 0.f, 0.f, hyper, true, sflat, wp, wpt, table_dev, n_desc, total_blocks, gaps_dev,
+                           n_gaps, stream);
+}
+
 __global__ void relu_mask_bits_kernel(const bf16x8* __restrict__ x, const uint8_t* __restrict__ m, bf16x8* __restrict__ y, size_t n8) {
     const size_t stride = (size_t)gridDim.x * blockDim.x;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n8; i += stride) {
@@ -194,6 +399,8 @@ __global__ void relu_mask_bits_kernel(const bf16x8* __restrict__ x, const uint8_
 }
 
 }  // namespace
+
+extern "C" int mi_head_mask_enabled(void) { return mi_sw().head_mask != 0; }
 
 extern "C" int mi_relu_mask(const void* x, const void* msk, void* y, size_t n, int bits, void* stream) {
     MI_REQUIRE(x && msk && y && n > 0 && n % 8 == 0, "mi_relu_mask: bad argument (n %% 8 == 0)");

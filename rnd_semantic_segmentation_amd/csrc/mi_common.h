@@ -56,6 +56,9 @@ struct MiSwitches {
     int pp_trace_wg;       // MI_PP_TRACE_WG      0 (-DMI_PP_TRACE builds only)
     int stem_wgrad_splits; // MI_STEM_WGRAD_SPLITS 512: workgroups (= fp32 partials of 56 KiB) the direct stem weight gradient splits the pixels over (two per CU)
     int stem_direct;       // MI_STEM_DIRECT      1: the stem conv and its weight gradient on raw image rows (stem_direct.hip); 0: patch matrix + GEMM
+    int stem_pool_wgrad;   // MI_STEM_POOL_WGRAD  1: the direct stem weight gradient builds dy from the pooled gradient in its staging; 0: mi_stem_pool_bwd writes dy first
+    int sgd_pack;          // MI_SGD_PACK         1: the backbone's SGD step also writes the bf16 operand packs (mi_sgd_step_pack); 0: mi_sgd_step, then mi_pack_weights_multi
+    int head_mask;         // MI_HEAD_MASK        1: the source-only step masks the backbone output's gradient in the head's data-gradient epilogue; 0: stand-alone pass
 };
 const MiSwitches& mi_sw();
 

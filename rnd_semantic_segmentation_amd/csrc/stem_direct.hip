@@ -23,6 +23,9 @@ constexpr int SD_WG_TH = 4;                  // output rows of a weight-gradient
 constexpr int SD_WG_ROWS = 2 * SD_WG_TH + 5;
 constexpr int SD_DYROWB = SD_TW * 128;       // one staged dy row: 64 pixels x 64 channels bf16
 constexpr int SD_PART = 64 * 7 * 32;         // floats of one weight-gradient partial [o][ky][k]
+constexpr int SD_PP_ROWS = SD_WG_TH / 2 + 1; // pooled rows whose 3x3/2/1 windows reach a weight-gradient tile's 4 conv rows (the tile starts on an even row)
+constexpr int SD_PP_COLS = SD_TW / 2 + 1;    // ... and pooled columns that reach its 64 conv columns
+constexpr int SD_PP_ITEMS = SD_PP_ROWS * SD_PP_COLS * 8;      // (pooled pixel, 8-channel chunk) items of that patch
 
 // ---- image pack -----------------------------------------------------------------------------------------------------------------------------
 // fp32 NCHW -> bf16 [B][H][W][4]: a thread converts pixels p, p + 256, p + 512, p + 768 of its block's 1024 (every load instruction of a wave
@@ -210,6 +213,55 @@ struct StemWgradParams {
     const bf16x8* dy;
     float* part;
     int B, H, W, Ho, Wo, tiles_x, tiles_y, tiles, S;
+    // POOL: dy is not in memory; it is built per tile from the pooled gradient, the argmax bytes and the BatchNorm scale
+    const bf16x8* dpool;
+    const uint2* idx;
+    const float* scale;
+    int Hp, Wp;
+};
+
+// POOL staging: the patch of dpool [B,Hp,Wp,64] and of the argmax bytes that a tile's dy is built from, SD_PP_ROWS x SD_PP_COLS pooled pixels from
+// (hp0, wp0) = (ho0 / 2, wo0 / 2).  It travels in registers like the image rows; store() packs the 8 argmax bytes of an item into 8 nibbles (a byte
+// above 15 becomes 15: like every byte above 8 it matches no tap), and pooled pixels outside the map get nibble 15 everywhere.
+struct PoolPatch {
+    static constexpr int N = (SD_PP_ITEMS + 255) / 256;
+    bf16x8 g[N];
+    uint2 ib[N];
+    __device__ __forceinline__ void load(const bf16x8* __restrict__ dpool, const uint2* __restrict__ idx, int b, int hp0, int wp0, int Hp, int Wp, int tid) {
+#pragma unroll
+        for (int j = 0; j < N; ++j) {
+            const int i = tid + j * 256;
+            const int c = i & 7, px = i >> 3;
+            const int pr = px / SD_PP_COLS, pc = px - pr * SD_PP_COLS;
+            const int hp = hp0 + pr, wp = wp0 + pc;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) g[j][e] = (__bf16)0.f;
+            ib[j] = make_uint2(~0u, ~0u);
+            if (i < SD_PP_ITEMS && hp < Hp && wp < Wp) {
+                const long off = (((long)b * Hp + hp) * Wp + wp) * 8 + c;
+                g[j] = dpool[off];
+                ib[j] = idx[off];
+            }
+        }
+    }
+    static __device__ __forceinline__ unsigned nibbles(unsigned x) {          // 4 bytes -> 4 nibbles in the low 16 bits
+        unsigned t = (x >> 4) & 0x0f0f0f0fu;                                    // bit 0 of each byte of t: the byte of x is above 15
+        t |= t >> 1;
+        t |= t >> 2;
+        x = (x & 0x0f0f0f0fu) | ((t & 0x01010101u) * 15u);
+        x = (x | (x >> 4)) & 0x00ff00ffu;
+        return (x | (x >> 8)) & 0xffffu;
+    }
+    __device__ __forceinline__ void store(bf16x8* sdp, unsigned* sidx, int tid) const {
+#pragma unroll
+        for (int j = 0; j < N; ++j) {
+            const int i = tid + j * 256;
+            if (i < SD_PP_ITEMS) {
+                sdp[i] = g[j];
+                sidx[i] = nibbles(ib[j].x) | (nibbles(ib[j].y) << 16);
+            }
+        }
+    }
 };
 
 // Workgroup s walks tiles [s*tiles/S, (s+1)*tiles/S) of 4 output rows x 64 output columns and keeps dw[64][7][32] in the accumulators of its four
@@ -220,9 +272,16 @@ struct StemWgradParams {
 //   x operand (B, column = k): the staged image row; pixel P's patch row is the 64 bytes at 16*P, so a half reads one span of 144 bytes.
 // Pixels past Wo: their dy is staged as zero and their x fragment elements are zeroed too (the image there can hold anything, 0 * NaN is NaN);
 // rows past Ho are skipped.
+// POOL (mi_stem_conv_wgrad_pool): the staged dy rows are not loaded but built, between two barriers of their own, from the staged patch of the
+// pooled gradient - the max-pool / ReLU / BatchNorm backward of stem_pool_bwd_kernel (stem.hip) per (pixel, 8-channel chunk) item, with the same
+// <= 4 windows in the same (ho, wo) order, fp32 accumulation and (__bf16)(acc * scale[c]): the staged rows, and with them dw, have the bits of that
+// kernel's dy, which is then never written (152 MB at B = 8, 769 x 769) nor read back.
+template <bool POOL>
 __global__ __launch_bounds__(256, 2) void stem_direct_wgrad_kernel(StemWgradParams p) {
     __shared__ __attribute__((aligned(16))) uint2 sx[SD_WG_ROWS * SD_ROWPX];
     __shared__ __attribute__((aligned(16))) bf16x8 sdy[SD_WG_TH * SD_TW * 8];
+    __shared__ __attribute__((aligned(16))) bf16x8 sdp[POOL ? SD_PP_ITEMS : 1];
+    __shared__ unsigned sidx[POOL ? SD_PP_ITEMS : 1];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int kt = wave & 1, oh = wave >> 1;
@@ -242,19 +301,29 @@ __global__ __launch_bounds__(256, 2) void stem_direct_wgrad_kernel(StemWgradPara
 
     // the next tile's image rows and dy rows travel in registers while the current tile is contracted
     ImageRows<SD_WG_ROWS> nx;
-    bf16x8 ny[8];
+    bf16x8 ny[POOL ? 1 : 8];
+    PoolPatch np;
+    float sc[8];                                                 // POOL: the BatchNorm scale of this thread's 8 channels (chunk tid & 7 of every item)
+    if constexpr (POOL) {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) sc[e] = p.scale[(tid & 7) * 8 + e];
+    }
     auto load_tile = [&](int t) {
         const int tx = t % p.tiles_x, ty = (t / p.tiles_x) % p.tiles_y, b = t / (p.tiles_x * p.tiles_y);
         const int wo0 = tx * SD_TW, ho0 = ty * SD_WG_TH;
         nx.load(p.x4 + (long)b * p.H * p.W, 2 * ho0 - 3, 2 * wo0 - 3, p.H, p.W, tid);
+        if constexpr (POOL) {
+            np.load(p.dpool, p.idx, b, ho0 >> 1, wo0 >> 1, p.Hp, p.Wp, tid);
+        } else {
 #pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const int i = tid + j * 256;
-            const int c = i & 7, P = (i >> 3) & 63, rr = i >> 9;
-            const int ho = ho0 + rr, wo = wo0 + P;
+            for (int j = 0; j < 8; ++j) {
+                const int i = tid + j * 256;
+                const int c = i & 7, P = (i >> 3) & 63, rr = i >> 9;
+                const int ho = ho0 + rr, wo = wo0 + P;
 #pragma unroll
-            for (int e = 0; e < 8; ++e) ny[j][e] = (__bf16)0.f;
-            if (ho < p.Ho && wo < p.Wo) ny[j] = p.dy[(((long)b * p.Ho + ho) * p.Wo + wo) * 8 + c];
+                for (int e = 0; e < 8; ++e) ny[j][e] = (__bf16)0.f;
+                if (ho < p.Ho && wo < p.Wo) ny[j] = p.dy[(((long)b * p.Ho + ho) * p.Wo + wo) * 8 + c];
+            }
         }
     };
     load_tile(t_begin);
@@ -263,14 +332,50 @@ __global__ __launch_bounds__(256, 2) void stem_direct_wgrad_kernel(StemWgradPara
         const int wo0 = tx * SD_TW, ho0 = ty * SD_WG_TH;
         __syncthreads();                                         // the previous tile's fragment reads are done
         nx.store(sx, tid);
+        if constexpr (POOL) {
+            np.store(sdp, sidx, tid);
+        } else {
 #pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const int i = tid + j * 256;
-            const int c = i & 7, P = (i >> 3) & 63, rr = i >> 9;
-            sdy[(rr * SD_TW + P) * 8 + (c ^ (P & 7))] = ny[j];
+            for (int j = 0; j < 8; ++j) {
+                const int i = tid + j * 256;
+                const int c = i & 7, P = (i >> 3) & 63, rr = i >> 9;
+                sdy[(rr * SD_TW + P) * 8 + (c ^ (P & 7))] = ny[j];
+            }
         }
         __syncthreads();
         if (t + 1 < t_end) load_tile(t + 1);
+        if constexpr (POOL) {
+            // item j of this thread: conv row rr = j >> 1, column P, chunk c - the items of the plain staging above.  Conv row ho0 + rr (ho0 even) lies in
+            // the windows of pooled rows (rr >> 1) .. ((rr + 1) >> 1) of the patch at kernel row rr - 2*hl + 1, and likewise along the columns.
+            const int c = tid & 7;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const int rr = j >> 1, P = (tid >> 3) + 32 * (j & 1);
+                bf16x8 o;
+#pragma unroll
+                for (int e = 0; e < 8; ++e) o[e] = (__bf16)0.f;
+                if (ho0 + rr < p.Ho && wo0 + P < p.Wo) {
+                    float a[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                    for (int hl = rr >> 1; hl <= ((rr + 1) >> 1); ++hl) {
+                        const int ky = rr - 2 * hl + 1;
+                        for (int wl = P >> 1; wl <= ((P + 1) >> 1); ++wl) {
+                            const unsigned tap = (unsigned)(ky * 3 + (P - 2 * wl + 1));
+                            const int it = (hl * SD_PP_COLS + wl) * 8 + c;
+                            const bf16x8 gv = sdp[it];
+                            const unsigned nib = sidx[it];
+#pragma unroll
+                            for (int e = 0; e < 8; ++e)
+                                if (((nib >> (4 * e)) & 15u) == tap) a[e] += (float)gv[e];
+                        }
+                    }
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) o[e] = (__bf16)(a[e] * sc[e]);
+                }
+                sdy[(rr * SD_TW + P) * 8 + (c ^ (P & 7))] = o;
+            }
+            __syncthreads();
+        }
         const int nrows = min(SD_WG_TH, p.Ho - ho0);
         for (int rr = 0; rr < nrows; ++rr) {
 #pragma unroll
@@ -401,28 +506,52 @@ extern "C" size_t mi_stem_conv_wgrad_workspace(int B, int Ho, int Wo) {
     return (size_t)stem_wgrad_splits(B, Ho, Wo) * SD_PART * sizeof(float);
 }
 
-extern "C" int mi_stem_conv_wgrad(const void* dy, const void* x4, float* dw, int B, int H, int W, int O, int Ho, int Wo, void* workspace,
-                                  size_t workspace_bytes, void* stream) {
-    MI_REQUIRE(dy && x4 && dw && workspace, "mi_stem_conv_wgrad: null operand");
-    MI_REQUIRE(O == 64, "mi_stem_conv_wgrad: O=%d (the stem has 64 output channels)", O);
+namespace {
+// both weight-gradient entries: pool false -> dy from memory; true -> dy built in the launch from (dpool, idx, scale)
+int stem_wgrad_launch(const char* who, bool pool, const void* dy, const void* dpool, const uint8_t* idx, const float* scale, const void* x4, float* dw, int B,
+                      int H, int W, int O, int Ho, int Wo, int Hp, int Wp, void* workspace, size_t workspace_bytes, void* stream) {
+    MI_REQUIRE((pool ? dpool && idx && scale : dy != nullptr) && x4 && dw && workspace, "%s: null operand", who);
+    MI_REQUIRE(O == 64, "%s: O=%d (the stem has 64 output channels)", who, O);
     const char* bad = stem_direct_geometry(B, H, W, Ho, Wo);
-    MI_REQUIRE(!bad, "mi_stem_conv_wgrad: %s", bad);
-    MI_REQUIRE((reinterpret_cast<uintptr_t>(x4) & 7) == 0 && mi_aligned16(dy) && mi_aligned16(workspace) && (reinterpret_cast<uintptr_t>(dw) & 3) == 0,
-               "mi_stem_conv_wgrad: alignment");
-    MI_REQUIRE(workspace_bytes >= mi_stem_conv_wgrad_workspace(B, Ho, Wo), "mi_stem_conv_wgrad: workspace holds %zu bytes, %zu needed", workspace_bytes,
+    MI_REQUIRE(!bad, "%s: %s", who, bad);
+    MI_REQUIRE(!pool || (Hp == (Ho + 2 - 3) / 2 + 1 && Wp == (Wo + 2 - 3) / 2 + 1), "%s: pooled size must be that of a 3x3/2/1 max-pool of the conv output", who);
+    MI_REQUIRE((reinterpret_cast<uintptr_t>(x4) & 7) == 0 && mi_aligned16(workspace) && (reinterpret_cast<uintptr_t>(dw) & 3) == 0 &&
+                   (pool ? mi_aligned16(dpool) && (reinterpret_cast<uintptr_t>(idx) & 7) == 0 && (reinterpret_cast<uintptr_t>(scale) & 3) == 0 : mi_aligned16(dy)),
+               "%s: alignment", who);
+    MI_REQUIRE(workspace_bytes >= mi_stem_conv_wgrad_workspace(B, Ho, Wo), "%s: workspace holds %zu bytes, %zu needed", who, workspace_bytes,
                mi_stem_conv_wgrad_workspace(B, Ho, Wo));
     StemWgradParams p;
     p.x4 = (const uint2*)x4;
     p.dy = (const bf16x8*)dy;
+    p.dpool = (const bf16x8*)dpool;
+    p.idx = (const uint2*)idx;
+    p.scale = scale;
+    p.Hp = Hp, p.Wp = Wp;
     p.part = (float*)workspace;
     p.B = B, p.H = H, p.W = W, p.Ho = Ho, p.Wo = Wo;
     p.tiles_x = (Wo + SD_TW - 1) / SD_TW;
     p.tiles_y = (Ho + SD_WG_TH - 1) / SD_WG_TH;
     p.tiles = B * p.tiles_x * p.tiles_y;
     p.S = stem_wgrad_splits(B, Ho, Wo);
-    hipLaunchKernelGGL(stem_direct_wgrad_kernel, dim3((unsigned)p.S), dim3(256), 0, (hipStream_t)stream, p);
-    MI_CHECK_LAUNCH("mi_stem_conv_wgrad");
+    if (!pool)
+        hipLaunchKernelGGL(stem_direct_wgrad_kernel<false>, dim3((unsigned)p.S), dim3(256), 0, (hipStream_t)stream, p);
+    else
+        hipLaunchKernelGGL(stem_direct_wgrad_kernel<true>, dim3((unsigned)p.S), dim3(256), 0, (hipStream_t)stream, p);
+    MI_CHECK_LAUNCH(who);
     hipLaunchKernelGGL(stem_direct_wgrad_reduce_kernel, dim3(SD_PART / 256), dim3(256), 0, (hipStream_t)stream, (const float*)workspace, dw, p.S);
-    MI_CHECK_LAUNCH("mi_stem_conv_wgrad (reduce)");
+    MI_CHECK_LAUNCH(who);
     return MI_OK;
+}
+}  // namespace
+
+extern "C" int mi_stem_conv_wgrad(const void* dy, const void* x4, float* dw, int B, int H, int W, int O, int Ho, int Wo, void* workspace,
+                                  size_t workspace_bytes, void* stream) {
+    return stem_wgrad_launch("mi_stem_conv_wgrad", false, dy, nullptr, nullptr, nullptr, x4, dw, B, H, W, O, Ho, Wo, 0, 0, workspace, workspace_bytes, stream);
+}
+
+extern "C" int mi_stem_pool_wgrad_enabled(void) { return mi_sw().stem_pool_wgrad != 0; }
+
+extern "C" int mi_stem_conv_wgrad_pool(const void* dpool, const uint8_t* idx, const float* scale, const void* x4, float* dw, int B, int H, int W, int O,
+                                       int Ho, int Wo, int Hp, int Wp, void* workspace, size_t workspace_bytes, void* stream) {
+    return stem_wgrad_launch("mi_stem_conv_wgrad_pool", true, nullptr, dpool, idx, scale, x4, dw, B, H, W, O, Ho, Wo, Hp, Wp, workspace, workspace_bytes, stream);
 }

@@ -92,8 +92,22 @@ __global__ void ce_fwd_kernel(const float* __restrict__ logits, const int64_t* _
 
 __global__ void ce_finalize_kernel(const float* __restrict__ partial, int n, float* __restrict__ loss_out) {
     __shared__ float red[512];
+    // thread t adds pairs t, t + 256, ... in ascending order (the order every CE head's loss bits rest on); the loads of 16 pairs are issued
+    // together before their ordered adds, so one workgroup does not pay a memory round trip per pair (24 608 pairs at B = 8, 769 x 769)
     float s = 0.f, c = 0.f;
-    for (int i = threadIdx.x; i < n; i += 256) {
+    const float2* pairs = reinterpret_cast<const float2*>(partial);
+    int i = threadIdx.x;
+    for (; i + 15 * 256 < n; i += 16 * 256) {
+        float2 v[16];
+#pragma unroll
+        for (int j = 0; j < 16; ++j) v[j] = pairs[i + j * 256];
+#pragma unroll
+        for (int j = 0; j < 16; ++j) {
+            s += v[j].x;
+            c += v[j].y;
+        }
+    }
+    for (; i < n; i += 256) {
         s += partial[2 * i];
         c += partial[2 * i + 1];
     }

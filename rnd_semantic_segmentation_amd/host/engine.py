@@ -212,6 +212,8 @@ class StageEngine:
         self._pack_sig = None
         self._have_dgrad = False
         self.batch_stats = False               # True: trainable BatchNorm2d in train(): no fold, unscaled data-gradient operands
+        self.eval_mode = False                 # True: the owner is in eval() (set per forward by resnet_feature_extractor.forward)
+        self._fused_current = False            # the packs in the buffers were written by the optimizer's fused step (mark_packed)
 
     # -- preparation: FrozenBN folds and bf16 operand packs, redone only when their sources changed
     def _signature(self):
@@ -242,11 +244,30 @@ class StageEngine:
             blk += -(-c.cout // 32) * -(-c.cin // 128)        # one block per 32 (o) x 128 (i) channels
         self._pack_blocks = blk
         self._table_train = torch.tensor(rows, dtype=torch.int64, device=dev)
+        gaps = K.pack_table_gaps(rows, store.total)          # what the fused SGD + pack launch updates besides the conv weights (the stem weight)
+        self._gaps = torch.tensor(gaps, dtype=torch.int64, device=dev) if gaps else None
         self._table_batch = torch.tensor([r[:1] + [-1] + r[2:] for r in rows], dtype=torch.int64, device=dev)     # no folded scale
         for r in rows:
             r[3] = -1
         self._table_eval = torch.tensor(rows, dtype=torch.int64, device=dev)
         self._plan_store = store
+        self._fused_current = False
+        store.pack_plan = self             # FusedSGD.step: this store's update can write the packs as well (sgd_step_pack)
+
+    # -- the optimizer's side of the packs: FusedSGD.step over the whole store calls these
+    def fused_step_args(self, store):
+        """(scale, wp, wpt, table, rows, blocks, gaps) for K.sgd_step_pack when the update of `store` may also write the packs: the plan belongs to
+        this store and the packs standing in the buffers are the TRAINING packs of the weights as they are now (FrozenBN scale folded into the
+        data-gradient operand).  Else None, and prepare() packs as ever: first step, batch statistics, an evaluation or a refold in between."""
+        if (getattr(self, "_plan_store", None) is not store or self.batch_stats or not self._have_dgrad
+                or self._pack_sig != self._signature() + (False,)):
+            return None
+        return self._scale_flat, self._wp_flat, self._wpt_flat, self._table_train, len(self.convs), self._pack_blocks, self._gaps
+
+    def mark_packed(self):
+        """After sgd_step_pack and the bump of store.generation: the packs are those of the new weights."""
+        self._pack_sig = self._signature() + (False,)
+        self._fused_current = True
 
     def prepare(self, train):
         store = getattr(self.convs[0].weight, "_mi_store", None)
@@ -266,7 +287,11 @@ class StageEngine:
                     rt.shift.copy_(sh)
                 self._bn_sig = bn_sig
         sig = self._signature() + (self.batch_stats,)
-        if sig != self._pack_sig or refold or (train and not self._have_dgrad):
+        # packs written by the optimizer's fused step serve training steps only: an evaluation in between (eval(), or weights that want no gradient)
+        # goes back to mi_pack_weights_multi once, like a refold, batch statistics or a moved store
+        stale = self._fused_current and (self.eval_mode or not train)
+        if sig != self._pack_sig or refold or stale or (train and not self._have_dgrad):
+            self._fused_current = False
             table = self._table_batch if self.batch_stats else (self._table_train if train else self._table_eval)
             K.pack_weights_multi(store.data, self._scale_flat, self._wp_flat, self._wpt_flat, table, len(self.convs), self._pack_blocks)
             self._pack_sig = sig
@@ -417,9 +442,10 @@ class StageEngine:
         c = rt.spec
         return K.conv_gemm(dy, rt.wpt, in_hw, c.k, c.stride, c.pad, c.dil, K.GATHER_DGRAD, res=res, bits=bits)
 
-    def backward(self, saved, fbits, dfeat, need_dx):
-        """dfeat: d loss / d feat (bf16 NHWC); fbits: sign bits of feat.  Returns d loss / d x of the first block."""
-        g = K.relu_mask(dfeat, fbits)                     # through the last block's ReLU
+    def backward(self, saved, fbits, dfeat, need_dx, premasked=False):
+        """dfeat: d loss / d feat (bf16 NHWC); fbits: sign bits of feat.  Returns d loss / d x of the first block.
+        premasked: every contribution to dfeat was already masked with fbits where it was computed (FeatureMask), so the pass over it is skipped."""
+        g = dfeat if premasked else K.relu_mask(dfeat, fbits)      # through the last block's ReLU
         store = getattr(self.convs[0].weight, "_mi_store", None)
         sched = WgradScheduler.on(dfeat.device)
         chain = self.chain_mode() in ("all", "bwd") and self._chain_fits(dfeat)
@@ -757,8 +783,19 @@ class StemFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dpool):
         idx, scale = ctx.saved_tensors[:2]
+        if K.stem_direct_enabled() and K.stem_pool_wgrad_enabled():      # dy [B,Hc,Wc,64] is built tile by tile inside the weight gradient's launch
+            return None, K.stem_wgrad_pool(dpool.contiguous(), idx, scale.contiguous(), ctx.saved_tensors[2]), None, None
         dy = K.stem_pool_bwd(dpool.contiguous(), idx, scale, ctx.conv_hw)                      # [B,Hc,Wc,64] bf16 NHWC
         return None, stem_conv_wgrad(dy, ctx.saved_tensors[2:]), None, None
+
+
+class FeatureMask:
+    """The ReLU mask of the backbone output, on its way to a consumer that can apply it where it computes the output's gradient (the ASPP head's
+    data-gradient epilogue).  Masking is idempotent and linear: a consumer masks whenever it is handed one, and StagesFn.backward skips its own pass
+    over the gradient only when the caller of the forward declared that consumer to be the output's ONLY one (`sole`) and the consumer did apply it."""
+
+    def __init__(self, bits, sole):
+        self.bits, self.sole, self.applied = bits, bool(sole), False
 
 
 class StagesFn(torch.autograd.Function):
@@ -770,13 +807,17 @@ class StagesFn(torch.autograd.Function):
         eng.prepare(train)
         feat, saved, fbits = eng.forward(x, save=train)
         ctx.eng, ctx.saved, ctx.fbits = eng, saved, fbits
+        # the opt-in holds for this one forward (resnet_feature_extractor.forward sets it)
+        ctx.fmask = eng.feature_mask = FeatureMask(fbits, getattr(eng, "sole_consumer_next", False)) if train else None
+        eng.sole_consumer_next = False
         return feat
 
     @staticmethod
     def backward(ctx, dfeat):
         dfeat = dfeat.contiguous()
-        dx = ctx.eng.backward(ctx.saved, ctx.fbits, dfeat, ctx.needs_input_grad[0])
-        ctx.saved = ctx.fbits = None
+        fm = ctx.fmask
+        dx = ctx.eng.backward(ctx.saved, ctx.fbits, dfeat, ctx.needs_input_grad[0], premasked=fm is not None and fm.sole and fm.applied)
+        ctx.saved = ctx.fbits = ctx.fmask = None
         return (dx, None) + (None,) * (len(ctx.needs_input_grad) - 2)
 
 
@@ -830,8 +871,14 @@ class AsppEngine:
         b4, _ = self._b4()
         return K.aspp_col2im(z, b4, B, h, w, self.K, self.rates)
 
-    def backward(self, x, dlow, need_dx, msk=None):
-        """dlow [B,h,w,K] fp32 = d loss / d low.  Writes weight/bias grads, returns d loss / d x (bf16)."""
+    def take_feature_mask(self):
+        """The FeatureMask that ASPP_Classifier_V2.loss left for the autograd node it is about to create (or None); it holds for that one node."""
+        fm, self.feature_mask_next = getattr(self, "feature_mask_next", None), None
+        return fm
+
+    def backward(self, x, dlow, need_dx, msk=None, fmask=None):
+        """dlow [B,h,w,K] fp32 = d loss / d low.  Writes weight/bias grads, returns d loss / d x (bf16).
+        fmask: the FeatureMask of x - d loss / d x leaves the data-gradient GEMM's epilogue masked with its sign bits (+0 where x is 0)."""
         h, w = x.shape[1], x.shape[2]
         g = K.aspp_im2col(dlow, self.rates)
         w4, ws = self._w4()
@@ -863,7 +910,10 @@ class AsppEngine:
 
         # off the critical path: runs beside the data-gradient GEMM below; joined right after it is enqueued
         sched.run(weight_and_bias_grads, g, x, dlow)
-        dx = K.conv_gemm(g, self.wallT, (h, w), msk=msk, flop_cols=36 * self.K) if need_dx else None
+        bits = fmask.bits if fmask is not None and msk is None else None
+        dx = K.conv_gemm(g, self.wallT, (h, w), msk=msk, bits=bits, flop_cols=36 * self.K) if need_dx else None
+        if bits is not None and need_dx:
+            fmask.applied = True
         sched.join()
         store = getattr(ws[0], "_mi_store", None)
         if store is not None and store.grad_hooks:
@@ -907,7 +957,7 @@ class AsppLossFn(torch.autograd.Function):
         else:
             loss_out, dlow = K.upsample_ce(low, labels, want_grad=train, ignore_index=ignore_index, class_weights=class_weights,
                                            label_smoothing=label_smoothing)
-        ctx.eng, ctx.x, ctx.dlow = eng, (x if train else None), dlow
+        ctx.eng, ctx.x, ctx.dlow, ctx.fmask = eng, (x if train else None), dlow, eng.take_feature_mask()
         ctx.loss_out = eng.last_loss_out = loss_out          # [loss, n_valid, out-of-range labels, -]: see K.check_labels
         # every step's count goes into a persistent device counter (the kernel zeroes its own per call): the trainer reads it once per logging
         # window, so a bad label in ANY step of the window raises, as torch's device assert would - also under HIP-graph replay (the add is captured)
@@ -920,8 +970,8 @@ class AsppLossFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gout):
         dlow = ctx.dlow * gout
-        dx = ctx.eng.backward(ctx.x, dlow, ctx.needs_input_grad[0])
-        ctx.x = ctx.dlow = None
+        dx = ctx.eng.backward(ctx.x, dlow, ctx.needs_input_grad[0], fmask=ctx.fmask)
+        ctx.x = ctx.dlow = ctx.fmask = None
         return (dx, None, None, None, None, None, None) + (None,) * (len(ctx.needs_input_grad) - 7)
 
 
@@ -937,7 +987,7 @@ class AsppOhemLossFn(AsppLossFn):
         inv_t = 1.0 / temperature             # criterion(pred.div(T), label): the mining sees the scaled logits too
         loss_out, dlow, _ = K.upsample_ce_ohem(low if temperature == 1.0 else low * inv_t, labels, thresh, min_kept, want_grad=train,
                                                grad_scale=1.0 if temperature == 1.0 else inv_t, ignore_index=ignore_index)
-        ctx.eng, ctx.x, ctx.dlow = eng, (x if train else None), dlow
+        ctx.eng, ctx.x, ctx.dlow, ctx.fmask = eng, (x if train else None), dlow, eng.take_feature_mask()
         ctx.loss_out = eng.last_loss_out = loss_out          # [loss, n_kept, out-of-range labels, t]
         bad = getattr(eng, "bad_labels", None)
         if bad is None or bad.device != loss_out.device:
@@ -958,7 +1008,7 @@ class AsppFocalLossFn(AsppLossFn):
         inv_t = 1.0 / temperature             # criterion(pred.div(T), label): the modulation sees the scaled logits
         loss_out, dlow = K.upsample_ce_focal(low if temperature == 1.0 else low * inv_t, labels, gamma, want_grad=train,
                                              grad_scale=1.0 if temperature == 1.0 else inv_t, ignore_index=ignore_index, class_weights=class_weights)
-        ctx.eng, ctx.x, ctx.dlow = eng, (x if train else None), dlow
+        ctx.eng, ctx.x, ctx.dlow, ctx.fmask = eng, (x if train else None), dlow, eng.take_feature_mask()
         ctx.loss_out = eng.last_loss_out = loss_out          # [loss, weight sum of the valid pixels, out-of-range labels, -]
         bad = getattr(eng, "bad_labels", None)
         if bad is None or bad.device != loss_out.device:

@@ -137,8 +137,12 @@ class resnet_feature_extractor(nn.Module):
                 m._mi_sync = bool(on)
         return self
 
-    def forward(self, x):
+    def forward(self, x, sole_consumer=False):
+        """sole_consumer: the caller's promise that the returned feature goes to exactly one consumer, and that this consumer is handed
+        self.feature_mask() (ASPP_Classifier_V2.loss(..., feature_mask=)): the backward pass then takes the feature's gradient as already masked by
+        the feature's ReLU and skips its own pass over it.  Without the promise nothing changes, whoever masks besides."""
         _require_gpu(x, "resnet_feature_extractor")
+        self._engine.feature_mask = None
         if self.precision == "fp32":
             if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
                 raise _lib.MiError("the fp32 path is forward-only (evaluation): call it under torch.no_grad(), or "
@@ -148,6 +152,7 @@ class resnet_feature_extractor(nn.Module):
         bb = self.backbone
         xb = x          # engine.stem_conv_forward packs the image for the stem conv (fp32 NCHW or bf16 channels_last) in one pass
         self._engine.batch_stats = (not self.freeze_bn) and self.training
+        self._engine.eval_mode = not self.training
         if self._engine.batch_stats:
             # trainable BatchNorm2d in train(): batch statistics between each conv and its normalise pass, two autograd nodes with hand-written
             # backward (engine.BnStemFn, engine.BnStagesFn)
@@ -158,8 +163,15 @@ class resnet_feature_extractor(nn.Module):
         scale, shift = self._stem_fold()
         y = engine.StemFn.apply(xb, bb.conv1.weight, scale, shift)                       # [B,Hp,Wp,64] bf16 NHWC
         weights = [rt.weight for rt in self._engine.convs]
+        self._engine.sole_consumer_next = bool(sole_consumer)
         feat = engine.StagesFn.apply(y, self._engine, *weights)
         return feat.permute(0, 3, 1, 2)                  # NCHW-shaped view of NHWC memory (channels_last)
+
+
+    def feature_mask(self):
+        """engine.FeatureMask of the feature the last forward returned (its packed sign bits), or None when that forward kept nothing for a backward
+        pass or ran on batch statistics."""
+        return getattr(self._engine, "feature_mask", None)
 
 
 class ASPP_Classifier_V2(nn.Module):
@@ -231,16 +243,19 @@ class ASPP_Classifier_V2(nn.Module):
             return engine.UpsampleFn.apply(low, tuple(int(s) for s in size))           # [B,K,H,W] fp32
         return low.permute(0, 3, 1, 2)
 
-    def loss(self, x, label, ignore_index=255, temperature=1.0, class_weights=None, label_smoothing=0.0, ohem=None, focal_gamma=0.0):
+    def loss(self, x, label, ignore_index=255, temperature=1.0, class_weights=None, label_smoothing=0.0, ohem=None, focal_gamma=0.0,
+             feature_mask=None):
         """criterion(self(x, label.shape[-2:]).div(temperature), label) fused (never writes the upsampled logits); class_weights ([K] fp32 on the
         device) and label_smoothing are the criterion's weight= and label_smoothing= (not used by the reference: host/config.py).
         ohem = (thresh, min_kept): the cross-entropy over the hard pixels only (mi_upsample_ce_ohem), mined on the logits after the division.
         focal_gamma > 0: the focal loss -w_y (1 - p_y)^gamma log p_y (mi_upsample_ce_focal), with class_weights if given, on the logits after the division.
+        feature_mask: resnet_feature_extractor.feature_mask() of x - d loss / d x is then masked by x's ReLU where the head computes it.
         Leaves the 1/8-resolution logits [B,K,h,w] (detached) in `self.last_low`."""
         engine.K.refuse_ohem_with_weights(ohem, class_weights, label_smoothing)
         focal_gamma = engine.K.refuse_focal_with(focal_gamma, ohem, label_smoothing)
         _require_gpu(x, "ASPP_Classifier_V2")
         self.ensure_flat()
+        self._engine.feature_mask_next = feature_mask          # taken by the loss node created below
         if focal_gamma > 0.0:
             out = engine.AsppFocalLossFn.apply(self._nhwc(x), label.long().contiguous(), self._engine, int(ignore_index), float(temperature),
                                                class_weights, focal_gamma, *self._params())

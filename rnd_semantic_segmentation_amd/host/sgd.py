@@ -83,13 +83,21 @@ class FusedSGD(torch.optim.SGD):
             if whole:
                 for p in params:
                     flat = self._momentum_view(p, st)
-                if self.device_hyper is not None:
-                    if not torch.cuda.is_current_stream_capturing():     # an eager step between graph replays: refresh the device copy
-                        self.push_hyper()
+                plan = getattr(st, "pack_plan", None)
+                # a backbone store whose engine keeps bf16 packs of the weights: the update writes them too, from the registers that hold the new
+                # weights, instead of a second pass over the store at the next forward (MI_SGD_PACK, default on)
+                fused = plan.fused_step_args(st) if plan is not None and K.sgd_pack_enabled() else None
+                if self.device_hyper is not None and not torch.cuda.is_current_stream_capturing():
+                    self.push_hyper()                                    # an eager step between graph replays: refresh the device copy
+                if fused is not None:
+                    K.sgd_step_pack(st.data, st.grad, flat, self.device_hyper if self.device_hyper is not None else lr, mu, wd, *fused)
+                elif self.device_hyper is not None:
                     K.sgd_step_dev(st.data, st.grad, flat, self.device_hyper)
                 else:
                     K.sgd_step(st.data, st.grad, flat, lr, mu, wd)       # one launch for the whole module
                 st.generation += 1
+                if fused is not None:
+                    plan.mark_packed()
             else:
                 for p in params:
                     state = self.state[p]

@@ -18,9 +18,10 @@ import time
 import torch
 import torch.distributed as dist
 
+from .. import kernels as _kernels
 from . import ddp
 from .metrics import MetricLogger, adjust_learning_rate, dump_json, strip_prefix_if_present
-from .modules import build_classifier, build_feature_extractor
+from .modules import ASPP_Classifier_V2, build_classifier, build_feature_extractor
 from .plugin import BaseTrainer
 from .sgd import FusedSGD
 
@@ -155,11 +156,22 @@ class ASPPTrainer(BaseTrainer):
         st["graph"].replay()
         return st["loss"].clone()
 
+    def _feature(self, src_input):
+        """The source-only step's feature and, as keyword arguments for classifier.loss, its ReLU mask: the fused loss is the feature's single
+        consumer here, so the head's data gradient applies the mask in its epilogue and the backbone skips its pass over that gradient
+        (MI_HEAD_MASK, default on).  Other backbones / heads, or the switch off: the plain call."""
+        fe = self.feature_extractor
+        if not (hasattr(fe, "feature_mask") and isinstance(self.classifier, ASPP_Classifier_V2) and _kernels.head_mask_enabled()):
+            return fe(src_input), {}
+        feat = fe(src_input, sole_consumer=True)
+        fm = fe.feature_mask()
+        return feat, ({} if fm is None else {"feature_mask": fm})
+
     def _step_core(self, src_input, src_label):
         self.optimizer_fea.zero_grad()
         self.optimizer_cls.zero_grad()
-        feat = self.feature_extractor(src_input)
-        loss = self.classifier.loss(feat, src_label, self.cfg.INPUT.IGNORE_LABEL, **self.ce_kwargs)
+        feat, fmask = self._feature(src_input)
+        loss = self.classifier.loss(feat, src_label, self.cfg.INPUT.IGNORE_LABEL, **self.ce_kwargs, **fmask)
         loss.backward()
         self.optimizer_fea.step()
         self.optimizer_cls.step()
@@ -198,9 +210,9 @@ class ASPPTrainer(BaseTrainer):
         self.optimizer_cls.zero_grad()
         src_input = src_input.to(self.device, non_blocking=True)
         src_label = src_label.to(self.device, non_blocking=True).long()
-        feat = self.feature_extractor(src_input)
+        feat, fmask = self._feature(src_input)
         if hasattr(self.classifier, "loss"):
-            loss = self.classifier.loss(feat, src_label, self.cfg.INPUT.IGNORE_LABEL, **self.ce_kwargs)
+            loss = self.classifier.loss(feat, src_label, self.cfg.INPUT.IGNORE_LABEL, **self.ce_kwargs, **fmask)
         else:
             output = self.classifier(feat, src_label.shape[-2:])
             loss = torch.nn.functional.cross_entropy(output, src_label, ignore_index=self.cfg.INPUT.IGNORE_LABEL)

@@ -881,6 +881,39 @@ def stem_wgrad_direct(dy, x4):
     return dw
 
 
+def stem_pool_wgrad_enabled():
+    """MI_STEM_POOL_WGRAD (default 1): the direct stem weight gradient builds dy from the pooled gradient inside its launch; 0: stem_pool_bwd first."""
+    return bool(_lib.lib().mi_stem_pool_wgrad_enabled())
+
+
+def stem_wgrad_pool(dpool, idx, scale, x4):
+    """stem_wgrad_direct(stem_pool_bwd(dpool, idx, scale, conv size), x4) in one launch, bit-equal, without dy in memory: dpool [B,Hp,Wp,64] bf16
+    NHWC, idx uint8 of the same shape (stem_pool_fwd), scale fp32 [64], x4 [B,H,W,4] bf16 -> fp32 [64,3,7,7]."""
+    _chk(dpool, torch.bfloat16, "dpool")
+    _chk(idx, torch.uint8, "idx")
+    _chk(scale, torch.float32, "scale")
+    _chk(x4, torch.bfloat16, "x4")
+    B, H, W, C4 = x4.shape
+    Ho, Wo = _stem_out_hw(H, W)
+    Hp, Wp = (Ho - 1) // 2 + 1, (Wo - 1) // 2 + 1
+    O = dpool.shape[-1]
+    if C4 != 4 or tuple(dpool.shape[:3]) != (B, Hp, Wp) or idx.shape != dpool.shape or scale.numel() != O:
+        raise _lib.MiError("stem_wgrad_pool: dpool %s / idx %s / scale %s do not belong to x4 %s" % (
+            tuple(dpool.shape), tuple(idx.shape), tuple(scale.shape), tuple(x4.shape)))
+    L = _lib.lib()
+    dw = torch.empty((O, 3, 7, 7), dtype=torch.float32, device=dpool.device)
+    ws = _workspace(L.mi_stem_conv_wgrad_workspace(B, Ho, Wo), dpool.device, "stem_wgrad")
+    check(_timed("stem_direct_wgrad_kernel<pool>+reduce", 2.0 * B * Ho * Wo * O * 147, lambda: L.mi_stem_conv_wgrad_pool(
+        _p(dpool), _p(idx), _p(scale), _p(x4), _p(dw), B, H, W, O, Ho, Wo, Hp, Wp, _p(ws), ws.numel(), _stream()),
+        tag=("wgrad", 7, 4, O, B * Ho * Wo, 0, 1)), "mi_stem_conv_wgrad_pool")
+    return dw
+
+
+def head_mask_enabled():
+    """MI_HEAD_MASK (default 1): the source-only training step lets the head's data gradient mask the backbone output's gradient in its epilogue."""
+    return bool(_lib.lib().mi_head_mask_enabled())
+
+
 def bias_grad_bf16(dy, db, accumulate=False):
     """db[n] (+)= sum over pixels of dy[..., n];  dy bf16 [B,H,W,N]"""
     _chk(dy, torch.bfloat16, "dy")
@@ -961,6 +994,47 @@ def sgd_step_dev(p, g, buf, hyper):
     for t, n in ((p, "p"), (g, "g"), (buf, "buf"), (hyper, "hyper")):
         _chk(t, torch.float32, n)
     check(_lib.lib().mi_sgd_step_dev(_p(p), _p(g), _p(buf), p.numel(), _p(hyper), _stream()), "mi_sgd_step_dev")
+
+
+def sgd_pack_enabled():
+    """MI_SGD_PACK (default 1): FusedSGD's step over a backbone store also writes the bf16 operand packs (sgd_step_pack)."""
+    return bool(_lib.lib().mi_sgd_pack_enabled())
+
+
+def pack_table_gaps(rows, n):
+    """[lo, hi) element ranges of a flat store of n floats that no row of a pack table covers (rows: lists [w_off, scale_off, wp_off, wpt_off, O, I, T,
+    first_block]), as sgd_step_pack wants them; raises if two rows overlap or one runs past n."""
+    gaps, pos = [], 0
+    for lo, hi in sorted((int(r[0]), int(r[0]) + int(r[4]) * int(r[5]) * int(r[6])) for r in rows):
+        if lo < pos or hi > n:
+            raise _lib.MiError("pack table: row [%d, %d) overlaps its neighbour or leaves the store of %d floats" % (lo, hi, n))
+        if lo > pos:
+            gaps.append([pos, lo])
+        pos = hi
+    if pos < n:
+        gaps.append([pos, n])
+    return gaps
+
+
+def sgd_step_pack(p, g, buf, hyper_or_lr, momentum, weight_decay, sflat, wp, wpt, table_dev, n_desc, total_blocks, gaps_dev):
+    """sgd_step (hyper_or_lr a float, with momentum / weight_decay) or sgd_step_dev (hyper_or_lr the 3-float device tensor) over the whole flat store
+    plus pack_weights_multi of the updated weights, in one launch (see include/mi355seg.h).  gaps_dev: int64 [n_gaps, 2] on the device
+    (pack_table_gaps), or None when the rows cover the store."""
+    for t, n in ((p, "p"), (g, "g"), (buf, "buf")):
+        _chk(t, torch.float32, n)
+    _chk(wp, torch.bfloat16, "wp")
+    _chk(table_dev, torch.int64, "table")
+    n_gaps = 0 if gaps_dev is None else int(gaps_dev.shape[0])
+    if n_gaps:
+        _chk(gaps_dev, torch.int64, "gaps")
+    L = _lib.lib()
+    if torch.is_tensor(hyper_or_lr):
+        _chk(hyper_or_lr, torch.float32, "hyper")
+        check(L.mi_sgd_step_pack_dev(_p(p), _p(g), _p(buf), p.numel(), _p(hyper_or_lr), _p(sflat), _p(wp), _p(wpt), _p(table_dev), int(n_desc),
+                                     int(total_blocks), _p(gaps_dev) if n_gaps else None, n_gaps, _stream()), "mi_sgd_step_pack_dev")
+    else:
+        check(L.mi_sgd_step_pack(_p(p), _p(g), _p(buf), p.numel(), float(hyper_or_lr), float(momentum), float(weight_decay), _p(sflat), _p(wp), _p(wpt),
+                                 _p(table_dev), int(n_desc), int(total_blocks), _p(gaps_dev) if n_gaps else None, n_gaps, _stream()), "mi_sgd_step_pack")
 
 
 def relu_mask(x, msk, out=None):
