@@ -405,6 +405,33 @@ int mi_polyp_score(const float* low, const int64_t* labels, int B, int h, int w,
  * in the same launch, bit-equal to the mirror of image b.  Ho == H && Wo == W reproduces the input bit for bit. */
 int mi_image_resize_ac(const float* x, float* out, int B, int C, int H, int W, int Ho, int Wo, int with_mirror, void* stream);
 
+/* ---- locally connected CRF refinement of a probability map (TEST.CRF; not in the reference: the third part of DeepLabV2 as published) ----
+ * Mean field over a dilated window with Gaussian position and bilateral kernels and Potts compatibility (the form of ConvCRF).  Per image:
+ * p [K][H][W] fp32 probabilities, I [3][H][W] the normalised input image at the same size, cs0..cs2 the factors that turn a difference of the
+ * normalised image into a difference in 0..255 units.  eps = 1e-5; all arithmetic fp32.
+ *   U_i[c]   = log(max(p_i[c], eps))
+ *   offsets  o = (dy, dx) * dilation, dy, dx in [-(window/2), window/2], (dy, dx) != (0, 0), in row-major order
+ *   in(i,o)  = 1 if pixel i + o lies inside the image, else 0
+ *   gp(o)    = exp(-|o|^2 / (2 pos_xy^2));   gb(o) = exp(-|o|^2 / (2 bi_xy^2))
+ *   gc(i,o)  = exp(-sum_ch (cs[ch] (I_{i+o}[ch] - I_i[ch]))^2 / (2 bi_rgb^2))
+ *   Np_i     = sum_o in(i,o) gp(o);   Nb_i = sum_o in(i,o) gb(o)      (geometry only: never near zero because of colour)
+ *   k(i,o)   = in(i,o) [pos_w gp(o) / Np_i + bi_w gb(o) gc(i,o) / Nb_i]      (a term whose N is 0 is 0)
+ *   Q^0      = softmax_c(U);   Q^{t+1}_i = softmax_c(U_i[c] + sum_o k(i,o) Q^t_{i+o}[c]),  t = 0 .. iters-1
+ * Outputs, each optional: out_probs = Q^{iters}; pred = the lowest class index among its maxima; conf = that maximum.  iters == 0: softmax(U).
+ * What an output receives does not depend on which other outputs are requested, and two calls give the same bits (fixed neighbour order, no
+ * atomics).  1 + iters launches on `stream`, nothing read back in between (capturable in a HIP graph); Q ping-pongs between the two halves of
+ * the workspace (mi_crf_workspace bytes, 16-byte aligned, no initialisation needed; unused for iters == 0).  probs is read by every launch:
+ * out_probs may alias neither it nor the image.
+ * Refused before any launch (MI_EINVAL unless stated): a NULL probs / image, all three outputs NULL, K outside 1..32, window even or outside
+ * 3..11, dilation outside 1..16, iters outside 0..32, a sigma that is not positive and finite, a weight that is negative or not finite,
+ * B * H * W >= 2^31, a workspace that is too small (MI_ENOMEM). */
+size_t mi_crf_workspace(int B, int K, int H, int W);
+int mi_crf_refine(const float* probs /*[B][K][H][W]*/, const float* image /*[B][3][H][W]*/, float cs0, float cs1, float cs2,
+                  float* out_probs /*[B][K][H][W] or NULL*/, uint8_t* pred /*[B][H][W] or NULL*/, float* conf /*[B][H][W] or NULL*/,
+                  int B, int K, int H, int W, int iters, int window, int dilation,
+                  float pos_w, float pos_xy, float bi_w, float bi_xy, float bi_rgb,
+                  void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- optimiser: torch.optim.SGD(momentum, weight_decay) on flat fp32 buffers (aspp_trainer.py:25-26,94-95)
  * g' = g + wd*p; buf = mu*buf + g'; p -= lr*buf  (buf zero-initialised == torch's first-step buf = g'). */
 int mi_sgd_step(float* p, const float* g, float* buf, size_t n, float lr, float momentum, float weight_decay, void* stream);

@@ -63,6 +63,8 @@ SIGNATURES = {
     "mi_polyp_score_workspace": (Z, [I] * 5),
     "mi_polyp_score": (I, [P, P] + [I] * 5 + [P, P, P, P, P, P, Z, P]),
     "mi_image_resize_ac": (I, [P, P] + [I] * 7 + [P]),
+    "mi_crf_workspace": (Z, [I] * 4),
+    "mi_crf_refine": (I, [P, P, F, F, F, P, P, P] + [I] * 7 + [F] * 5 + [P, Z, P]),
     "mi_stem_pool_fwd": (I, [P, P, P, P, P] + [I] * 6 + [P]),
     "mi_stem_pool_bwd": (I, [P, P, P, P] + [I] * 6 + [P]),
     "mi_stem_im2col": (I, [P, P] + [I] * 6 + [P]),

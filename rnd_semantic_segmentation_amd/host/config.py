@@ -200,9 +200,18 @@ def default_tree():
         # pass (metrics.classwise_settings; PSEUDO_PORTION changed while PSEUDO_CLASSWISE is False is refused);
         # POLYP_METRICS True (PranetTester only; the other testers refuse it) = besides the intersection / union lines, the polyp-segmentation
         # metrics PraNet is published with - mean Dice / IoU over 256 thresholds, F-beta, S-measure, E-measure, MAE - from one fused evaluation
-        # tail (mi_polyp_score), logged and written to OUTPUT_DIR/pranet_polyp_metrics.json; labels must be 0 / 1
+        # tail (mi_polyp_score), logged and written to OUTPUT_DIR/pranet_polyp_metrics.json; labels must be 0 / 1;
+        # CRF True (ASPPTester only; the other testers refuse it) = the third part of DeepLabV2 as published, in its locally connected form: the
+        # full-resolution probability map is refined by CRF_ITER mean-field iterations over a CRF_WINDOW x CRF_WINDOW window dilated by
+        # CRF_DILATION, with a position kernel (weight CRF_POS_W, sigma CRF_POS_XY pixels) and a bilateral kernel (weight CRF_BI_W, sigmas
+        # CRF_BI_XY pixels and CRF_BI_RGB in 0..255 colour units), in one HIP kernel family (mi_crf_refine) between the evaluation tail and the
+        # argmax; the tester then takes the literal scoring path whatever FUSED_SCORE says.  The defaults are the customary dense-CRF values
+        # (3 / 3, 10 / 80 / 13, 5 iterations); they are NOT tuned on any dataset here.  A CRF_* key changed while CRF is False is refused
+        # (metrics.crf_settings)
         "TEST": {"BATCH_SIZE": 1, "PRECISION": "fp32", "SCALES": (1.0,), "FLIP": False, "FUSED_SCORE": True, "PSEUDO_THRESHOLD": 0.0,
-                 "PSEUDO_CLASSWISE": False, "PSEUDO_PORTION": 0.5, "POLYP_METRICS": False},
+                 "PSEUDO_CLASSWISE": False, "PSEUDO_PORTION": 0.5, "POLYP_METRICS": False,
+                 "CRF": False, "CRF_ITER": 5, "CRF_WINDOW": 7, "CRF_DILATION": 4, "CRF_POS_W": 3.0, "CRF_POS_XY": 3.0, "CRF_BI_W": 10.0,
+                 "CRF_BI_XY": 80.0, "CRF_BI_RGB": 13.0},
         "OUTPUT_DIR": ".",
         "resume": "",
         "PSEUDO_DIR": "",

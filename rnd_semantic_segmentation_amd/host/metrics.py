@@ -20,6 +20,8 @@ Differences that are deliberate and documented:
  * the polyp metrics (polyp_image_stats, PolypMeter, polyp_settings; TEST.POLYP_METRICS) are not in the reference either: mean Dice / IoU,
    F-beta, E-measure, S-measure and MAE as PraNet and its successors report them on Kvasir, derived in float64 from the per-image histogram
    and moment sums of mi_polyp_score - the host never sees the probability map.
+ * the CRF refinement (crf_settings, crf_channel_scale, crf_refine_output; TEST.CRF) is not in the reference either: the locally connected
+   form of DeepLabV2's CRF stage, one HIP kernel family (mi_crf_refine) on the literal path's probability map.
 """
 import json
 import logging
@@ -464,6 +466,80 @@ def classwise_pseudo_labels(feature_extractor, classifier, image, label, flip=Fa
         return _engine_masks(feature_extractor, classifier, image, size, flip, tuple(scales), class_threshold=_class_table(class_threshold, K, "cpu"),
                              want_pseudo=True)[1]
     return literal_pseudo(_literal_output(feature_extractor, classifier, image, label, flip, tuple(scales)), class_threshold)
+
+
+# ----------------------------------------------------------------------------- CRF refinement (TEST.CRF)
+CRF_DEFAULTS = OrderedDict((("CRF_ITER", 5), ("CRF_WINDOW", 7), ("CRF_DILATION", 4), ("CRF_POS_W", 3.0), ("CRF_POS_XY", 3.0),
+                                        ("CRF_BI_W", 10.0), ("CRF_BI_XY", 80.0), ("CRF_BI_RGB", 13.0)))      # TEST.CRF_* of host/config.py
+CRF_MAX_CLASSES = 32
+
+
+def crf_settings(cfg):
+    """None while TEST.CRF is False (absent = False), else the keyword arguments of kernels.crf_refine: iters, window, dilation, pos_w, pos_xy,
+    bi_w, bi_xy, bi_rgb.  Validates on the host what mi_crf_refine validates (include/mi355seg.h).  A CRF_* key that differs from its default
+    while CRF is False is refused instead of ignored."""
+    test = cfg.TEST
+    on = test["CRF"] if "CRF" in test else False
+    if not isinstance(on, bool):
+        raise ValueError("TEST.CRF %r must be True or False" % (on,))
+    v = OrderedDict((k, test[k] if k in test else d) for k, d in CRF_DEFAULTS.items())
+    if not on:
+        stray = [k for k, d in CRF_DEFAULTS.items() if isinstance(v[k], bool) or v[k] != d]
+        if stray:
+            raise NotImplementedError("TEST.%s %r belongs to TEST.CRF True" % (stray[0], v[stray[0]]))
+        return None
+    for k in ("CRF_ITER", "CRF_WINDOW", "CRF_DILATION"):
+        if isinstance(v[k], bool) or not isinstance(v[k], int):
+            raise ValueError("TEST.%s %r must be an integer" % (k, v[k]))
+    for k in ("CRF_POS_W", "CRF_POS_XY", "CRF_BI_W", "CRF_BI_XY", "CRF_BI_RGB"):
+        if isinstance(v[k], bool) or not isinstance(v[k], (int, float)) or not math.isfinite(v[k]):
+            raise ValueError("TEST.%s %r must be a finite number" % (k, v[k]))
+    if not 0 <= v["CRF_ITER"] <= 32:
+        raise ValueError("TEST.CRF_ITER %r lies outside 0..32" % (v["CRF_ITER"],))
+    if not 3 <= v["CRF_WINDOW"] <= 11 or v["CRF_WINDOW"] % 2 == 0:
+        raise ValueError("TEST.CRF_WINDOW %r must be odd and in 3..11" % (v["CRF_WINDOW"],))
+    if not 1 <= v["CRF_DILATION"] <= 16:
+        raise ValueError("TEST.CRF_DILATION %r lies outside 1..16" % (v["CRF_DILATION"],))
+    for k in ("CRF_POS_XY", "CRF_BI_XY", "CRF_BI_RGB"):
+        if not v[k] > 0:
+            raise ValueError("TEST.%s %r must be positive" % (k, v[k]))
+    for k in ("CRF_POS_W", "CRF_BI_W"):
+        if v[k] < 0:
+            raise ValueError("TEST.%s %r must not be negative" % (k, v[k]))
+    K = int(cfg.MODEL.NUM_CLASSES) if "MODEL" in cfg and "NUM_CLASSES" in cfg.MODEL else 1
+    if not 1 <= K <= CRF_MAX_CLASSES:
+        raise ValueError("TEST.CRF: MODEL.NUM_CLASSES %d lies outside 1..%d" % (K, CRF_MAX_CLASSES))
+    return dict(iters=v["CRF_ITER"], window=v["CRF_WINDOW"], dilation=v["CRF_DILATION"], pos_w=float(v["CRF_POS_W"]), pos_xy=float(v["CRF_POS_XY"]),
+                bi_w=float(v["CRF_BI_W"]), bi_xy=float(v["CRF_BI_XY"]), bi_rgb=float(v["CRF_BI_RGB"]))
+
+
+def require_no_crf(cfg, who):
+    """The CRF refinement sits between ASPPTester's evaluation tail and its argmax: the other testers refuse the key rather than ignore it
+    (a stray CRF_* key is refused by crf_settings itself)."""
+    if crf_settings(cfg) is not None:
+        raise NotImplementedError("%s: TEST.CRF - the CRF refinement exists for the DeepLab (feature extractor, classifier) pair only "
+                                  "(ASPPTester); leave it False" % (who,))
+
+
+def crf_channel_scale(cfg):
+    """The three factors that turn a difference of the normalised input tensor into a difference in 0..255 colour units: the transform divides
+    by INPUT.PIXEL_STD after scaling the image to 0..255 (TO_BGR255) or to 0..1 (otherwise)."""
+    std = [float(s) for s in cfg.INPUT.PIXEL_STD]
+    if len(std) != 3:
+        raise ValueError("TEST.CRF needs three INPUT.PIXEL_STD values, got %r" % (std,))
+    return tuple(s * (1.0 if cfg.INPUT.TO_BGR255 else 255.0) for s in std)
+
+
+def crf_refine_output(output, image, size, cs, settings):
+    """The refined [1,K,H,W] map of one literal-path output: image 0 brought to the label's size (bilinear, align_corners, as the evaluation
+    itself resizes), then kernels.crf_refine.  The engine only: there is no torch-op CRF to fall back to."""
+    from .. import kernels
+    if not output.is_cuda:
+        raise NotImplementedError("TEST.CRF runs on the GPU only (mi_crf_refine); got a %s tensor" % (output.device,))
+    x0 = image[:1].float().contiguous()
+    if tuple(x0.shape[-2:]) != tuple(size):
+        x0 = kernels.image_resize_ac(x0, tuple(size))
+    return kernels.crf_refine(output[:1].float().contiguous(), x0, cs, **settings).probs
 
 
 # ----------------------------------------------------------------------------- polyp metrics (TEST.POLYP_METRICS)

@@ -6,9 +6,10 @@ import os
 import numpy as np
 import torch
 
-from .metrics import (PSEUDO_BINS, AverageMeter, class_thresholds, classwise_pseudo_labels, classwise_settings, confusion_matrix, dump_json, inference,
-                      intersectionAndUnionGPU, literal_histogram, literal_pseudo, multi_scale_inference, predict_and_score, require_no_polyp_metrics,
-                      score_settings, strip_prefix_if_present, threshold_table, tta_settings)
+from .metrics import (PSEUDO_BINS, AverageMeter, class_thresholds, classwise_pseudo_labels, classwise_settings, confusion_matrix, crf_channel_scale,
+                      crf_refine_output, crf_settings, dump_json, inference, intersectionAndUnionGPU, literal_histogram, literal_pseudo,
+                      multi_scale_inference, predict_and_score, require_no_polyp_metrics, score_settings, strip_prefix_if_present, threshold_table,
+                      tta_settings)
 from .modules import build_classifier, build_feature_extractor
 
 
@@ -26,6 +27,8 @@ class ASPPTester:
         self.saveres = saveres
         classwise_settings(cfg)                            # a stray TEST.PSEUDO_PORTION is refused before anything is built
         require_no_polyp_metrics(cfg, "ASPPTester")
+        self.crf = crf_settings(cfg)                       # TEST.CRF: None, or the parameters of kernels.crf_refine (a stray CRF_* key is refused)
+        self.crf_scale = crf_channel_scale(cfg) if self.crf is not None else None
         self.feature_extractor = self.build_feature_extractor(cfg)
         self.feature_extractor.to(device)
         self.classifier = self.build_classifier(cfg)
@@ -60,9 +63,14 @@ class ASPPTester:
 
     def _literal_output(self, x, y, single, scales, flip):
         if single:
-            return inference(self.feature_extractor, self.classifier, x, y, flip=False)     # [1,K,H,W]
-        # the call aspp_tester.py:61 keeps commented out
-        return multi_scale_inference(self.feature_extractor, self.classifier, x, y, flip=flip, scales=list(scales))
+            output = inference(self.feature_extractor, self.classifier, x, y, flip=False)     # [1,K,H,W]
+        else:
+            # the call aspp_tester.py:61 keeps commented out
+            output = multi_scale_inference(self.feature_extractor, self.classifier, x, y, flip=flip, scales=list(scales))
+        if self.crf is None:
+            return output
+        # TEST.CRF: everything downstream (argmax, thresholds, histogram, metrics, masks) works on the refined probabilities
+        return crf_refine_output(output, x, tuple(y.shape[-2:]), self.crf_scale, self.crf)
 
     def test(self):
         num_classes = self.cfg.MODEL.NUM_CLASSES
@@ -76,6 +84,11 @@ class ASPPTester:
         classwise, portion, cap = classwise_settings(self.cfg)
         # one kernel after the logits (argmax, threshold, counts) instead of the probability map and the torch-op metrics: same integers, same files
         fused = fused and self.device.type == "cuda" and hasattr(self.classifier, "predict_mask_multi")
+        if self.crf is not None:
+            # the refinement needs the probability map the fused tail never writes: the literal path, whatever TEST.FUSED_SCORE says
+            fused = False
+            self.logger.info("TEST.CRF: {iters} mean-field iterations, window {window} x dilation {dilation}; scoring takes the literal path "
+                             "on the refined map.".format(**self.crf))
         # TEST.PSEUDO_CLASSWISE: this loop is pass 1 - the metrics as ever, no masks, and the confidence histogram of the whole set on the device
         hist = torch.zeros(num_classes, PSEUDO_BINS, dtype=torch.int64, device=self.device) if classwise else None
         for x, y, name in self.test_loader:

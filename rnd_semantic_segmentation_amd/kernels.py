@@ -758,6 +758,36 @@ def image_resize_ac(x, size, with_mirror=False):
     return out
 
 
+CrfResult = collections.namedtuple("CrfResult", "probs pred conf")
+
+
+def crf_refine(probs, image, cs, iters, window, dilation, pos_w, pos_xy, bi_w, bi_xy, bi_rgb, want_probs=True, want_pred=False, want_conf=False):
+    """Locally connected CRF refinement (mi_crf_refine, the definition: include/mi355seg.h): probs [B,K,H,W] fp32 probabilities, image [B,3,H,W]
+    fp32 (the normalised input at the same size), cs the three factors from the normalised image to 0..255 units -> CrfResult of device tensors:
+    probs fp32 [B,K,H,W] (Q after `iters` mean-field iterations), pred uint8 [B,H,W] (its argmax, lowest index among ties), conf fp32 [B,H,W]
+    (its maximum); None where not asked for.  An output's bits do not depend on which others are requested.  1 + iters launches on the current
+    stream, workspace cached per stream."""
+    _chk(probs, torch.float32, "probs")
+    _chk(image, torch.float32, "image")
+    if probs.dim() != 4 or image.dim() != 4 or image.shape[1] != 3 or image.shape[0] != probs.shape[0] or image.shape[2:] != probs.shape[2:] \
+            or image.device != probs.device:
+        raise _lib.MiError("crf_refine: probs [B,K,H,W] and image [B,3,H,W] on one device, got %s on %s and %s on %s"
+                           % (tuple(probs.shape), probs.device, tuple(image.shape), image.device))
+    cs = [float(v) for v in cs]
+    if len(cs) != 3:
+        raise _lib.MiError("crf_refine: cs must hold three channel factors, got %d" % len(cs))
+    B, K, H, W = probs.shape
+    dev = probs.device
+    out = torch.empty_like(probs) if want_probs else None
+    pred = torch.empty((B, H, W), dtype=torch.uint8, device=dev) if want_pred else None
+    conf = torch.empty((B, H, W), dtype=torch.float32, device=dev) if want_conf else None
+    ws = _workspace(_lib.lib().mi_crf_workspace(B, K, H, W), dev, "crf")
+    check(_lib.lib().mi_crf_refine(_p(probs), _p(image), cs[0], cs[1], cs[2], _p(out), _p(pred), _p(conf), B, K, H, W, int(iters), int(window),
+                                   int(dilation), float(pos_w), float(pos_xy), float(bi_w), float(bi_xy), float(bi_rgb), _p(ws), ws.numel(),
+                                   _stream()), "mi_crf_refine")
+    return CrfResult(out, pred, conf)
+
+
 def stem_pool_fwd(y, scale, shift):
     """y [B,Hc,Wc,C] bf16 (conv1 output) -> (pool [B,Hp,Wp,C] bf16, idx uint8): FrozenBN + ReLU + maxpool 3x3/2/1."""
     _chk(y, torch.bfloat16, "y")
