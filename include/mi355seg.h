@@ -862,6 +862,44 @@ typedef struct MiPraSample {
  * out_img [B][3][out_h][out_w] fp32, out_mask [B][out_h][out_w] fp32 (NULL when no sample has a mask). */
 int mi_augment_pra_batch(const void* table_dev, const void* table_host, int B, int out_h, int out_w, float* out_img, float* out_mask, void* stream);
 
+/* ---- online self-training: mean teacher + ClassMix (DACS / DAFormer) on the device (csrc/classmix.hip; host/self_train.py AsppClassMix) ----------
+ * The three entries are enqueue-only (no host read, no synchronisation; the memsets below are stream-ordered), use no floating-point atomics and
+ * are bit-reproducible from run to run.  Bad arguments return MI_EINVAL before anything is enqueued.
+ *
+ * mi_label_classes: labels [B][H][W] int64 -> present [B] uint32, bit c of present[b] set iff class c in [0, K) occurs in image b.  Values outside
+ * [0, K) - the ignore value included - set nothing.  present is zeroed by the entry (whatever it held).  OR within the thread, the wave, the
+ * workgroup, then one integer atomic OR per workgroup.  K in 1..32 (K = 32 uses bit 31); two labels per load when H*W is even and labels is
+ * 16-byte aligned.  Refused: NULL pointers, B outside 1..65535, H or W < 1, K outside 1..32. */
+int mi_label_classes(const int64_t* labels, uint32_t* present, int B, int H, int W, int K, void* stream);
+
+/* mi_classmix: the pseudo-label and mixing pass of one iteration, without the [B][K][H][W] probability map.
+ *   src_img, tgt_img, mix_img  [B][3][H][W] fp32      src_lab, mix_lab  [B][H][W] int64      mask  [B][H][W] uint8 or NULL
+ *   teacher_low  [B][h][w][K] fp32 NHWC: the teacher head's low-resolution logits of the target images
+ *   present      [B] uint32 (mi_label_classes of src_lab)      priority  [B][K] uint8, every row a permutation of 0..K-1 drawn by the host
+ *   counts       [B][2] int64, zeroed by the entry
+ * chosen(b) = the ceil(n/2) classes of present[b] (bits below K) with the smallest priority[b][c], n their number; n = 0: the empty set.  Every
+ * workgroup recomputes it from present and priority: no launch of its own, no round trip through the host.
+ * Per pixel: M = src_lab in [0, K) and in chosen(b);  mix_img = M ? src_img : tgt_img (per channel; the other image is not read);
+ * mix_lab = M ? src_lab : pseudo;  mask = M;  pseudo = (max_k p_k >= threshold) ? the LOWEST class index among the maxima : ignore_index, with
+ * p_k exactly the K values of mi_upsample_predict_score for one source, no mirror, div_a = div_b = 1 (one shared device function: the labels
+ * are bit-equal to that entry's pseudo output, 255 there = ignore_index here).  A pasted pixel does not read the teacher's logits.
+ * counts[b][0] = pasted pixels, counts[b][1] = unpasted pixels whose pseudo-label was kept: 32-bit sums per workgroup, one 64-bit integer atomic
+ * add per counter and workgroup.  mix_img may be a slice of a larger buffer; it must not overlap the inputs.
+ * Two pixels per lane when W is even, the images are 8-byte, the labels 16-byte and mask 2-byte aligned.  Traffic per pixel: 8 (label) + 12 (the
+ * image shown) read, 12 + 8 (+ 1 with mask) written, plus the low-resolution logits once per 64 pixels at 1/8 resolution.
+ * Refused: NULL pointers (mask apart), B outside 1..65535, non-positive sizes, H < h, W < w, K outside 1..32, threshold outside [0, 1] or NaN,
+ * ignore_index inside [0, K). */
+int mi_classmix(const float* src_img, const float* tgt_img, const int64_t* src_lab, const float* teacher_low, const uint32_t* present,
+                const uint8_t* priority, float threshold, int ignore_index, float* mix_img, int64_t* mix_lab, uint8_t* mask, int64_t* counts,
+                int B, int h, int w, int K, int H, int W, void* stream);
+
+/* mi_ema_update: teacher[i] = a * teacher[i] + b * student[i] for i < n over flat fp32 stores, a = hyper[0] read from DEVICE memory by the kernel
+ * (a captured HIP graph replays with whatever the host wrote there), b the fp32 difference 1.0f - a; both products and the sum are rounded fp32
+ * operations (a = 0 copies the student, a = 1 leaves the teacher).  16-byte accesses; any n and any 4-byte alignment of the two pointers: the
+ * teacher's 16-byte boundaries hand out the ranges (a scalar head and tail of at most 3 elements each), the student is read at whatever
+ * alignment it has.  Refused: NULL pointers, n = 0, a pointer that is not 4-byte aligned. */
+int mi_ema_update(float* teacher, const float* student, size_t n, const float* hyper /*[1], device*/, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -154,6 +154,9 @@ SIGNATURES = {
     "mi_gpoint_f32": (I, [I, P, L, P, L, P, P, I, P, L, L, I, P]),
     "mi_augment_batch": (I, [P, P, I, I, I, I, I, P, P, P]),
     "mi_augment_pra_batch": (I, [P, P, I, I, I, P, P, P]),
+    "mi_label_classes": (I, [P, P, I, I, I, I, P]),
+    "mi_classmix": (I, [P] * 6 + [F, I] + [P] * 4 + [I] * 6 + [P]),
+    "mi_ema_update": (I, [P, P, Z, P, P]),
 }
 
 class MiProbSource(ctypes.Structure):

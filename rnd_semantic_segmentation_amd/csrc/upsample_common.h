@@ -1,5 +1,5 @@
-// What the bilinear-upsample sources (upsample_ce.hip, upsample_infer.hip, fada.hip) share: the source-index arithmetic, the fixed-order reductions,
-// the per-pixel softmax core, the prologue / pixel / epilogue helpers of the two kernel skeletons of the fused upsample + loss heads (x-tile and row-walk), the LDS layout of the first,
+// What the bilinear-upsample sources (upsample_ce.hip, upsample_infer.hip, fada.hip, classmix.hip) share: the source-index arithmetic, the fixed-order reductions,
+// the per-pixel softmax core, the per-pixel probabilities and prediction of the inference tails, the prologue / pixel / epilogue helpers of the two kernel skeletons of the fused upsample + loss heads (x-tile and row-walk), the LDS layout of the first,
 // and the launch planning.  Everything is file-local to the source that includes it (anonymous namespace): kernel names do not change.
 #pragma once
 #include "mi_common.h"
@@ -134,6 +134,121 @@ __device__ __forceinline__ float softmax_terms(const float* c0, const float* c1,
         }
     }
     return exp_terms<PICK>(v, kr, mx, K, lab, picked, term);
+}
+
+// ------------------------------------------------------------------------------------------------ the per-pixel probabilities of the inference tails
+// Shared by the inference tails of upsample_infer.hip and the self-training pass of classmix.hip, so that the pseudo-labels written during
+// evaluation and those drawn inside a training step cannot drift apart.
+// The per-source arithmetic: the bilinear (align_corners) sample of the NHWC map `low` (one image) at output pixel
+// (y, x), then v[k] = exp(value - max); returns 1 / sum (the probabilities are v[k] * result) and the first arg max.
+// The interpolation is written out operation by operation - row0 = fma(lx, v01, (1-lx) v00), row1 = fma(1-lx, v10, lx v11),
+// value = (1-ly) row0 + ly row1 with both products rounded - because that is the order mi_upsample_softmax has always computed (what the
+// compiler's contraction made of lerp2 there) and two kernels have to agree on it bit for bit; contraction is off so that it stays put.
+template <int KR>
+__device__ __forceinline__ float interp_softmax_terms(const float* __restrict__ low, int K, const Axis& ay, const Axis& ax, int y, int x,
+                                                      float (&v)[KR], int& arg) {
+#pragma clang fp contract(off)
+    const int w = ax.n_in;
+    int y0, y1, x0, x1;
+    float ly, lx;
+    ay.src(y, y0, y1, ly);
+    ax.src(x, x0, x1, lx);
+    const float* p00 = low + ((long)y0 * w + x0) * K;
+    const float* p01 = low + ((long)y0 * w + x1) * K;
+    const float* p10 = low + ((long)y1 * w + x0) * K;
+    const float* p11 = low + ((long)y1 * w + x1) * K;
+    const float mlx = 1.f - lx, mly = 1.f - ly;
+    float mx = -3.0e38f;
+    arg = 0;
+#pragma unroll
+    for (int k = 0; k < KR; ++k) {
+        if (k < K) {
+            const float row0 = __builtin_fmaf(lx, p01[k], mlx * p00[k]);
+            const float row1 = __builtin_fmaf(mlx, p10[k], lx * p11[k]);
+            v[k] = mly * row0 + ly * row1;
+            if (v[k] > mx) {
+                mx = v[k];
+                arg = k;
+            }
+        }
+    }
+    return 1.f / exp_terms(v, KR, mx, K);
+}
+
+struct ProbSrc {
+    const float* low;
+    Axis ay, ax;
+    int mirror;
+};
+constexpr int MAX_PROB_SRC = 16;
+struct ProbSrcs {
+    ProbSrc s[MAX_PROB_SRC];      // by value in the kernel arguments: no device table
+};
+
+__device__ __forceinline__ float add_rounded_product(float acc, float a, float b) {
+#pragma clang fp contract(off)
+    const float p = a * b;
+    return acc + p;
+}
+
+// The per-pixel arithmetic of the multi-scale tails, shared by the probability kernel, the predict-and-score kernel and the ClassMix pass so that
+// they cannot drift apart: acc[p][k] = ((p_0 + ... + p_{n-1}) / div_a) / div_b for the P pixels (y, xb .. xb+P-1), summed in source order from
+// rounded products, with true divisions (the second one skipped when div_b == 1).  s_all: the n sources.
+template <int KR, int P>
+__device__ __forceinline__ void multi_probs(const ProbSrc* s_all, int n, int K, int W, int y, int xb, float div_a, float div_b, float (&acc)[P][KR]) {
+#pragma unroll
+    for (int p = 0; p < P; ++p)
+#pragma unroll
+        for (int k = 0; k < KR; ++k) acc[p][k] = 0.f;      // 0 + p_0 == p_0 exactly (p_0 >= +0)
+    for (int i = 0; i < n; ++i) {
+        const ProbSrc& s = s_all[i];
+#pragma unroll
+        for (int p = 0; p < P; ++p) {
+            const int x = xb + p;
+            float v[KR];
+            int arg;
+            const float rse = interp_softmax_terms<KR>(s.low, K, s.ay, s.ax, y, s.mirror ? W - 1 - x : x, v, arg);
+#pragma unroll
+            for (int k = 0; k < KR; ++k) {
+                if (k < K) acc[p][k] = add_rounded_product(acc[p][k], v[k], rse);
+            }
+            __builtin_amdgcn_sched_barrier(0);      // one pixel's loads at a time: interleaving the P pixels costs P times the registers
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < KR; ++k) {
+        if (k < K) {
+#pragma unroll
+            for (int p = 0; p < P; ++p) {
+                acc[p][k] = acc[p][k] / div_a;
+                if (div_b != 1.f) acc[p][k] = acc[p][k] / div_b;
+            }
+        }
+    }
+}
+
+struct ClassThr {
+    float t[KMAX];                // by value in the kernel arguments, as ProbSrcs is: no device table
+};
+
+// The prediction of one pixel from its K values a[]: the LOWEST class index among their maxima (torch.max(dim) / numpy.argmax), the maximum in
+// `best` and the threshold it is held against in `tb`: thr.t[0], or with CW the threshold of the WINNING class - thr.t[k] travels with the running
+// maximum through the unrolled loop, so the table is read with compile-time indices (scalar registers straight from the kernel arguments), never
+// with a per-lane index.  The pseudo-label is `best >= tb ? result : ignore`.
+template <bool CW, int KR>
+__device__ __forceinline__ int first_max(const float (&a)[KR], int K, const ClassThr& thr, float& best, float& tb) {
+    best = a[0];
+    tb = thr.t[0];
+    int arg = 0;
+#pragma unroll
+    for (int k = 1; k < KR; ++k) {
+        if (k < K && a[k] > best) {           // strict: the first of equal maxima stays
+            best = a[k];
+            arg = k;
+            if constexpr (CW) tb = thr.t[k];
+        }
+    }
+    return arg;
 }
 
 // ------------------------------------------------------------------------------------------------ the x-tile skeleton

@@ -7,42 +7,8 @@
 namespace {
 
 // ------------------------------------------------------------------------------------------------ inference tails
-// The per-source arithmetic of both inference tails: the bilinear (align_corners) sample of the NHWC map `low` (one image) at output pixel
-// (y, x), then v[k] = exp(value - max); returns 1 / sum (the probabilities are v[k] * result) and the first arg max.
-// The interpolation is written out operation by operation - row0 = fma(lx, v01, (1-lx) v00), row1 = fma(1-lx, v10, lx v11),
-// value = (1-ly) row0 + ly row1 with both products rounded - because that is the order mi_upsample_softmax has always computed (what the
-// compiler's contraction made of lerp2 there) and two kernels have to agree on it bit for bit; contraction is off so that it stays put.
-template <int KR>
-__device__ __forceinline__ float interp_softmax_terms(const float* __restrict__ low, int K, const Axis& ay, const Axis& ax, int y, int x,
-                                                      float (&v)[KR], int& arg) {
-#pragma clang fp contract(off)
-    const int w = ax.n_in;
-    int y0, y1, x0, x1;
-    float ly, lx;
-    ay.src(y, y0, y1, ly);
-    ax.src(x, x0, x1, lx);
-    const float* p00 = low + ((long)y0 * w + x0) * K;
-    const float* p01 = low + ((long)y0 * w + x1) * K;
-    const float* p10 = low + ((long)y1 * w + x0) * K;
-    const float* p11 = low + ((long)y1 * w + x1) * K;
-    const float mlx = 1.f - lx, mly = 1.f - ly;
-    float mx = -3.0e38f;
-    arg = 0;
-#pragma unroll
-    for (int k = 0; k < KR; ++k) {
-        if (k < K) {
-            const float row0 = __builtin_fmaf(lx, p01[k], mlx * p00[k]);
-            const float row1 = __builtin_fmaf(mlx, p10[k], lx * p11[k]);
-            v[k] = mly * row0 + ly * row1;
-            if (v[k] > mx) {
-                mx = v[k];
-                arg = k;
-            }
-        }
-    }
-    return 1.f / exp_terms(v, KR, mx, K);
-}
-
+// The per-source arithmetic of both inference tails (interp_softmax_terms) and the per-pixel arithmetic of the multi-scale tails (multi_probs, first_max)
+// live in upsample_common.h: the ClassMix pass of classmix.hip draws its pseudo-labels from the same device code.
 // probs NCHW + optional argmax
 __global__ void upsample_softmax_kernel(const float* __restrict__ low, float* __restrict__ probs, uint8_t* __restrict__ pred, int B, int K,
                                         Axis ay, Axis ax) {
@@ -65,58 +31,6 @@ __global__ void upsample_softmax_kernel(const float* __restrict__ low, float* __
 // p_i = softmax(bilinear(low_i -> H x W)), read at column W-1-x for a mirrored source.  The reference adds materialised fp32 tensors, so every
 // p_i[k] is a rounded product before it is added (no fma), the sum runs in source order and the divisions are true divisions.
 // One thread owns P consecutive pixels of a row (2 when W is even, else 1) and keeps their K sums in registers; each class plane is written once.
-struct ProbSrc {
-    const float* low;
-    Axis ay, ax;
-    int mirror;
-};
-constexpr int MAX_PROB_SRC = 16;
-struct ProbSrcs {
-    ProbSrc s[MAX_PROB_SRC];      // by value in the kernel arguments: no device table
-};
-
-__device__ __forceinline__ float add_rounded_product(float acc, float a, float b) {
-#pragma clang fp contract(off)
-    const float p = a * b;
-    return acc + p;
-}
-
-// The per-pixel arithmetic of the multi-scale tails, shared by the probability kernel and the predict-and-score kernel so that the two cannot
-// drift apart: acc[p][k] = ((p_0 + ... + p_{n-1}) / div_a) / div_b for the P pixels (y, xb .. xb+P-1), summed in source order from rounded
-// products, with true divisions (the second one skipped when div_b == 1).
-template <int KR, int P>
-__device__ __forceinline__ void multi_probs(const ProbSrcs& srcs, int n, int K, int W, int y, int xb, float div_a, float div_b, float (&acc)[P][KR]) {
-#pragma unroll
-    for (int p = 0; p < P; ++p)
-#pragma unroll
-        for (int k = 0; k < KR; ++k) acc[p][k] = 0.f;      // 0 + p_0 == p_0 exactly (p_0 >= +0)
-    for (int i = 0; i < n; ++i) {
-        const ProbSrc& s = srcs.s[i];
-#pragma unroll
-        for (int p = 0; p < P; ++p) {
-            const int x = xb + p;
-            float v[KR];
-            int arg;
-            const float rse = interp_softmax_terms<KR>(s.low, K, s.ay, s.ax, y, s.mirror ? W - 1 - x : x, v, arg);
-#pragma unroll
-            for (int k = 0; k < KR; ++k) {
-                if (k < K) acc[p][k] = add_rounded_product(acc[p][k], v[k], rse);
-            }
-            __builtin_amdgcn_sched_barrier(0);      // one pixel's loads at a time: interleaving the P pixels costs P times the registers
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < KR; ++k) {
-        if (k < K) {
-#pragma unroll
-            for (int p = 0; p < P; ++p) {
-                acc[p][k] = acc[p][k] / div_a;
-                if (div_b != 1.f) acc[p][k] = acc[p][k] / div_b;
-            }
-        }
-    }
-}
-
 // Waves per SIMD the register budget is held to.  A pixel has 4 x K corner loads in flight besides the P x K sums: one pixel per lane runs at
 // 4 waves, two pixels per lane (8-byte stores, 512 contiguous bytes per wave and class plane) at 2.  Four pixels per lane spill.  No variant here does.
 template <int KT, int P>
@@ -130,7 +44,7 @@ __global__ __launch_bounds__(256, P == 1 ? 4 : 2) void upsample_softmax_multi_ke
     if (idx >= (long)H * WP) return;
     const int xb = (int)(idx % WP) * P, y = (int)(idx / WP);
     float acc[P][KR];
-    multi_probs<KR, P>(srcs, n, K, W, y, xb, div_a, div_b, acc);
+    multi_probs<KR, P>(srcs.s, n, K, W, y, xb, div_a, div_b, acc);
     float* o = probs + (long)y * W + xb;
 #pragma unroll
     for (int k = 0; k < KR; ++k) {
@@ -156,9 +70,6 @@ __global__ __launch_bounds__(256, P == 1 ? 4 : 2) void upsample_softmax_multi_ke
 //   - the threshold of the WINNING class: thr.t[k] travels with the running maximum through the unrolled arg-max loop, so the table is read with
 //     compile-time indices (scalar registers straight from the kernel arguments), never with a per-lane index;
 //   - hist[pred * 1024 + bin] += 1, bin = min(1023, int(best * 1024)): the confidence histogram per predicted class (lds_hist_add below).
-struct ClassThr {
-    float t[KMAX];                // by value in the kernel arguments, as ProbSrcs is: no device table
-};
 constexpr int HIST_BINS = 1024;   // confidence bins per class: the cell of a pixel is pred * HIST_BINS + bin
 constexpr int HIST_LINE = 16;     // cells per line of the workgroup's table: 16 neighbouring bins of one class = 128 contiguous bytes of hist
 constexpr int HIST_LINES = 128;   // lines of the table (open-addressed by line number)
@@ -238,21 +149,13 @@ __global__ __launch_bounds__(256, P == 1 ? 4 : 2) void upsample_predict_score_ke
     if (idx < (long)H * WP) {
         const int xb = (int)(idx % WP) * P, y = (int)(idx / WP);
         float acc[P][KR];
-        multi_probs<KR, P>(srcs, n, K, W, y, xb, div_a, div_b, acc);
+        multi_probs<KR, P>(srcs.s, n, K, W, y, xb, div_a, div_b, acc);
         uint8_t pd[P], ps[P];
         float bs[P];
 #pragma unroll
         for (int p = 0; p < P; ++p) {
-            float best = acc[p][0], tb = thr.t[0];
-            int arg = 0;
-#pragma unroll
-            for (int k = 1; k < KR; ++k) {
-                if (k < K && acc[p][k] > best) {           // strict: the first of equal maxima stays
-                    best = acc[p][k];
-                    arg = k;
-                    if constexpr (CW) tb = thr.t[k];
-                }
-            }
+            float best, tb;
+            const int arg = first_max<CW>(acc[p], K, thr, best, tb);
             pd[p] = (uint8_t)arg;
             ps[p] = best >= tb ? (uint8_t)arg : (uint8_t)255;
             bs[p] = best;

@@ -25,6 +25,7 @@ ALIASES = {
     "core.models.discriminator": _PKG + "fada",                       # core/models/discriminator.py:31-50 (PixelDiscriminator)
     "core.adapters.fada_adapter": _PKG + "fada",                      # core/adapters/fada_adapter.py:6-31
     "core.combos.aspp_fada": _PKG + "fada",                           # core/combos/aspp_fada.py:13-198
+    "core.combos.aspp_classmix": _PKG + "self_train",                 # AsppClassMix (not in the reference: mean teacher + ClassMix, host/self_train.py)
     "core.testers.aspp_tester": _PKG + "tester",                      # core/testers/aspp_tester.py
     "core.utils.utility": _PKG + "metrics",                           # core/utils/utility.py (DeepLab subset)
     "core.utils.adapt_lr": _PKG + "metrics",                          # core/utils/adapt_lr.py:12-17

@@ -14,7 +14,8 @@ import yaml
 
 _VALID = (tuple, list, str, int, float, bool, type(None))
 _RANGES = {"TEST.PSEUDO_THRESHOLD": (0.0, 1.0), "TEST.PSEUDO_PORTION": (0.0, 1.0), "SOLVER.TVERSKY_ALPHA": (0.0, 1.0), "SOLVER.LABEL_SMOOTHING": (0.0, 1.0),
-           "SOLVER.OHEM_THRESH": (0.0, 1.0), "SOLVER.OHEM_MIN_KEPT": (1, float("inf")), "SOLVER.FOCAL_GAMMA": (0.0, 8.0)}      # closed intervals a merged value has to lie in
+           "SOLVER.OHEM_THRESH": (0.0, 1.0), "SOLVER.OHEM_MIN_KEPT": (1, float("inf")), "SOLVER.FOCAL_GAMMA": (0.0, 8.0),
+           "SOLVER.EMA_ALPHA": (0.0, 1.0), "SOLVER.MIX_THRESHOLD": (0.0, 1.0)}      # closed intervals a merged value has to lie in
 _CHOICES = {"SOLVER.LOSS": ("ce", "gdl", "tversky", "ohem"), "SOLVER.GDL_WEIGHT": ("square", "identity", "sqrt")}      # the only values a merged key may take
 
 
@@ -189,6 +190,12 @@ def default_tree():
             # focal loss -w_y (1 - p_y)^FOCAL_GAMMA log p_y inside the fused heads (mi_upsample_ce_focal): OHEM's smooth counterpart.  It composes with
             # CLASS_WEIGHTS; any other LOSS ("ohem" included), LABEL_SMOOTHING > 0 and PraNetTrainer refuse it (plugin.focal_options)
             "FOCAL_GAMMA": 0.0,
+            # not in the reference either: the online form of pseudo-labelling + self-distillation, AsppClassMix (host/self_train.py; train_adv.py --model
+            # aspp_classmix): EMA_ALPHA in [0, 1] is the ceiling of the mean teacher's decay, a = min(1 - 1 / (it + 1), EMA_ALPHA) in iteration it (from 0:
+            # the first update copies the student); MIX_THRESHOLD in [0, 1] keeps a target pixel's pseudo-label where the teacher's winning probability
+            # reaches it (0.968: DACS's value) and ignores the pixel below, inside the mixing kernel (mi_classmix).  Either key changed under any other
+            # trainer or combo is refused (plugin.self_train_options)
+            "EMA_ALPHA": 0.99, "MIX_THRESHOLD": 0.968,
         },
         # not in the reference: PRECISION fp32 = exact evaluation path, bf16 = training engine; SCALES / FLIP other than these defaults make
         # ASPPTester call multi_scale_inference (utility.py:193-209) instead of inference(flip=False); FUSED_SCORE True = argmax, threshold and

@@ -106,7 +106,28 @@ def focal_options(cfg, who):
     return gamma
 
 
+SELF_TRAIN_DEFAULTS = (0.99, 0.968)          # SOLVER.EMA_ALPHA, SOLVER.MIX_THRESHOLD of host/config.py (DACS's values)
+
+
+def self_train_options(cfg, who, self_training=False):
+    """SOLVER.EMA_ALPHA / SOLVER.MIX_THRESHOLD (not in the reference) as (alpha, threshold) for the student trainer of AsppClassMix (host/self_train.py),
+    else None.  The keys changed under any other trainer or combo are refused instead of ignored."""
+    solver = getattr(cfg, "SOLVER", None)
+    alpha = getattr(solver, "EMA_ALPHA", SELF_TRAIN_DEFAULTS[0])
+    thresh = getattr(solver, "MIX_THRESHOLD", SELF_TRAIN_DEFAULTS[1])
+    if not self_training:
+        if (alpha, thresh) != SELF_TRAIN_DEFAULTS:
+            raise NotImplementedError("SOLVER.EMA_ALPHA / SOLVER.MIX_THRESHOLD belong to the mean-teacher + ClassMix combo (train_adv.py --model aspp_classmix); "
+                                      "{} does not know them".format(who))
+        return None
+    for key, v in (("EMA_ALPHA", alpha), ("MIX_THRESHOLD", thresh)):          # (a merged value was checked there; this one was assigned)
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not 0.0 <= v <= 1.0:
+            raise ValueError("SOLVER.{} {!r} lies outside [0, 1]".format(key, v))
+    return float(alpha), float(thresh)
+
+
 class BaseTrainer:
+    SELF_TRAINING = False     # True: the trainer is the student of a self-training combo, which reads SOLVER.EMA_ALPHA / SOLVER.MIX_THRESHOLD
     LOSSES = ("ce",)          # the criteria the trainer implements, as SOLVER.LOSS values
     MINED = ()                # SOLVER.LOSS values that are a LOSSES entry over mined pixels ("ohem" = "ce" over the hard pixels): accepted like LOSSES
 
@@ -116,6 +137,7 @@ class BaseTrainer:
         weights, self.ce_smoothing = ce_options(cfg, who)          # CrossEntropyLoss(weight=, label_smoothing=): refused early where they do not apply
         self.ohem = ohem_options(cfg, who)                          # (thresh, min_kept) under SOLVER.LOSS "ohem", else None
         self.focal_gamma = focal_options(cfg, who)                  # SOLVER.FOCAL_GAMMA: > 0 = the focal loss in place of "ce", 0 = off
+        self.self_train = self_train_options(cfg, who, self.SELF_TRAINING)      # (EMA_ALPHA, MIX_THRESHOLD) for AsppClassMix's student, else None
         self.cfg = cfg
         self.logger = setup_logger(name + "_train", cfg.OUTPUT_DIR, local_rank) if logger is None else logger
         self.train_loader = train_loader

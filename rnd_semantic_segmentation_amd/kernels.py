@@ -718,6 +718,80 @@ def split_counts(counts, K):
     return counts[:K * K].reshape(K, K), counts[K * K:K * K + K], counts[K * K + K:K * K + 2 * K], counts[K * K + 2 * K:K * K + 3 * K]
 
 
+# ---- online self-training: mean teacher + ClassMix (csrc/classmix.hip) -----------------------------------------------------------------------
+def label_classes(labels, num_classes, out=None):
+    """mi_label_classes: labels [B,H,W] int64 -> present int32 [B] (the uint32 bit set, read as numpy uint32 by tests): bit c set iff class c in
+    [0, num_classes) occurs in image b; anything else - the ignore value included - sets nothing.  `out` is overwritten, whatever it held."""
+    _chk(labels, torch.int64, "labels")
+    if labels.dim() != 3:
+        raise _lib.MiError("labels must be [B,H,W], got %s" % (tuple(labels.shape),))
+    B, H, W = labels.shape
+    present = torch.empty(B, dtype=torch.int32, device=labels.device) if out is None else _chk(out, torch.int32, "present")
+    if present.numel() != B or present.device != labels.device:
+        raise _lib.MiError("present must hold %d words on %s" % (B, labels.device))
+    check(_lib.lib().mi_label_classes(_p(labels), _p(present), B, H, W, int(num_classes), _stream()), "mi_label_classes")
+    return present
+
+
+ClassMix = collections.namedtuple("ClassMix", "image label mask counts")
+
+
+def classmix(src_img, tgt_img, src_lab, teacher_low, present, priority, threshold, ignore_index=255, out_img=None, out_label=None, want_mask=False):
+    """mi_classmix: the pseudo-label and mixing pass without the probability map.  src_img / tgt_img [B,3,H,W] fp32, src_lab [B,H,W] int64,
+    teacher_low [B,h,w,K] fp32 NHWC (the teacher's low-resolution logits of tgt_img), present int32 [B] (label_classes of src_lab), priority uint8
+    [B,K] on the device (every row a permutation of 0..K-1).  Returns ClassMix(image [B,3,H,W] fp32 - written into out_img when given, which may be a
+    contiguous slice of a larger buffer, as out_label may -, label [B,H,W] int64, mask [B,H,W] uint8 or None, counts int64 [B,2] = pasted pixels, kept pseudo-labels
+    among the unpasted ones).  Pseudo-labels are bit-equal to upsample_predict_score([teacher_low[b]], [False], (H, W), 1, 1, threshold=...)'s."""
+    _chk(src_img, torch.float32, "src_img")
+    _chk(tgt_img, torch.float32, "tgt_img")
+    _chk(src_lab, torch.int64, "src_lab")
+    _chk(teacher_low, torch.float32, "teacher_low")
+    _chk(present, torch.int32, "present")
+    _chk(priority, torch.uint8, "priority")
+    dev = src_img.device
+    if src_img.dim() != 4 or src_img.shape[1] != 3 or tgt_img.shape != src_img.shape:
+        raise _lib.MiError("src_img and tgt_img must both be [B,3,H,W], got %s and %s" % (tuple(src_img.shape), tuple(tgt_img.shape)))
+    B, _, H, W = src_img.shape
+    if tuple(src_lab.shape) != (B, H, W):
+        raise _lib.MiError("src_lab must be [%d,%d,%d], got %s" % (B, H, W, tuple(src_lab.shape)))
+    if teacher_low.dim() != 4 or teacher_low.shape[0] != B:
+        raise _lib.MiError("teacher_low must be [%d,h,w,K], got %s" % (B, tuple(teacher_low.shape)))
+    _, h, w, K = teacher_low.shape
+    if present.numel() != B or tuple(priority.shape) != (B, K):
+        raise _lib.MiError("present must hold %d words and priority be [%d,%d], got %s and %s" % (B, B, K, tuple(present.shape), tuple(priority.shape)))
+    for t, n in ((tgt_img, "tgt_img"), (src_lab, "src_lab"), (teacher_low, "teacher_low"), (present, "present"), (priority, "priority")):
+        if t.device != dev:
+            raise _lib.MiError("%s lives on %s, src_img on %s" % (n, t.device, dev))
+    if out_img is None:
+        out_img = torch.empty_like(src_img)
+    else:
+        _chk(out_img, torch.float32, "out_img")
+        if out_img.shape != src_img.shape or out_img.device != dev:
+            raise _lib.MiError("out_img must be %s on %s, got %s on %s" % (tuple(src_img.shape), dev, tuple(out_img.shape), out_img.device))
+    if out_label is None:
+        out_label = torch.empty((B, H, W), dtype=torch.int64, device=dev)
+    else:
+        _chk(out_label, torch.int64, "out_label")
+        if tuple(out_label.shape) != (B, H, W) or out_label.device != dev:
+            raise _lib.MiError("out_label must be [%d,%d,%d] on %s, got %s on %s" % (B, H, W, dev, tuple(out_label.shape), out_label.device))
+    label = out_label
+    mask = torch.empty((B, H, W), dtype=torch.uint8, device=dev) if want_mask else None
+    counts = torch.empty((B, 2), dtype=torch.int64, device=dev)
+    check(_lib.lib().mi_classmix(_p(src_img), _p(tgt_img), _p(src_lab), _p(teacher_low), _p(present), _p(priority), float(threshold), int(ignore_index),
+                                 _p(out_img), _p(label), _p(mask), _p(counts), B, h, w, K, H, W, _stream()), "mi_classmix")
+    return ClassMix(out_img, label, mask, counts)
+
+
+def ema_update(teacher, student, hyper):
+    """mi_ema_update: teacher = a * teacher + (1 - a) * student in place over two flat fp32 tensors of equal length (any 4-byte alignment: views
+    into larger buffers are fine), a = hyper[0] read from the device by the kernel (hyper: a one-float device tensor)."""
+    for t, n in ((teacher, "teacher"), (student, "student"), (hyper, "hyper")):
+        _chk(t, torch.float32, n)
+    if teacher.dim() != 1 or teacher.shape != student.shape or hyper.numel() < 1:
+        raise _lib.MiError("ema_update: teacher and student must be flat and of one length (got %s and %s), hyper one float" % (tuple(teacher.shape), tuple(student.shape)))
+    check(_lib.lib().mi_ema_update(_p(teacher), _p(student), teacher.numel(), _p(hyper), _stream()), "mi_ema_update")
+
+
 POLYP_SUMS, POLYP_COUNTS = 24, 4            # MI_POLYP_SUMS, MI_POLYP_COUNTS
 PolypScore = collections.namedtuple("PolypScore", "hist sums counts prob pred")
 

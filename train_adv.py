@@ -1,6 +1,7 @@
 """Adversarial (FADA) training entry point: same flags as the reference's train_adv.py:62-105
 (`-cfg FILE [--local_rank N] KEY VAL ...`) plus `--model` (the reference hard-codes main("gald_fada", ...) at :105 although
-the DeepLab YAMLs need "aspp_fada"; `--model gald_fada -cfg configs/gald_adv.yaml` is the reference's default run).  Source and target loaders each carry BATCH_SIZE // 2 images (train_adv.py:29,39),
+the DeepLab YAMLs need "aspp_fada"; `--model gald_fada -cfg configs/gald_adv.yaml` is the reference's default run; `--model aspp_classmix
+-cfg configs/deeplabv2_r101_classmix.yaml` is the mean-teacher + ClassMix self-training of host/self_train.py, fed by the same two loaders).  Source and target loaders each carry BATCH_SIZE // 2 images (train_adv.py:29,39),
 the target set is repeated 9x (:17).  Under torchrun (WORLD_SIZE > 1) it runs data-parallel over RCCL."""
 import argparse
 import os
@@ -32,8 +33,12 @@ def main(name, cfg, local_rank):
     elif name == "gald_fada":                                # what the reference's train_adv.py:105 runs (HarDNet-68 + GCPA decoder + FADA)
         from rnd_semantic_segmentation_amd.host.gald_fada import GaldFada
         combo = GaldFada
+    elif name == "aspp_classmix":                            # not in the reference: online pseudo-labels from an EMA teacher + ClassMix
+        from rnd_semantic_segmentation_amd.host.self_train import AsppClassMix
+        combo = AsppClassMix
     else:
-        raise NotImplementedError("combo %r: 'aspp_fada' (DeepLabV2-ResNet + ASPP + FADA) and 'gald_fada' (GALD + FADA) are on the MI355X hot path" % name)
+        raise NotImplementedError("combo %r: 'aspp_fada' (DeepLabV2-ResNet + ASPP + FADA), 'gald_fada' (GALD + FADA) and 'aspp_classmix' (DeepLabV2 + mean "
+                                  "teacher + ClassMix) are on the MI355X hot path" % name)
     src_loader, tgt_loader = loader(src, build_collate_fn(cfg)), loader(tgt, None)
     run_trainer(combo(name, cfg, src_loader, tgt_loader, local_rank), src_loader, tgt_loader)
 
