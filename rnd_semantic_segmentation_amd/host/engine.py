@@ -945,26 +945,19 @@ class AsppLossFn(torch.autograd.Function):
     [B,K,H,W] logits.  The loss gradient w.r.t. the low-resolution logits is produced in the same pass."""
 
     @staticmethod
-    def forward(ctx, x, labels, eng, ignore_index, temperature, class_weights, label_smoothing, *params):
-        """class_weights ([K] fp32 on the device, or None) / label_smoothing: CrossEntropyLoss(weight=, label_smoothing=), K.upsample_ce."""
+    def forward(ctx, x, labels, eng, ignore_index, temperature, crit, *params):
+        """crit: the K.CeCriterion (class weights / label smoothing, OHEM or focal loss) that K.upsample_ce_head launches."""
         train = any(ctx.needs_input_grad)
         eng.prepare(train)
         low = eng.forward(x)
         eng.last_low = low                   # FADA derives its soft labels from these (aspp_fada.py:85-87)
-        if temperature != 1.0:               # criterion(pred.div(T), label): bilinear upsampling commutes with the scaling
-            loss_out, dlow = K.upsample_ce(low * (1.0 / temperature), labels, want_grad=train, grad_scale=1.0 / temperature,
-                                           ignore_index=ignore_index, class_weights=class_weights, label_smoothing=label_smoothing)
-        else:
-            loss_out, dlow = K.upsample_ce(low, labels, want_grad=train, ignore_index=ignore_index, class_weights=class_weights,
-                                           label_smoothing=label_smoothing)
+        inv_t = 1.0 / temperature            # criterion(pred.div(T), label): bilinear upsampling commutes with the scaling (mining and focal see it too)
+        loss_out, dlow = K.upsample_ce_head(low if temperature == 1.0 else low * inv_t, labels, crit, want_grad=train,
+                                            grad_scale=1.0 if temperature == 1.0 else inv_t, ignore_index=ignore_index)
         ctx.eng, ctx.x, ctx.dlow, ctx.fmask = eng, (x if train else None), dlow, eng.take_feature_mask()
-        ctx.loss_out = eng.last_loss_out = loss_out          # [loss, n_valid, out-of-range labels, -]: see K.check_labels
-        # every step's count goes into a persistent device counter (the kernel zeroes its own per call): the trainer reads it once per logging
-        # window, so a bad label in ANY step of the window raises, as torch's device assert would - also under HIP-graph replay (the add is captured)
-        bad = getattr(eng, "bad_labels", None)
-        if bad is None or bad.device != loss_out.device:
-            bad = eng.bad_labels = torch.zeros(1, dtype=torch.float32, device=loss_out.device)
-        bad.add_(loss_out[2:3])
+        # [loss, n_valid (weight sum with weights / focal, n_kept with OHEM), out-of-range labels, - (OHEM: its threshold)]: see K.check_labels
+        ctx.loss_out = eng.last_loss_out = loss_out
+        K.count_bad_labels(eng, loss_out)
         return loss_out[0].clone()
 
     @staticmethod
@@ -972,49 +965,7 @@ class AsppLossFn(torch.autograd.Function):
         dlow = ctx.dlow * gout
         dx = ctx.eng.backward(ctx.x, dlow, ctx.needs_input_grad[0], fmask=ctx.fmask)
         ctx.x = ctx.dlow = ctx.fmask = None
-        return (dx, None, None, None, None, None, None) + (None,) * (len(ctx.needs_input_grad) - 7)
-
-
-class AsppOhemLossFn(AsppLossFn):
-    """AsppLossFn with the cross-entropy averaged over the hard pixels only (OHEM: K.upsample_ce_ohem); the backward is AsppLossFn's."""
-
-    @staticmethod
-    def forward(ctx, x, labels, eng, ignore_index, temperature, thresh, min_kept, *params):
-        train = any(ctx.needs_input_grad)
-        eng.prepare(train)
-        low = eng.forward(x)
-        eng.last_low = low
-        inv_t = 1.0 / temperature             # criterion(pred.div(T), label): the mining sees the scaled logits too
-        loss_out, dlow, _ = K.upsample_ce_ohem(low if temperature == 1.0 else low * inv_t, labels, thresh, min_kept, want_grad=train,
-                                               grad_scale=1.0 if temperature == 1.0 else inv_t, ignore_index=ignore_index)
-        ctx.eng, ctx.x, ctx.dlow, ctx.fmask = eng, (x if train else None), dlow, eng.take_feature_mask()
-        ctx.loss_out = eng.last_loss_out = loss_out          # [loss, n_kept, out-of-range labels, t]
-        bad = getattr(eng, "bad_labels", None)
-        if bad is None or bad.device != loss_out.device:
-            bad = eng.bad_labels = torch.zeros(1, dtype=torch.float32, device=loss_out.device)
-        bad.add_(loss_out[2:3])
-        return loss_out[0].clone()
-
-
-class AsppFocalLossFn(AsppLossFn):
-    """AsppLossFn with the focal loss -w_y (1 - p_y)^gamma log p_y (K.upsample_ce_focal, gamma > 0); the backward is AsppLossFn's."""
-
-    @staticmethod
-    def forward(ctx, x, labels, eng, ignore_index, temperature, class_weights, gamma, *params):
-        train = any(ctx.needs_input_grad)
-        eng.prepare(train)
-        low = eng.forward(x)
-        eng.last_low = low
-        inv_t = 1.0 / temperature             # criterion(pred.div(T), label): the modulation sees the scaled logits
-        loss_out, dlow = K.upsample_ce_focal(low if temperature == 1.0 else low * inv_t, labels, gamma, want_grad=train,
-                                             grad_scale=1.0 if temperature == 1.0 else inv_t, ignore_index=ignore_index, class_weights=class_weights)
-        ctx.eng, ctx.x, ctx.dlow, ctx.fmask = eng, (x if train else None), dlow, eng.take_feature_mask()
-        ctx.loss_out = eng.last_loss_out = loss_out          # [loss, weight sum of the valid pixels, out-of-range labels, -]
-        bad = getattr(eng, "bad_labels", None)
-        if bad is None or bad.device != loss_out.device:
-            bad = eng.bad_labels = torch.zeros(1, dtype=torch.float32, device=loss_out.device)
-        bad.add_(loss_out[2:3])
-        return loss_out[0].clone()
+        return (dx, None, None, None, None, None) + (None,) * (len(ctx.needs_input_grad) - 6)
 
 
 class UpsampleFn(torch.autograd.Function):

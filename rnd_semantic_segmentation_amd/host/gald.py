@@ -86,27 +86,15 @@ class _GaldRun(Run):
             acc(b, gk.gbinary(gk.OP_MUL, gm, a.t), True)
         return self.node(o, back)
 
-    def ce_head(self, low, labels, ignore_index, inv_t=None, class_weights=None, label_smoothing=0.0, ohem=None, focal_gamma=0.0):
+    def ce_head(self, low, labels, ignore_index, crit, inv_t=None):
         """criterion(F.interpolate(low, size=labels.shape[-2:], mode="bilinear"), labels) (gcpa_cc2.py:78-81 + gald_trainer.py:76-79) fused: the
         full-resolution logits are never written; d loss / d low comes out of the same pass.  inv_t: criterion(out.div(T), labels) of
         gald_fada.py:85-88 as the same kernel on low * (1 / T) - bilinear upsampling is linear, so scaling before it is scaling after it.
-        class_weights / label_smoothing: the criterion's weight= and label_smoothing= (mi_upsample_ce_w).  ohem = (thresh, min_kept): the
-        cross-entropy over this head's hard pixels only (mi_upsample_ce_ohem), mined on the logits after the scaling.  focal_gamma > 0: the focal
-        loss -w_y (1 - p_y)^gamma log p_y (mi_upsample_ce_focal) on the logits after the scaling, with class_weights if given."""
+        crit: the K.CeCriterion - weight= / label_smoothing= (mi_upsample_ce_w), the cross-entropy over this head's hard pixels only
+        (mi_upsample_ce_ohem) or the focal loss (mi_upsample_ce_focal), the last two mining / modulating on the logits after the scaling."""
         src = low.t if inv_t is None else low.t * inv_t
-        if focal_gamma > 0.0:
-            loss_out, dlow = K.upsample_ce_focal(src, labels, focal_gamma, want_grad=self.rec, ignore_index=ignore_index, align_corners=False,
-                                                 class_weights=class_weights)
-            _count_bad_labels(self.net, loss_out)
-            return self.node(loss_out[0].clone(), lambda g: acc(low, dlow * (g if inv_t is None else g * inv_t), True))
-        if ohem is not None:
-            loss_out, dlow, _ = K.upsample_ce_ohem(src, labels, ohem[0], ohem[1], want_grad=self.rec, ignore_index=ignore_index, align_corners=False)
-            _count_bad_labels(self.net, loss_out)
-            return self.node(loss_out[0].clone(), lambda g: acc(low, dlow * (g if inv_t is None else g * inv_t), True))
-        loss_out, dlow = K.upsample_ce(src, labels, want_grad=self.rec, ignore_index=ignore_index, align_corners=False, class_weights=class_weights,
-                                       label_smoothing=label_smoothing)
-        _count_bad_labels(self.net, loss_out)
-        return self.node(loss_out[0].clone(), lambda g: acc(low, dlow * (g if inv_t is None else g * inv_t), True))
+        loss_out, dlow = K.upsample_ce_head(src, labels, crit, want_grad=self.rec, ignore_index=ignore_index, align_corners=False)
+        return self._loss_node(low, loss_out, dlow, inv_t)
 
     def gdl_head(self, low, labels, ignore_index, weight_type, inv_t=None):
         """GeneralizedDiceLoss(F.interpolate(low, size=labels.shape[-2:], mode="bilinear"), labels, weight_type=...) (utility.py:399-447 on the outputs
@@ -114,7 +102,12 @@ class _GaldRun(Run):
         or probabilities, and its gradient pass has run by the time the loss exists (the coefficients stay on the device)."""
         src = low.t if inv_t is None else low.t * inv_t
         loss_out, dlow, _ = K.upsample_gdl(src, labels, want_grad=self.rec, ignore_index=ignore_index, weight_type=weight_type, align_corners=False)
-        _count_bad_labels(self.net, loss_out)
+        return self._loss_node(low, loss_out, dlow, inv_t)
+
+    def _loss_node(self, low, loss_out, dlow, inv_t):
+        """The tail of the fused heads: the labels the kernel skipped go into the decoder's counter, and the loss becomes a node whose backward hands
+        `low` the gradient the head's own pass left in dlow (times inv_t where the head ran on low * inv_t)."""
+        K.count_bad_labels(self.net, loss_out)
         return self.node(loss_out[0].clone(), lambda g: acc(low, dlow * (g if inv_t is None else g * inv_t), True))
 
     def criss_cross(self, x, uq, uk, uv, gamma):
@@ -144,18 +137,8 @@ class _GaldRun(Run):
         return self.node(gk.gbn_apply(agg, gvec, zero, 0, add=x.t), back)
 
 
-def _count_bad_labels(holder, loss_out):
-    """Labels outside [0, K) that are not ignore_index are skipped AND counted by the cross-entropy kernels (loss_out[2]); torch's
-    CrossEntropyLoss (gald_trainer.py:107) would device-assert on them.  Every call's count goes into a persistent device counter on `holder`
-    (the decoder / the criterion module), read by GALDTrainer where it fetches the loss anyway."""
-    bad = holder.__dict__.get("bad_labels")
-    if bad is None or bad.device != loss_out.device:
-        bad = holder.__dict__["bad_labels"] = torch.zeros(1, dtype=torch.float32, device=loss_out.device)
-    bad.add_(loss_out[2:3])
-
-
 def take_bad_labels(*holders):
-    """Sum and reset the counters of `_count_bad_labels` (one host sync); under torch.distributed the sum is all-reduced first so that every rank
+    """Sum and reset the counters of `K.count_bad_labels` (one host sync); under torch.distributed the sum is all-reduced first so that every rank
     sees the same count and raises (or not) together."""
     bads = [h.__dict__.get("bad_labels") for h in holders]
     bads = [b for b in bads if b is not None]
@@ -387,23 +370,18 @@ class GCPADecoder(Engine):
             self.last_low = low2.t.detach().permute(0, 3, 1, 2)
             if out2 == "low":
                 return [low2]
-            return [run.ce_head(low2, self._ce_labels, self._ce_ignore, inv_t=out2, **self._ce_extra())]
+            return [run.ce_head(low2, self._ce_labels, self._ce_ignore, self._ce_crit, inv_t=out2)]
         lows = [run.tap("linear%d" % i, run.conv_bias(v, self._lin[i])) for i, v in ((5, top), (4, o4), (3, o3), (2, o2))]
         labels = self.__dict__.get("_ce_labels")
         if labels is not None:                                                                 # the trainer's fused path: four scalar losses
             if self.__dict__.get("_gdl_weight") is not None:
                 return [run.gdl_head(v, labels, self._ce_ignore, self._gdl_weight) for v in lows]
-            return [run.ce_head(v, labels, self._ce_ignore, **self._ce_extra()) for v in lows]
+            return [run.ce_head(v, labels, self._ce_ignore, self._ce_crit) for v in lows]
         size = (x.t.shape[1], x.t.shape[2])
         return [run.tap("out%d" % i, run.resize(v, None, False, size=size)) for i, v in enumerate(lows)]      # F.interpolate(..., size=x.size()[2:], mode="bilinear")
 
     def forward(self, x, feats):
         return super().forward(x, *feats)
-
-    def _ce_extra(self):
-        """The cross-entropy's weight= / label_smoothing= / mining / focal exponent of the running losses() / loss() call, as ce_head's keywords."""
-        return {"class_weights": self.__dict__.get("_ce_weights"), "label_smoothing": self.__dict__.get("_ce_smoothing") or 0.0,
-                "ohem": self.__dict__.get("_ce_ohem"), "focal_gamma": self.__dict__.get("_ce_focal") or 0.0}
 
     def losses(self, x, feats, labels, ignore_index=255, criterion="ce", weight_type="square", class_weights=None, label_smoothing=0.0, ohem=None,
                focal_gamma=0.0):
@@ -417,24 +395,21 @@ class GCPADecoder(Engine):
             raise ValueError("criterion must be 'ce', 'gdl' or 'ohem', got %r" % (criterion,))
         if (criterion == "ohem") != (ohem is not None):
             raise ValueError("criterion 'ohem' and ohem=(thresh, min_kept) go together, got criterion %r with ohem %r" % (criterion, ohem))
-        K.refuse_ohem_with_weights(ohem, class_weights, label_smoothing)
-        focal_gamma = K.refuse_focal_with(focal_gamma, ohem, label_smoothing)
-        if ohem is not None:
-            ohem = K.check_ohem(ohem)
+        crit = K.CeCriterion.of(class_weights, label_smoothing, ohem, focal_gamma)
+        if crit.ohem is not None:
             criterion = "ce"          # the cross-entropy head, with the mining entry
-        if criterion != "ce" and focal_gamma > 0.0:
+        if criterion != "ce" and crit.focal_gamma > 0.0:
             raise ValueError("focal_gamma belongs to criterion 'ce', got %r" % (criterion,))
-        if criterion != "ce" and (class_weights is not None or float(label_smoothing) != 0.0):
+        if criterion != "ce" and (class_weights is not None or crit.label_smoothing != 0.0):
             raise ValueError("class_weights / label_smoothing belong to criterion 'ce', got %r" % (criterion,))
         if criterion == "gdl" and weight_type not in K.GDL_WEIGHT_TYPES:
             raise ValueError("Check out the weight_type: %r (one of %s)" % (weight_type, ", ".join(K.GDL_WEIGHT_TYPES)))
-        self._ce_labels, self._ce_ignore = labels.long().contiguous(), int(ignore_index)
-        self._gdl_weight = weight_type if criterion == "gdl" else None
-        self._ce_weights, self._ce_smoothing, self._ce_ohem, self._ce_focal = class_weights, float(label_smoothing), ohem, focal_gamma
+        self._ce_labels, self._ce_ignore, self._ce_crit, self._gdl_weight = (labels.long().contiguous(), int(ignore_index), crit,
+                                                                            weight_type if criterion == "gdl" else None)
         try:
             return super().forward(x, *feats)
         finally:
-            self._ce_labels = self._gdl_weight = self._ce_weights = self._ce_smoothing = self._ce_ohem = self._ce_focal = None
+            self._ce_labels = self._ce_ignore = self._ce_crit = self._gdl_weight = None
 
     def loss(self, x, feats, label, ignore_index=255, temperature=1.0, class_weights=None, label_smoothing=0.0, ohem=None, focal_gamma=0.0):
         """criterion(self(x, feats)[-1].div(temperature), label) of gald_fada.py:80-88 fused: out2 alone (linear5/4/3 are not run and get no
@@ -442,16 +417,12 @@ class GCPADecoder(Engine):
         bilinear upsampling is linear, so dividing the low-resolution logits divides the upsampled ones.  Leaves the 1/4-resolution linear2 logits
         [B,K,h,w] fp32 (detached, before the division) in `self.last_low`.  ohem = (thresh, min_kept): the hard pixels only, as losses();
         focal_gamma > 0: the focal loss, as losses()."""
-        K.refuse_ohem_with_weights(ohem, class_weights, label_smoothing)
-        focal_gamma = K.refuse_focal_with(focal_gamma, ohem, label_smoothing)
-        self._ce_labels, self._ce_ignore, self._ce_focal = label.long().contiguous(), int(ignore_index), focal_gamma
-        self._out2 = 1.0 / float(temperature)
-        self._ce_weights, self._ce_smoothing = class_weights, float(label_smoothing)
-        self._ce_ohem = None if ohem is None else K.check_ohem(ohem)
+        crit = K.CeCriterion.of(class_weights, label_smoothing, ohem, focal_gamma)
+        self._ce_labels, self._ce_ignore, self._ce_crit, self._out2 = label.long().contiguous(), int(ignore_index), crit, 1.0 / float(temperature)
         try:
             return super().forward(x, *feats)
         finally:
-            self._ce_labels = self._out2 = self._ce_weights = self._ce_smoothing = self._ce_ohem = self._ce_focal = None
+            self._ce_labels = self._ce_ignore = self._ce_crit = self._out2 = None
 
     def low2(self, x, feats):
         """The 1/4-resolution linear2 logits [B,K,h,w] fp32 (NCHW-shaped view of NHWC memory) without a tape, in the module's mode: in train() the
@@ -545,7 +516,7 @@ class _NhwcCEFn(torch.autograd.Function):
             out, d = K.upsample_ce(nhwc, labels.contiguous(), want_grad=logits_nchw.requires_grad, ignore_index=ignore_index, align_corners=False,
                                    class_weights=weight, label_smoothing=label_smoothing)
         if holder is not None:
-            _count_bad_labels(holder, out)
+            K.count_bad_labels(holder, out)
         ctx.d = d
         return out[0].clone()
 

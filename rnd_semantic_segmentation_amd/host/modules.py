@@ -251,24 +251,11 @@ class ASPP_Classifier_V2(nn.Module):
         focal_gamma > 0: the focal loss -w_y (1 - p_y)^gamma log p_y (mi_upsample_ce_focal), with class_weights if given, on the logits after the division.
         feature_mask: resnet_feature_extractor.feature_mask() of x - d loss / d x is then masked by x's ReLU where the head computes it.
         Leaves the 1/8-resolution logits [B,K,h,w] (detached) in `self.last_low`."""
-        engine.K.refuse_ohem_with_weights(ohem, class_weights, label_smoothing)
-        focal_gamma = engine.K.refuse_focal_with(focal_gamma, ohem, label_smoothing)
+        crit = engine.K.CeCriterion.of(class_weights, label_smoothing, ohem, focal_gamma)
         _require_gpu(x, "ASPP_Classifier_V2")
         self.ensure_flat()
         self._engine.feature_mask_next = feature_mask          # taken by the loss node created below
-        if focal_gamma > 0.0:
-            out = engine.AsppFocalLossFn.apply(self._nhwc(x), label.long().contiguous(), self._engine, int(ignore_index), float(temperature),
-                                               class_weights, focal_gamma, *self._params())
-            self.last_low = self._engine.last_low.detach().permute(0, 3, 1, 2)
-            return out
-        if ohem is not None:
-            thresh, min_kept = engine.K.check_ohem(ohem)
-            out = engine.AsppOhemLossFn.apply(self._nhwc(x), label.long().contiguous(), self._engine, int(ignore_index), float(temperature),
-                                              thresh, min_kept, *self._params())
-            self.last_low = self._engine.last_low.detach().permute(0, 3, 1, 2)
-            return out
-        out = engine.AsppLossFn.apply(self._nhwc(x), label.long().contiguous(), self._engine, int(ignore_index), float(temperature),
-                                      class_weights, float(label_smoothing), *self._params())
+        out = engine.AsppLossFn.apply(self._nhwc(x), label.long().contiguous(), self._engine, int(ignore_index), float(temperature), crit, *self._params())
         self.last_low = self._engine.last_low.detach().permute(0, 3, 1, 2)
         return out
 

@@ -7,6 +7,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
+from ..kernels import FOCAL_GAMMA_MAX          # SOLVER.FOCAL_GAMMA's range in host/config.py is mi_upsample_ce_focal's
 from .metrics import setup_logger
 
 
@@ -76,9 +77,6 @@ def ohem_options(cfg, who):
     if isinstance(min_kept, bool) or not isinstance(min_kept, int) or min_kept < 1:
         raise ValueError("SOLVER.OHEM_MIN_KEPT {!r} must be an integer >= 1".format(min_kept))
     return float(thresh), int(min_kept)
-
-
-FOCAL_GAMMA_MAX = 8.0          # SOLVER.FOCAL_GAMMA's range in host/config.py, mi_upsample_ce_focal's too
 
 
 def focal_options(cfg, who):

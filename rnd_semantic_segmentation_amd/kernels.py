@@ -462,27 +462,37 @@ def softmax_ce_bwd(logits, labels, loss_out, grad_scale=1.0, ignore_index=255):
     return d
 
 
+def _head_buffers(low, target, workspace, tag, want_grad, target_dtype=torch.int64, target_name="labels"):
+    """What the fused upsample + loss wrappers share: low [B,h,w(,K)] fp32 and target [B,H,W] checked -> (dims = B, h, w(, K), H, W: the size
+    arguments of `workspace` and of the launch; the workspace; loss_out[4]; dlow or None)."""
+    _chk(low, torch.float32, "low")
+    _chk(target, target_dtype, target_name)
+    dims = tuple(low.shape) + tuple(target.shape[1:])
+    ws = _workspace(workspace(*dims), low.device, tag)
+    return dims, ws, torch.empty(4, dtype=torch.float32, device=low.device), (torch.empty_like(low) if want_grad else None)
+
+
+def _chk_class_weights(class_weights, low, who):
+    """class_weights: None, or one fp32 weight per class of low [B,h,w,K] on low's device."""
+    if class_weights is not None:
+        _chk(class_weights, torch.float32, "class_weights")
+        K = low.shape[-1]
+        if tuple(class_weights.shape) != (K,) or class_weights.device != low.device:
+            raise _lib.MiError("%s: class_weights must be [%d] on %s, got %s on %s" % (who, K, low.device, tuple(class_weights.shape), class_weights.device))
+
+
 def upsample_ce(low, labels, want_grad=True, grad_scale=1.0, ignore_index=255, align_corners=True, class_weights=None, label_smoothing=0.0):
     """Fused classifier-upsample + CrossEntropyLoss.  Returns (loss_out[4], dlow or None).  align_corners False: F.interpolate(size=) default.
     class_weights ([K] fp32 on low's device) / label_smoothing: CrossEntropyLoss(weight=, label_smoothing=) through mi_upsample_ce_w, where
     loss_out[1] is the weight sum of the valid pixels; with both at their defaults the call is mi_upsample_ce_ex as ever."""
-    _chk(low, torch.float32, "low")
-    _chk(labels, torch.int64, "labels")
-    B, h, w, K = low.shape
-    _, H, W = labels.shape
     L = _lib.lib()
-    ws = _workspace(L.mi_upsample_ce_workspace(B, h, w, K, H, W), low.device, "upce")
-    out = torch.empty(4, dtype=torch.float32, device=low.device)
-    dlow = torch.empty_like(low) if want_grad else None
+    dims, ws, out, dlow = _head_buffers(low, labels, L.mi_upsample_ce_workspace, "upce", want_grad)
     if class_weights is None and float(label_smoothing) == 0.0:
-        check(L.mi_upsample_ce_ex(_p(low), _p(labels), _p(out), _p(dlow), B, h, w, K, H, W, ignore_index, float(grad_scale), int(bool(align_corners)),
+        check(L.mi_upsample_ce_ex(_p(low), _p(labels), _p(out), _p(dlow), *dims, ignore_index, float(grad_scale), int(bool(align_corners)),
                                   _p(ws), ws.numel(), _stream()), "mi_upsample_ce")
         return out, dlow
-    if class_weights is not None:
-        _chk(class_weights, torch.float32, "class_weights")
-        if tuple(class_weights.shape) != (K,) or class_weights.device != low.device:
-            raise _lib.MiError("upsample_ce: class_weights must be [%d] on %s, got %s on %s" % (K, low.device, tuple(class_weights.shape), class_weights.device))
-    check(L.mi_upsample_ce_w(_p(low), _p(labels), _p(class_weights), _p(out), _p(dlow), B, h, w, K, H, W, ignore_index, float(label_smoothing),
+    _chk_class_weights(class_weights, low, "upsample_ce")
+    check(L.mi_upsample_ce_w(_p(low), _p(labels), _p(class_weights), _p(out), _p(dlow), *dims, ignore_index, float(label_smoothing),
                              float(grad_scale), int(bool(align_corners)), _p(ws), ws.numel(), _stream()), "mi_upsample_ce_w")
     return out, dlow
 
@@ -532,25 +542,28 @@ def refuse_focal_with(focal_gamma, ohem, label_smoothing):
     return g
 
 
+class CeCriterion(collections.namedtuple("CeCriterion", "class_weights label_smoothing ohem focal_gamma")):
+    """The criterion of a fused upsample + cross-entropy head as one checked value: CrossEntropyLoss's weight= ([K] fp32 on the device, or None) and
+    label_smoothing=, OHEM's (thresh, min_kept) or None, the focal exponent (0 = off).  Build it with `of`; upsample_ce_head launches it."""
+    __slots__ = ()
+
+    @classmethod
+    def of(cls, class_weights=None, label_smoothing=0.0, ohem=None, focal_gamma=0.0):
+        """The one place that applies the combination rules (in this order: with everything set, OHEM's refusal is the one reported)."""
+        refuse_ohem_with_weights(ohem, class_weights, label_smoothing)
+        focal_gamma = refuse_focal_with(focal_gamma, ohem, label_smoothing)
+        return cls(class_weights, float(label_smoothing), None if ohem is None else check_ohem(ohem), focal_gamma)
+
+
 def upsample_ce_focal(low, labels, gamma, want_grad=True, grad_scale=1.0, ignore_index=255, align_corners=True, class_weights=None):
     """Fused upsample + focal loss -w_y (1 - p_y)^gamma log p_y over the valid pixels, divided by their weight sum (mi_upsample_ce_focal).
     Returns (loss_out[4] = loss, S, bad labels, scratch; dlow or None).  class_weights: [K] fp32 on low's device, or None; gamma in [0, 8],
     0 = the weighted cross-entropy's launches and bits."""
-    _chk(low, torch.float32, "low")
-    _chk(labels, torch.int64, "labels")
-    gamma = check_focal_gamma(gamma)
-    B, h, w, K = low.shape
-    _, H, W = labels.shape
-    if class_weights is not None:
-        _chk(class_weights, torch.float32, "class_weights")
-        if tuple(class_weights.shape) != (K,) or class_weights.device != low.device:
-            raise _lib.MiError("upsample_ce_focal: class_weights must be [%d] on %s, got %s on %s" % (K, low.device, tuple(class_weights.shape),
-                                                                                                      class_weights.device))
     L = _lib.lib()
-    ws = _workspace(L.mi_upsample_ce_workspace(B, h, w, K, H, W), low.device, "upce")
-    out = torch.empty(4, dtype=torch.float32, device=low.device)
-    dlow = torch.empty_like(low) if want_grad else None
-    check(L.mi_upsample_ce_focal(_p(low), _p(labels), _p(class_weights), _p(out), _p(dlow), B, h, w, K, H, W, ignore_index, gamma, float(grad_scale),
+    dims, ws, out, dlow = _head_buffers(low, labels, L.mi_upsample_ce_workspace, "upce", want_grad)
+    gamma = check_focal_gamma(gamma)
+    _chk_class_weights(class_weights, low, "upsample_ce_focal")
+    check(L.mi_upsample_ce_focal(_p(low), _p(labels), _p(class_weights), _p(out), _p(dlow), *dims, ignore_index, gamma, float(grad_scale),
                                  int(bool(align_corners)), _p(ws), ws.numel(), _stream()), "mi_upsample_ce_focal")
     return out, dlow
 
@@ -559,19 +572,24 @@ def upsample_ce_ohem(low, labels, thresh, min_kept, want_grad=True, grad_scale=1
     """Fused upsample + cross-entropy over the hard pixels only (OHEM, mi_upsample_ce_ohem): kept = valid and softmax[label] <= t,
     t = max(thresh, min(min_kept, n valid)-th smallest softmax[label]).  Returns (loss_out[4] = loss, n_kept, bad labels, t; dlow or None;
     prob [B,H,W] = softmax[label] of every pixel, 2.0 where it is not valid, or None).  Nothing is read back between its launches."""
-    _chk(low, torch.float32, "low")
-    _chk(labels, torch.int64, "labels")
-    thresh, min_kept = check_ohem((thresh, min_kept))
-    B, h, w, K = low.shape
-    _, H, W = labels.shape
     L = _lib.lib()
-    ws = _workspace(L.mi_upsample_ce_ohem_workspace(B, h, w, K, H, W), low.device, "upohem")
-    out = torch.empty(4, dtype=torch.float32, device=low.device)
-    dlow = torch.empty_like(low) if want_grad else None
-    prob = torch.empty(B, H, W, dtype=torch.float32, device=low.device) if want_prob else None
-    check(L.mi_upsample_ce_ohem(_p(low), _p(labels), _p(out), _p(dlow), _p(prob), B, h, w, K, H, W, ignore_index, thresh, min_kept, float(grad_scale),
+    dims, ws, out, dlow = _head_buffers(low, labels, L.mi_upsample_ce_ohem_workspace, "upohem", want_grad)
+    thresh, min_kept = check_ohem((thresh, min_kept))
+    prob = torch.empty(labels.shape, dtype=torch.float32, device=low.device) if want_prob else None
+    check(L.mi_upsample_ce_ohem(_p(low), _p(labels), _p(out), _p(dlow), _p(prob), *dims, ignore_index, thresh, min_kept, float(grad_scale),
                                 int(bool(align_corners)), _p(ws), ws.numel(), _stream()), "mi_upsample_ce_ohem")
     return out, dlow, prob
+
+
+def upsample_ce_head(low, labels, crit, want_grad=True, grad_scale=1.0, ignore_index=255, align_corners=True):
+    """The fused upsample + cross-entropy head of a CeCriterion: focal_gamma > 0 -> mi_upsample_ce_focal, OHEM -> mi_upsample_ce_ohem, weights or
+    smoothing -> mi_upsample_ce_w, else mi_upsample_ce_ex.  Returns (loss_out[4], dlow or None), as the wrapper it calls."""
+    kw = {"want_grad": want_grad, "grad_scale": grad_scale, "ignore_index": ignore_index, "align_corners": align_corners}
+    if crit.focal_gamma > 0.0:
+        return upsample_ce_focal(low, labels, crit.focal_gamma, class_weights=crit.class_weights, **kw)
+    if crit.ohem is not None:
+        return upsample_ce_ohem(low, labels, *crit.ohem, **kw)[:2]
+    return upsample_ce(low, labels, class_weights=crit.class_weights, label_smoothing=crit.label_smoothing, **kw)
 
 
 GDL_WEIGHT_TYPES = {"square": 0, "identity": 1, "sqrt": 2}          # MI_GDL_* of include/mi355seg.h
@@ -580,18 +598,12 @@ GDL_WEIGHT_TYPES = {"square": 0, "identity": 1, "sqrt": 2}          # MI_GDL_* o
 def upsample_gdl(low, labels, want_grad=True, grad_scale=1.0, ignore_index=255, weight_type="square", eps=1e-5, align_corners=True, want_sums=False):
     """Fused upsample + GeneralizedDiceLoss (reference utility.py:399-447, label form).  Returns (loss_out[4] = loss, valid pixels, bad labels, 0;
     dlow or None; sums[3K] = T, I, P2 or None).  Nothing is read back between its launches."""
-    _chk(low, torch.float32, "low")
-    _chk(labels, torch.int64, "labels")
+    L = _lib.lib()
+    dims, ws, out, dlow = _head_buffers(low, labels, L.mi_upsample_gdl_workspace, "upgdl", want_grad)
     if weight_type not in GDL_WEIGHT_TYPES:
         raise ValueError("Check out the weight_type: %r (one of %s)" % (weight_type, ", ".join(GDL_WEIGHT_TYPES)))
-    B, h, w, K = low.shape
-    _, H, W = labels.shape
-    L = _lib.lib()
-    ws = _workspace(L.mi_upsample_gdl_workspace(B, h, w, K, H, W), low.device, "upgdl")
-    out = torch.empty(4, dtype=torch.float32, device=low.device)
-    dlow = torch.empty_like(low) if want_grad else None
-    sums = torch.empty(3 * K, dtype=torch.float32, device=low.device) if want_sums else None
-    check(L.mi_upsample_gdl(_p(low), _p(labels), _p(out), _p(dlow), _p(sums), B, h, w, K, H, W, ignore_index, GDL_WEIGHT_TYPES[weight_type], float(eps),
+    sums = torch.empty(3 * low.shape[-1], dtype=torch.float32, device=low.device) if want_sums else None
+    check(L.mi_upsample_gdl(_p(low), _p(labels), _p(out), _p(dlow), _p(sums), *dims, ignore_index, GDL_WEIGHT_TYPES[weight_type], float(eps),
                             float(grad_scale), int(bool(align_corners)), _p(ws), ws.numel(), _stream()), "mi_upsample_gdl")
     return out, dlow, sums
 
@@ -600,23 +612,28 @@ def upsample_tversky_bce(low, mask, want_grad=True, grad_scale=1.0, alpha=0.7, e
     """Fused upsample + CompoundLoss([TverskyLoss(alpha, eps), BinaryCrossEntropyLoss()], weights) (reference attn/loss.py) for one-channel logits:
     low [B,h,w] fp32, mask [B,H,W] fp32 in [0, 1] (H >= h, W >= w; the same size: no upsample).  Returns (loss_out[4] = loss, tversky, bce, 0;
     dlow [B,h,w] or None; sums[3] = TP, FN, FP or None).  Nothing is read back between its launches."""
-    _chk(low, torch.float32, "low")
-    _chk(mask, torch.float32, "mask")
     if low.dim() != 3 or mask.dim() != 3 or mask.shape[0] != low.shape[0] or mask.device != low.device:
         raise _lib.MiError("upsample_tversky_bce: low [B,h,w] and mask [B,H,W] on one device, got %s on %s and %s on %s"
                            % (tuple(low.shape), low.device, tuple(mask.shape), mask.device))
     if len(weights) != 2:
         raise ValueError("upsample_tversky_bce: weights = (tversky, bce), got %r" % (weights,))
-    B, h, w = low.shape
-    _, H, W = mask.shape
     L = _lib.lib()
-    ws = _workspace(L.mi_upsample_tversky_bce_workspace(B, h, w, H, W), low.device, "uptvb")
-    out = torch.empty(4, dtype=torch.float32, device=low.device)
-    dlow = torch.empty_like(low) if want_grad else None
+    dims, ws, out, dlow = _head_buffers(low, mask, L.mi_upsample_tversky_bce_workspace, "uptvb", want_grad, torch.float32, "mask")
     sums = torch.empty(3, dtype=torch.float32, device=low.device) if want_sums else None
-    check(L.mi_upsample_tversky_bce(_p(low), _p(mask), _p(out), _p(dlow), _p(sums), B, h, w, H, W, float(alpha), float(eps), float(weights[0]),
+    check(L.mi_upsample_tversky_bce(_p(low), _p(mask), _p(out), _p(dlow), _p(sums), *dims, float(alpha), float(eps), float(weights[0]),
                                     float(weights[1]), float(grad_scale), int(bool(align_corners)), _p(ws), ws.numel(), _stream()), "mi_upsample_tversky_bce")
     return out, dlow, sums
+
+
+def count_bad_labels(holder, loss_out):
+    """Labels outside [0, K) that are not ignore_index are skipped AND counted by the loss kernels (loss_out[2]); torch's CrossEntropyLoss would
+    device-assert on them.  Every call's count goes into a persistent device counter `holder.bad_labels` (the kernel zeroes its own per call), which
+    the trainer reads once per logging window where it fetches the loss anyway: a bad label in ANY step of the window raises.  The add is issued on
+    every call, so it is captured under HIP-graph replay too."""
+    bad = holder.__dict__.get("bad_labels")
+    if bad is None or bad.device != loss_out.device:
+        bad = holder.__dict__["bad_labels"] = torch.zeros(1, dtype=torch.float32, device=loss_out.device)
+    bad.add_(loss_out[2:3])
 
 
 def check_labels(loss_out, num_classes, what="labels"):
