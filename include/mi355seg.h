@@ -299,6 +299,32 @@ int mi_upsample_gdl(const float* low, const int64_t* labels, float* loss_out /*[
                     int B, int h, int w, int K, int H, int W, int ignore_index, int weight_type, float eps, float grad_scale,
                     int align_corners, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- fused upsample + Lovasz-Softmax (Berman, Triki, Blaschko, CVPR 2018; classes = 'present', over the whole batch) on a 1024-cell order ----
+ * Operands and restrictions as mi_upsample_ce_ex; bins must be 1024 and B H W < 2^31.  With p = softmax(bilinear(low)) and valid = label is not
+ * ignore_index and lies in [0, K) (other labels are left out and counted), for every class c over the valid pixels i:
+ *   e_i = 1 - p_i[c] where y_i == c (foreground), p_i[c] elsewhere (background);  cell_i = min(bins - 1, floor(e_i * bins))
+ *   F[b], N[b] = foreground / background pixels in cell b;  G = sum_b F[b];  a_b, n_b = foreground / background pixels in strictly higher cells
+ *   g_fg[b] = 1 / (G + n_b),  g_bg[b] = (G - a_b - F[b]) / ((G + n_b) (G + n_b + N[b]))
+ *   loss_c = sum_i e_i g[cell_i];  loss = mean of loss_c over the classes with G > 0 (none, i.e. no valid pixel: nan, as the other heads)
+ * This is the Lovasz gradient of the order "descending cell; inside a cell the foreground pixels first, then the background pixels with their Jaccard
+ * increments averaged" - a subgradient of the Lovasz extension, so per class 0 <= exact (sorted) loss - loss_c <= 1 / bins.
+ *   d loss / d z_k = p_k (s_k - sum_c s_c p_c),  s_c = -g_fg[cell] / C (foreground), +g_bg[cell] / C (background), 0 for a class that is not present,
+ * C = number of present classes; the order is a constant of the backward pass.  d loss / d low = transposed bilinear of that, times grad_scale.
+ * loss_out: [0] = loss, [1] = valid pixels, [2] = out-of-range labels, [3] = C.  dlow may be NULL (loss only, same loss bits); an entry of dlow
+ * that no valid pixel touches is exactly 0.  hist (may be NULL) [K][bins][2] receives F and N, exact integers.  err (may be NULL; for tests and
+ * diagnosis, never in training) [B][K][H][W] fp32 receives the kernel's own e of every (pixel, class), 2.0 where the pixel is not valid; the
+ * foreground error is (sum of the other classes' exponentials) / (sum of all), not 1 - p.  Every pass forms e with the same device function, so
+ * the cells the gradient looks up are the cells that were counted, and they are floor(err * 1024) exactly.
+ * Launches: one memset, a counting pass (integer atomics only), a scan with one workgroup per class (coefficients formed in fp64), the loss /
+ * x-gradient pass, a one-workgroup loss finalize, with dlow the y-gradient pass, with hist one device copy.  No floating-point atomic, every sum
+ * in a fixed order: two calls give the same bits.  Nothing is read back in between, so the call can be captured in a HIP graph; a replay reads
+ * low and labels anew.  Refused before any launch: what mi_upsample_ce_ex refuses, bins != 1024, B H W >= 2^31, a grad_scale that is not finite,
+ * a short workspace (MI_ENOMEM). */
+size_t mi_upsample_lovasz_workspace(int B, int h, int w, int K, int H, int W);
+int mi_upsample_lovasz(const float* low, const int64_t* labels, float* loss_out /*[4]*/, float* dlow, uint32_t* hist /*[K][bins][2], may be NULL*/,
+                       float* err /*[B][K][H][W], may be NULL*/, int B, int h, int w, int K, int H, int W, int ignore_index, int bins,
+                       float grad_scale, int align_corners, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- fused upsample + Tversky + binary cross-entropy (TverskyLoss / BinaryCrossEntropyLoss / CompoundLoss, reference
  * core/models/classifiers/attn/loss.py:7-27, 42-74) for one-channel logits ----
  * low [B][h][w] fp32 logits, mask [B][H][W] fp32 in [0, 1] (may be soft), H >= h, W >= w, either bilinear convention; h == H, w == W is the identity.

@@ -54,6 +54,8 @@ SIGNATURES = {
     "mi_upsample_ce_ohem": (I, [P, P, P, P, P] + [I] * 7 + [F, L, F, I, P, Z, P]),
     "mi_upsample_gdl_workspace": (Z, [I] * 6),
     "mi_upsample_gdl": (I, [P, P, P, P, P] + [I] * 8 + [F, F, I, P, Z, P]),
+    "mi_upsample_lovasz_workspace": (Z, [I] * 6),
+    "mi_upsample_lovasz": (I, [P, P, P, P, P, P] + [I] * 8 + [F, I, P, Z, P]),
     "mi_upsample_tversky_bce_workspace": (Z, [I] * 5),
     "mi_upsample_tversky_bce": (I, [P, P, P, P, P] + [I] * 5 + [F] * 5 + [I, P, Z, P]),
     "mi_upsample_softmax": (I, [P, P, P] + [I] * 6 + [P]),

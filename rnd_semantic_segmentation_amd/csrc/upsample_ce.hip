@@ -839,42 +839,6 @@ inline OhemLayout ohem_layout(int B, int w, int K, int H, int W) {
     return l;
 }
 
-// ------------------------------------------------------------------------------------------------ launch helpers of the fused heads
-// What every fused head requires of its shapes; `who` names the entry that was called, ktext what its K may be.
-int head_check(const char* who, int B, int h, int w, int K, int H, int W, const char* ktext = " (K <= 32)") {
-    MI_REQUIRE(B > 0 && h > 0 && w > 0 && H > 0 && W > 0 && K > 0 && K <= KMAX, "%s: bad dimension%s", who, ktext);
-    MI_REQUIRE(H >= h && W >= w, "%s: only upsampling (H >= h, W >= w) is supported", who);
-    MI_REQUIRE(H <= 65535 && B <= 65535, "%s: grid dimension overflow", who);
-    return MI_OK;
-}
-
-struct HeadPlan {          // the two axes and the x-tile grid
-    Axis ay, ax;
-    int jt_cols, tiles, npx_max;
-};
-HeadPlan head_plan(int h, int w, int H, int W, int align_corners) {
-    HeadPlan p;
-    p.ay = make_axis(h, H, align_corners);
-    p.ax = make_axis(w, W, align_corners);
-    p.jt_cols = pick_jt(w, W);
-    p.tiles = (w + p.jt_cols - 1) / p.jt_cols;
-    p.npx_max = pass1_npx_max(p.ax, p.jt_cols);
-    return p;
-}
-
-// Launch of an x-tile kernel.  Its LDS varies with the upsample factor: the maximum is allowed once per (kernel, device).
-template <auto Kern, class... Args>
-void launch_xtile(const HeadPlan& p, int H, int B, size_t lds, hipStream_t st, Args... args) {
-    static std::atomic<uint64_t> lds_set;
-    mi_allow_dynamic_lds((const void*)Kern, MI_LDS_MAX, lds_set);
-    hipLaunchKernelGGL(Kern, dim3(p.tiles, H, B), dim3(256), lds, st, args...);
-}
-
-int launch_failed(const char* who, const char* step) {
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? MI_OK : mi_set_error(MI_EHIP, "%s %s: %s", who, step, hipGetErrorString(e));
-}
-
 }  // namespace
 
 extern "C" int mi_upsample_ac_fwd(const float* low, float* up, int B, int h, int w, int K, int H, int W, void* stream) {

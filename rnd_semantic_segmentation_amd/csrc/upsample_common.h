@@ -1,4 +1,4 @@
-// What the bilinear-upsample sources (upsample_ce.hip, upsample_infer.hip, fada.hip, classmix.hip) share: the source-index arithmetic, the fixed-order reductions,
+// What the bilinear-upsample sources (upsample_ce.hip, upsample_lovasz.hip, upsample_infer.hip, fada.hip, classmix.hip) share: the source-index arithmetic, the fixed-order reductions,
 // the per-pixel softmax core, the per-pixel probabilities and prediction of the inference tails, the prologue / pixel / epilogue helpers of the two kernel skeletons of the fused upsample + loss heads (x-tile and row-walk), the LDS layout of the first,
 // and the launch planning.  Everything is file-local to the source that includes it (anonymous namespace): kernel names do not change.
 #pragma once
@@ -51,6 +51,14 @@ inline Axis make_axis(int n_in, int n_out, int align_corners = 1) {
     a.off = align_corners ? 0.f : 0.5f;
     a.scale = align_corners ? ((n_out > 1) ? (float)(n_in - 1) / (float)(n_out - 1) : 0.f) : (float)n_in / (float)n_out;      // (a size was given: in / out)
     return a;
+}
+
+// (1 - l) a + l b from two rounded products, whatever the compiler would contract at the call site: what two kernels that have to agree bit for bit
+// (the passes of the Lovasz head) interpolate with.
+__device__ __forceinline__ float lerp_rounded(float l, float a, float b) {
+#pragma clang fp contract(off)
+    const float pa = (1.f - l) * a, pb = l * b;
+    return pa + pb;
 }
 
 __device__ __forceinline__ float lerp2(float v00, float v01, float v10, float v11, float lx, float ly) {
@@ -272,6 +280,8 @@ struct TileLds {
 };
 
 // tile_stage: pstart[q] = first pixel (relative to xa) whose x0 >= j0 - 1 + q, and the touched source columns (from cbase) interpolated along y into vrow.
+// PINNED: the interpolation is lerp_rounded (the same bits as rowwalk_stage<true>).
+template <bool PINNED = false>
 __device__ __forceinline__ void tile_stage(const float* __restrict__ low, int K, const Axis& ay, const Axis& ax, int b, int y, int j0, int j1, int xa,
                                            int* pstart, float* vrow, int& cbase) {
     const int h = ay.n_in, w = ax.n_in;
@@ -285,7 +295,10 @@ __device__ __forceinline__ void tile_stage(const float* __restrict__ low, int K,
     if (threadIdx.x < j1 - j0 + 2) pstart[threadIdx.x] = ax.first_with_i0_ge(j0 - 1 + (int)threadIdx.x) - xa;
     for (int e = threadIdx.x; e < ncol * K; e += 256) {
         const long o = (long)cbase * K + e;
-        vrow[e] = (1.f - ly) * row0[o] + ly * row1[o];
+        if constexpr (PINNED)
+            vrow[e] = lerp_rounded(ly, row0[o], row1[o]);
+        else
+            vrow[e] = (1.f - ly) * row0[o] + ly * row1[o];
     }
 }
 
@@ -323,6 +336,7 @@ struct XPixel {
 };
 
 // The prologue: carves the LDS, decodes the grid and stages (tile_stage).  The caller's __syncthreads() publishes the staging.
+template <bool PINNED = false>
 __device__ __forceinline__ XTile xtile_begin(const TileLds& L, const float* __restrict__ low, int K, const Axis& ay, const Axis& ax, int npx_max,
                                              int jt_cols) {
     extern __shared__ __attribute__((aligned(16))) float sh[];
@@ -339,7 +353,7 @@ __device__ __forceinline__ XTile xtile_begin(const TileLds& L, const float* __re
     t.xa = ax.first_with_i0_ge(t.j0 - 1);                                   // pixels with x0 in [j0-1, j1-1]
     t.npx = min(ax.first_with_i0_ge(t.j1) - t.xa, npx_max);
     t.row = (long)b * ay.n_out + y;
-    tile_stage(low, K, ay, ax, b, y, t.j0, t.j1, t.xa, t.pstart, t.vrow, t.cbase);
+    tile_stage<PINNED>(low, K, ay, ax, b, y, t.j0, t.j1, t.xa, t.pstart, t.vrow, t.cbase);
     return t;
 }
 
@@ -400,13 +414,19 @@ __device__ __forceinline__ RowWalk rowwalk_begin(const Axis& ay, const Axis& ax,
     return r;
 }
 
+template <bool PINNED = false>
 __device__ __forceinline__ void rowwalk_stage(const RowWalk& r, const float* __restrict__ low, float* vrow, int K, const Axis& ay, int w, int y) {
     int y0, y1;
     float ly;
     ay.src(y, y0, y1, ly);
     const float* row0 = low + (((long)r.b * ay.n_in + y0) * w + r.cbase) * K;
     const float* row1 = low + (((long)r.b * ay.n_in + y1) * w + r.cbase) * K;
-    for (int e = threadIdx.x; e < r.ncol * K; e += 256) vrow[e] = (1.f - ly) * row0[e] + ly * row1[e];
+    for (int e = threadIdx.x; e < r.ncol * K; e += 256) {
+        if constexpr (PINNED)
+            vrow[e] = lerp_rounded(ly, row0[e], row1[e]);
+        else
+            vrow[e] = (1.f - ly) * row0[e] + ly * row1[e];
+    }
     __syncthreads();
 }
 
@@ -479,6 +499,42 @@ inline void with_kt(int K, F&& f) {
         f(std::integral_constant<int, 19>{});
     else
         f(std::integral_constant<int, 0>{});
+}
+
+// ------------------------------------------------------------------------------------------------ launch helpers of the fused heads (upsample_ce.hip, upsample_lovasz.hip)
+// What every fused head requires of its shapes; `who` names the entry that was called, ktext what its K may be.
+inline int head_check(const char* who, int B, int h, int w, int K, int H, int W, const char* ktext = " (K <= 32)") {
+    MI_REQUIRE(B > 0 && h > 0 && w > 0 && H > 0 && W > 0 && K > 0 && K <= KMAX, "%s: bad dimension%s", who, ktext);
+    MI_REQUIRE(H >= h && W >= w, "%s: only upsampling (H >= h, W >= w) is supported", who);
+    MI_REQUIRE(H <= 65535 && B <= 65535, "%s: grid dimension overflow", who);
+    return MI_OK;
+}
+
+struct HeadPlan {          // the two axes and the x-tile grid
+    Axis ay, ax;
+    int jt_cols, tiles, npx_max;
+};
+inline HeadPlan head_plan(int h, int w, int H, int W, int align_corners) {
+    HeadPlan p;
+    p.ay = make_axis(h, H, align_corners);
+    p.ax = make_axis(w, W, align_corners);
+    p.jt_cols = pick_jt(w, W);
+    p.tiles = (w + p.jt_cols - 1) / p.jt_cols;
+    p.npx_max = pass1_npx_max(p.ax, p.jt_cols);
+    return p;
+}
+
+// Launch of an x-tile kernel.  Its LDS varies with the upsample factor: the maximum is allowed once per (kernel, device).
+template <auto Kern, class... Args>
+void launch_xtile(const HeadPlan& p, int H, int B, size_t lds, hipStream_t st, Args... args) {
+    static std::atomic<uint64_t> lds_set;
+    mi_allow_dynamic_lds((const void*)Kern, MI_LDS_MAX, lds_set);
+    hipLaunchKernelGGL(Kern, dim3(p.tiles, H, B), dim3(256), lds, st, args...);
+}
+
+inline int launch_failed(const char* who, const char* step) {
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? MI_OK : mi_set_error(MI_EHIP, "%s %s: %s", who, step, hipGetErrorString(e));
 }
 
 }  // namespace

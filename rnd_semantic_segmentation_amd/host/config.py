@@ -15,8 +15,8 @@ import yaml
 _VALID = (tuple, list, str, int, float, bool, type(None))
 _RANGES = {"TEST.PSEUDO_THRESHOLD": (0.0, 1.0), "TEST.PSEUDO_PORTION": (0.0, 1.0), "SOLVER.TVERSKY_ALPHA": (0.0, 1.0), "SOLVER.LABEL_SMOOTHING": (0.0, 1.0),
            "SOLVER.OHEM_THRESH": (0.0, 1.0), "SOLVER.OHEM_MIN_KEPT": (1, float("inf")), "SOLVER.FOCAL_GAMMA": (0.0, 8.0),
-           "SOLVER.EMA_ALPHA": (0.0, 1.0), "SOLVER.MIX_THRESHOLD": (0.0, 1.0)}      # closed intervals a merged value has to lie in
-_CHOICES = {"SOLVER.LOSS": ("ce", "gdl", "tversky", "ohem"), "SOLVER.GDL_WEIGHT": ("square", "identity", "sqrt")}      # the only values a merged key may take
+           "SOLVER.EMA_ALPHA": (0.0, 1.0), "SOLVER.MIX_THRESHOLD": (0.0, 1.0), "SOLVER.LOVASZ_CE": (0.0, float("inf"))}      # closed intervals a merged value has to lie in
+_CHOICES = {"SOLVER.LOSS": ("ce", "gdl", "tversky", "ohem", "lovasz"), "SOLVER.GDL_WEIGHT": ("square", "identity", "sqrt")}      # the only values a merged key may take
 
 
 class CfgNode(dict):
@@ -190,6 +190,11 @@ def default_tree():
             # focal loss -w_y (1 - p_y)^FOCAL_GAMMA log p_y inside the fused heads (mi_upsample_ce_focal): OHEM's smooth counterpart.  It composes with
             # CLASS_WEIGHTS; any other LOSS ("ohem" included), LABEL_SMOOTHING > 0 and PraNetTrainer refuse it (plugin.focal_options)
             "FOCAL_GAMMA": 0.0,
+            # LOSS "lovasz" (ASPPTrainer, GALDTrainer) = Lovasz-Softmax (Berman et al., CVPR 2018; classes present, over the batch), the surrogate of the
+            # Jaccard index itself, on a 1024-cell order inside the fused heads (mi_upsample_lovasz), plus LOVASZ_CE (>= 0) times the plain cross-entropy of
+            # the same head: 1.0 is the sum people train with, 0 the Lovasz term alone (it trains poorly from scratch).  LOVASZ_CE changed under any other
+            # LOSS is refused (plugin.lovasz_options); "lovasz" refuses CLASS_WEIGHTS, LABEL_SMOOTHING, FOCAL_GAMMA and the OHEM keys.
+            "LOVASZ_CE": 1.0,
             # not in the reference either: the online form of pseudo-labelling + self-distillation, AsppClassMix (host/self_train.py; train_adv.py --model
             # aspp_classmix): EMA_ALPHA in [0, 1] is the ceiling of the mean teacher's decay, a = min(1 - 1 / (it + 1), EMA_ALPHA) in iteration it (from 0:
             # the first update copies the student); MIX_THRESHOLD in [0, 1] keeps a target pixel's pseudo-label where the teacher's winning probability

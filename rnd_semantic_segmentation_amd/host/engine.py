@@ -946,14 +946,16 @@ class AsppLossFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, labels, eng, ignore_index, temperature, crit, *params):
-        """crit: the K.CeCriterion (class weights / label smoothing, OHEM or focal loss) that K.upsample_ce_head launches."""
+        """crit: the K.CeCriterion (class weights / label smoothing, OHEM or focal loss) that K.upsample_ce_head launches, or the K.LovaszCriterion
+        (Lovasz-Softmax + weighted cross-entropy) that K.upsample_lovasz_head launches."""
         train = any(ctx.needs_input_grad)
+        head = K.upsample_lovasz_head if isinstance(crit, K.LovaszCriterion) else K.upsample_ce_head
         eng.prepare(train)
         low = eng.forward(x)
         eng.last_low = low                   # FADA derives its soft labels from these (aspp_fada.py:85-87)
         inv_t = 1.0 / temperature            # criterion(pred.div(T), label): bilinear upsampling commutes with the scaling (mining and focal see it too)
-        loss_out, dlow = K.upsample_ce_head(low if temperature == 1.0 else low * inv_t, labels, crit, want_grad=train,
-                                            grad_scale=1.0 if temperature == 1.0 else inv_t, ignore_index=ignore_index)
+        loss_out, dlow = head(low if temperature == 1.0 else low * inv_t, labels, crit, want_grad=train,
+                              grad_scale=1.0 if temperature == 1.0 else inv_t, ignore_index=ignore_index)
         ctx.eng, ctx.x, ctx.dlow, ctx.fmask = eng, (x if train else None), dlow, eng.take_feature_mask()
         # [loss, n_valid (weight sum with weights / focal, n_kept with OHEM), out-of-range labels, - (OHEM: its threshold)]: see K.check_labels
         ctx.loss_out = eng.last_loss_out = loss_out

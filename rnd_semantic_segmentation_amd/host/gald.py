@@ -104,6 +104,14 @@ class _GaldRun(Run):
         loss_out, dlow, _ = K.upsample_gdl(src, labels, want_grad=self.rec, ignore_index=ignore_index, weight_type=weight_type, align_corners=False)
         return self._loss_node(low, loss_out, dlow, inv_t)
 
+    def lovasz_head(self, low, labels, ignore_index, crit, inv_t=None):
+        """Lovasz-Softmax (classes present, whole batch; a 1024-cell order) + crit.ce_weight * cross-entropy of F.interpolate(low, size=labels.shape[-2:],
+        mode="bilinear"), shaped like gdl_head: mi_upsample_lovasz and - where the weight is positive - mi_upsample_ce_ex on the same low, their two
+        gradients added at the low resolution (K.upsample_lovasz_head)."""
+        src = low.t if inv_t is None else low.t * inv_t
+        loss_out, dlow = K.upsample_lovasz_head(src, labels, crit, want_grad=self.rec, ignore_index=ignore_index, align_corners=False)
+        return self._loss_node(low, loss_out, dlow, inv_t)
+
     def _loss_node(self, low, loss_out, dlow, inv_t):
         """The tail of the fused heads: the labels the kernel skipped go into the decoder's counter, and the loss becomes a node whose backward hands
         `low` the gradient the head's own pass left in dlow (times inv_t where the head ran on low * inv_t)."""
@@ -376,6 +384,8 @@ class GCPADecoder(Engine):
         if labels is not None:                                                                 # the trainer's fused path: four scalar losses
             if self.__dict__.get("_gdl_weight") is not None:
                 return [run.gdl_head(v, labels, self._ce_ignore, self._gdl_weight) for v in lows]
+            if isinstance(self._ce_crit, K.LovaszCriterion):
+                return [run.lovasz_head(v, labels, self._ce_ignore, self._ce_crit) for v in lows]
             return [run.ce_head(v, labels, self._ce_ignore, self._ce_crit) for v in lows]
         size = (x.t.shape[1], x.t.shape[2])
         return [run.tap("out%d" % i, run.resize(v, None, False, size=size)) for i, v in enumerate(lows)]      # F.interpolate(..., size=x.size()[2:], mode="bilinear")
@@ -384,24 +394,31 @@ class GCPADecoder(Engine):
         return super().forward(x, *feats)
 
     def losses(self, x, feats, labels, ignore_index=255, criterion="ce", weight_type="square", class_weights=None, label_smoothing=0.0, ohem=None,
-               focal_gamma=0.0):
+               focal_gamma=0.0, lovasz=None):
         """(loss5, loss4, loss3, loss2) = criterion(out_i, labels) of gald_trainer.py:76-79 without materialising the four [B,19,H,W] logit tensors:
         what GALDTrainer.train_step calls.  criterion "ce": upsample + cross-entropy fused (mi_upsample_ce_ex; with class_weights [K] fp32 on the
         device or label_smoothing, CrossEntropyLoss(weight=, label_smoothing=): mi_upsample_ce_w); "gdl": upsample +
         GeneralizedDiceLoss(weight_type) fused (mi_upsample_gdl; gald_trainer.py:70-73); "ohem" with ohem = (thresh, min_kept): upsample +
         cross-entropy over the hard pixels only (mi_upsample_ce_ohem), each of the four heads mining on its own logits.  focal_gamma > 0 with
-        criterion "ce": the focal loss -w_y (1 - p_y)^gamma log p_y on every head (mi_upsample_ce_focal), with class_weights if given."""
-        if criterion not in ("ce", "gdl", "ohem"):
-            raise ValueError("criterion must be 'ce', 'gdl' or 'ohem', got %r" % (criterion,))
+        criterion "ce": the focal loss -w_y (1 - p_y)^gamma log p_y on every head (mi_upsample_ce_focal), with class_weights if given.
+        "lovasz": Lovasz-Softmax on a 1024-cell order (mi_upsample_lovasz) + lovasz (the weight, None = 1.0; 0 = none) times the plain cross-entropy on
+        every head; it takes none of the other criterion arguments."""
+        if criterion not in ("ce", "gdl", "ohem", "lovasz"):
+            raise ValueError("criterion must be 'ce', 'gdl', 'ohem' or 'lovasz', got %r" % (criterion,))
         if (criterion == "ohem") != (ohem is not None):
             raise ValueError("criterion 'ohem' and ohem=(thresh, min_kept) go together, got criterion %r with ohem %r" % (criterion, ohem))
-        crit = K.CeCriterion.of(class_weights, label_smoothing, ohem, focal_gamma)
-        if crit.ohem is not None:
-            criterion = "ce"          # the cross-entropy head, with the mining entry
-        if criterion != "ce" and crit.focal_gamma > 0.0:
-            raise ValueError("focal_gamma belongs to criterion 'ce', got %r" % (criterion,))
-        if criterion != "ce" and (class_weights is not None or crit.label_smoothing != 0.0):
-            raise ValueError("class_weights / label_smoothing belong to criterion 'ce', got %r" % (criterion,))
+        if criterion != "lovasz" and lovasz is not None:
+            raise ValueError("lovasz (the weight of its cross-entropy term) belongs to criterion 'lovasz', got %r" % (criterion,))
+        if criterion == "lovasz":          # (refuses the four cross-entropy arguments itself)
+            crit = K.LovaszCriterion.of(1.0 if lovasz is None else lovasz, class_weights, label_smoothing, ohem, focal_gamma)
+        else:
+            crit = K.CeCriterion.of(class_weights, label_smoothing, ohem, focal_gamma)
+            if crit.ohem is not None:
+                criterion = "ce"          # the cross-entropy head, with the mining entry
+            if criterion != "ce" and crit.focal_gamma > 0.0:
+                raise ValueError("focal_gamma belongs to criterion 'ce', got %r" % (criterion,))
+            if criterion != "ce" and (class_weights is not None or crit.label_smoothing != 0.0):
+                raise ValueError("class_weights / label_smoothing belong to criterion 'ce', got %r" % (criterion,))
         if criterion == "gdl" and weight_type not in K.GDL_WEIGHT_TYPES:
             raise ValueError("Check out the weight_type: %r (one of %s)" % (weight_type, ", ".join(K.GDL_WEIGHT_TYPES)))
         self._ce_labels, self._ce_ignore, self._ce_crit, self._gdl_weight = (labels.long().contiguous(), int(ignore_index), crit,
@@ -556,6 +573,7 @@ class GALDTrainer(BaseTrainer):
 
     LOSSES = ("ce", "gdl")
     MINED = ("ohem",)          # decoder.losses(criterion="ohem", ohem=(SOLVER.OHEM_THRESH, SOLVER.OHEM_MIN_KEPT)): each head mines on its own logits
+    COMPOUND = ("lovasz",)     # decoder.losses(criterion="lovasz", lovasz=SOLVER.LOVASZ_CE): Lovasz-Softmax + weighted cross-entropy on every head
 
     def __init__(self, name, cfg, train_loader, local_rank, logger=None):
         super().__init__(name, cfg, train_loader, local_rank, logger)

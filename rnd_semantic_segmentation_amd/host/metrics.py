@@ -756,6 +756,49 @@ def GeneralizedDiceLoss(output, target, eps=1e-5, weight_type='square', ignore_l
     return (loss, counts) if with_counts else loss
 
 
+def LovaszSoftmax(output, target, ignore_label=255, bins=None):
+    """Lovasz-Softmax (Berman, Triki, Blaschko, CVPR 2018; classes present, over the whole batch) written with torch ops on materialised tensors:
+    output [N,C,H,W] logits (fp32, or fp64 kept as it is), target [N,H,W] labels; autograd does the backward.  Any device.  bins=None sorts the errors
+    of every present class (the paper's form); bins=B orders them by the cell min(B - 1, floor(e * B)) instead - inside a cell the foreground pixels
+    first, then the background pixels with their Jaccard increments averaged - which is what the fused heads compute with B = 1024
+    (mi_upsample_lovasz) and lies within 1 / B below the sorted loss.  Labels outside [0, C) are left out like ignore_label; no valid pixel: nan.
+    The literal form: it exists for comparisons (tools/gald_bench.py --literal, the tests), the trainers run the fused head."""
+    if output.dim() != 4 or target.dim() != 3 or tuple(target.shape) != (output.shape[0],) + tuple(output.shape[2:]):
+        raise ValueError("LovaszSoftmax: output [N,C,H,W] logits and target [N,H,W] labels, got %s and %s" % (tuple(output.shape), tuple(target.shape)))
+    if bins is not None and (int(bins) != bins or bins < 1):
+        raise ValueError("LovaszSoftmax: bins must be None (sorted) or a positive integer, got %r" % (bins,))
+    C = output.shape[1]
+    p = torch.softmax(output if output.dtype == torch.float64 else output.float(), dim=1).permute(0, 2, 3, 1).reshape(-1, C)
+    y = target.reshape(-1).long()
+    valid = (y != ignore_label) & (y >= 0) & (y < C)
+    p, y = p[valid], y[valid]
+    losses = []
+    for c in range(C):
+        fg = y == c
+        if not bool(fg.any()):
+            continue
+        e = torch.where(fg, 1.0 - p[:, c], p[:, c])
+        if bins is None:
+            es, perm = torch.sort(e, descending=True)
+            f = fg[perm].to(e.dtype)
+            G = f.sum()
+            jac = 1.0 - (G - f.cumsum(0)) / (G + (1.0 - f).cumsum(0))
+            g = torch.cat([jac[:1], jac[1:] - jac[:-1]])
+            losses.append((es * g).sum())
+        else:
+            cell = (e.detach() * bins).floor().long().clamp_(0, int(bins) - 1)
+            F = torch.bincount(cell[fg], minlength=int(bins)).double()
+            N = torch.bincount(cell[~fg], minlength=int(bins)).double()
+            G = F.sum()
+            a = F.flip(0).cumsum(0).flip(0) - F          # pixels in strictly higher cells
+            n = N.flip(0).cumsum(0).flip(0) - N
+            g_fg, g_bg = 1.0 / (G + n), (G - a - F) / ((G + n) * (G + n + N))
+            losses.append((e * torch.where(fg, g_fg[cell], g_bg[cell]).to(e.dtype)).sum())
+    if not losses:
+        return output.sum() * float("nan")
+    return torch.stack(losses).mean()
+
+
 def load_json(path):
     with open(path, "r") as f:
         return json.load(f)

@@ -244,14 +244,19 @@ class ASPP_Classifier_V2(nn.Module):
         return low.permute(0, 3, 1, 2)
 
     def loss(self, x, label, ignore_index=255, temperature=1.0, class_weights=None, label_smoothing=0.0, ohem=None, focal_gamma=0.0,
-             feature_mask=None):
+             feature_mask=None, lovasz=None):
         """criterion(self(x, label.shape[-2:]).div(temperature), label) fused (never writes the upsampled logits); class_weights ([K] fp32 on the
         device) and label_smoothing are the criterion's weight= and label_smoothing= (not used by the reference: host/config.py).
         ohem = (thresh, min_kept): the cross-entropy over the hard pixels only (mi_upsample_ce_ohem), mined on the logits after the division.
         focal_gamma > 0: the focal loss -w_y (1 - p_y)^gamma log p_y (mi_upsample_ce_focal), with class_weights if given, on the logits after the division.
+        lovasz = w (None: off): Lovasz-Softmax on a 1024-cell order (mi_upsample_lovasz) + w * the plain cross-entropy, both on the logits after the
+        division; it refuses the four criterion arguments before it.
         feature_mask: resnet_feature_extractor.feature_mask() of x - d loss / d x is then masked by x's ReLU where the head computes it.
         Leaves the 1/8-resolution logits [B,K,h,w] (detached) in `self.last_low`."""
-        crit = engine.K.CeCriterion.of(class_weights, label_smoothing, ohem, focal_gamma)
+        if lovasz is not None:
+            crit = engine.K.LovaszCriterion.of(lovasz, class_weights, label_smoothing, ohem, focal_gamma)
+        else:
+            crit = engine.K.CeCriterion.of(class_weights, label_smoothing, ohem, focal_gamma)
         _require_gpu(x, "ASPP_Classifier_V2")
         self.ensure_flat()
         self._engine.feature_mask_next = feature_mask          # taken by the loss node created below

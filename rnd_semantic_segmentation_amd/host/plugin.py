@@ -11,7 +11,9 @@ from ..kernels import FOCAL_GAMMA_MAX          # SOLVER.FOCAL_GAMMA's range in h
 from .metrics import setup_logger
 
 
-_LOSS_HOME = {"gdl": "the generalized Dice loss ('gdl') is wired into GALD: GALDTrainer (configs/gald_src_dice.yaml)",
+_LOSS_HOME = {"lovasz": "the Lovasz-Softmax loss ('lovasz') is wired into the fused heads of ASPPTrainer (configs/deeplabv2_r101_src_lovasz.yaml) and "
+                        "GALDTrainer (configs/gald_src_lovasz.yaml); the FADA combos, AsppClassMix and PraNet do not train with it",
+              "gdl": "the generalized Dice loss ('gdl') is wired into GALD: GALDTrainer (configs/gald_src_dice.yaml)",
               "ohem": "online hard example mining ('ohem') is wired into the fused cross-entropy heads of ASPPTrainer (configs/deeplabv2_r101_src_ohem.yaml) "
                       "and GALDTrainer (configs/gald_src_ohem.yaml)",
               "tversky": "the Tversky + BCE loss ('tversky') is wired into PraNet: PraNetTrainer (configs/pranet_src_polyp_tversky.yaml)"}
@@ -104,6 +106,25 @@ def focal_options(cfg, who):
     return gamma
 
 
+LOVASZ_CE_DEFAULT = 1.0          # SOLVER.LOVASZ_CE of host/config.py
+
+
+def lovasz_options(cfg, who):
+    """SOLVER.LOVASZ_CE (not in the reference) as a float when SOLVER.LOSS is "lovasz" - the step's loss is Lovasz-Softmax + LOVASZ_CE * cross-entropy,
+    0 = the Lovasz head alone - else None.  The key changed while SOLVER.LOSS is something else is refused instead of ignored.  (CLASS_WEIGHTS,
+    LABEL_SMOOTHING, FOCAL_GAMMA and the OHEM keys under "lovasz" are refused by their own option readers: each belongs to another LOSS.)"""
+    solver = getattr(cfg, "SOLVER", None)
+    weight = getattr(solver, "LOVASZ_CE", LOVASZ_CE_DEFAULT)
+    loss = getattr(solver, "LOSS", "ce")
+    if loss != "lovasz":
+        if weight != LOVASZ_CE_DEFAULT:
+            raise NotImplementedError("SOLVER.LOVASZ_CE belongs to SOLVER.LOSS 'lovasz' (got {!r} for {})".format(loss, who))
+        return None
+    if isinstance(weight, bool) or not isinstance(weight, (int, float)) or not 0.0 <= weight < float("inf"):      # (a merged value was checked there; this one was assigned)
+        raise ValueError("SOLVER.LOVASZ_CE {!r} must be a finite number >= 0".format(weight))
+    return float(weight)
+
+
 SELF_TRAIN_DEFAULTS = (0.99, 0.968)          # SOLVER.EMA_ALPHA, SOLVER.MIX_THRESHOLD of host/config.py (DACS's values)
 
 
@@ -128,13 +149,15 @@ class BaseTrainer:
     SELF_TRAINING = False     # True: the trainer is the student of a self-training combo, which reads SOLVER.EMA_ALPHA / SOLVER.MIX_THRESHOLD
     LOSSES = ("ce",)          # the criteria the trainer implements, as SOLVER.LOSS values
     MINED = ()                # SOLVER.LOSS values that are a LOSSES entry over mined pixels ("ohem" = "ce" over the hard pixels): accepted like LOSSES
+    COMPOUND = ()             # SOLVER.LOSS values that add a term to a weighted LOSSES entry ("lovasz" = Lovasz-Softmax + LOVASZ_CE x "ce"): accepted like LOSSES
 
     def __init__(self, name, cfg, train_loader, local_rank, logger=None):
-        require_loss(cfg, type(self).__name__, self.LOSSES + self.MINED)
+        require_loss(cfg, type(self).__name__, self.LOSSES + self.MINED + self.COMPOUND)
         who = "PraNetTrainer" if any(c.__name__ == "PraNetTrainer" for c in type(self).__mro__) else type(self).__name__
         weights, self.ce_smoothing = ce_options(cfg, who)          # CrossEntropyLoss(weight=, label_smoothing=): refused early where they do not apply
         self.ohem = ohem_options(cfg, who)                          # (thresh, min_kept) under SOLVER.LOSS "ohem", else None
         self.focal_gamma = focal_options(cfg, who)                  # SOLVER.FOCAL_GAMMA: > 0 = the focal loss in place of "ce", 0 = off
+        self.lovasz = lovasz_options(cfg, who)                      # SOLVER.LOVASZ_CE under SOLVER.LOSS "lovasz", else None
         self.self_train = self_train_options(cfg, who, self.SELF_TRAINING)      # (EMA_ALPHA, MIX_THRESHOLD) for AsppClassMix's student, else None
         self.cfg = cfg
         self.logger = setup_logger(name + "_train", cfg.OUTPUT_DIR, local_rank) if logger is None else logger
@@ -164,6 +187,8 @@ class BaseTrainer:
             self.ce_kwargs = {"focal_gamma": self.focal_gamma}
             if self.ce_weights is not None:
                 self.ce_kwargs["class_weights"] = self.ce_weights
+        if self.lovasz is not None:         # (the other readers refused their keys under "lovasz")
+            self.ce_kwargs = {"lovasz": self.lovasz}
         self.init_params()
         if cfg.resume:
             self.logger.info("Loading checkpoint from {}".format(self.cfg.resume))

@@ -28,6 +28,7 @@ from .sgd import FusedSGD
 
 class ASPPTrainer(BaseTrainer):
     MINED = ("ohem",)          # "ohem": classifier.loss(ohem=(SOLVER.OHEM_THRESH, SOLVER.OHEM_MIN_KEPT)), the fused head's mining entry
+    COMPOUND = ("lovasz",)     # "lovasz": classifier.loss(lovasz=SOLVER.LOVASZ_CE), Lovasz-Softmax + weighted cross-entropy in the fused head
 
     def __init__(self, name, cfg, train_loader, local_rank, logger=None):
         super(ASPPTrainer, self).__init__(name, cfg, train_loader, local_rank, logger)
@@ -46,7 +47,7 @@ class ASPPTrainer(BaseTrainer):
         self.classifier = self.build_classifier(self.cfg)
         self.classifier.to(self.device)
         if self.ce_kwargs and not (hasattr(self.classifier, "loss") and self.device.type == "cuda"):
-            raise NotImplementedError("SOLVER.LOSS 'ohem' and SOLVER.CLASS_WEIGHTS / SOLVER.LABEL_SMOOTHING run inside the fused head (classifier.loss on the GPU); "
+            raise NotImplementedError("SOLVER.LOSS 'ohem' / 'lovasz' and SOLVER.CLASS_WEIGHTS / SOLVER.LABEL_SMOOTHING run inside the fused head (classifier.loss on the GPU); "
                                       "this classifier / device trains through the unfused fallback, which does not know them")
         for m in (self.feature_extractor, self.classifier):
             if hasattr(m, "ensure_flat") and self.device.type == "cuda":

@@ -608,6 +608,61 @@ def upsample_gdl(low, labels, want_grad=True, grad_scale=1.0, ignore_index=255, 
     return out, dlow, sums
 
 
+LOVASZ_BINS = 1024          # the cells of mi_upsample_lovasz's order
+
+
+def check_lovasz_ce(weight):
+    """The weight of the cross-entropy term beside a Lovasz head (SOLVER.LOVASZ_CE) as a finite float >= 0; 0 = the Lovasz head alone."""
+    try:
+        w = float(weight)
+    except (TypeError, ValueError):
+        raise ValueError("lovasz must be the weight of the cross-entropy term, a number >= 0, got %r" % (weight,))
+    if not 0.0 <= w < float("inf"):          # (a nan fails both comparisons)
+        raise ValueError("lovasz: the cross-entropy weight %r is not a finite number >= 0" % (weight,))
+    return w
+
+
+def upsample_lovasz(low, labels, want_grad=True, grad_scale=1.0, ignore_index=255, align_corners=True, want_hist=False, want_err=False):
+    """Fused upsample + Lovasz-Softmax (classes present, whole batch) on a 1024-cell order (mi_upsample_lovasz).  Returns (loss_out[4] = loss, valid
+    pixels, bad labels, present classes; dlow or None; hist [K,1024,2] int32 = foreground / background pixels per cell, or None; err [B,K,H,W] = the
+    kernel's e of every (pixel, class), 2.0 where the pixel is not valid, or None: tests and diagnosis only).  Nothing is read back between its launches."""
+    L = _lib.lib()
+    dims, ws, out, dlow = _head_buffers(low, labels, L.mi_upsample_lovasz_workspace, "uplovasz", want_grad)
+    K = low.shape[-1]
+    hist = torch.empty((K, LOVASZ_BINS, 2), dtype=torch.int32, device=low.device) if want_hist else None
+    err = torch.empty((low.shape[0], K) + tuple(labels.shape[1:]), dtype=torch.float32, device=low.device) if want_err else None
+    check(L.mi_upsample_lovasz(_p(low), _p(labels), _p(out), _p(dlow), _p(hist), _p(err), *dims, ignore_index, LOVASZ_BINS, float(grad_scale),
+                               int(bool(align_corners)), _p(ws), ws.numel(), _stream()), "mi_upsample_lovasz")
+    return out, dlow, hist, err
+
+
+class LovaszCriterion(collections.namedtuple("LovaszCriterion", "ce_weight")):
+    """The criterion Lovasz-Softmax + ce_weight * cross-entropy of a fused head as one checked value (ce_weight 0: the Lovasz head alone).  Build it
+    with `of`; upsample_lovasz_head launches it."""
+    __slots__ = ()
+
+    @classmethod
+    def of(cls, ce_weight, class_weights=None, label_smoothing=0.0, ohem=None, focal_gamma=0.0):
+        """Refuses what the Lovasz term has no place for, instead of ignoring it."""
+        if class_weights is not None or float(label_smoothing) != 0.0 or ohem is not None or float(focal_gamma) != 0.0:
+            raise NotImplementedError("lovasz (Lovasz-Softmax + cross-entropy) cannot be combined with class_weights / label_smoothing / ohem / focal_gamma: "
+                                      "its cross-entropy term is the plain one and the Lovasz term has no class weights")
+        return cls(check_lovasz_ce(ce_weight))
+
+
+def upsample_lovasz_head(low, labels, crit, want_grad=True, grad_scale=1.0, ignore_index=255, align_corners=True):
+    """The fused head of a LovaszCriterion: mi_upsample_lovasz and, where ce_weight > 0, mi_upsample_ce_ex on the same low; the two dlow are added at
+    the low resolution.  Returns (loss_out[4] = Lovasz + ce_weight * CE, valid pixels, bad labels, present classes; dlow or None), as upsample_ce_head."""
+    kw = {"want_grad": want_grad, "grad_scale": grad_scale, "ignore_index": ignore_index, "align_corners": align_corners}
+    out, dlow = upsample_lovasz(low, labels, **kw)[:2]
+    if crit.ce_weight > 0.0:
+        ce_out, ce_dlow = upsample_ce(low, labels, **kw)
+        out[0:1].add_(ce_out[0:1], alpha=crit.ce_weight)
+        if dlow is not None:
+            dlow.add_(ce_dlow, alpha=crit.ce_weight)
+    return out, dlow
+
+
 def upsample_tversky_bce(low, mask, want_grad=True, grad_scale=1.0, alpha=0.7, eps=1.0, weights=(0.5, 0.5), align_corners=False, want_sums=False):
     """Fused upsample + CompoundLoss([TverskyLoss(alpha, eps), BinaryCrossEntropyLoss()], weights) (reference attn/loss.py) for one-channel logits:
     low [B,h,w] fp32, mask [B,H,W] fp32 in [0, 1] (H >= h, W >= w; the same size: no upsample).  Returns (loss_out[4] = loss, tversky, bce, 0;

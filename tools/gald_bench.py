@@ -1,8 +1,8 @@
 """GALD (HarDNet-68 + GCPA decoder; configs/gald_src.yaml: batch 6, 1280 x 720 crops) training-step throughput on one MI355X: encoder + decoder forward,
 four head losses, backward, both Adam steps.
 
-    python tools/gald_bench.py [--batch 6] [--height 720] [--width 1280] [--steps 10] [--loss ce|gdl|ohem] [--literal] [--alternate ROUNDS]
-                               [--class-weights median] [--label-smoothing S] [--ohem-thresh T] [--ohem-min-kept M] [--focal-gamma G]
+    python tools/gald_bench.py [--batch 6] [--height 720] [--width 1280] [--steps 10] [--loss ce|gdl|ohem|lovasz] [--literal] [--alternate ROUNDS]
+                               [--class-weights median] [--label-smoothing S] [--ohem-thresh T] [--ohem-min-kept M] [--focal-gamma G] [--lovasz-ce W]
 
 --loss ce: the four fused upsample + cross-entropy heads (the default); --loss gdl: the four fused upsample + generalized Dice heads
 (configs/gald_src_dice.yaml).  --literal (with gdl): the composition without the fused kernel - decoder(x, feats) materialises the four [B,19,H,W]
@@ -17,6 +17,9 @@ ohem --literal.
 --focal-gamma G (with ce, combinable with --class-weights): the focal loss -w_y (1 - p_y)^G log p_y inside the fused heads (mi_upsample_ce_focal;
 configs/gald_src_focal.yaml); with --literal: the four materialised outputs through a focal loss written with F.log_softmax / gather / pow and
 autograd.  With --alternate the variants are ce, ce-focal and ce-focal --literal.
+--loss lovasz: the four fused upsample + Lovasz-Softmax heads (mi_upsample_lovasz; configs/gald_src_lovasz.yaml) plus W (--lovasz-ce, default 1) times
+the plain fused cross-entropy of each head; with --literal: the four materialised outputs through metrics.LovaszSoftmax (softmax and 19 torch.sort
+calls per head, autograd through the gather) plus W * F.cross_entropy.  With --alternate the variants are ce, lovasz and lovasz --literal.
 --alternate N: ce, gdl and gdl --literal - and, when weights or smoothing are given, ce weighted fused and ce weighted literal - one after the other, N
 times over, in this one process (one JSON line per variant and round), so that they are compared on one box under the same conditions; the peak of
 allocated memory is reset before every variant."""
@@ -31,7 +34,7 @@ import torch.nn.functional as F
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import class_weights as cw  # noqa: E402  (tools/class_weights.py)
-from rnd_semantic_segmentation_amd.host import gald, pranet, synth  # noqa: E402
+from rnd_semantic_segmentation_amd.host import gald, metrics, pranet, synth  # noqa: E402
 
 
 def torch_gdl(output, target, eps=1e-5, weight_type="square", ignore_label=255):
@@ -81,7 +84,7 @@ def main():
     ap.add_argument("--width", type=int, default=1280)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--loss", choices=("ce", "gdl", "ohem"), default="ce")
+    ap.add_argument("--loss", choices=("ce", "gdl", "ohem", "lovasz"), default="ce")
     ap.add_argument("--literal", action="store_true", help="materialised outputs through a torch-op Dice loss / F.cross_entropy with autograd")
     ap.add_argument("--alternate", type=int, default=0, metavar="ROUNDS", help="run the variants in turn, ROUNDS times, in this process")
     ap.add_argument("--class-weights", choices=("median",), default=None, help="with ce: median-frequency class weights from the bench's own labels")
@@ -89,6 +92,7 @@ def main():
     ap.add_argument("--ohem-thresh", type=float, default=0.7, metavar="T", help="with ohem: SOLVER.OHEM_THRESH")
     ap.add_argument("--ohem-min-kept", type=int, default=100000, metavar="M", help="with ohem: SOLVER.OHEM_MIN_KEPT")
     ap.add_argument("--focal-gamma", type=float, default=0.0, metavar="G", help="with ce: SOLVER.FOCAL_GAMMA (combinable with --class-weights)")
+    ap.add_argument("--lovasz-ce", type=float, default=1.0, metavar="W", help="with lovasz: SOLVER.LOVASZ_CE, the weight of the cross-entropy term")
     a = ap.parse_args()
     focal = a.focal_gamma > 0.0
     if focal and (a.loss != "ce" or a.label_smoothing != 0.0):
@@ -122,6 +126,12 @@ def main():
             l5, l4, l3, l2 = [torch_ohem(o.float().contiguous(), lab, a.ohem_thresh, a.ohem_min_kept) for o in dec(x, enc(x))]
         elif loss_name == "ohem":
             l5, l4, l3, l2 = dec.losses(x, enc(x), lab, criterion="ohem", ohem=(a.ohem_thresh, a.ohem_min_kept))
+        elif literal and loss_name == "lovasz":
+            outs = [o.float().contiguous() for o in dec(x, enc(x))]
+            l5, l4, l3, l2 = [metrics.LovaszSoftmax(o, lab) + (a.lovasz_ce * F.cross_entropy(o, lab, ignore_index=255) if a.lovasz_ce > 0 else 0.0)
+                              for o in outs]
+        elif loss_name == "lovasz":
+            l5, l4, l3, l2 = dec.losses(x, enc(x), lab, criterion="lovasz", lovasz=a.lovasz_ce)
         elif literal:
             l5, l4, l3, l2 = [F.cross_entropy(o.float().contiguous(), lab, weight=extra.get("class_weights"), ignore_index=255,
                                               label_smoothing=extra.get("label_smoothing", 0.0)) for o in dec(x, enc(x))]
@@ -155,6 +165,8 @@ def main():
                 variants = (("ce", False), ("ohem", False), ("ohem", True))
             if focal:
                 variants = (("ce", False), ("ce-focal", False), ("ce-focal", True))
+            if a.loss == "lovasz":
+                variants = (("ce", False), ("lovasz", False), ("lovasz", True))
             for loss_name, literal in variants:
                 measure(loss_name, literal, a.warmup if r == 0 else 1)
     else:
