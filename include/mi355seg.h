@@ -399,6 +399,31 @@ int mi_upsample_predict_score_cw(const MiProbSource* src, int n, int K, int H, i
                                  int ignore_index, const float* class_threshold, uint8_t* pred, uint8_t* pseudo, int64_t* counts, int bins,
                                  int64_t* hist, void* stream);
 
+/* ---- sliding-window evaluation tails (TEST.SLIDE): sources that each cover a rectangle of the output ---------
+ * Crop-sized windows slid over the picture with an overlap, each evaluated as inference() evaluates a picture (utility.py:179-191), the
+ * windows' probabilities averaged where they overlap.  win is a HOST array of n windows, 1 <= n <= MI_SLIDE_MAX_WINDOWS, copied by value into
+ * the kernel arguments (as MiProbSource is: no device table, no extra copy; 64 descriptors stay far below the kernel-argument limit and allow
+ * an 8 x 8 grid).  Every window has the same low map size h x w ([h][w][K] fp32 NHWC logits of the crop; low_mirror: those of the mirrored
+ * crop, NULL without flip, on all windows or on none) and owns the output rectangle [y0, y0 + wh) x [x0, x0 + ww): label coordinates.
+ * Arithmetic contract, per output pixel (y, x) and class k, fp32, no contraction:
+ *  - for every window i IN ORDER that contains the pixel, local coordinates yl = y - y0_i, xl = x - x0_i:
+ *      p  = softmax_k(bilinear_align_corners(low_i: h x w -> wh x ww)) at (yl, xl), the device code of mi_upsample_softmax (a rounded product);
+ *      pm = the same on low_mirror_i at (yl, ww-1-xl): the mirrored source evaluated AT the mirrored output column;
+ *      q  = (p + pm) / 2 with mirror maps, p without;   acc = acc + q, starting from 0;
+ *  - result = acc / (float)cover, a true division by the number of windows that contain the pixel.
+ *  - cover == 1 without mirror maps is bit-equal to mi_upsample_softmax on that window.
+ * mi_upsample_softmax_slide writes probs [K][H][W]; mi_upsample_predict_score_slide derives pred, pseudo, counts and hist from the same K
+ * values exactly as mi_upsample_predict_score(_cw) do from theirs (one kernel body, another value provider): class_threshold == NULL,
+ * hist == NULL and bins == 0 is the plain entry with `threshold`; otherwise the class-wise entry's rules hold and `threshold` is not used.
+ * Refused before launch: everything those entries refuse; n outside 1..64; wh < h or ww < w; a window that leaves [0,H) x [0,W); mirror maps
+ * on some windows only; an output pixel that no window covers (it would be 0 / 0; checked on the host over the distinct window edges). */
+#define MI_SLIDE_MAX_WINDOWS 64
+typedef struct { const float* low; const float* low_mirror; int y0, x0; } MiSlideWindow;
+int mi_upsample_softmax_slide(const MiSlideWindow* win, int n, int h, int w, int wh, int ww, float* probs, int K, int H, int W, void* stream);
+int mi_upsample_predict_score_slide(const MiSlideWindow* win, int n, int h, int w, int wh, int ww, int K, int H, int W, const int64_t* labels,
+                                    int ignore_index, float threshold, const float* class_threshold, uint8_t* pred, uint8_t* pseudo,
+                                    int64_t* counts, int bins, int64_t* hist, void* stream);
+
 /* ---- polyp evaluation tail: what Dice / IoU / F-beta / E-measure / S-measure / MAE need of PraNet's map, without the host ever seeing the map ----
  * low [B][h][w] fp32 (the res2 logits), labels [B][H][W] int64 (ground truth in {0, 1}).  Per output pixel, all in fp32:
  *   z = bilinear(low -> H x W), align_corners False, ATen's source index, each axis interpolated as a + lambda (b - a): a constant map stays constant

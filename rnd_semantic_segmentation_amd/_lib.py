@@ -62,6 +62,8 @@ SIGNATURES = {
     "mi_upsample_softmax_multi": (I, [P, I, P, I, I, I, F, F, P]),
     "mi_upsample_predict_score": (I, [P, I, I, I, I, F, F, P, I, F, P, P, P, P]),
     "mi_upsample_predict_score_cw": (I, [P, I, I, I, I, F, F, P, I, P, P, P, P, I, P, P]),
+    "mi_upsample_softmax_slide": (I, [P, I, I, I, I, I, P, I, I, I, P]),
+    "mi_upsample_predict_score_slide": (I, [P] + [I] * 8 + [P, I, F, P, P, P, P, I, P, P]),
     "mi_polyp_score_workspace": (Z, [I] * 5),
     "mi_polyp_score": (I, [P, P] + [I] * 5 + [P, P, P, P, P, P, Z, P]),
     "mi_image_resize_ac": (I, [P, P] + [I] * 7 + [P]),
@@ -164,6 +166,15 @@ SIGNATURES = {
 class MiProbSource(ctypes.Structure):
     """One source of mi_upsample_softmax_multi (include/mi355seg.h): low [h][w][K] fp32 NHWC on the device, mirror flag."""
     _fields_ = [("low", c_void_p), ("h", c_int), ("w", c_int), ("mirror", c_int)]
+
+
+class MiSlideWindow(ctypes.Structure):
+    """One window of the sliding-window tails (include/mi355seg.h): low / low_mirror [h][w][K] fp32 NHWC on the device (low_mirror NULL without
+    flip), origin in label coordinates."""
+    _fields_ = [("low", c_void_p), ("low_mirror", c_void_p), ("y0", c_int), ("x0", c_int)]
+
+
+SLIDE_MAX_WINDOWS = 64      # MI_SLIDE_MAX_WINDOWS of include/mi355seg.h
 
 
 class MiAugSample(ctypes.Structure):

@@ -1,4 +1,4 @@
-// What the bilinear-upsample sources (upsample_ce.hip, upsample_lovasz.hip, upsample_infer.hip, fada.hip, classmix.hip) share: the source-index arithmetic, the fixed-order reductions,
+// What the bilinear-upsample sources (upsample_ce.hip, upsample_lovasz.hip, upsample_infer.hip, upsample_slide.hip, fada.hip, classmix.hip) share: the source-index arithmetic, the fixed-order reductions,
 // the per-pixel softmax core, the per-pixel probabilities and prediction of the inference tails, the prologue / pixel / epilogue helpers of the two kernel skeletons of the fused upsample + loss heads (x-tile and row-walk), the LDS layout of the first,
 // and the launch planning.  Everything is file-local to the source that includes it (anonymous namespace): kernel names do not change.
 #pragma once
@@ -235,8 +235,84 @@ __device__ __forceinline__ void multi_probs(const ProbSrc* s_all, int n, int K, 
     }
 }
 
+// The per-pixel arithmetic of the sliding-window tails (upsample_slide.hip), shared by their probability kernel and their predict-and-score
+// kernel.  A source covers a rectangle of the output, not the whole of it: window i owns [y0, y0 + ay.n_out) x [x0, x0 + ax.n_out), every window
+// has the same low-map and label-pixel size, hence ONE Axis pair.
+struct SlideWin {
+    const float* low;             // [h][w][K] logits of the window
+    const float* low_mirror;      // the same of the mirrored crop (MIRROR instantiations only)
+    int y0, x0;                   // origin in output coordinates
+};
+constexpr int MAX_SLIDE_WIN = 64;
+struct SlideWins {
+    SlideWin w[MAX_SLIDE_WIN];    // by value in the kernel arguments, as ProbSrcs is: no device table
+};
+
+// acc[p][k] = (q_a + q_b + ...) / cover for the P pixels (y, xb .. xb+P-1): the windows that contain the pixel, in window order from 0, with
+// q_i = softmax(bilinear(low_i)) at the pixel's window-local coordinates (the device code of mi_upsample_softmax) or, with MIRROR,
+// (p + pm) / 2 where pm is the same on low_mirror_i at the mirrored local column (inference(), utility.py:187-190).  Every product and sum is
+// rounded on its own, the last division is a true division by the integer cover count.  cover == 1 without MIRROR: 0 + p == p and p / 1 == p,
+// the bits of mi_upsample_softmax.  Nearly wave-uniform: lanes differ only at window edges; the P pixels are tested one by one (an odd x0
+// puts a window edge between them).  A pixel no window covers would be 0 / 0: the launchers refuse such a grid.
+template <int KR, int P, bool MIRROR>
+__device__ __forceinline__ void slide_probs(const SlideWin* w_all, int n, int K, const Axis& ay, const Axis& ax, int y, int xb, float (&acc)[P][KR]) {
+#pragma clang fp contract(off)
+    int cover[P];
+#pragma unroll
+    for (int p = 0; p < P; ++p) {
+        cover[p] = 0;
+#pragma unroll
+        for (int k = 0; k < KR; ++k) acc[p][k] = 0.f;
+    }
+    for (int i = 0; i < n; ++i) {
+        const SlideWin& s = w_all[i];
+        const int yl = y - s.y0;
+        if ((unsigned)yl >= (unsigned)ay.n_out) continue;
+#pragma unroll
+        for (int p = 0; p < P; ++p) {
+            const int xl = xb + p - s.x0;
+            if ((unsigned)xl < (unsigned)ax.n_out) {
+                float v[KR];
+                int arg;
+                const float rse = interp_softmax_terms<KR>(s.low, K, ay, ax, yl, xl, v, arg);
+                if constexpr (MIRROR) {
+                    float q[KR];
+#pragma unroll
+                    for (int k = 0; k < KR; ++k) {
+                        if (k < K) q[k] = v[k] * rse;
+                    }
+                    const float rsm = interp_softmax_terms<KR>(s.low_mirror, K, ay, ax, yl, ax.n_out - 1 - xl, v, arg);
+#pragma unroll
+                    for (int k = 0; k < KR; ++k) {
+                        if (k < K) {
+                            const float pm = v[k] * rsm;
+                            const float two = q[k] + pm;
+                            acc[p][k] = acc[p][k] + two / 2.f;
+                        }
+                    }
+                } else {
+#pragma unroll
+                    for (int k = 0; k < KR; ++k) {
+                        if (k < K) acc[p][k] = add_rounded_product(acc[p][k], v[k], rse);
+                    }
+                }
+                ++cover[p];
+            }
+            __builtin_amdgcn_sched_barrier(0);      // one pixel's loads at a time, as in multi_probs
+        }
+    }
+#pragma unroll
+    for (int p = 0; p < P; ++p) {
+        const float c = (float)cover[p];
+#pragma unroll
+        for (int k = 0; k < KR; ++k) {
+            if (k < K) acc[p][k] = acc[p][k] / c;
+        }
+    }
+}
+
 struct ClassThr {
-    float t[KMAX];                // by value in the kernel arguments, as ProbSrcs is: no device table
+    float t[KMAX];               // by value in the kernel arguments, as ProbSrcs is: no device table
 };
 
 // The prediction of one pixel from its K values a[]: the LOWEST class index among their maxima (torch.max(dim) / numpy.argmax), the maximum in

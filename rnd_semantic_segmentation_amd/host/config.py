@@ -219,11 +219,18 @@ def default_tree():
         # CRF_BI_XY pixels and CRF_BI_RGB in 0..255 colour units), in one HIP kernel family (mi_crf_refine) between the evaluation tail and the
         # argmax; the tester then takes the literal scoring path whatever FUSED_SCORE says.  The defaults are the customary dense-CRF values
         # (3 / 3, 10 / 80 / 13, 5 iterations); they are NOT tuned on any dataset here.  A CRF_* key changed while CRF is False is refused
-        # (metrics.crf_settings)
+        # (metrics.crf_settings);
+        # SLIDE True (ASPPTester only; the other testers refuse it) = sliding-window evaluation, the protocol DeepLab and PSPNet report Cityscapes
+        # under: the picture stays at INPUT_SIZE_TEST, windows of SLIDE_CROP (width, height; the size the net was trained on) are slid over it
+        # with SLIDE_STRIDE, each is evaluated as inference() evaluates a picture (with FLIP: averaged with its mirror) and the windows'
+        # probabilities are averaged where they overlap - on the fused path in one kernel after the windows' backbone passes
+        # (mi_upsample_predict_score_slide).  SCALES must stay (1.0,); a SLIDE_* key changed while SLIDE is False is refused
+        # (metrics.slide_settings)
         "TEST": {"BATCH_SIZE": 1, "PRECISION": "fp32", "SCALES": (1.0,), "FLIP": False, "FUSED_SCORE": True, "PSEUDO_THRESHOLD": 0.0,
                  "PSEUDO_CLASSWISE": False, "PSEUDO_PORTION": 0.5, "POLYP_METRICS": False,
                  "CRF": False, "CRF_ITER": 5, "CRF_WINDOW": 7, "CRF_DILATION": 4, "CRF_POS_W": 3.0, "CRF_POS_XY": 3.0, "CRF_BI_W": 10.0,
-                 "CRF_BI_XY": 80.0, "CRF_BI_RGB": 13.0},
+                 "CRF_BI_XY": 80.0, "CRF_BI_RGB": 13.0,
+                 "SLIDE": False, "SLIDE_CROP": (769, 769), "SLIDE_STRIDE": (513, 513)},
         "OUTPUT_DIR": ".",
         "resume": "",
         "PSEUDO_DIR": "",

@@ -24,7 +24,7 @@ from .. import _lib
 from .. import gk
 from .. import kernels as K
 from . import arch
-from .metrics import (AverageMeter, adjust_learning_rate, confusion_matrix, dump_json, intersectionAndUnionGPU, require_no_crf,
+from .metrics import (AverageMeter, adjust_learning_rate, confusion_matrix, dump_json, intersectionAndUnionGPU, require_no_crf, require_no_slide,
                       require_no_polyp_metrics, require_plain_argmax, require_single_scale)
 from .plugin import BaseTrainer
 from .tape import Engine, FlatAdam, Run, Unit, acc, grad_target, rup32, tile_route
@@ -672,6 +672,7 @@ class GALDTester:
         require_plain_argmax(cfg, "GALDTester")
         require_no_polyp_metrics(cfg, "GALDTester")
         require_no_crf(cfg, "GALDTester")
+        require_no_slide(cfg, "GALDTester")
         self.cfg, self.logger, self.test_loader, self.device = cfg, logger, test_loader, device
         self.palette, self.saveres, self.trainid2name = palette, saveres, trainid2name
         self.encoder = GCPAEncoder()

@@ -22,6 +22,10 @@ Differences that are deliberate and documented:
    and moment sums of mi_polyp_score - the host never sees the probability map.
  * the CRF refinement (crf_settings, crf_channel_scale, crf_refine_output; TEST.CRF) is not in the reference either: the locally connected
    form of DeepLabV2's CRF stage, one HIP kernel family (mi_crf_refine) on the literal path's probability map.
+ * sliding-window evaluation (slide_plan, slide_windows, slide_inference, slide_settings; TEST.SLIDE) is not in the reference either: the
+   protocol DeepLab and PSPNet report Cityscapes under - crop-sized windows slid over the full-resolution picture, each evaluated as
+   inference() evaluates a picture, averaged where they overlap.  slide_inference is the literal composition; predict_and_score(slide=...)
+   on the engine runs the windows' backbone passes and then ONE kernel (mi_upsample_predict_score_slide).
 """
 import json
 import logging
@@ -240,6 +244,141 @@ def multi_scale_inference(feature_extractor, classifier, image, label, flip=True
     return output / div_b if flip else output
 
 
+# ----------------------------------------------------------------------------- sliding-window evaluation (TEST.SLIDE)
+SLIDE_MAX_WINDOWS = 64                  # MI_SLIDE_MAX_WINDOWS of include/mi355seg.h: the descriptors travel in the kernel arguments
+SLIDE_CHUNK = 4                         # images per backbone batch of the engine's sliding-window paths
+SLIDE_DEFAULTS = OrderedDict((("SLIDE_CROP", (769, 769)), ("SLIDE_STRIDE", (513, 513))))      # TEST.SLIDE_* of host/config.py, (width, height)
+
+
+def slide_plan(size, crop, stride):
+    """The window grid of sliding-window evaluation for an image of size (H, W); crop and stride are (h, w) here.  Returns (rows, cols,
+    (wh, ww)): the row origins, the column origins and the one size every window has, (min(ch, H), min(cw, W)).  Per axis of length L:
+    n = max(L - c + s - 1, 0) // s + 1 windows; window i starts at i * s, ends at min(i * s + c, L) and its start is then pulled back to
+    max(end - c, 0): the first starts at 0, the last ends at L.  Windows are numbered row-major (row origin outer, column origin inner).
+    Refused: a non-positive crop, a stride outside 1 .. crop, more than SLIDE_MAX_WINDOWS windows."""
+    (H, W), (ch, cw), (sh, sw) = [tuple(int(v) for v in t) for t in (size, crop, stride)]
+    if H < 1 or W < 1:
+        raise ValueError("slide_plan: empty image %d x %d" % (H, W))
+    if ch < 1 or cw < 1:
+        raise ValueError("slide_plan: crop %r must be positive" % ((ch, cw),))
+    if not (1 <= sh <= ch and 1 <= sw <= cw):
+        raise ValueError("slide_plan: stride %r lies outside 1 .. crop %r" % ((sh, sw), (ch, cw)))
+
+    def axis(L, c, s):
+        out = []
+        for i in range(max(L - c + s - 1, 0) // s + 1):
+            b = min(i * s + c, L)
+            out.append(max(b - c, 0))
+        return out
+
+    rows, cols = axis(H, ch, sh), axis(W, cw, sw)
+    if len(rows) * len(cols) > SLIDE_MAX_WINDOWS:
+        raise ValueError("slide_plan: %d x %d windows of %r with stride %r over %d x %d exceed the cap of %d windows"
+                         % (len(rows), len(cols), (ch, cw), (sh, sw), H, W, SLIDE_MAX_WINDOWS))
+    return rows, cols, (min(ch, H), min(cw, W))
+
+
+def slide_label_factor(image_size, label_size):
+    """The whole factor r by which the label is larger than the image, the same on both axes (1024 x 512 input, 2048 x 1024 label: 2)."""
+    (H, W), (Hl, Wl) = [tuple(int(v) for v in t) for t in (image_size, label_size)]
+    r = Hl // H if H > 0 else 0
+    if r < 1 or Hl != r * H or Wl != r * W:
+        raise ValueError("sliding-window evaluation needs a label that is a whole multiple of the image, the same on both axes: image %d x %d, "
+                         "label %d x %d" % (H, W, Hl, Wl))
+    return r
+
+
+def slide_windows(image_size, label_size, crop, stride):
+    """(origins, (wh, ww), r): the image-coordinate origins (y0, x0) of slide_plan's windows in row-major order, their size and the label
+    factor.  Window (y0, x0) owns the label rectangle [r*y0, r*(y0+wh)) x [r*x0, r*(x0+ww))."""
+    r = slide_label_factor(image_size, label_size)
+    rows, cols, window = slide_plan(image_size, crop, stride)
+    return [(y0, x0) for y0 in rows for x0 in cols], window, r
+
+
+def _slide_feats(feature_extractor, image, origins, window, flip):
+    """The backbone passes both engine paths of sliding-window evaluation share, so that they feed it identical batches: the crops of image 0
+    in window order - with flip every crop followed by its horizontal mirror - in chunks of SLIDE_CHUNK images.  Returns the feature maps."""
+    wh, ww = window
+    x0 = image[:1]
+    crops = []
+    for y0, xo in origins:
+        c = x0[:, :, y0:y0 + wh, xo:xo + ww]
+        crops.append(c)
+        if flip:
+            crops.append(torch.flip(c, [3]))
+    return [feature_extractor(torch.cat(crops[i:i + SLIDE_CHUNK], 0).contiguous()) for i in range(0, len(crops), SLIDE_CHUNK)]
+
+
+def slide_inference(feature_extractor, classifier, image, label, crop, stride, flip=False):
+    """Sliding-window evaluation as DeepLab and PSPNet report Cityscapes: windows of `crop` slid over image 0 with `stride` (both (h, w);
+    slide_plan), each evaluated as inference() evaluates a picture - against its rectangle of the label, with (p + p_mirrored.flip) / 2 under
+    flip - and the windows' probabilities averaged where they overlap: summed in window order, then one true division by the integer cover
+    count.  [1,K,Hl,Wl] fp32 at the LABEL's size, which may be a whole multiple r of the image's.  This literal composition is the
+    definition mi_upsample_softmax_slide is held to.  On the engine (a classifier with slide_lows, CUDA tensors) the windows' 1/8-resolution
+    logits come from the batches the fused path uses (_slide_feats) and kernels.upsample_softmax turns each into probabilities; a substituted
+    / foreign classifier or CPU tensors call inference() per window."""
+    size = tuple(label.shape[-2:])
+    origins, (wh, ww), r = slide_windows(image.shape[-2:], size, crop, stride)
+    canvas = count = None
+    engine = hasattr(classifier, "slide_lows") and image.is_cuda
+    if engine:
+        from .. import kernels
+        with torch.no_grad():
+            lows, mirror_lows = classifier.slide_lows(_slide_feats(feature_extractor, image, origins, (wh, ww), flip), flip)
+    for i, (y0, x0) in enumerate(origins):
+        ys, xs = slice(r * y0, r * (y0 + wh)), slice(r * x0, r * (x0 + ww))
+        if engine:
+            q = kernels.upsample_softmax(lows[i].unsqueeze(0), (r * wh, r * ww), want_pred=False)[0]
+            if flip:
+                pm = kernels.upsample_softmax(mirror_lows[i].unsqueeze(0), (r * wh, r * ww), want_pred=False)[0]
+                q = (q[0] + pm[0].flip(2)) / 2
+                q = q.unsqueeze(0)
+        else:
+            q = inference(feature_extractor, classifier, image[:1, :, y0:y0 + wh, x0:x0 + ww], label[..., ys, xs], flip=flip)
+        if canvas is None:
+            canvas = torch.zeros((1, q.shape[1]) + size, dtype=q.dtype, device=q.device)
+            count = torch.zeros((1, 1) + size, dtype=q.dtype, device=q.device)
+        canvas[:, :, ys, xs] += q
+        count[:, :, ys, xs] += 1
+    return canvas / count
+
+
+def slide_settings(cfg):
+    """None while TEST.SLIDE is False (absent = False), else (crop, stride), each (h, w): TEST.SLIDE_CROP / TEST.SLIDE_STRIDE are written
+    (width, height) like the INPUT.*_SIZE_* keys.  A SLIDE_* key that differs from its default while SLIDE is False is refused instead of
+    ignored; so is TEST.SCALES other than (1.0,) with SLIDE (multi-scale sliding would need a resize of probability maps the reference does
+    not define).  TEST.FLIP is supported."""
+    test = cfg.TEST
+    on = test["SLIDE"] if "SLIDE" in test else False
+    if not isinstance(on, bool):
+        raise ValueError("TEST.SLIDE %r must be True or False" % (on,))
+    v = OrderedDict((k, tuple(test[k]) if k in test else d) for k, d in SLIDE_DEFAULTS.items())
+    if not on:
+        stray = [k for k, d in SLIDE_DEFAULTS.items() if v[k] != d]
+        if stray:
+            raise NotImplementedError("TEST.%s %r belongs to TEST.SLIDE True" % (stray[0], v[stray[0]]))
+        return None
+    for k, t in v.items():
+        if len(t) != 2 or any(isinstance(a, bool) or not isinstance(a, int) for a in t):
+            raise ValueError("TEST.%s %r must be two integers (width, height)" % (k, t))
+    scales, _ = tta_settings(cfg)
+    if scales != (1.0,):
+        raise NotImplementedError("TEST.SLIDE with TEST.SCALES %r: sliding-window evaluation is single-scale (TEST.FLIP is supported); leave "
+                                  "SCALES at (1.0,)" % (scales,))
+    crop, stride = (v["SLIDE_CROP"][1], v["SLIDE_CROP"][0]), (v["SLIDE_STRIDE"][1], v["SLIDE_STRIDE"][0])
+    slide_plan(crop, crop, stride)                          # the crop and stride rules, before anything is built
+    return crop, stride
+
+
+def require_no_slide(cfg, who):
+    """Sliding-window evaluation is built on the DeepLab evaluation tail: the other testers refuse the key rather than ignore it (a stray
+    SLIDE_* key is refused by slide_settings itself)."""
+    if slide_settings(cfg) is not None:
+        raise NotImplementedError("%s: TEST.SLIDE - sliding-window evaluation exists for the DeepLab (feature extractor, classifier) pair only "
+                                  "(ASPPTester); leave it False" % (who,))
+
+
 def tta_settings(cfg):
     """(scales, flip) of cfg.TEST (SCALES / FLIP are not reference keys; absent = the defaults (1.0,) / False = plain inference())."""
     scales = tuple(cfg.TEST.SCALES) if "SCALES" in cfg.TEST else (1.0,)
@@ -388,7 +527,23 @@ def _engine_masks(feature_extractor, classifier, image, size, flip, scales, **kw
         return classifier.predict_mask_multi(feats, mirrors, size, divisors, **kw)
 
 
-def _literal_output(feature_extractor, classifier, image, label, flip, scales):
+def _engine_masks_slide(feature_extractor, classifier, image, size, flip, slide, **kw):
+    """(pred, pseudo, counts) of the engine's sliding-window tail: the backbone passes of slide_inference (_slide_feats), then ONE kernel."""
+    origins, (wh, ww), r = slide_windows(image.shape[-2:], size, *slide)
+    with torch.no_grad():
+        feats = _slide_feats(feature_extractor, image, origins, (wh, ww), flip)
+        return classifier.predict_mask_slide(feats, flip, [(r * y0, r * x0) for y0, x0 in origins], (r * wh, r * ww), size, **kw)
+
+
+def _require_single_scale_slide(scales):
+    if tuple(scales) != (1.0,):
+        raise NotImplementedError("sliding-window evaluation is single-scale: scales %r" % (tuple(scales),))
+
+
+def _literal_output(feature_extractor, classifier, image, label, flip, scales, slide=None):
+    if slide is not None:
+        _require_single_scale_slide(scales)
+        return slide_inference(feature_extractor, classifier, image, label, slide[0], slide[1], flip=flip)
     if tuple(scales) == (1.0,) and not flip:
         return inference(feature_extractor, classifier, image, label, flip=False)
     return multi_scale_inference(feature_extractor, classifier, image, label, flip=flip, scales=list(scales))
@@ -418,14 +573,16 @@ def literal_pseudo(output, class_threshold):
 
 
 def predict_and_score(feature_extractor, classifier, image, label, flip=False, scales=(1.0,), *, num_classes, ignore_index=255, threshold=0.0,
-                      class_threshold=None, hist=None):
+                      class_threshold=None, hist=None, slide=None):
     """One image of ASPPTester.test(): inference(flip=False) (scales == (1.0,), no flip) or multi_scale_inference, then the argmax mask, the
     pseudo-label mask (argmax where the winning probability >= threshold, else 255; None for threshold 0), confusion_matrix and
     intersectionAndUnionGPU against label[:1].  On the engine (a classifier with predict_mask_multi, CUDA tensors) the backbone passes are
     those of inference / multi_scale_inference and everything after the logits is ONE kernel, which never writes the probability map; the
     integers are the same.  A substituted / foreign classifier or CPU tensors run the literal composition.
     Class-wise pseudo-labels: hist (the caller's int64 [K, PSEUDO_BINS] tensor, kept across images) receives this image's confidence histogram;
-    class_threshold (K values in [0, 1]) replaces threshold in the pseudo-label mask: argmax where the winning probability >= its class's."""
+    class_threshold (K values in [0, 1]) replaces threshold in the pseudo-label mask: argmax where the winning probability >= its class's.
+    slide = (crop, stride), each (h, w) (slide_settings): sliding-window evaluation - slide_inference instead of inference, on the engine
+    ONE mi_upsample_predict_score_slide after the windows' backbone passes; scales must be (1.0,).  None: no sliding."""
     K = int(num_classes)
     if not 0.0 <= float(threshold) <= 1.0:
         raise ValueError("threshold %r lies outside [0, 1]" % (threshold,))
@@ -440,9 +597,13 @@ def predict_and_score(feature_extractor, classifier, image, label, flip=False, s
             kw.update(class_threshold=_class_table(class_threshold, K, "cpu"), want_pseudo=True)
         if hist is not None:
             kw.update(hist=hist, want_pseudo=class_threshold is not None)
-        pred, pseudo, counts = _engine_masks(feature_extractor, classifier, image, size, flip, scales, **kw)
+        if slide is not None:
+            _require_single_scale_slide(scales)
+            pred, pseudo, counts = _engine_masks_slide(feature_extractor, classifier, image, size, flip, slide, **kw)
+        else:
+            pred, pseudo, counts = _engine_masks(feature_extractor, classifier, image, size, flip, scales, **kw)
         return scores_from_counts(counts, K, pred, pseudo)
-    output = _literal_output(feature_extractor, classifier, image, label, flip, scales)
+    output = _literal_output(feature_extractor, classifier, image, label, flip, scales, slide)
     top = output.max(1)
     pred = top[1]
     pseudo = None
@@ -457,15 +618,19 @@ def predict_and_score(feature_extractor, classifier, image, label, flip=False, s
     return ScoreResult(pred[0].to(torch.uint8), pseudo, cmt, ai, union, at, ao)
 
 
-def classwise_pseudo_labels(feature_extractor, classifier, image, label, flip=False, scales=(1.0,), *, num_classes, class_threshold):
+def classwise_pseudo_labels(feature_extractor, classifier, image, label, flip=False, scales=(1.0,), *, num_classes, class_threshold, slide=None):
     """The second pass of class-wise pseudo-labelling for one image: the uint8 [H,W] mask, argmax where the winning probability >= its class's
-    threshold, else 255.  No metric counting, no histogram.  Engine and literal composition as in predict_and_score."""
+    threshold, else 255.  No metric counting, no histogram.  Engine and literal composition, and `slide`, as in predict_and_score."""
     K = int(num_classes)
     size = tuple(label.shape[-2:])
     if hasattr(classifier, "predict_mask_multi") and image.is_cuda:
+        if slide is not None:
+            _require_single_scale_slide(scales)
+            return _engine_masks_slide(feature_extractor, classifier, image, size, flip, slide,
+                                       class_threshold=_class_table(class_threshold, K, "cpu"), want_pseudo=True)[1]
         return _engine_masks(feature_extractor, classifier, image, size, flip, tuple(scales), class_threshold=_class_table(class_threshold, K, "cpu"),
                              want_pseudo=True)[1]
-    return literal_pseudo(_literal_output(feature_extractor, classifier, image, label, flip, tuple(scales)), class_threshold)
+    return literal_pseudo(_literal_output(feature_extractor, classifier, image, label, flip, tuple(scales), slide), class_threshold)
 
 
 # ----------------------------------------------------------------------------- CRF refinement (TEST.CRF)

@@ -316,6 +316,37 @@ class ASPP_Classifier_V2(nn.Module):
                                                   ignore_index=ignore_index, threshold=threshold, want_pseudo=want_pseudo,
                                                   class_threshold=class_threshold, hist=hist)
 
+    def slide_lows(self, feats, flip):
+        """The 1/8-resolution logits of sliding-window evaluation: feats = feature maps [b,C,h,w] whose images are, in order, the windows'
+        crops (flip False) or every crop followed by its horizontal mirror (flip True).  Returns (lows, mirror_lows): per window [h,w,K] fp32,
+        mirror_lows None without flip."""
+        lows, _ = self._lows_multi(feats, [(False,) * f.shape[0] for f in feats], "slide_lows")
+        if not flip:
+            return lows, None
+        if len(lows) % 2:
+            raise ValueError("slide_lows: flip needs a crop and its mirror per window, got %d images" % len(lows))
+        return lows[0::2], lows[1::2]
+
+    def predict_probs_slide(self, feats, flip, origins, window, size):
+        """The tail of metrics.slide_inference in one kernel (kernels.upsample_softmax_slide): feats as in slide_lows, origins[i] = (y0, x0)
+        of window i in label coordinates, window = (wh, ww) label pixels per window, size = the label's.  [1,K,H,W] fp32: the windows'
+        probabilities (flip: each the mean of the crop's and the mirrored crop's) averaged where they overlap."""
+        from .. import kernels
+        with torch.no_grad():
+            lows, mirror_lows = self.slide_lows(feats, flip)
+            return kernels.upsample_softmax_slide(lows, mirror_lows, origins, tuple(int(s) for s in window), tuple(int(s) for s in size))
+
+    def predict_mask_slide(self, feats, flip, origins, window, size, labels=None, ignore_index=255, threshold=0.0, want_pseudo=False,
+                           class_threshold=None, hist=None):
+        """predict_probs_slide(feats, flip, origins, window, size).max(1) without the probability map: (pred, pseudo, counts) of
+        kernels.upsample_predict_score_slide; the keywords are those of predict_mask_multi."""
+        from .. import kernels
+        with torch.no_grad():
+            lows, mirror_lows = self.slide_lows(feats, flip)
+            return kernels.upsample_predict_score_slide(lows, mirror_lows, origins, tuple(int(s) for s in window), tuple(int(s) for s in size),
+                                                        labels=labels, ignore_index=ignore_index, threshold=threshold, want_pseudo=want_pseudo,
+                                                        class_threshold=class_threshold, hist=hist)
+
     def predict_mask(self, x, size, labels=None, ignore_index=255, threshold=0.0, want_pseudo=False, class_threshold=None, hist=None):
         """predict_probs(x, size)[:1].max(1) without the probability map: the whole batch goes through the head as in predict_probs, image 0's
         logits are scored (inference() keeps image 0, utility.py:190)."""

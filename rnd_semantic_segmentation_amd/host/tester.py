@@ -8,8 +8,8 @@ import torch
 
 from .metrics import (PSEUDO_BINS, AverageMeter, class_thresholds, classwise_pseudo_labels, classwise_settings, confusion_matrix, crf_channel_scale,
                       crf_refine_output, crf_settings, dump_json, inference, intersectionAndUnionGPU, literal_histogram, literal_pseudo,
-                      multi_scale_inference, predict_and_score, require_no_polyp_metrics, score_settings, strip_prefix_if_present, threshold_table,
-                      tta_settings)
+                      multi_scale_inference, predict_and_score, require_no_polyp_metrics, score_settings, slide_inference, slide_plan, slide_settings,
+                      strip_prefix_if_present, threshold_table, tta_settings)
 from .modules import build_classifier, build_feature_extractor
 
 
@@ -29,6 +29,7 @@ class ASPPTester:
         require_no_polyp_metrics(cfg, "ASPPTester")
         self.crf = crf_settings(cfg)                       # TEST.CRF: None, or the parameters of kernels.crf_refine (a stray CRF_* key is refused)
         self.crf_scale = crf_channel_scale(cfg) if self.crf is not None else None
+        self.slide = slide_settings(cfg)                   # TEST.SLIDE: None, or (crop, stride), each (h, w) (a stray SLIDE_* key is refused)
         self.feature_extractor = self.build_feature_extractor(cfg)
         self.feature_extractor.to(device)
         self.classifier = self.build_classifier(cfg)
@@ -62,7 +63,9 @@ class ASPPTester:
         mask.save(os.path.join(folder, name[0] + ".png"))
 
     def _literal_output(self, x, y, single, scales, flip):
-        if single:
+        if self.slide is not None:
+            output = slide_inference(self.feature_extractor, self.classifier, x, y, self.slide[0], self.slide[1], flip=flip)
+        elif single:
             output = inference(self.feature_extractor, self.classifier, x, y, flip=False)     # [1,K,H,W]
         else:
             # the call aspp_tester.py:61 keeps commented out
@@ -91,12 +94,19 @@ class ASPPTester:
                              "on the refined map.".format(**self.crf))
         # TEST.PSEUDO_CLASSWISE: this loop is pass 1 - the metrics as ever, no masks, and the confidence histogram of the whole set on the device
         hist = torch.zeros(num_classes, PSEUDO_BINS, dtype=torch.int64, device=self.device) if classwise else None
+        grid = None
         for x, y, name in self.test_loader:
             x = x.to(self.device, non_blocking=True)
             y = y.to(self.device, non_blocking=True).long()
+            if self.slide is not None and grid != tuple(x.shape[-2:]):
+                grid = tuple(x.shape[-2:])
+                rows, cols, (wh, ww) = slide_plan(grid, *self.slide)
+                self.logger.info("TEST.SLIDE: {} x {} windows of {} x {}, stride {} over {} x {} pictures.".format(
+                    len(rows), len(cols), wh, ww, " x ".join(str(s) for s in (self.slide[1][:1] if self.slide[1][0] == self.slide[1][1] else self.slide[1])), grid[0], grid[1]))
             if fused:
                 r = predict_and_score(self.feature_extractor, self.classifier, x, y, flip=flip, scales=scales, num_classes=num_classes,
-                                      ignore_index=self.cfg.INPUT.IGNORE_LABEL, threshold=0.0 if classwise else threshold, hist=hist)
+                                      ignore_index=self.cfg.INPUT.IGNORE_LABEL, threshold=0.0 if classwise else threshold, hist=hist,
+                                      slide=self.slide)
                 if self.saveres and not classwise:
                     self.save_mask(r.pred if r.pseudo is None else r.pseudo, name)
                 cmt = cmt + r.cmt
@@ -148,7 +158,7 @@ class ASPPTester:
             y = y.to(self.device, non_blocking=True).long()
             if fused:
                 mask = classwise_pseudo_labels(self.feature_extractor, self.classifier, x, y, flip=flip, scales=scales, num_classes=num_classes,
-                                               class_threshold=thresholds)
+                                               class_threshold=thresholds, slide=self.slide)
             else:
                 mask = literal_pseudo(self._literal_output(x, y, single, scales, flip), thresholds)
             self.save_mask(mask, name)

@@ -785,6 +785,82 @@ def upsample_predict_score(lows, mirrors, size, div_a, div_b=1.0, labels=None, i
     return pred, pseudo, counts
 
 
+def _slide_windows(who, lows, mirror_lows, origins, window, size):
+    """The MiSlideWindow array of the sliding-window tails and (n, h, w, K, device).  lows: per-window [h,w,K] fp32 NHWC logits, all of one size;
+    mirror_lows: None, or the logits of the mirrored crops, one per window; origins: per-window (y0, x0) in label coordinates; window = (wh, ww)
+    label pixels per window; size = (H, W) of the label.  What depends on the geometry (bounds, cover) is the launcher's to refuse."""
+    n = len(lows)
+    if not 1 <= n <= _lib.SLIDE_MAX_WINDOWS:
+        raise _lib.MiError("%s: 1..%d windows (got %d)" % (who, _lib.SLIDE_MAX_WINDOWS, n))
+    if len(origins) != n or (mirror_lows is not None and len(mirror_lows) != n):
+        raise _lib.MiError("%s: %d windows but %d origins / %s mirror maps" % (who, n, len(origins), "no" if mirror_lows is None else len(mirror_lows)))
+    shape, dev = tuple(lows[0].shape), lows[0].device
+    if len(shape) != 3:
+        raise _lib.MiError("%s: lows[0] must be [h,w,K], got %s" % (who, shape))
+    win = (_lib.MiSlideWindow * n)()
+    for i in range(n):
+        for what, low in (("lows", lows[i]), ("mirror_lows", None if mirror_lows is None else mirror_lows[i])):
+            if low is None:
+                continue
+            _chk(low, torch.float32, "%s[%d]" % (what, i))
+            if tuple(low.shape) != shape or low.device != dev:
+                raise _lib.MiError("%s[%d] must be %s on %s, got %s on %s" % (what, i, shape, dev, tuple(low.shape), low.device))
+        win[i].low = lows[i].data_ptr()
+        win[i].low_mirror = None if mirror_lows is None else mirror_lows[i].data_ptr()
+        win[i].y0, win[i].x0 = int(origins[i][0]), int(origins[i][1])
+    return win, n, shape[0], shape[1], shape[2], dev
+
+
+def upsample_softmax_slide(lows, mirror_lows, origins, window, size):
+    """Sliding-window inference tail in one launch (mi_upsample_softmax_slide): window i covers the label rectangle origins[i] + window; per
+    pixel, the windows that contain it contribute softmax(bilinear(low_i -> window)) at its window-local coordinates - averaged with the
+    mirrored crop's map read at the mirrored column when mirror_lows is given, as inference(flip=True) does - summed in window order and
+    divided by their number.  Returns [1,K,H,W] fp32.  Arguments: _slide_windows."""
+    win, n, h, w, K, dev = _slide_windows("upsample_softmax_slide", lows, mirror_lows, origins, window, size)
+    H, W = size
+    probs = torch.empty((1, K, H, W), dtype=torch.float32, device=dev)
+    check(_lib.lib().mi_upsample_softmax_slide(ctypes.cast(win, ctypes.c_void_p), n, h, w, int(window[0]), int(window[1]), _p(probs), K, H, W,
+                                               _stream()), "mi_upsample_softmax_slide")
+    return probs
+
+
+def upsample_predict_score_slide(lows, mirror_lows, origins, window, size, labels=None, ignore_index=255, threshold=0.0, want_pseudo=False, *,
+                                 class_threshold=None, hist=None):
+    """The evaluation tail of upsample_softmax_slide without the probability map (mi_upsample_predict_score_slide).  Returns (pred, pseudo,
+    counts) and takes labels, ignore_index, threshold, want_pseudo, class_threshold and hist exactly as upsample_predict_score does: the
+    kernel body after the per-pixel values is the same."""
+    who = "upsample_predict_score_slide"
+    win, n, h, w, K, dev = _slide_windows(who, lows, mirror_lows, origins, window, size)
+    H, W = size
+    counts = None
+    if labels is not None:
+        _chk(labels, torch.int64, "labels")
+        if tuple(labels.shape) != (H, W) or labels.device != dev:
+            raise _lib.MiError("labels must be [%d,%d] on %s, got %s on %s" % (H, W, dev, tuple(labels.shape), labels.device))
+        counts = torch.zeros(K * K + 3 * K, dtype=torch.int64, device=dev)
+    table = None
+    if class_threshold is not None:
+        values = [float(v) for v in (class_threshold.tolist() if hasattr(class_threshold, "tolist") else class_threshold)]
+        if len(values) != K:
+            raise _lib.MiError("class_threshold must hold %d values, got %d" % (K, len(values)))
+        table = (ctypes.c_float * K)(*values)
+    elif want_pseudo and hist is not None:
+        raise _lib.MiError("%s: want_pseudo with hist needs class_threshold (the scalar threshold is the plain tail's)" % who)
+    bins = 0
+    if hist is not None:
+        _chk(hist, torch.int64, "hist")
+        if hist.dim() != 2 or hist.shape[0] != K or hist.device != dev:
+            raise _lib.MiError("hist must be [%d,bins] on %s, got %s on %s" % (K, dev, tuple(hist.shape), hist.device))
+        bins = int(hist.shape[1])
+    pred = torch.empty((H, W), dtype=torch.uint8, device=dev)
+    pseudo = torch.empty((H, W), dtype=torch.uint8, device=dev) if want_pseudo else None
+    check(_lib.lib().mi_upsample_predict_score_slide(ctypes.cast(win, ctypes.c_void_p), n, h, w, int(window[0]), int(window[1]), K, H, W, _p(labels),
+                                                     int(ignore_index), float(threshold),
+                                                     ctypes.cast(table, ctypes.c_void_p) if table is not None else None, _p(pred), _p(pseudo),
+                                                     _p(counts), bins, _p(hist), _stream()), "mi_upsample_predict_score_slide")
+    return pred, pseudo, counts
+
+
 def split_counts(counts, K):
     """The layout of mi_upsample_predict_score's counts (include/mi355seg.h): (cmt [K,K], intersection [K], output [K], target [K])."""
     return counts[:K * K].reshape(K, K), counts[K * K:K * K + K], counts[K * K + K:K * K + 2 * K], counts[K * K + 2 * K:K * K + 3 * K]
