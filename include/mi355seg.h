@@ -483,6 +483,32 @@ int mi_crf_refine(const float* probs /*[B][K][H][W]*/, const float* image /*[B][
                   float pos_w, float pos_xy, float bi_w, float bi_xy, float bi_rgb,
                   void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- Boundary IoU and trimap IoU of one picture (TEST.BOUNDARY; not in the reference: Cheng et al., CVPR 2021, and DeepLab's trimap plot) ----
+ * pred [H][W] uint8, labels [H][W] int64, K classes, ignore_index outside [0, K), D the largest band width asked for.  Two class maps:
+ *   G(p) = labels(p) where it lies in [0, K), else 255
+ *   P(p) = 255 where labels(p) == ignore_index, else pred(p) where it is < K, else 255      (intersectionAndUnionGPU: output[target == ignore] = ignore)
+ * For a map L and a pixel with L(p) < K, e_L(p) is the number of 3 x 3 erosions (outside the picture = background) p survives in the binary
+ * mask L == L(p), capped at D: the largest r <= D whose (2r+1) x (2r+1) window around p lies inside the picture and is uniformly L(p).
+ * Separably: a(y,x) = min(D, the largest r with L(y, x-r..x+r) inside the row and all equal to L(y,x)); radius r + 1 holds iff rows y +- (r+1)
+ * exist, carry L(y,x) in column x, and the minimum of a over rows y-(r+1) .. y+(r+1) of column x is >= r + 1.  p lies in the boundary band of
+ * width d of its class iff e_L(p) < d (mask - erode^d(mask)).
+ * The call ADDS to hist, int64 [5][K][D+1] on the device (the caller zeroes it; calls into one buffer add up):
+ *   hist[0][k][eG]           G == k             ground-truth band sizes, trimap target area
+ *   hist[1][k][eP]           P == k             prediction band sizes
+ *   hist[2][k][max(eG, eP)]  G == P == k        Boundary-IoU intersection
+ *   hist[3][k][eG]           G == P == k        trimap intersection
+ *   hist[4][k][eG]           P == k, G < K      trimap output area, by predicted class
+ * With S_i[k] = sum of hist[i][k][0 .. d-1]: Boundary IoU at width d = S2 / (S0 + S1 - S2), trimap IoU = S3 / (S0 + S4 - S3).  Summed over
+ * all D + 1 cells, hist[3], hist[4] and hist[0] are intersectionAndUnionGPU's area_intersection, area_output and area_target.
+ * Integers only (no floating point, integer atomics): two calls give the same bits.  Two launches on `stream`, nothing read back (capturable
+ * in a HIP graph).  The workspace (mi_boundary_score_workspace bytes, 4-byte aligned, no initialisation needed) holds one 32-bit word per pixel
+ * between them; mi_boundary_score_workspace returns 0 for sizes the call refuses.
+ * Refused before any launch (MI_EINVAL unless stated): a NULL pred / labels / hist / workspace, a non-positive size, H * W >= 2^31, K outside
+ * 1..32, D outside 1..64, ignore_index inside [0, K), a workspace that is too small (MI_ENOMEM). */
+size_t mi_boundary_score_workspace(int H, int W);
+int mi_boundary_score(const uint8_t* pred /*[H][W]*/, const int64_t* labels /*[H][W]*/, int H, int W, int K, int ignore_index, int D,
+                      int64_t* hist /*[5][K][D+1], added to*/, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- optimiser: torch.optim.SGD(momentum, weight_decay) on flat fp32 buffers (aspp_trainer.py:25-26,94-95)
  * g' = g + wd*p; buf = mu*buf + g'; p -= lr*buf  (buf zero-initialised == torch's first-step buf = g'). */
 int mi_sgd_step(float* p, const float* g, float* buf, size_t n, float lr, float momentum, float weight_decay, void* stream);

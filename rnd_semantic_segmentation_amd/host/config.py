@@ -225,12 +225,19 @@ def default_tree():
         # with SLIDE_STRIDE, each is evaluated as inference() evaluates a picture (with FLIP: averaged with its mirror) and the windows'
         # probabilities are averaged where they overlap - on the fused path in one kernel after the windows' backbone passes
         # (mi_upsample_predict_score_slide).  SCALES must stay (1.0,); a SLIDE_* key changed while SLIDE is False is refused
-        # (metrics.slide_settings)
+        # (metrics.slide_settings);
+        # BOUNDARY True (ASPPTester only; the other testers refuse it) = besides the region metrics, Boundary IoU (Cheng et al., CVPR 2021) and
+        # DeepLab's trimap IoU per class: both restricted to the band of BOUNDARY_WIDTHS pixels (3 x 3 erosions) inside each class's contours,
+        # counted on the mask the evaluation already has by one HIP kernel pair per picture (mi_boundary_score), whatever SCALES, FLIP, CRF, SLIDE
+        # or the thresholds are; logged and written to OUTPUT_DIR/aspp_boundary_metrics.json.  BOUNDARY_WIDTHS () = 2 % of the label's diagonal
+        # (46 at 1024 x 2048; every label must then have the first one's size), else strictly increasing integers in 1..64.  BOUNDARY_WIDTHS
+        # changed while BOUNDARY is False is refused (metrics.boundary_settings)
         "TEST": {"BATCH_SIZE": 1, "PRECISION": "fp32", "SCALES": (1.0,), "FLIP": False, "FUSED_SCORE": True, "PSEUDO_THRESHOLD": 0.0,
                  "PSEUDO_CLASSWISE": False, "PSEUDO_PORTION": 0.5, "POLYP_METRICS": False,
                  "CRF": False, "CRF_ITER": 5, "CRF_WINDOW": 7, "CRF_DILATION": 4, "CRF_POS_W": 3.0, "CRF_POS_XY": 3.0, "CRF_BI_W": 10.0,
                  "CRF_BI_XY": 80.0, "CRF_BI_RGB": 13.0,
-                 "SLIDE": False, "SLIDE_CROP": (769, 769), "SLIDE_STRIDE": (513, 513)},
+                 "SLIDE": False, "SLIDE_CROP": (769, 769), "SLIDE_STRIDE": (513, 513),
+                 "BOUNDARY": False, "BOUNDARY_WIDTHS": ()},
         "OUTPUT_DIR": ".",
         "resume": "",
         "PSEUDO_DIR": "",

@@ -26,6 +26,9 @@ Differences that are deliberate and documented:
    protocol DeepLab and PSPNet report Cityscapes under - crop-sized windows slid over the full-resolution picture, each evaluated as
    inference() evaluates a picture, averaged where they overlap.  slide_inference is the literal composition; predict_and_score(slide=...)
    on the engine runs the windows' backbone passes and then ONE kernel (mi_upsample_predict_score_slide).
+ * the boundary metrics (boundary_survival, literal_boundary_histograms, boundary_summary, boundary_settings; TEST.BOUNDARY) are not in the
+   reference either: Boundary IoU (Cheng et al., CVPR 2021) and DeepLab's trimap IoU at every band width up to 64 from five integer
+   histograms of erosion counts, which mi_boundary_score adds up on the device in two launches per picture.
 """
 import json
 import logging
@@ -377,6 +380,136 @@ def require_no_slide(cfg, who):
     if slide_settings(cfg) is not None:
         raise NotImplementedError("%s: TEST.SLIDE - sliding-window evaluation exists for the DeepLab (feature extractor, classifier) pair only "
                                   "(ASPPTester); leave it False" % (who,))
+
+
+# ----------------------------------------------------------------------------- boundary metrics (TEST.BOUNDARY)
+BOUNDARY_MAX_WIDTH = 64                 # D of mi_boundary_score (include/mi355seg.h, where the definition stands)
+BOUNDARY_MAX_CLASSES = 32
+BOUNDARY_MAPS = 5                       # ground-truth bands, prediction bands, Boundary-IoU intersection, trimap intersection, trimap output area
+
+
+def boundary_width(size):
+    """The band width Boundary IoU is published with: 2 % of the picture's diagonal, at least 1 (23 for 512 x 1024, 46 for 1024 x 2048)."""
+    return max(1, int(round(0.02 * math.hypot(int(size[0]), int(size[1])))))
+
+
+def _boundary_check(K, ignore_index, D):
+    if not 1 <= K <= BOUNDARY_MAX_CLASSES:
+        raise ValueError("boundary metrics: %d classes lie outside 1..%d" % (K, BOUNDARY_MAX_CLASSES))
+    if not 1 <= D <= BOUNDARY_MAX_WIDTH:
+        raise ValueError("boundary metrics: width %d lies outside 1..%d" % (D, BOUNDARY_MAX_WIDTH))
+    if ignore_index is not None and 0 <= ignore_index < K:
+        raise ValueError("boundary metrics: ignore_index %d names a class (%d classes)" % (ignore_index, K))
+
+
+def boundary_survival(L, K, D):
+    """e_L of include/mi355seg.h in torch ops: for a class map L [H,W] (values outside [0, K) = no class) the number of 3 x 3 erosions, with
+    everything outside the picture background, each pixel survives in the binary mask of its own class, capped at D; int64 [H,W], 0 where L
+    has no class.  Literally: the masks of all classes side by side as channels, eroded D times by max_pool2d of the negated, zero-padded mask."""
+    K, D = int(K), int(D)
+    _boundary_check(K, None, D)
+    L = L.reshape(L.shape[-2:]).long()
+    m = torch.stack([L == k for k in range(K)]).unsqueeze(0).float()                 # [1,K,H,W]
+    e = torch.zeros_like(m)
+    for _ in range(D):
+        m = -torch.nn.functional.max_pool2d(torch.nn.functional.pad(-m, (1, 1, 1, 1), value=0.0), 3, 1)
+        e += m
+    return e.sum(1)[0].long()
+
+
+def literal_boundary_histograms(pred, labels, K, ignore_index, D):
+    """What mi_boundary_score adds to hist for one picture, composed from torch ops on the inputs' device: int64 [5, K, D + 1].  The definition
+    the kernel is tested against, and the path of CPU tensors."""
+    K, D, ignore_index = int(K), int(D), int(ignore_index)
+    _boundary_check(K, ignore_index, D)
+    labels = labels.reshape(labels.shape[-2:]).long()
+    pred = pred.reshape(pred.shape[-2:]).long()
+    if pred.shape != labels.shape:
+        raise ValueError("boundary metrics: pred %s and labels %s differ in size" % (tuple(pred.shape), tuple(labels.shape)))
+    none = torch.full_like(labels, 255)
+    G = torch.where((labels >= 0) & (labels < K), labels, none)
+    P = torch.where((labels != ignore_index) & (pred >= 0) & (pred < K), pred, none)
+    eG, eP = boundary_survival(G, K, D), boundary_survival(P, K, D)
+    g, p = G < K, P < K
+    hit = g & (G == P)
+
+    def cells(sel, k, e):
+        return torch.bincount(k[sel] * (D + 1) + e[sel], minlength=K * (D + 1)).reshape(K, D + 1)
+
+    return torch.stack([cells(g, G, eG), cells(p, P, eP), cells(hit, G, torch.maximum(eG, eP)), cells(hit, G, eG), cells(p & g, P, eG)])
+
+
+def boundary_accumulate(pred, label, K, ignore_index, D, hist):
+    """One picture into the data set's hist (int64 [5, K, D + 1] on the picture's device): mi_boundary_score on the GPU, the literal composition
+    for CPU tensors - the same integers."""
+    if pred.is_cuda:
+        from .. import kernels
+        return kernels.boundary_score(pred.to(torch.uint8).contiguous(), label.long().contiguous(), K, ignore_index, D, hist)
+    hist += literal_boundary_histograms(pred, label, K, ignore_index, D)
+    return hist
+
+
+def boundary_summary(hist, widths, names=None):
+    """Boundary IoU and trimap IoU from hist (int64 [5, K, D + 1]) at every width d of `widths` (1 <= d <= D): with S_i[k] the sum of
+    hist[i][k][:d], S2 / (S0 + S1 - S2) and S3 / (S0 + S4 - S3) per class.  A class whose union is 0 is None and left out of the mean (None
+    when no class is left).  Returns widths, classes, boundary_iou / trimap_iou [width][class], mean_boundary_iou / mean_trimap_iou [width]."""
+    hist = torch.as_tensor(hist).cpu().long()
+    if hist.dim() != 3 or hist.shape[0] != BOUNDARY_MAPS:
+        raise ValueError("boundary_summary: hist must be [%d, K, D + 1], got %s" % (BOUNDARY_MAPS, tuple(hist.shape)))
+    K, D = hist.shape[1], hist.shape[2] - 1
+    widths = [int(d) for d in widths]
+    if any(not 1 <= d <= D for d in widths):
+        raise ValueError("boundary_summary: widths %r lie outside 1..%d" % (widths, D))
+    names = [str(n) for n in names] if names is not None and len(names) == K else [str(k) for k in range(K)]
+    out = {"widths": widths, "classes": names, "boundary_iou": [], "trimap_iou": [], "mean_boundary_iou": [], "mean_trimap_iou": []}
+    for d in widths:
+        S = hist[:, :, :d].sum(2).tolist()
+        for key, inter, other in (("boundary_iou", S[2], S[1]), ("trimap_iou", S[3], S[4])):
+            union = [S[0][k] + other[k] - inter[k] for k in range(K)]
+            row = [inter[k] / union[k] if union[k] > 0 else None for k in range(K)]
+            kept = [v for v in row if v is not None]
+            out[key].append(row)
+            out["mean_" + key].append(sum(kept) / len(kept) if kept else None)
+    return out
+
+
+def boundary_settings(cfg):
+    """None while TEST.BOUNDARY is False (absent = False), else the tuple of band widths: empty = the 2 % width of the first label's size
+    (boundary_width), otherwise strictly increasing integers in 1..64.  TEST.BOUNDARY_WIDTHS changed while BOUNDARY is False is refused
+    instead of ignored."""
+    test = cfg.TEST
+    on = test["BOUNDARY"] if "BOUNDARY" in test else False
+    if not isinstance(on, bool):
+        raise ValueError("TEST.BOUNDARY %r must be True or False" % (on,))
+    widths = test["BOUNDARY_WIDTHS"] if "BOUNDARY_WIDTHS" in test else ()
+    if not isinstance(widths, (tuple, list)):
+        raise ValueError("TEST.BOUNDARY_WIDTHS %r must be a list of integers" % (widths,))
+    widths = tuple(widths)
+    if not on:
+        if widths != ():
+            raise NotImplementedError("TEST.BOUNDARY_WIDTHS %r belongs to TEST.BOUNDARY True" % (widths,))
+        return None
+    if any(isinstance(d, bool) or not isinstance(d, int) for d in widths):
+        raise ValueError("TEST.BOUNDARY_WIDTHS %r must be integers" % (widths,))
+    if any(not 1 <= d <= BOUNDARY_MAX_WIDTH for d in widths):
+        raise ValueError("TEST.BOUNDARY_WIDTHS %r lie outside 1..%d" % (widths, BOUNDARY_MAX_WIDTH))
+    if any(b <= a for a, b in zip(widths, widths[1:])):
+        raise ValueError("TEST.BOUNDARY_WIDTHS %r must be strictly increasing" % (widths,))
+    K = int(cfg.MODEL.NUM_CLASSES) if "MODEL" in cfg and "NUM_CLASSES" in cfg.MODEL else 1
+    if not 1 <= K <= BOUNDARY_MAX_CLASSES:
+        raise ValueError("TEST.BOUNDARY: MODEL.NUM_CLASSES %d lies outside 1..%d" % (K, BOUNDARY_MAX_CLASSES))
+    ignore = int(cfg.INPUT.IGNORE_LABEL) if "INPUT" in cfg and "IGNORE_LABEL" in cfg.INPUT else 255
+    if 0 <= ignore < K:
+        raise ValueError("TEST.BOUNDARY: INPUT.IGNORE_LABEL %d names one of the %d classes" % (ignore, K))
+    return widths
+
+
+def require_no_boundary(cfg, who):
+    """The boundary metrics are counted on ASPPTester's masks: the other testers refuse the key rather than ignore it (a stray BOUNDARY_WIDTHS
+    is refused by boundary_settings itself)."""
+    if boundary_settings(cfg) is not None:
+        raise NotImplementedError("%s: TEST.BOUNDARY - Boundary IoU and trimap IoU exist for the DeepLab (feature extractor, classifier) pair "
+                                  "only (ASPPTester); leave it False" % (who,))
 
 
 def tta_settings(cfg):

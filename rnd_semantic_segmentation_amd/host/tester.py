@@ -6,7 +6,8 @@ import os
 import numpy as np
 import torch
 
-from .metrics import (PSEUDO_BINS, AverageMeter, class_thresholds, classwise_pseudo_labels, classwise_settings, confusion_matrix, crf_channel_scale,
+from .metrics import (BOUNDARY_MAPS, BOUNDARY_MAX_WIDTH, PSEUDO_BINS, AverageMeter, boundary_accumulate, boundary_settings, boundary_summary,
+                      boundary_width, class_thresholds, classwise_pseudo_labels, classwise_settings, confusion_matrix, crf_channel_scale,
                       crf_refine_output, crf_settings, dump_json, inference, intersectionAndUnionGPU, literal_histogram, literal_pseudo,
                       multi_scale_inference, predict_and_score, require_no_polyp_metrics, score_settings, slide_inference, slide_plan, slide_settings,
                       strip_prefix_if_present, threshold_table, tta_settings)
@@ -30,6 +31,7 @@ class ASPPTester:
         self.crf = crf_settings(cfg)                       # TEST.CRF: None, or the parameters of kernels.crf_refine (a stray CRF_* key is refused)
         self.crf_scale = crf_channel_scale(cfg) if self.crf is not None else None
         self.slide = slide_settings(cfg)                   # TEST.SLIDE: None, or (crop, stride), each (h, w) (a stray SLIDE_* key is refused)
+        self.boundary = boundary_settings(cfg)             # TEST.BOUNDARY: None, or the band widths (empty = 2 % of the label's diagonal)
         self.feature_extractor = self.build_feature_extractor(cfg)
         self.feature_extractor.to(device)
         self.classifier = self.build_classifier(cfg)
@@ -95,6 +97,7 @@ class ASPPTester:
         # TEST.PSEUDO_CLASSWISE: this loop is pass 1 - the metrics as ever, no masks, and the confidence histogram of the whole set on the device
         hist = torch.zeros(num_classes, PSEUDO_BINS, dtype=torch.int64, device=self.device) if classwise else None
         grid = None
+        self.boundary_hist = self.boundary_size = None     # TEST.BOUNDARY: one int64 [5, K, D + 1] buffer on the device for the whole set
         for x, y, name in self.test_loader:
             x = x.to(self.device, non_blocking=True)
             y = y.to(self.device, non_blocking=True).long()
@@ -109,6 +112,8 @@ class ASPPTester:
                                       slide=self.slide)
                 if self.saveres and not classwise:
                     self.save_mask(r.pred if r.pseudo is None else r.pseudo, name)
+                if self.boundary is not None:
+                    self._boundary_count(r.pred, y[0])
                 cmt = cmt + r.cmt
                 self.meter.update(*[t.numpy() for t in (r.intersection, r.union, r.target, r.output)])
                 continue
@@ -122,6 +127,8 @@ class ASPPTester:
                 top = output.max(1)
                 self.save_mask(torch.where(top[0] >= threshold, pred, torch.full_like(pred, 255))[0], name)
             y0 = y[:1]                                    # inference() keeps image 0 only (utility.py:190)
+            if self.boundary is not None:
+                self._boundary_count(pred[0].to(torch.uint8), y0[0])
             cmt = cmt + confusion_matrix(self.cfg, torch.flatten(pred), torch.flatten(y0))
             inter, union, target, res = intersectionAndUnionGPU(pred, y0, num_classes, self.cfg.INPUT.IGNORE_LABEL)
             self.meter.update(*[t.cpu().numpy() for t in (inter, union, target, res)])
@@ -129,9 +136,44 @@ class ASPPTester:
         os.makedirs(self.cfg.OUTPUT_DIR, exist_ok=True)
         dump_json(os.path.join(self.cfg.OUTPUT_DIR, "aspp_confusion_matrix.json"),
                   {"cmt": cmt.tolist(), "classes": list(self.trainid2name.values())})
+        if self.boundary is not None:
+            self._boundary_report()
         if classwise:
             self._classwise_masks(hist, portion, cap, fused, single, scales, flip)
         return cmt
+
+    def _boundary_count(self, pred, label):
+        """TEST.BOUNDARY, one picture: the mask the evaluation already has (uint8 [H,W]) and label 0 into the set's histograms.  The widths are
+        fixed at the first label: the configured ones, or the 2 % width of its size."""
+        size = tuple(label.shape[-2:])
+        if self.boundary_hist is None:
+            self.boundary_size = size
+            self.boundary_widths = self.boundary if self.boundary else (boundary_width(size),)
+            if self.boundary_widths[-1] > BOUNDARY_MAX_WIDTH:
+                raise ValueError("TEST.BOUNDARY_WIDTHS (): 2 % of the diagonal of a {} x {} label is {} pixels, more than {}; set the widths".format(
+                    size[0], size[1], self.boundary_widths[-1], BOUNDARY_MAX_WIDTH))
+            self.boundary_hist = torch.zeros(BOUNDARY_MAPS, self.cfg.MODEL.NUM_CLASSES, self.boundary_widths[-1] + 1, dtype=torch.int64,
+                                             device=label.device)
+            self.logger.info("TEST.BOUNDARY: Boundary IoU and trimap IoU at band widths {}.".format(", ".join(str(d) for d in self.boundary_widths)))
+        elif not self.boundary and size != self.boundary_size:
+            raise ValueError("TEST.BOUNDARY_WIDTHS (): the band width is 2 % of the first label's diagonal ({} x {}), and this label is {} x {}; "
+                             "set TEST.BOUNDARY_WIDTHS for a set of mixed sizes".format(*(self.boundary_size + size)))
+        boundary_accumulate(pred, label, self.cfg.MODEL.NUM_CLASSES, self.cfg.INPUT.IGNORE_LABEL, self.boundary_widths[-1], self.boundary_hist)
+
+    def _boundary_report(self):
+        """After the loop of TEST.BOUNDARY: one device-to-host copy, one line per width and class, OUTPUT_DIR/aspp_boundary_metrics.json."""
+        if self.boundary_hist is None:
+            return
+        self.boundary_hist = hist = self.boundary_hist.cpu()
+        self.boundary_metrics = table = boundary_summary(hist, self.boundary_widths, list(self.trainid2name.values()))
+        for i, d in enumerate(table["widths"]):
+            self.logger.info("Boundary metric, width {}: mean Boundary IoU/trimap IoU {}/{}.".format(
+                d, *("n/a" if v is None else "{:.4f}".format(v) for v in (table["mean_boundary_iou"][i], table["mean_trimap_iou"][i]))))
+            for c, cls in enumerate(table["classes"]):
+                self.logger.info("Boundary metric, width {}, class {} ({}): Boundary IoU/trimap IoU {}/{}.".format(
+                    d, c, cls, *("n/a" if v is None else "{:.4f}".format(v) for v in (table["boundary_iou"][i][c], table["trimap_iou"][i][c]))))
+        table = dict(table, max_width=int(hist.shape[2] - 1), hist=hist.tolist())
+        dump_json(os.path.join(self.cfg.OUTPUT_DIR, "aspp_boundary_metrics.json"), table)
 
     def _classwise_masks(self, hist, portion, cap, fused, single, scales, flip):
         """After pass 1 of TEST.PSEUDO_CLASSWISE: the thresholds from the histogram (one device-to-host copy), their table to the logger and to

@@ -1010,6 +1010,26 @@ def crf_refine(probs, image, cs, iters, window, dilation, pos_w, pos_xy, bi_w, b
     return CrfResult(out, pred, conf)
 
 
+def boundary_score(pred, labels, num_classes, ignore_index, max_width, hist):
+    """Boundary IoU / trimap IoU histograms of one picture (mi_boundary_score, the definition: include/mi355seg.h): pred uint8 [H,W], labels
+    int64 [H,W], hist int64 [5, num_classes, max_width + 1] on the same device.  ADDS this picture's counts to hist (the caller zeroes it once
+    per data set) and returns it.  Two launches on the current stream, nothing read back; workspace cached per stream."""
+    _chk(pred, torch.uint8, "pred")
+    _chk(labels, torch.int64, "labels")
+    _chk(hist, torch.int64, "hist")
+    K, D = int(num_classes), int(max_width)
+    if pred.dim() != 2 or labels.shape != pred.shape or labels.device != pred.device or hist.device != pred.device:
+        raise _lib.MiError("boundary_score: pred and labels [H,W] on one device with hist, got %s on %s, %s on %s, hist on %s"
+                           % (tuple(pred.shape), pred.device, tuple(labels.shape), labels.device, hist.device))
+    if tuple(hist.shape) != (5, K, D + 1):
+        raise _lib.MiError("boundary_score: hist must be [5, %d, %d], got %s" % (K, D + 1, tuple(hist.shape)))
+    H, W = pred.shape
+    ws = _workspace(_lib.lib().mi_boundary_score_workspace(H, W), pred.device, "boundary")
+    check(_lib.lib().mi_boundary_score(_p(pred), _p(labels), H, W, K, int(ignore_index), D, _p(hist), _p(ws), ws.numel(), _stream()),
+          "mi_boundary_score")
+    return hist
+
+
 def stem_pool_fwd(y, scale, shift):
     """y [B,Hc,Wc,C] bf16 (conv1 output) -> (pool [B,Hp,Wp,C] bf16, idx uint8): FrozenBN + ReLU + maxpool 3x3/2/1."""
     _chk(y, torch.bfloat16, "y")
