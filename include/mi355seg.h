@@ -424,6 +424,34 @@ int mi_upsample_predict_score_slide(const MiSlideWindow* win, int n, int h, int 
                                     int ignore_index, float threshold, const float* class_threshold, uint8_t* pred, uint8_t* pseudo,
                                     int64_t* counts, int bins, int64_t* hist, void* stream);
 
+/* ---- precision-recall and calibration histograms of the evaluation tails (TEST.CURVES) ---------
+ * What a confidence is worth on a labelled picture, as integer histograms of the per-pixel values a_0 .. a_{K-1} of the tails above:
+ * mi_upsample_curves takes those of mi_upsample_softmax_multi (same src, n, div_a, div_b), mi_upsample_curves_slide those of
+ * mi_upsample_softmax_slide (same windows): the same device code (multi_probs / slide_probs), so the histograms are functions of exactly
+ * the bits those entries write.  Only pixels whose label lies in [0, K) count - the confusion matrix's rule: 255, the ignore value and any
+ * other value outside count nowhere.  For every counted pixel with label g:
+ *   pr  DEVICE int64 [K][256][2] or NULL:  for every class k   pr[k][b][g == k] += 1,   b = min(255, max(0, int(a_k * 256)))
+ *       (a power-of-two scale and a truncation, exact in fp32: the bin is a function of the fp32 value alone);
+ *   cal DEVICE int64 [ece_bins][3] or NULL:  conf = max_k a_k, pred = the LOWEST index among the maxima,
+ *       m = min(ece_bins-1, max(0, int(conf * (float)ece_bins)))  (an fp32 product, truncated):
+ *       cal[m] += (1, pred == g, int(conf * 2^24))   - the last a fixed-point sum: the scale is exact, the integer sum has no order.
+ * Both are ADDED to (zeroed by the caller once per data set; launches into one buffer add up); one of them may be NULL.  Integer sums:
+ * bit-reproducible.  From pr the host reads per class the precision and recall at the 256 thresholds j/256, average precision, best F1 and
+ * the threshold that reaches a target precision; from cal ECE, MCE, accuracy and mean confidence (host/metrics.py curves_summary).
+ * Overflow: a picture adds at most H * W < 2^31 to a cell of pr and at most H * W * (2^24 + 1) to a cell of cal; 5 000 pictures of
+ * 2 M pixels each adding at most 2^24 + 1 are 1.7 * 10^17 < 2^63 = 9.2 * 10^18.
+ * Kernel: a dense per-workgroup LDS table (32-bit counters in the layout of pr, 64-bit calibration cells; dynamic, 2048 K + 24 ece_bins
+ * bytes), the two cells nearly every pixel hits - (k, bin 0, negative) and (k, bin 255, positive) - aggregated in the wave by ballots, a grid
+ * capped at 1024 workgroups that stride over the pixel tiles and flush once with 64-bit global adds.  One launch, capturable, no host
+ * round trip.  Two pixels per lane when W is even and labels is 16-byte aligned.
+ * Refused before launch: everything the corresponding predict-and-score entry refuses about its sources or windows (n, K > 32, a zero
+ * divisor, a bad source; the window geometry and the cover check), NULL labels, pr and cal both NULL, ece_bins outside 1..64 when cal is
+ * given, H * W >= 2^31 (the 32-bit counters of a workgroup could overflow). */
+int mi_upsample_curves(const MiProbSource* src, int n, int K, int H, int W, float div_a, float div_b, const int64_t* labels, int ece_bins,
+                       int64_t* pr, int64_t* cal, void* stream);
+int mi_upsample_curves_slide(const MiSlideWindow* win, int n, int h, int w, int wh, int ww, int K, int H, int W, const int64_t* labels,
+                             int ece_bins, int64_t* pr, int64_t* cal, void* stream);
+
 /* ---- polyp evaluation tail: what Dice / IoU / F-beta / E-measure / S-measure / MAE need of PraNet's map, without the host ever seeing the map ----
  * low [B][h][w] fp32 (the res2 logits), labels [B][H][W] int64 (ground truth in {0, 1}).  Per output pixel, all in fp32:
  *   z = bilinear(low -> H x W), align_corners False, ATen's source index, each axis interpolated as a + lambda (b - a): a constant map stays constant

@@ -64,6 +64,8 @@ SIGNATURES = {
     "mi_upsample_predict_score_cw": (I, [P, I, I, I, I, F, F, P, I, P, P, P, P, I, P, P]),
     "mi_upsample_softmax_slide": (I, [P, I, I, I, I, I, P, I, I, I, P]),
     "mi_upsample_predict_score_slide": (I, [P] + [I] * 8 + [P, I, F, P, P, P, P, I, P, P]),
+    "mi_upsample_curves": (I, [P, I, I, I, I, F, F, P, I, P, P, P]),
+    "mi_upsample_curves_slide": (I, [P] + [I] * 8 + [P, I, P, P, P]),
     "mi_polyp_score_workspace": (Z, [I] * 5),
     "mi_polyp_score": (I, [P, P] + [I] * 5 + [P, P, P, P, P, P, Z, P]),
     "mi_image_resize_ac": (I, [P, P] + [I] * 7 + [P]),

@@ -3,7 +3,8 @@
 // evaluation protocol of DeepLab / PSPNet on Cityscapes.  A source covers a rectangle of the output, not the whole of it.
 // The per-pixel arithmetic is slide_probs (upsample_common.h); the two kernel bodies are those of the multi-source tails (upsample_score.h) with
 // another value provider: arg max, thresholds, counting and the histogram are the same device code.  All arithmetic fp32.
-#include "upsample_score.h"
+// mi_upsample_curves_slide (TEST.CURVES) is the kernel body of upsample_curves.h with the same providers, behind the same window checks.
+#include "upsample_curves.h"
 
 namespace {
 
@@ -103,6 +104,23 @@ extern "C" int mi_upsample_predict_score_slide(const MiSlideWindow* win, int n, 
         launch_score_kernel(SlideProv<true>{wins, n, ay, ax}, K, H, W, labels, ignore_index, thr, cw, pred, pseudo, counts, hist, stream);
     else
         launch_score_kernel(SlideProv<false>{wins, n, ay, ax}, K, H, W, labels, ignore_index, thr, cw, pred, pseudo, counts, hist, stream);
+    MI_CHECK_LAUNCH(who);
+    return MI_OK;
+}
+
+extern "C" int mi_upsample_curves_slide(const MiSlideWindow* win, int n, int h, int w, int wh, int ww, int K, int H, int W, const int64_t* labels,
+                                        int ece_bins, int64_t* pr, int64_t* cal, void* stream) {
+    static const char* who = "mi_upsample_curves_slide";
+    MI_REQUIRE(win, "%s: null operand", who);
+    SlideWins wins;
+    bool mirror;
+    if (const int rc = slide_windows(who, win, n, h, w, wh, ww, K, H, W, wins, mirror)) return rc;
+    if (const int rc = curves_check(who, H, W, labels, ece_bins, pr, cal)) return rc;
+    const Axis ay = make_axis(h, wh), ax = make_axis(w, ww);
+    if (mirror)
+        launch_curves_kernel(SlideProv<true>{wins, n, ay, ax}, K, H, W, labels, ece_bins, pr, cal, stream);
+    else
+        launch_curves_kernel(SlideProv<false>{wins, n, ay, ax}, K, H, W, labels, ece_bins, pr, cal, stream);
     MI_CHECK_LAUNCH(who);
     return MI_OK;
 }

@@ -231,13 +231,25 @@ def default_tree():
         # counted on the mask the evaluation already has by one HIP kernel pair per picture (mi_boundary_score), whatever SCALES, FLIP, CRF, SLIDE
         # or the thresholds are; logged and written to OUTPUT_DIR/aspp_boundary_metrics.json.  BOUNDARY_WIDTHS () = 2 % of the label's diagonal
         # (46 at 1024 x 2048; every label must then have the first one's size), else strictly increasing integers in 1..64.  BOUNDARY_WIDTHS
-        # changed while BOUNDARY is False is refused (metrics.boundary_settings)
+        # changed while BOUNDARY is False is refused (metrics.boundary_settings);
+        # CURVES True (ASPPTester only; the other testers refuse it) = what a confidence is worth on a labelled split: per class the
+        # precision-recall curve over 256 probability thresholds (average precision, best F1, and the lowest threshold >= 0.5 whose
+        # pseudo-labels reach the precision CURVES_PRECISION, with the recall kept there) and the calibration of the winning probability over
+        # CURVES_ECE_BINS (1..64) bins (ECE, MCE, accuracy, mean confidence).  Integer histograms of the values the evaluation tail holds in
+        # registers, counted by one more launch per picture (mi_upsample_curves / mi_upsample_curves_slide), or from the map on the literal
+        # path (FUSED_SCORE False, CRF: then of the refined map); logged and written to OUTPUT_DIR/aspp_curves.json.  A CURVES_* key changed
+        # while CURVES is False is refused (metrics.curves_settings);
+        # PSEUDO_CLASS_THRESHOLDS = NUM_CLASSES thresholds in [0, 1] (() = off): with --saveres the pseudo-label masks keep a pixel where the
+        # winning probability reaches its class's threshold, in a single pass - for instance the "pseudo_class_thresholds" of an
+        # aspp_curves.json counted on a labelled split.  Refused together with PSEUDO_CLASSWISE or a non-zero PSEUDO_THRESHOLD
+        # (metrics.class_threshold_settings)
         "TEST": {"BATCH_SIZE": 1, "PRECISION": "fp32", "SCALES": (1.0,), "FLIP": False, "FUSED_SCORE": True, "PSEUDO_THRESHOLD": 0.0,
                  "PSEUDO_CLASSWISE": False, "PSEUDO_PORTION": 0.5, "POLYP_METRICS": False,
                  "CRF": False, "CRF_ITER": 5, "CRF_WINDOW": 7, "CRF_DILATION": 4, "CRF_POS_W": 3.0, "CRF_POS_XY": 3.0, "CRF_BI_W": 10.0,
                  "CRF_BI_XY": 80.0, "CRF_BI_RGB": 13.0,
                  "SLIDE": False, "SLIDE_CROP": (769, 769), "SLIDE_STRIDE": (513, 513),
-                 "BOUNDARY": False, "BOUNDARY_WIDTHS": ()},
+                 "BOUNDARY": False, "BOUNDARY_WIDTHS": (),
+                 "CURVES": False, "CURVES_ECE_BINS": 15, "CURVES_PRECISION": 0.9, "PSEUDO_CLASS_THRESHOLDS": ()},
         "OUTPUT_DIR": ".",
         "resume": "",
         "PSEUDO_DIR": "",

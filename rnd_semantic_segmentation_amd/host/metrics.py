@@ -512,6 +512,196 @@ def require_no_boundary(cfg, who):
                                   "only (ASPPTester); leave it False" % (who,))
 
 
+# ----------------------------------------------------------------------------- precision-recall curves and calibration (TEST.CURVES)
+CURVE_BINS = 256                        # probability bins per class (CV_BINS of csrc/upsample_curves.h)
+CURVE_MAX_ECE_BINS = 64
+CURVE_FIXED = 1 << 24                   # the fixed-point scale of the summed confidences
+CURVE_DEFAULTS = OrderedDict((("CURVES_ECE_BINS", 15), ("CURVES_PRECISION", 0.9)))      # TEST.CURVES_* of host/config.py
+
+
+def _curves_check(K, ece_bins):
+    if not 1 <= K:
+        raise ValueError("curves: %d classes" % (K,))
+    if isinstance(ece_bins, bool) or not isinstance(ece_bins, int) or not 1 <= ece_bins <= CURVE_MAX_ECE_BINS:
+        raise ValueError("curves: ece_bins %r lies outside 1..%d" % (ece_bins, CURVE_MAX_ECE_BINS))
+
+
+def literal_curves(output, label, K, ece_bins):
+    """What mi_upsample_curves adds to (pr, cal) for one picture, composed from torch ops on the map's device: the definition the kernel is
+    tested against, and the path of CPU tensors, of TEST.FUSED_SCORE False and of TEST.CRF.  output [1,K,H,W] fp32 probabilities, label[0]
+    the labels.  Only pixels whose label lies in [0, K) count (the confusion matrix's rule: 255, the ignore value and every other value
+    outside count nowhere).  Returns two int64 tensors:
+      pr  [K, 256, 2]   for every counted pixel and class k: pr[k, b, label == k] += 1, b = min(255, max(0, int(p_k * 256))) - a power-of-two
+                        scale and a truncation, exact in fp32, like confidence_bin;
+      cal [M, 3]        M = ece_bins; conf = the maximum of the K values, pred = the lowest index among the maxima,
+                        m = min(M - 1, max(0, int(conf * float32(M)))) (an fp32 product, truncated):
+                        cal[m] += (1, pred == label, int(conf * 2**24)) - the last a fixed-point sum: the scale is exact and the integer sum
+                        does not depend on the order."""
+    K, M = int(K), ece_bins
+    _curves_check(K, M)
+    p = output[0].float()
+    if p.dim() != 3 or p.shape[0] != K:
+        raise ValueError("curves: the map must be [1, %d, H, W], got %s" % (K, tuple(output.shape)))
+    lab = label[0] if label.dim() == 3 else label
+    lab = lab.reshape(p.shape[-2:]).long().to(p.device)
+    counted = (lab >= 0) & (lab < K)
+    lc = lab[counted]
+    pc = p[:, counted]                                                   # [K, n]
+    pr = torch.empty(K, CURVE_BINS, 2, dtype=torch.int64, device=p.device)
+    for k in range(K):
+        b = (pc[k] * float(CURVE_BINS)).long().clamp_(0, CURVE_BINS - 1)
+        pr[k] = torch.bincount(b * 2 + (lc == k).long(), minlength=CURVE_BINS * 2).reshape(CURVE_BINS, 2)
+    cal = torch.zeros(M, 3, dtype=torch.int64, device=p.device)
+    if lc.numel():
+        conf, pred = pc.max(0)                                           # the lowest index among equal maxima
+        m = (conf * float(M)).long().clamp_(0, M - 1)
+        cal[:, 0] = torch.bincount(m, minlength=M)
+        cal[:, 1] = torch.bincount(m[pred == lc], minlength=M)
+        cal[:, 2].index_add_(0, m, (conf * float(CURVE_FIXED)).long())
+    return pr, cal
+
+
+def _none_if_nan(v):
+    v = float(v)
+    return None if v != v else v
+
+
+def curves_summary(pr, cal, names=None, target_precision=0.9):
+    """Curves and calibration numbers, in float64, from pr int64 [K, 256, 2] and cal int64 [M, 3] (literal_curves / mi_upsample_curves).
+    Per class k, at the thresholds t_j = j / 256, j = 0..255: TP_j = sum of pr[k, b, 1] over b >= j, FP_j the same of pr[k, b, 0];
+    precision P_j = TP_j / (TP_j + FP_j), or 1 where nothing is left; recall R_j = TP_j / TP_0.
+      ap            sum_j (R_j - R_{j+1}) P_j with R_256 = 0: sklearn's average_precision_score on the scores b / 256; a class without a
+                    positive pixel (TP_0 == 0) has none (None) and is left out of mAP;
+      best_f1 / best_f1_threshold      the largest 2 P R / (P + R) and the lowest t_j that reaches it;
+      threshold_at_precision / recall_at_precision      the lowest t_j >= 0.5 with P_j >= target_precision and the recall kept there, None if none.
+    Above one half "p_c >= t" implies "c is the prediction" (two values above one half cannot sum to one; at t = 0.5 itself the one exception is
+    a pixel where two classes hold exactly 0.5 each), so for t >= 0.5 P_j and R_j are the precision and the coverage of the pseudo-labels
+    TEST.PSEUDO_THRESHOLD = t would write for class c;
+    pseudo_class_thresholds is the list TEST.PSEUDO_CLASS_THRESHOLDS takes: threshold_at_precision, and 1.0 where there is none.
+    Calibration: per bin m its count n_m, accuracy and mean confidence (None when empty); ece = sum_m n_m / N |acc_m - conf_m|, mce the largest
+    gap of a non-empty bin, accuracy and confidence over all counted pixels.  The bins are [m / M, (m + 1) / M) by truncation; Guo et al. (2017)
+    use (m / M, (m + 1) / M]: the two differ only for a confidence exactly on a bin edge."""
+    pr = np.asarray(torch.as_tensor(pr).cpu().numpy(), dtype=np.int64)
+    cal = np.asarray(torch.as_tensor(cal).cpu().numpy(), dtype=np.int64)
+    if pr.ndim != 3 or pr.shape[1:] != (CURVE_BINS, 2) or cal.ndim != 2 or cal.shape[1] != 3:
+        raise ValueError("curves_summary: pr must be [K, %d, 2] and cal [M, 3], got %s and %s" % (CURVE_BINS, pr.shape, cal.shape))
+    target = float(target_precision)
+    if not 0.0 < target <= 1.0:
+        raise ValueError("curves_summary: target precision %r lies outside (0, 1]" % (target_precision,))
+    K, M = pr.shape[0], cal.shape[0]
+    names = [str(n) for n in names] if names is not None and len(names) == K else [str(k) for k in range(K)]
+    out = {"bins": CURVE_BINS, "classes": names, "target_precision": target, "positives": [], "ap": [], "best_f1": [], "best_f1_threshold": [],
+           "threshold_at_precision": [], "recall_at_precision": [], "pseudo_class_thresholds": []}
+    half = CURVE_BINS // 2
+    for k in range(K):
+        tp = np.cumsum(pr[k, ::-1, 1])[::-1].astype(np.float64)
+        fp = np.cumsum(pr[k, ::-1, 0])[::-1].astype(np.float64)
+        kept = tp + fp
+        prec = np.where(kept > 0, tp / np.where(kept > 0, kept, 1.0), 1.0)
+        out["positives"].append(int(tp[0]))
+        if tp[0] == 0:
+            for key in ("ap", "best_f1", "best_f1_threshold", "threshold_at_precision", "recall_at_precision"):
+                out[key].append(None)
+            out["pseudo_class_thresholds"].append(1.0)
+            continue
+        rec = tp / tp[0]
+        out["ap"].append(float(np.sum((rec - np.append(rec[1:], 0.0)) * prec)))
+        den = prec + rec
+        f1 = np.where(den > 0, 2.0 * prec * rec / np.where(den > 0, den, 1.0), 0.0)
+        j = int(np.argmax(f1))
+        out["best_f1"].append(float(f1[j]))
+        out["best_f1_threshold"].append(j / CURVE_BINS)
+        ok = np.nonzero(prec[half:] >= target)[0]
+        if ok.size:
+            j = half + int(ok[0])
+            out["threshold_at_precision"].append(j / CURVE_BINS)
+            out["recall_at_precision"].append(float(rec[j]))
+            out["pseudo_class_thresholds"].append(j / CURVE_BINS)
+        else:
+            out["threshold_at_precision"].append(None)
+            out["recall_at_precision"].append(None)
+            out["pseudo_class_thresholds"].append(1.0)
+    aps = [v for v in out["ap"] if v is not None]
+    out["map"] = sum(aps) / len(aps) if aps else None
+    n = cal[:, 0].astype(np.float64)
+    N = float(n.sum())
+    acc = np.where(n > 0, cal[:, 1] / np.where(n > 0, n, 1.0), np.nan)
+    conf = np.where(n > 0, cal[:, 2] / (np.where(n > 0, n, 1.0) * CURVE_FIXED), np.nan)
+    gap = np.abs(acc - conf)
+    out["calibration"] = {"bins": M, "count": [int(v) for v in cal[:, 0]], "accuracy": [_none_if_nan(v) for v in acc],
+                          "confidence": [_none_if_nan(v) for v in conf],
+                          "ece": float(np.sum(np.where(n > 0, n * gap, 0.0)) / N) if N else None,
+                          "mce": float(np.nanmax(gap)) if N else None,
+                          "overall_accuracy": float(cal[:, 1].sum() / N) if N else None,
+                          "mean_confidence": float(cal[:, 2].sum() / (N * CURVE_FIXED)) if N else None}
+    return out
+
+
+def curves_accumulate(output, label, K, curves):
+    """literal_curves of one [1,K,H,W] map into the data set's (pr, cal)."""
+    pr, cal = literal_curves(output, label, K, int(curves[1].shape[0]))
+    curves[0].add_(pr.to(curves[0].device))
+    curves[1].add_(cal.to(curves[1].device))
+
+
+def curves_settings(cfg):
+    """None while TEST.CURVES is False (absent = False), else (ece_bins, target_precision): CURVES_ECE_BINS an integer in 1..64, CURVES_PRECISION
+    in (0, 1].  A CURVES_* key changed while CURVES is False is refused instead of ignored."""
+    test = cfg.TEST
+    on = test["CURVES"] if "CURVES" in test else False
+    if not isinstance(on, bool):
+        raise ValueError("TEST.CURVES %r must be True or False" % (on,))
+    bins = test["CURVES_ECE_BINS"] if "CURVES_ECE_BINS" in test else CURVE_DEFAULTS["CURVES_ECE_BINS"]
+    target = test["CURVES_PRECISION"] if "CURVES_PRECISION" in test else CURVE_DEFAULTS["CURVES_PRECISION"]
+    if isinstance(bins, bool) or not isinstance(bins, int) or not 1 <= bins <= CURVE_MAX_ECE_BINS:
+        raise ValueError("TEST.CURVES_ECE_BINS %r must be an integer in 1..%d" % (bins, CURVE_MAX_ECE_BINS))
+    if isinstance(target, bool) or not isinstance(target, (int, float)) or not 0.0 < target <= 1.0:      # (false for a NaN)
+        raise ValueError("TEST.CURVES_PRECISION %r lies outside (0, 1]" % (target,))
+    if not on:
+        for key, v in (("CURVES_ECE_BINS", bins), ("CURVES_PRECISION", target)):
+            if v != CURVE_DEFAULTS[key]:
+                raise NotImplementedError("TEST.%s %r belongs to TEST.CURVES True" % (key, v))
+        return None
+    return int(bins), float(target)
+
+
+def require_no_curves(cfg, who):
+    """The curves are counted in ASPPTester's evaluation tail: the other testers refuse the key rather than ignore it (a stray CURVES_* key is
+    refused by curves_settings itself), and TEST.PSEUDO_CLASS_THRESHOLDS with it."""
+    if curves_settings(cfg) is not None:
+        raise NotImplementedError("%s: TEST.CURVES - precision-recall curves and calibration exist for the DeepLab (feature extractor, classifier) "
+                                  "pair only (ASPPTester); leave it False" % (who,))
+    if "PSEUDO_CLASS_THRESHOLDS" in cfg.TEST and tuple(cfg.TEST["PSEUDO_CLASS_THRESHOLDS"]) != ():
+        raise NotImplementedError("%s: TEST.PSEUDO_CLASS_THRESHOLDS - per-class pseudo-label thresholds exist for the DeepLab (feature extractor, "
+                                  "classifier) pair only (ASPPTester); leave it ()" % (who,))
+
+
+def class_threshold_settings(cfg):
+    """None while TEST.PSEUDO_CLASS_THRESHOLDS is () (absent = ()), else the tuple of MODEL.NUM_CLASSES thresholds in [0, 1] the pseudo-label
+    masks are written with in a single pass (pred where the winning probability >= its class's threshold, else 255) - for instance
+    "pseudo_class_thresholds" of an aspp_curves.json counted on a labelled split.  Refused: together with PSEUDO_CLASSWISE (which takes its own
+    thresholds from the set) or a non-zero PSEUDO_THRESHOLD, a wrong length, a value outside [0, 1]."""
+    test = cfg.TEST
+    values = test["PSEUDO_CLASS_THRESHOLDS"] if "PSEUDO_CLASS_THRESHOLDS" in test else ()
+    if not isinstance(values, (tuple, list)):
+        raise ValueError("TEST.PSEUDO_CLASS_THRESHOLDS %r must be a list of numbers" % (values,))
+    values = tuple(values)
+    if values == ():
+        return None
+    if any(isinstance(v, bool) or not isinstance(v, (int, float)) or not 0.0 <= v <= 1.0 for v in values):
+        raise ValueError("TEST.PSEUDO_CLASS_THRESHOLDS %r must be numbers in [0, 1]" % (values,))
+    K = int(cfg.MODEL.NUM_CLASSES)
+    if len(values) != K:
+        raise ValueError("TEST.PSEUDO_CLASS_THRESHOLDS holds %d values for %d classes" % (len(values), K))
+    classwise, _, _ = classwise_settings(cfg)
+    if classwise:
+        raise NotImplementedError("TEST.PSEUDO_CLASS_THRESHOLDS and TEST.PSEUDO_CLASSWISE True: the thresholds are given or taken from the set, not both")
+    _, threshold = score_settings(cfg)
+    if threshold != 0.0:
+        raise NotImplementedError("TEST.PSEUDO_CLASS_THRESHOLDS and TEST.PSEUDO_THRESHOLD %r: one threshold or one per class, not both" % (threshold,))
+    return tuple(float(v) for v in values)
+
+
 def tta_settings(cfg):
     """(scales, flip) of cfg.TEST (SCALES / FLIP are not reference keys; absent = the defaults (1.0,) / False = plain inference())."""
     scales = tuple(cfg.TEST.SCALES) if "SCALES" in cfg.TEST else (1.0,)
@@ -706,7 +896,7 @@ def literal_pseudo(output, class_threshold):
 
 
 def predict_and_score(feature_extractor, classifier, image, label, flip=False, scales=(1.0,), *, num_classes, ignore_index=255, threshold=0.0,
-                      class_threshold=None, hist=None, slide=None):
+                      class_threshold=None, hist=None, slide=None, curves=None):
     """One image of ASPPTester.test(): inference(flip=False) (scales == (1.0,), no flip) or multi_scale_inference, then the argmax mask, the
     pseudo-label mask (argmax where the winning probability >= threshold, else 255; None for threshold 0), confusion_matrix and
     intersectionAndUnionGPU against label[:1].  On the engine (a classifier with predict_mask_multi, CUDA tensors) the backbone passes are
@@ -715,7 +905,10 @@ def predict_and_score(feature_extractor, classifier, image, label, flip=False, s
     Class-wise pseudo-labels: hist (the caller's int64 [K, PSEUDO_BINS] tensor, kept across images) receives this image's confidence histogram;
     class_threshold (K values in [0, 1]) replaces threshold in the pseudo-label mask: argmax where the winning probability >= its class's.
     slide = (crop, stride), each (h, w) (slide_settings): sliding-window evaluation - slide_inference instead of inference, on the engine
-    ONE mi_upsample_predict_score_slide after the windows' backbone passes; scales must be (1.0,).  None: no sliding."""
+    ONE mi_upsample_predict_score_slide after the windows' backbone passes; scales must be (1.0,).  None: no sliding.
+    curves = (pr, cal) (TEST.CURVES): the caller's int64 [K, 256, 2] and [ece_bins, 3] tensors, kept across images, receive this image's
+    precision-recall and calibration histograms: on the engine one more launch on the same logits (mi_upsample_curves / _slide; the backbone passes
+    and source lists are not recomputed), else literal_curves on the map."""
     K = int(num_classes)
     if not 0.0 <= float(threshold) <= 1.0:
         raise ValueError("threshold %r lies outside [0, 1]" % (threshold,))
@@ -730,6 +923,8 @@ def predict_and_score(feature_extractor, classifier, image, label, flip=False, s
             kw.update(class_threshold=_class_table(class_threshold, K, "cpu"), want_pseudo=True)
         if hist is not None:
             kw.update(hist=hist, want_pseudo=class_threshold is not None)
+        if curves is not None:
+            kw.update(curves=curves)
         if slide is not None:
             _require_single_scale_slide(scales)
             pred, pseudo, counts = _engine_masks_slide(feature_extractor, classifier, image, size, flip, slide, **kw)
@@ -746,6 +941,8 @@ def predict_and_score(feature_extractor, classifier, image, label, flip=False, s
         pseudo = torch.where(top[0] >= threshold, pred, torch.full_like(pred, 255))[0].to(torch.uint8)
     if hist is not None:
         hist.add_(literal_histogram(output, K).to(hist.device))
+    if curves is not None:
+        curves_accumulate(output, y0, K, curves)
     cmt = confusion_matrix(types.SimpleNamespace(MODEL=types.SimpleNamespace(NUM_CLASSES=K)), torch.flatten(pred), torch.flatten(y0))
     ai, union, at, ao = [t.cpu() for t in intersectionAndUnionGPU(pred.clone(), y0.long(), K, ignore_index)]
     return ScoreResult(pred[0].to(torch.uint8), pseudo, cmt, ai, union, at, ao)

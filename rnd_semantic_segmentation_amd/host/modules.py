@@ -304,17 +304,22 @@ class ASPP_Classifier_V2(nn.Module):
             return kernels.upsample_softmax_multi(lows, flags, tuple(int(s) for s in size), float(divisors[0]), float(divisors[1]))
 
     def predict_mask_multi(self, feats, mirrors, size, divisors, labels=None, ignore_index=255, threshold=0.0, want_pseudo=False, class_threshold=None,
-                           hist=None):
+                           hist=None, curves=None):
         """predict_probs_multi(feats, mirrors, size, divisors).max(1) without the probability map: (pred, pseudo, counts) of
         kernels.upsample_predict_score - the argmax mask, the thresholded pseudo-label mask and, with labels [H,W] int64, the confusion matrix
         and intersection / output / target areas.  class_threshold (K host floats, instead of threshold) and hist (the caller's int64
-        [K, PSEUDO_BINS] device tensor, added to) are the class-wise pseudo-label extras of that wrapper."""
+        [K, PSEUDO_BINS] device tensor, added to) are the class-wise pseudo-label extras of that wrapper.  curves = (pr, cal) (TEST.CURVES): one more
+        launch on the same source list, kernels.upsample_curves, adds the picture's precision-recall and calibration histograms to them."""
         from .. import kernels
         with torch.no_grad():
             lows, flags = self._lows_multi(feats, mirrors, "predict_mask_multi")
-            return kernels.upsample_predict_score(lows, flags, tuple(int(s) for s in size), float(divisors[0]), float(divisors[1]), labels=labels,
-                                                  ignore_index=ignore_index, threshold=threshold, want_pseudo=want_pseudo,
-                                                  class_threshold=class_threshold, hist=hist)
+            out = kernels.upsample_predict_score(lows, flags, tuple(int(s) for s in size), float(divisors[0]), float(divisors[1]), labels=labels,
+                                                 ignore_index=ignore_index, threshold=threshold, want_pseudo=want_pseudo,
+                                                 class_threshold=class_threshold, hist=hist)
+            if curves is not None:
+                kernels.upsample_curves(lows, flags, tuple(int(s) for s in size), float(divisors[0]), float(divisors[1]), labels, pr=curves[0],
+                                        cal=curves[1])
+            return out
 
     def slide_lows(self, feats, flip):
         """The 1/8-resolution logits of sliding-window evaluation: feats = feature maps [b,C,h,w] whose images are, in order, the windows'
@@ -337,17 +342,21 @@ class ASPP_Classifier_V2(nn.Module):
             return kernels.upsample_softmax_slide(lows, mirror_lows, origins, tuple(int(s) for s in window), tuple(int(s) for s in size))
 
     def predict_mask_slide(self, feats, flip, origins, window, size, labels=None, ignore_index=255, threshold=0.0, want_pseudo=False,
-                           class_threshold=None, hist=None):
+                           class_threshold=None, hist=None, curves=None):
         """predict_probs_slide(feats, flip, origins, window, size).max(1) without the probability map: (pred, pseudo, counts) of
         kernels.upsample_predict_score_slide; the keywords are those of predict_mask_multi."""
         from .. import kernels
         with torch.no_grad():
             lows, mirror_lows = self.slide_lows(feats, flip)
-            return kernels.upsample_predict_score_slide(lows, mirror_lows, origins, tuple(int(s) for s in window), tuple(int(s) for s in size),
-                                                        labels=labels, ignore_index=ignore_index, threshold=threshold, want_pseudo=want_pseudo,
-                                                        class_threshold=class_threshold, hist=hist)
+            out = kernels.upsample_predict_score_slide(lows, mirror_lows, origins, tuple(int(s) for s in window), tuple(int(s) for s in size),
+                                                       labels=labels, ignore_index=ignore_index, threshold=threshold, want_pseudo=want_pseudo,
+                                                       class_threshold=class_threshold, hist=hist)
+            if curves is not None:
+                kernels.upsample_curves_slide(lows, mirror_lows, origins, tuple(int(s) for s in window), tuple(int(s) for s in size), labels,
+                                              pr=curves[0], cal=curves[1])
+            return out
 
-    def predict_mask(self, x, size, labels=None, ignore_index=255, threshold=0.0, want_pseudo=False, class_threshold=None, hist=None):
+    def predict_mask(self, x, size, labels=None, ignore_index=255, threshold=0.0, want_pseudo=False, class_threshold=None, hist=None, curves=None):
         """predict_probs(x, size)[:1].max(1) without the probability map: the whole batch goes through the head as in predict_probs, image 0's
         logits are scored (inference() keeps image 0, utility.py:190)."""
         _require_gpu(x, "ASPP_Classifier_V2")
@@ -358,9 +367,12 @@ class ASPP_Classifier_V2(nn.Module):
             else:
                 self._engine.prepare(False)
                 low = self._engine.forward(self._nhwc(x))
-            return kernels.upsample_predict_score([low[0]], [False], tuple(int(s) for s in size), 1.0, 1.0, labels=labels,
-                                                  ignore_index=ignore_index, threshold=threshold, want_pseudo=want_pseudo,
-                                                  class_threshold=class_threshold, hist=hist)
+            out = kernels.upsample_predict_score([low[0]], [False], tuple(int(s) for s in size), 1.0, 1.0, labels=labels,
+                                                 ignore_index=ignore_index, threshold=threshold, want_pseudo=want_pseudo,
+                                                 class_threshold=class_threshold, hist=hist)
+            if curves is not None:
+                kernels.upsample_curves([low[0]], [False], tuple(int(s) for s in size), 1.0, 1.0, labels, pr=curves[0], cal=curves[1])
+            return out
 
 
 class CrossEntropyLoss(nn.Module):

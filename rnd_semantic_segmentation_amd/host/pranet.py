@@ -577,12 +577,14 @@ class PranetTester:
     OUTPUT_DIR/pranet_polyp_metrics.json; the intersection / union meters are then fed from that tail's mask."""
 
     def __init__(self, cfg, device, test_loader, logger):
-        from .metrics import polyp_settings, require_no_boundary, require_no_crf, require_no_slide, require_plain_argmax, require_single_scale
+        from .metrics import (polyp_settings, require_no_boundary, require_no_crf, require_no_curves, require_no_slide, require_plain_argmax,
+                              require_single_scale)
         require_single_scale(cfg, "PranetTester")
         require_plain_argmax(cfg, "PranetTester")
         require_no_crf(cfg, "PranetTester")
         require_no_slide(cfg, "PranetTester")
         require_no_boundary(cfg, "PranetTester")
+        require_no_curves(cfg, "PranetTester")
         self.cfg, self.logger, self.test_loader, self.device = cfg, logger, test_loader, device
         self.polyp_metrics = polyp_settings(cfg)                      # TEST.POLYP_METRICS: test() scores through kernels.polyp_score
         self.model = PraNet()

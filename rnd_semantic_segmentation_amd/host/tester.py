@@ -6,11 +6,12 @@ import os
 import numpy as np
 import torch
 
-from .metrics import (BOUNDARY_MAPS, BOUNDARY_MAX_WIDTH, PSEUDO_BINS, AverageMeter, boundary_accumulate, boundary_settings, boundary_summary,
-                      boundary_width, class_thresholds, classwise_pseudo_labels, classwise_settings, confusion_matrix, crf_channel_scale,
-                      crf_refine_output, crf_settings, dump_json, inference, intersectionAndUnionGPU, literal_histogram, literal_pseudo,
-                      multi_scale_inference, predict_and_score, require_no_polyp_metrics, score_settings, slide_inference, slide_plan, slide_settings,
-                      strip_prefix_if_present, threshold_table, tta_settings)
+from .metrics import (BOUNDARY_MAPS, BOUNDARY_MAX_WIDTH, CURVE_BINS, PSEUDO_BINS, AverageMeter, boundary_accumulate, boundary_settings,
+                      boundary_summary, boundary_width, class_threshold_settings, class_thresholds, classwise_pseudo_labels, classwise_settings,
+                      confusion_matrix, crf_channel_scale, crf_refine_output, crf_settings, curves_accumulate, curves_settings, curves_summary,
+                      dump_json, inference, intersectionAndUnionGPU, literal_histogram, literal_pseudo, multi_scale_inference, predict_and_score,
+                      require_no_polyp_metrics, score_settings, slide_inference, slide_plan, slide_settings, strip_prefix_if_present,
+                      threshold_table, tta_settings)
 from .modules import build_classifier, build_feature_extractor
 
 
@@ -32,6 +33,8 @@ class ASPPTester:
         self.crf_scale = crf_channel_scale(cfg) if self.crf is not None else None
         self.slide = slide_settings(cfg)                   # TEST.SLIDE: None, or (crop, stride), each (h, w) (a stray SLIDE_* key is refused)
         self.boundary = boundary_settings(cfg)             # TEST.BOUNDARY: None, or the band widths (empty = 2 % of the label's diagonal)
+        self.curves = curves_settings(cfg)                 # TEST.CURVES: None, or (ece_bins, target precision) (a stray CURVES_* key is refused)
+        self.class_table = class_threshold_settings(cfg)   # TEST.PSEUDO_CLASS_THRESHOLDS: None, or one pseudo-label threshold per class
         self.feature_extractor = self.build_feature_extractor(cfg)
         self.feature_extractor.to(device)
         self.classifier = self.build_classifier(cfg)
@@ -98,6 +101,19 @@ class ASPPTester:
         hist = torch.zeros(num_classes, PSEUDO_BINS, dtype=torch.int64, device=self.device) if classwise else None
         grid = None
         self.boundary_hist = self.boundary_size = None     # TEST.BOUNDARY: one int64 [5, K, D + 1] buffer on the device for the whole set
+        # TEST.CURVES: int64 pr [K, 256, 2] and cal [ece_bins, 3] on the device for the whole set; every picture adds to them
+        curves = None
+        if self.curves is not None:
+            curves = (torch.zeros(num_classes, CURVE_BINS, 2, dtype=torch.int64, device=self.device),
+                      torch.zeros(self.curves[0], 3, dtype=torch.int64, device=self.device))
+            self.logger.info("TEST.CURVES: precision-recall curves over {} thresholds per class, calibration over {} bins.".format(
+                CURVE_BINS, self.curves[0]))
+        table = self.class_table
+        extra = {}                                         # keywords of predict_and_score that only these two keys add
+        if curves is not None:
+            extra["curves"] = curves
+        if table is not None and self.saveres:
+            extra["class_threshold"] = table
         for x, y, name in self.test_loader:
             x = x.to(self.device, non_blocking=True)
             y = y.to(self.device, non_blocking=True).long()
@@ -109,7 +125,7 @@ class ASPPTester:
             if fused:
                 r = predict_and_score(self.feature_extractor, self.classifier, x, y, flip=flip, scales=scales, num_classes=num_classes,
                                       ignore_index=self.cfg.INPUT.IGNORE_LABEL, threshold=0.0 if classwise else threshold, hist=hist,
-                                      slide=self.slide)
+                                      slide=self.slide, **extra)
                 if self.saveres and not classwise:
                     self.save_mask(r.pred if r.pseudo is None else r.pseudo, name)
                 if self.boundary is not None:
@@ -119,8 +135,12 @@ class ASPPTester:
                 continue
             output = self._literal_output(x, y, single, scales, flip)
             pred = output.max(1)[1]
+            if curves is not None:
+                curves_accumulate(output, y[:1], num_classes, curves)
             if classwise:
                 hist += literal_histogram(output, num_classes)
+            elif self.saveres and table is not None:
+                self.save_mask(literal_pseudo(output, table), name)
             elif self.saveres and threshold == 0:
                 self.save_distill(output, name)
             elif self.saveres:
@@ -138,6 +158,8 @@ class ASPPTester:
                   {"cmt": cmt.tolist(), "classes": list(self.trainid2name.values())})
         if self.boundary is not None:
             self._boundary_report()
+        if curves is not None:
+            self._curves_report(curves)
         if classwise:
             self._classwise_masks(hist, portion, cap, fused, single, scales, flip)
         return cmt
@@ -174,6 +196,27 @@ class ASPPTester:
                     d, c, cls, *("n/a" if v is None else "{:.4f}".format(v) for v in (table["boundary_iou"][i][c], table["trimap_iou"][i][c]))))
         table = dict(table, max_width=int(hist.shape[2] - 1), hist=hist.tolist())
         dump_json(os.path.join(self.cfg.OUTPUT_DIR, "aspp_boundary_metrics.json"), table)
+
+    def _curves_report(self, curves):
+        """After the loop of TEST.CURVES: one device-to-host copy, one line per class and one for the set, OUTPUT_DIR/aspp_curves.json with the raw
+        histograms, the summary (metrics.curves_summary) and the settings."""
+        both = torch.cat([curves[0].flatten(), curves[1].flatten()]).cpu()
+        n = curves[0].numel()
+        self.curves_pr, self.curves_cal = pr, cal = both[:n].reshape(curves[0].shape), both[n:].reshape(curves[1].shape)
+        self.curves_metrics = table = curves_summary(pr, cal, list(self.trainid2name.values()), self.curves[1])
+
+        def show(v, spec="{:.4f}"):
+            return "n/a" if v is None else spec.format(v)
+
+        for c, cls in enumerate(table["classes"]):
+            self.logger.info("Curves, class {} ({}): AP {}, best F1 {} at threshold {}, precision {} from threshold {} with recall {}.".format(
+                c, cls, show(table["ap"][c]), show(table["best_f1"][c]), show(table["best_f1_threshold"][c]), table["target_precision"],
+                show(table["threshold_at_precision"][c]), show(table["recall_at_precision"][c])))
+        calib = table["calibration"]
+        self.logger.info("Curves: mAP {}, ECE {}, MCE {}, accuracy {}, mean confidence {}.".format(
+            show(table["map"]), show(calib["ece"]), show(calib["mce"]), show(calib["overall_accuracy"]), show(calib["mean_confidence"])))
+        table = dict(table, ece_bins=self.curves[0], pr=pr.tolist(), cal=cal.tolist())
+        dump_json(os.path.join(self.cfg.OUTPUT_DIR, "aspp_curves.json"), table)
 
     def _classwise_masks(self, hist, portion, cap, fused, single, scales, flip):
         """After pass 1 of TEST.PSEUDO_CLASSWISE: the thresholds from the histogram (one device-to-host copy), their table to the logger and to

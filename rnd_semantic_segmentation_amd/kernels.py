@@ -861,6 +861,63 @@ def upsample_predict_score_slide(lows, mirror_lows, origins, window, size, label
     return pred, pseudo, counts
 
 
+CURVE_BINS = 256            # probability bins per class of the curve tails (include/mi355seg.h)
+
+
+def _curves_operands(who, K, size, dev, labels, pr, cal):
+    """The checks both curve wrappers make on labels [H,W] int64 and the caller's int64 pr [K, 256, 2] / cal [M, 3] (either may be None)."""
+    H, W = size
+    if labels is None:
+        raise _lib.MiError("%s: labels are required" % who)
+    _chk(labels, torch.int64, "labels")
+    if tuple(labels.shape) != (H, W) or labels.device != dev:
+        raise _lib.MiError("labels must be [%d,%d] on %s, got %s on %s" % (H, W, dev, tuple(labels.shape), labels.device))
+    if pr is None and cal is None:
+        raise _lib.MiError("%s: neither pr nor cal" % who)
+    if pr is not None:
+        _chk(pr, torch.int64, "pr")
+        if tuple(pr.shape) != (K, CURVE_BINS, 2) or pr.device != dev:
+            raise _lib.MiError("pr must be [%d,%d,2] on %s, got %s on %s" % (K, CURVE_BINS, dev, tuple(pr.shape), pr.device))
+    if cal is not None:
+        _chk(cal, torch.int64, "cal")
+        if cal.dim() != 2 or cal.shape[1] != 3 or cal.device != dev:
+            raise _lib.MiError("cal must be [ece_bins,3] on %s, got %s on %s" % (dev, tuple(cal.shape), cal.device))
+    return 0 if cal is None else int(cal.shape[0])
+
+
+def upsample_curves(lows, mirrors, size, div_a, div_b=1.0, labels=None, *, pr=None, cal=None):
+    """Precision-recall and calibration histograms of one picture without the probability map (mi_upsample_curves): from the per-pixel values of
+    upsample_softmax_multi(lows, mirrors, size, div_a, div_b) and labels [H,W] int64, what metrics.literal_curves counts is ADDED to the caller's
+    int64 device tensors pr [K, 256, 2] and cal [ece_bins, 3] (either may be None; they persist across pictures).  Returns (pr, cal)."""
+    n = len(lows)
+    if not 1 <= n <= 16 or len(mirrors) != n:
+        raise _lib.MiError("upsample_curves: 1..16 sources with one mirror flag each (got %d / %d)" % (n, len(mirrors)))
+    K = lows[0].shape[-1]
+    dev = lows[0].device
+    src = (_lib.MiProbSource * n)()
+    for i, (low, m) in enumerate(zip(lows, mirrors)):
+        _chk(low, torch.float32, "lows[%d]" % i)
+        if low.dim() != 3 or low.shape[-1] != K or low.device != dev:
+            raise _lib.MiError("lows[%d] must be [h,w,%d] on %s, got %s on %s" % (i, K, dev, tuple(low.shape), low.device))
+        src[i].low, src[i].h, src[i].w, src[i].mirror = low.data_ptr(), low.shape[0], low.shape[1], int(bool(m))
+    H, W = size
+    M = _curves_operands("upsample_curves", K, (H, W), dev, labels, pr, cal)
+    check(_lib.lib().mi_upsample_curves(ctypes.cast(src, ctypes.c_void_p), n, K, H, W, float(div_a), float(div_b), _p(labels), M, _p(pr), _p(cal),
+                                        _stream()), "mi_upsample_curves")
+    return pr, cal
+
+
+def upsample_curves_slide(lows, mirror_lows, origins, window, size, labels=None, *, pr=None, cal=None):
+    """upsample_curves on the per-pixel values of upsample_softmax_slide (mi_upsample_curves_slide); the windows as in _slide_windows."""
+    who = "upsample_curves_slide"
+    win, n, h, w, K, dev = _slide_windows(who, lows, mirror_lows, origins, window, size)
+    H, W = size
+    M = _curves_operands(who, K, (H, W), dev, labels, pr, cal)
+    check(_lib.lib().mi_upsample_curves_slide(ctypes.cast(win, ctypes.c_void_p), n, h, w, int(window[0]), int(window[1]), K, H, W, _p(labels), M,
+                                              _p(pr), _p(cal), _stream()), "mi_upsample_curves_slide")
+    return pr, cal
+
+
 def split_counts(counts, K):
     """The layout of mi_upsample_predict_score's counts (include/mi355seg.h): (cmt [K,K], intersection [K], output [K], target [K])."""
     return counts[:K * K].reshape(K, K), counts[K * K:K * K + K], counts[K * K + K:K * K + 2 * K], counts[K * K + 2 * K:K * K + 3 * K]
