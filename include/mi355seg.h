@@ -537,6 +537,41 @@ size_t mi_boundary_score_workspace(int H, int W);
 int mi_boundary_score(const uint8_t* pred /*[H][W]*/, const int64_t* labels /*[H][W]*/, int H, int W, int K, int ignore_index, int D,
                       int64_t* hist /*[5][K][D+1], added to*/, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- surface-distance metrics of binary masks (TEST.SURFACE_METRICS; not in the reference: medpy's hd / hd95 / assd with connectivity 1, and
+ * surface Dice) ----
+ * pred [B][H][W] uint8, labels [B][H][W] int64; per image P = (pred == cls), G = (label == cls) on the H x W grid.
+ *   Surface S(M): the pixels of M with at least one of their four neighbours outside M.  A neighbour outside the image counts as outside M, so
+ *       foreground on the image frame is always surface: S(M) = M & ~binary_erosion(M, cross, border_value=0).
+ *   Directed distances: for every s in S(P), d2(s) = min over t in S(G) of (sx - tx)^2 + (sy - ty)^2, an exact integer; likewise from S(G).
+ *   HD = sqrt of the larger of the two directed maxima of d2.
+ *   HD-q = numpy's linear-interpolation percentile of the CONCATENATION of the two directed distance lists (medpy's convention, not a
+ *       per-direction percentile): rank r = q (n - 1) / 100 with n = |S(P)| + |S(G)|, value a[floor r] + frac(r) (a[floor r + 1] - a[floor r])
+ *       on the sorted distances.
+ *   ASSD = the mean of the two directed mean distances.
+ *   NSD(tau) = (|{s in S(P): d <= tau}| + |{s in S(G): d <= tau}|) / n, decided on integers as d2 <= floor(tau^2).
+ *   Both masks empty: every distance is 0 and NSD is 1.  Exactly one empty: the distances are undefined, NSD is 0.
+ * q_num: the integer percentile q in 1..100.  tol2: T values floor(tau^2) in HOST memory (read before the first launch; NULL when T == 0).
+ * Outputs, all written (not added to) by every call:
+ *   ints [B][MI_SURFACE_INTS] int64: 0 |P|, 1 |G|, 2 |S(P)|, 3 |S(G)|, 4 max d2 from S(P), 5 max d2 from S(G), 6 d2[floor r] and
+ *        7 d2[min(floor r + 1, n - 1)] of the sorted combined list, 8 floor r, 9 the remainder q (n - 1) mod 100 (frac(r) = remainder / 100),
+ *        10 defined (1) / undefined (0), then 11 + 2 t + direction: the surface pixels of P (direction 0) / G (direction 1) with
+ *        d2 <= tol2[t]; cells of t >= T are 0.  Fields 4..9 and the tolerance counts are 0 unless both masks have pixels.
+ *   sums [B][2] double: the sums of sqrt((double) d2) over S(P) and over S(G).
+ * Bit-reproducible run to run: everything but sums is integer arithmetic with integer atomics; sums uses no floating-point atomics - a thread
+ * adds its pixels of a row in ascending x, a wave adds in a xor butterfly, one partial per row goes to the workspace, a last launch adds the
+ * rows of an image in a fixed order.  Seven launches on `stream`, nothing read back in between (capturable in a HIP graph).  The workspace
+ * (mi_surface_score_workspace bytes, 8-byte aligned, no initialisation needed) holds 5 bytes per pixel, 16 bytes per row and 64 KiB of histograms
+ * per image; mi_surface_score_workspace returns 0 for sizes the call refuses.
+ * Refused before any launch (MI_EINVAL unless stated): a NULL pred / labels / ints / sums / workspace (tol2 with T > 0), a non-positive size,
+ * B > 65535, a side above 4096 (d2 < 2^25), cls outside 0..255, q_num outside 1..100, T outside 0..MI_SURFACE_MAX_TOL, a negative tol2, a
+ * workspace that is too small (MI_ENOMEM). */
+#define MI_SURFACE_MAX_TOL 8
+#define MI_SURFACE_INTS 27
+size_t mi_surface_score_workspace(int B, int H, int W);
+int mi_surface_score(const uint8_t* pred /*[B][H][W]*/, const int64_t* labels /*[B][H][W]*/, int B, int H, int W, int cls, int q_num,
+                     const int32_t* tol2 /*host [T]*/, int T, int64_t* ints /*[B][MI_SURFACE_INTS]*/, double* sums /*[B][2]*/, void* workspace,
+                     size_t workspace_bytes, void* stream);
+
 /* ---- optimiser: torch.optim.SGD(momentum, weight_decay) on flat fp32 buffers (aspp_trainer.py:25-26,94-95)
  * g' = g + wd*p; buf = mu*buf + g'; p -= lr*buf  (buf zero-initialised == torch's first-step buf = g'). */
 int mi_sgd_step(float* p, const float* g, float* buf, size_t n, float lr, float momentum, float weight_decay, void* stream);

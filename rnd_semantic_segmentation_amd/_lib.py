@@ -73,6 +73,8 @@ SIGNATURES = {
     "mi_crf_refine": (I, [P, P, F, F, F, P, P, P] + [I] * 7 + [F] * 5 + [P, Z, P]),
     "mi_boundary_score_workspace": (Z, [I] * 2),
     "mi_boundary_score": (I, [P, P] + [I] * 5 + [P, P, Z, P]),
+    "mi_surface_score_workspace": (Z, [I] * 3),
+    "mi_surface_score": (I, [P, P] + [I] * 5 + [P, I, P, P, P, Z, P]),
     "mi_stem_pool_fwd": (I, [P, P, P, P, P] + [I] * 6 + [P]),
     "mi_stem_pool_bwd": (I, [P, P, P, P] + [I] * 6 + [P]),
     "mi_stem_im2col": (I, [P, P] + [I] * 6 + [P]),

@@ -213,6 +213,11 @@ def default_tree():
         # POLYP_METRICS True (PranetTester only; the other testers refuse it) = besides the intersection / union lines, the polyp-segmentation
         # metrics PraNet is published with - mean Dice / IoU over 256 thresholds, F-beta, S-measure, E-measure, MAE - from one fused evaluation
         # tail (mi_polyp_score), logged and written to OUTPUT_DIR/pranet_polyp_metrics.json; labels must be 0 / 1;
+        # SURFACE_METRICS True (PranetTester only; the other testers refuse it) = the surface-distance metrics of the medical segmentation
+        # literature in medpy's conventions - Hausdorff distance, its SURFACE_PERCENTILE-th percentile (an integer in 1..100; HD95), average
+        # symmetric surface distance, and surface Dice at each of SURFACE_TOLERANCES (at most 8 pixel distances >= 0) - measured exactly on the
+        # device (mi_surface_score), logged and written to OUTPUT_DIR/pranet_surface_metrics.json; labels other than 1 are background
+        # (metrics.surface_settings);
         # CRF True (ASPPTester only; the other testers refuse it) = the third part of DeepLabV2 as published, in its locally connected form: the
         # full-resolution probability map is refined by CRF_ITER mean-field iterations over a CRF_WINDOW x CRF_WINDOW window dilated by
         # CRF_DILATION, with a position kernel (weight CRF_POS_W, sigma CRF_POS_XY pixels) and a bilateral kernel (weight CRF_BI_W, sigmas
@@ -245,6 +250,7 @@ def default_tree():
         # (metrics.class_threshold_settings)
         "TEST": {"BATCH_SIZE": 1, "PRECISION": "fp32", "SCALES": (1.0,), "FLIP": False, "FUSED_SCORE": True, "PSEUDO_THRESHOLD": 0.0,
                  "PSEUDO_CLASSWISE": False, "PSEUDO_PORTION": 0.5, "POLYP_METRICS": False,
+                 "SURFACE_METRICS": False, "SURFACE_PERCENTILE": 95, "SURFACE_TOLERANCES": (2.0,),
                  "CRF": False, "CRF_ITER": 5, "CRF_WINDOW": 7, "CRF_DILATION": 4, "CRF_POS_W": 3.0, "CRF_POS_XY": 3.0, "CRF_BI_W": 10.0,
                  "CRF_BI_XY": 80.0, "CRF_BI_RGB": 13.0,
                  "SLIDE": False, "SLIDE_CROP": (769, 769), "SLIDE_STRIDE": (513, 513),

@@ -29,6 +29,9 @@ Differences that are deliberate and documented:
  * the boundary metrics (boundary_survival, literal_boundary_histograms, boundary_summary, boundary_settings; TEST.BOUNDARY) are not in the
    reference either: Boundary IoU (Cheng et al., CVPR 2021) and DeepLab's trimap IoU at every band width up to 64 from five integer
    histograms of erosion counts, which mi_boundary_score adds up on the device in two launches per picture.
+ * the surface-distance metrics (surface_image_stats, SurfaceMeter, literal_surface_stats, surface_settings; TEST.SURFACE_METRICS) are not in
+   the reference either: Hausdorff distance, its percentile, average symmetric surface distance and surface Dice in medpy's conventions,
+   from 27 integers and two sums per image which mi_surface_score computes exactly on the device - the host never sees a distance map.
 """
 import json
 import logging
@@ -1200,6 +1203,154 @@ class PolypMeter(object):
         logger.info("Polyp metric, val result over {} images: mDice/mIoU {:.4f}/{:.4f}.".format(r["images"], r["mDice"], r["mIoU"]))
         logger.info("Polyp metric, val result: meanF/maxF {:.4f}/{:.4f}, S-measure {:.4f}.".format(r["meanF"], r["maxF"], r["S"]))
         logger.info("Polyp metric, val result: meanE/maxE {:.4f}/{:.4f}, MAE {:.4f}.".format(r["meanE"], r["maxE"], r["MAE"]))
+
+
+# ----------------------------------------------------------------------------- surface-distance metrics (TEST.SURFACE_METRICS)
+SURFACE_MAX_TOLERANCES = 8              # MI_SURFACE_MAX_TOL of include/mi355seg.h, where the definition stands
+SURFACE_INTS = 27                       # |P|, |G|, |S(P)|, |S(G)|, 2 maxima of d2, 2 order statistics, floor r, remainder, defined, 2 x 8 tolerance counts
+
+
+def _surface_check(percentile, tolerances, what):
+    if isinstance(percentile, bool) or not isinstance(percentile, (int, np.integer)) or not 1 <= int(percentile) <= 100:
+        raise ValueError("%s: the percentile %r must be an integer in 1..100" % (what, percentile))
+    if not isinstance(tolerances, (tuple, list)):
+        raise ValueError("%s: the tolerances %r must be a list of numbers" % (what, tolerances))
+    if len(tolerances) > SURFACE_MAX_TOLERANCES:
+        raise ValueError("%s: %d tolerances, at most %d" % (what, len(tolerances), SURFACE_MAX_TOLERANCES))
+    for t in tolerances:
+        if isinstance(t, bool) or not isinstance(t, (int, float, np.integer, np.floating)) or not (t >= 0 and math.isfinite(t)):
+            raise ValueError("%s: the tolerances %r must be finite numbers >= 0" % (what, tuple(tolerances)))
+    return int(percentile), tuple(float(t) for t in tolerances)
+
+
+def surface_settings(cfg):
+    """None while TEST.SURFACE_METRICS is False (not a reference key; absent = False), else (percentile, tolerances) from
+    TEST.SURFACE_PERCENTILE (an integer in 1..100, default 95) and TEST.SURFACE_TOLERANCES (at most 8 pixel distances >= 0, default (2.0,))."""
+    test = cfg.TEST
+    on = test["SURFACE_METRICS"] if "SURFACE_METRICS" in test else False
+    if not isinstance(on, bool):
+        raise ValueError("TEST.SURFACE_METRICS %r must be True or False" % (on,))
+    if not on:
+        return None
+    return _surface_check(test["SURFACE_PERCENTILE"] if "SURFACE_PERCENTILE" in test else 95,
+                          test["SURFACE_TOLERANCES"] if "SURFACE_TOLERANCES" in test else (2.0,), "TEST.SURFACE_PERCENTILE / TEST.SURFACE_TOLERANCES")
+
+
+def require_no_surface(cfg, who):
+    """The surface distances are measured on PranetTester's binary masks: testers of multi-class models refuse the key rather than ignore it."""
+    if surface_settings(cfg) is not None:
+        raise NotImplementedError("%s: TEST.SURFACE_METRICS - the surface-distance metrics (HD, HD95, ASSD, NSD) exist for PranetTester only; "
+                                  "leave it False" % (who,))
+
+
+def surface_keys(percentile, tolerances):
+    """The metric names of one setting: HD, HD<percentile>, ASSD, then NSD@<tau> per tolerance."""
+    return ["HD", "HD%d" % percentile, "ASSD"] + ["NSD@%g" % t for t in tolerances]
+
+
+def surface_image_stats(ints, sums, tolerances=(2.0,), percentile=95):
+    """One image's surface metrics from its row of mi_surface_score's ints [27] and sums [2] (or the same numbers computed elsewhere), float64
+    throughout: {"HD", "HD<percentile>", "ASSD", "NSD@<tau>" per tolerance, "defined"}.  The definitions: include/mi355seg.h.  The percentile is
+    numpy's linear interpolation between the two order statistics, with frac(r) = remainder / 100 from the kernel's integers.  Both masks empty:
+    distances 0, NSD 1.  Exactly one empty: defined False, the distances None, NSD 0."""
+    ints = np.asarray(ints.cpu() if isinstance(ints, torch.Tensor) else ints).astype(np.int64)
+    sums = np.asarray(sums.cpu() if isinstance(sums, torch.Tensor) else sums, dtype=np.float64)
+    percentile, tolerances = _surface_check(percentile, tuple(tolerances), "surface_image_stats")
+    if ints.shape != (SURFACE_INTS,) or sums.shape != (2,):
+        raise ValueError("surface_image_stats: ints must be [%d] and sums [2], got %s and %s" % (SURFACE_INTS, ints.shape, sums.shape))
+    keys = surface_keys(percentile, tolerances)
+    n_p, n_g = int(ints[2]), int(ints[3])
+    n = n_p + n_g
+    if bool(ints[10]) != ((n_p == 0) == (n_g == 0)) or (ints < 0).any():
+        raise ValueError("surface_image_stats: surface counts %d / %d contradict the defined flag %d" % (n_p, n_g, int(ints[10])))
+    if n == 0:
+        return dict([(k, 1.0 if k.startswith("NSD@") else 0.0) for k in keys], defined=True)
+    if n_p == 0 or n_g == 0:
+        return dict([(k, 0.0 if k.startswith("NSD@") else None) for k in keys], defined=False)
+    lo, hi = math.sqrt(float(ints[6])), math.sqrt(float(ints[7]))
+    out = {"HD": math.sqrt(float(max(ints[4], ints[5]))), keys[1]: lo + (float(ints[9]) / 100.0) * (hi - lo),
+           "ASSD": 0.5 * (float(sums[0]) / n_p + float(sums[1]) / n_g)}
+    for t, k in enumerate(keys[3:]):
+        out[k] = float(int(ints[11 + 2 * t]) + int(ints[12 + 2 * t])) / n
+    out["defined"] = True
+    return out
+
+
+SURFACE_CDIST_PAIRS = 1 << 22           # pairs per torch.cdist call of literal_surface_stats
+
+
+def literal_surface_stats(pred, label, cls=1, percentile=95, tolerances=(2.0,), pairs=SURFACE_CDIST_PAIRS):
+    """What a user would write without mi_surface_score, from torch ops on the inputs' device (pred, label [H,W]): surfaces from shifted
+    comparisons, their coordinates, chunked torch.cdist (fp32, exact differences rather than the matrix-product form), min, sort, and the
+    percentile by hand.  The same dict as surface_image_stats; its distances carry fp32 rounding, and NSD compares the fp32 distance with tau.
+    A cdist call sees at most `pairs` pairs: on the GPU, torch's exact-difference mode returned wrong distances for 4096 x 5330 points (2.2e7
+    pairs; 1024 x 5330 were right, as was the CPU - DESIGN.md 4.4j), so the chunk shrinks with the other list's length."""
+    percentile, tolerances = _surface_check(percentile, tuple(tolerances), "literal_surface_stats")
+    keys = surface_keys(percentile, tolerances)
+
+    def surface(m):
+        p = torch.nn.functional.pad(m, (1, 1, 1, 1))
+        return m & ~(p[:-2, 1:-1] & p[2:, 1:-1] & p[1:-1, :-2] & p[1:-1, 2:])
+
+    a = surface(pred == cls).nonzero().float()
+    b = surface(label == cls).nonzero().float()
+    n_p, n_g = a.shape[0], b.shape[0]
+    if n_p + n_g == 0:
+        return dict([(k, 1.0 if k.startswith("NSD@") else 0.0) for k in keys], defined=True)
+    if n_p == 0 or n_g == 0:
+        return dict([(k, 0.0 if k.startswith("NSD@") else None) for k in keys], defined=False)
+
+    def directed(src, dst):
+        chunk = max(1, int(pairs) // dst.shape[0])
+        return torch.cat([torch.cdist(src[i:i + chunk], dst, compute_mode="donot_use_mm_for_euclid_dist").min(1)[0] for i in range(0, src.shape[0], chunk)])
+
+    dp, dg = directed(a, b).double(), directed(b, a).double()
+    both = torch.sort(torch.cat([dp, dg]))[0]
+    n = n_p + n_g
+    fl, rem = divmod(percentile * (n - 1), 100)
+    lo, hi = float(both[fl]), float(both[min(fl + 1, n - 1)])
+    out = {"HD": float(both[-1]), keys[1]: lo + (rem / 100.0) * (hi - lo), "ASSD": 0.5 * (float(dp.mean()) + float(dg.mean()))}
+    for t, k in zip(tolerances, keys[3:]):
+        out[k] = float(int((dp <= t).sum()) + int((dg <= t).sum())) / n
+    out["defined"] = True
+    return out
+
+
+class SurfaceMeter(object):
+    """Dataset aggregation of surface_image_stats: HD, HD<percentile> and ASSD are means over the images where they are defined (0 when there is
+    none), NSD a mean over all images; `undefined` counts the images with exactly one empty mask."""
+
+    def __init__(self, percentile=95, tolerances=(2.0,)):
+        self.percentile, self.tolerances = _surface_check(percentile, tuple(tolerances), "SurfaceMeter")
+        self.keys = surface_keys(self.percentile, self.tolerances)
+        self.reset()
+
+    def reset(self):
+        self.sums = {k: 0.0 for k in self.keys}
+        self.count = 0
+        self.undefined = 0
+
+    def update(self, stats):
+        self.count += 1
+        if not stats["defined"]:
+            self.undefined += 1
+        for k in self.keys:
+            if k.startswith("NSD@") or stats["defined"]:
+                self.sums[k] += float(stats[k])
+
+    def as_dict(self):
+        n_all, n_def = float(max(self.count, 1)), float(max(self.count - self.undefined, 1))
+        out = {k: self.sums[k] / (n_all if k.startswith("NSD@") else n_def) for k in self.keys}
+        out["images"] = self.count
+        out["undefined"] = self.undefined
+        return out
+
+    def summary(self, logger):
+        r = self.as_dict()
+        logger.info("Surface metric, val result over {} images ({} undefined): HD/{} {:.4f}/{:.4f}, ASSD {:.4f}.".format(
+            r["images"], r["undefined"], self.keys[1], r["HD"], r[self.keys[1]], r["ASSD"]))
+        if self.tolerances:
+            logger.info("Surface metric, val result: " + ", ".join("{} {:.4f}".format(k, r[k]) for k in self.keys[3:]) + ".")
 
 
 # ----------------------------------------------------------------------------- io / logging

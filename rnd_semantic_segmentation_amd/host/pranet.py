@@ -574,11 +574,13 @@ class PranetTester:
     """pranet_tester.py:10-53: res2 -> resize to the label size (align_corners False) -> sigmoid -> min-max normalise over the batch ->
     {background, polyp} by which of (1 - p, p) is larger -> intersection / union meters.  TEST.POLYP_METRICS True (not in the reference) adds
     the polyp-segmentation metrics - mean Dice / IoU, F-beta, S-measure, E-measure, MAE - from one fused tail (score) and writes
-    OUTPUT_DIR/pranet_polyp_metrics.json; the intersection / union meters are then fed from that tail's mask."""
+    OUTPUT_DIR/pranet_polyp_metrics.json; the intersection / union meters are then fed from that tail's mask.  TEST.SURFACE_METRICS True (not
+    in the reference either) measures the same mask against the label with kernels.surface_score - Hausdorff distance, its percentile, average
+    symmetric surface distance, surface Dice - and writes OUTPUT_DIR/pranet_surface_metrics.json; the other outputs do not change."""
 
     def __init__(self, cfg, device, test_loader, logger):
         from .metrics import (polyp_settings, require_no_boundary, require_no_crf, require_no_curves, require_no_slide, require_plain_argmax,
-                              require_single_scale)
+                              require_single_scale, surface_settings)
         require_single_scale(cfg, "PranetTester")
         require_plain_argmax(cfg, "PranetTester")
         require_no_crf(cfg, "PranetTester")
@@ -587,6 +589,7 @@ class PranetTester:
         require_no_curves(cfg, "PranetTester")
         self.cfg, self.logger, self.test_loader, self.device = cfg, logger, test_loader, device
         self.polyp_metrics = polyp_settings(cfg)                      # TEST.POLYP_METRICS: test() scores through kernels.polyp_score
+        self.surface = surface_settings(cfg)                          # TEST.SURFACE_METRICS: None, or (percentile, tolerances) for kernels.surface_score
         self.model = PraNet()
         self.model.to(device)
         # The reference thresholds an fp32 forward (pranet_tester.py:36-46): TEST.PRECISION 'fp32' (default) evaluates in the reference's precision
@@ -620,13 +623,25 @@ class PranetTester:
             if counts[b, 3]:
                 name = names[b] if names is not None and len(names) > b else "#%d of the batch" % b
                 raise ValueError("PranetTester: TEST.POLYP_METRICS needs labels in {0, 1}; image %s has %d others" % (name, int(counts[b, 3])))
+        self.last_mask = r.pred                                       # the tail's uint8 mask, for surface()
         return r.pred.long(), [polyp_image_stats(hist[b], sums[b], y.shape[1], y.shape[2]) for b in range(y.shape[0])]
 
+    def surface_stats(self, mask, y):
+        """TEST.SURFACE_METRICS: one batch's mask (uint8 [B,H,W]) and labels through kernels.surface_score (foreground = 1, every other label is
+        background); one small copy to the host.  Returns [surface_image_stats per image]."""
+        from .. import kernels
+        from .metrics import surface_image_stats
+        percentile, tolerances = self.surface
+        r = kernels.surface_score(mask.contiguous(), y.contiguous(), 1, percentile, tolerances)
+        ints, sums = r.ints.cpu().numpy(), r.sums.cpu().numpy()
+        return [surface_image_stats(ints[b], sums[b], tolerances, percentile) for b in range(y.shape[0])]
+
     def test(self):
-        from .metrics import AverageMeter, PolypMeter, dump_json, intersectionAndUnionGPU
+        from .metrics import AverageMeter, PolypMeter, SurfaceMeter, dump_json, intersectionAndUnionGPU
         self.model.eval()
         self.meter = AverageMeter()
         self.polyp_meter = PolypMeter() if self.polyp_metrics else None
+        self.surface_meter = SurfaceMeter(*self.surface) if self.surface is not None else None
         for x, y, names in self.test_loader:
             x = x.to(self.device, non_blocking=True)
             y = y.to(self.device, non_blocking=True)
@@ -638,6 +653,9 @@ class PranetTester:
                     self.polyp_meter.update(s)
             else:
                 pred = self.predict(x, (h, w))
+            if self.surface is not None:
+                for s in self.surface_stats(self.last_mask if self.polyp_metrics else pred.to(torch.uint8), y):
+                    self.surface_meter.update(s)
             inter, union, target, res = intersectionAndUnionGPU(pred, y, self.cfg.MODEL.NUM_CLASSES, self.cfg.INPUT.IGNORE_LABEL)
             self.meter.update(inter.cpu().numpy(), union.cpu().numpy(), target.cpu().numpy(), res.cpu().numpy())
         self.meter.summary(self.logger, self.cfg.MODEL.NUM_CLASSES)
@@ -647,3 +665,8 @@ class PranetTester:
             curves = self.polyp_meter.mean_curves()
             dump_json(os.path.join(self.cfg.OUTPUT_DIR, "pranet_polyp_metrics.json"),
                       dict(self.polyp_meter.as_dict(), dice_curve=curves["dice"].tolist(), iou_curve=curves["iou"].tolist()))
+        if self.surface is not None:
+            self.surface_meter.summary(self.logger)
+            os.makedirs(self.cfg.OUTPUT_DIR, exist_ok=True)
+            dump_json(os.path.join(self.cfg.OUTPUT_DIR, "pranet_surface_metrics.json"),
+                      dict(self.surface_meter.as_dict(), percentile=self.surface[0], tolerances=list(self.surface[1])))

@@ -6,6 +6,7 @@ Layout: every activation handled here is an NHWC-contiguous tensor [B,H,W,C]
 """
 import collections
 import ctypes
+import math
 
 import torch
 
@@ -1085,6 +1086,43 @@ def boundary_score(pred, labels, num_classes, ignore_index, max_width, hist):
     check(_lib.lib().mi_boundary_score(_p(pred), _p(labels), H, W, K, int(ignore_index), D, _p(hist), _p(ws), ws.numel(), _stream()),
           "mi_boundary_score")
     return hist
+
+
+SURFACE_INTS, SURFACE_MAX_TOL = 27, 8       # MI_SURFACE_INTS, MI_SURFACE_MAX_TOL
+SurfaceScore = collections.namedtuple("SurfaceScore", "ints sums")
+
+
+def surface_tol2(tolerances):
+    """floor(tau^2) per tolerance, the integers mi_surface_score compares d2 with (math.floor of the float64 product)."""
+    return [int(math.floor(float(t) * float(t))) for t in tolerances]
+
+
+def surface_score(pred, labels, cls=1, percentile=95, tolerances=(2.0,)):
+    """Surface-distance tail (mi_surface_score, the definition: include/mi355seg.h): pred uint8 [B,H,W], labels int64 [B,H,W] on one device ->
+    SurfaceScore of device tensors: ints int64 [B,27] (|P|, |G|, |S(P)|, |S(G)|, the two directed maxima of d2, the two order statistics of the
+    combined list, floor r, q (n - 1) mod 100, defined, then 2 counts per tolerance) and sums float64 [B,2] (the directed sums of sqrt(d2)).
+    Foreground is pred == cls / labels == cls.  host/metrics.py surface_image_stats turns a row of each into HD, HD-q, ASSD and NSD.  Seven
+    launches on the current stream, nothing read back; workspace cached per stream."""
+    _chk(pred, torch.uint8, "pred")
+    _chk(labels, torch.int64, "labels")
+    if pred.dim() != 3 or labels.shape != pred.shape or labels.device != pred.device:
+        raise _lib.MiError("surface_score: pred and labels [B,H,W] on one device, got %s on %s and %s on %s"
+                           % (tuple(pred.shape), pred.device, tuple(labels.shape), labels.device))
+    tolerances = tuple(tolerances)
+    if len(tolerances) > SURFACE_MAX_TOL or any(not (float(t) >= 0.0 and math.isfinite(float(t))) for t in tolerances):
+        raise _lib.MiError("surface_score: at most %d finite, non-negative tolerances, got %r" % (SURFACE_MAX_TOL, tolerances))
+    if int(percentile) != percentile:
+        raise _lib.MiError("surface_score: the percentile must be an integer in 1..100, got %r" % (percentile,))
+    B, H, W = pred.shape
+    dev = pred.device
+    T = len(tolerances)
+    tol2 = (ctypes.c_int32 * max(T, 1))(*surface_tol2(tolerances))
+    ints = torch.empty((B, SURFACE_INTS), dtype=torch.int64, device=dev)
+    sums = torch.empty((B, 2), dtype=torch.float64, device=dev)
+    ws = _workspace(_lib.lib().mi_surface_score_workspace(B, H, W), dev, "surface")
+    check(_lib.lib().mi_surface_score(_p(pred), _p(labels), B, H, W, int(cls), int(percentile), ctypes.cast(tol2, ctypes.c_void_p), T, _p(ints), _p(sums),
+                                      _p(ws), ws.numel(), _stream()), "mi_surface_score")
+    return SurfaceScore(ints, sums)
 
 
 def stem_pool_fwd(y, scale, shift):
