@@ -341,6 +341,19 @@ int mi_upsample_tversky_bce(const float* low, const float* mask, float* loss_out
                             int B, int h, int w, int H, int W, float alpha, float eps, float w_tversky, float w_bce, float grad_scale,
                             int align_corners, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- the same head with the boundary loss of Kervadec et al. (MIDL 2019; not in the reference) as a third term ----
+ * phi [B][H][W] fp32: the signed distance map of the label (mi_signed_distance).  With S = sum p phi over the batch and N = B H W:
+ * boundary = S / N, loss = w_tversky tversky + w_bce bce + w_boundary boundary, d loss / d z gains (w_boundary / N) phi p (1 - p).
+ * w_boundary >= 0 and finite.  loss_out[3] = boundary (0 when w_boundary is 0: the term is off); sums (may be NULL) [4] fp32: TP, FN, FP, S.  Everything else - operands, launches, the fixed
+ * summation orders (one more partial per workgroup, one more coefficient in device memory), capturability - as mi_upsample_tversky_bce, whose kernels
+ * these are in another mode; one more 4-byte load per pixel in the reduction and in the gradient pass.  Refused before any launch: what
+ * mi_upsample_tversky_bce refuses, a NULL phi, a negative or non-finite w_boundary. */
+size_t mi_upsample_tversky_bce_sdf_workspace(int B, int h, int w, int H, int W);
+int mi_upsample_tversky_bce_sdf(const float* low, const float* mask, const float* phi, float* loss_out /*[4]*/, float* dlow,
+                                float* sums /*[4], may be NULL: TP, FN, FP, sum p*phi*/, int B, int h, int w, int H, int W, float alpha, float eps,
+                                float w_tversky, float w_bce, float w_boundary, float grad_scale, int align_corners, void* workspace,
+                                size_t workspace_bytes, void* stream);
+
 /* ---- inference tail: upsample to label size + softmax over classes (utility.py:185-186) ---------
  * probs [B][K][H][W] fp32; pred (optional, may be NULL) [B][H][W] uint8 argmax (first max wins). */
 int mi_upsample_softmax(const float* low, float* probs, uint8_t* pred, int B, int h, int w, int K, int H, int W, void* stream);
@@ -571,6 +584,27 @@ size_t mi_surface_score_workspace(int B, int H, int W);
 int mi_surface_score(const uint8_t* pred /*[B][H][W]*/, const int64_t* labels /*[B][H][W]*/, int B, int H, int W, int cls, int q_num,
                      const int32_t* tol2 /*host [T]*/, int T, int64_t* ints /*[B][MI_SURFACE_INTS]*/, double* sums /*[B][2]*/, void* workspace,
                      size_t workspace_bytes, void* stream);
+
+/* ---- exact signed Euclidean distance map of a batch of masks (SOLVER.BOUNDARY_WEIGHT; not in the reference: the level-set map of the boundary
+ * loss, edt(~G) * ~G - (edt(G) - 1) * G with scipy.ndimage.distance_transform_edt) ----
+ * mask [B][H][W] fp32; per image G = (mask >= thresh), a NaN is background.
+ *   d2(q) for q outside G = min over t in G of |q - t|^2; for q in G = min over t outside G of |q - t|^2: an exact integer.  Pixels outside the
+ *       image do not exist; they are neither foreground nor background.
+ *   phi(q) = +sqrt(d2) outside G and -(sqrt(d2) - 1) inside G (+0 where d2 = 1), formed from sqrt((double) d2) in float64 and rounded to float32
+ *       once: bit for bit the float32 cast of the line above.
+ *   An image whose G is empty or the whole image has no contour: phi = 0 and d2 = 0 everywhere.
+ * Outputs, all written by every call: phi [B][H][W] fp32; d2 (may be NULL) [B][H][W] int32; counts (may be NULL) [B][2] int32: foreground and
+ * background pixels.  Bit-reproducible: integer arithmetic with integer atomics up to the final square root.  A memset and two launches on `stream`
+ * (a column pass over the mask, a row pass with one workgroup per row), nothing read back (capturable in a HIP graph).  The workspace
+ * (mi_signed_distance_workspace bytes, 4-byte aligned, no initialisation needed) holds 4 bytes per pixel and 4 per image;
+ * mi_signed_distance_workspace returns 0 for sizes the call refuses.
+ * Refused before any launch (MI_EINVAL unless stated): a NULL mask / phi / workspace, a non-positive size, B > 65535, a side above 4096
+ * (d2 < 2^25), a thresh that is not finite, a workspace that is too small (MI_ENOMEM). */
+size_t mi_signed_distance_workspace(int B, int H, int W);
+int mi_signed_distance(const float* mask /*[B][H][W]*/, float thresh, float* phi /*[B][H][W]*/,
+                       int32_t* d2 /*[B][H][W], may be NULL: tests and diagnosis*/,
+                       int32_t* counts /*[B][2], may be NULL: foreground, background pixels*/, int B, int H, int W, void* workspace,
+                       size_t workspace_bytes, void* stream);
 
 /* ---- optimiser: torch.optim.SGD(momentum, weight_decay) on flat fp32 buffers (aspp_trainer.py:25-26,94-95)
  * g' = g + wd*p; buf = mu*buf + g'; p -= lr*buf  (buf zero-initialised == torch's first-step buf = g'). */

@@ -58,6 +58,8 @@ SIGNATURES = {
     "mi_upsample_lovasz": (I, [P, P, P, P, P, P] + [I] * 8 + [F, I, P, Z, P]),
     "mi_upsample_tversky_bce_workspace": (Z, [I] * 5),
     "mi_upsample_tversky_bce": (I, [P, P, P, P, P] + [I] * 5 + [F] * 5 + [I, P, Z, P]),
+    "mi_upsample_tversky_bce_sdf_workspace": (Z, [I] * 5),
+    "mi_upsample_tversky_bce_sdf": (I, [P, P, P, P, P, P] + [I] * 5 + [F] * 6 + [I, P, Z, P]),
     "mi_upsample_softmax": (I, [P, P, P] + [I] * 6 + [P]),
     "mi_upsample_softmax_multi": (I, [P, I, P, I, I, I, F, F, P]),
     "mi_upsample_predict_score": (I, [P, I, I, I, I, F, F, P, I, F, P, P, P, P]),
@@ -75,6 +77,8 @@ SIGNATURES = {
     "mi_boundary_score": (I, [P, P] + [I] * 5 + [P, P, Z, P]),
     "mi_surface_score_workspace": (Z, [I] * 3),
     "mi_surface_score": (I, [P, P] + [I] * 5 + [P, I, P, P, P, Z, P]),
+    "mi_signed_distance_workspace": (Z, [I] * 3),
+    "mi_signed_distance": (I, [P, F, P, P, P] + [I] * 3 + [P, Z, P]),
     "mi_stem_pool_fwd": (I, [P, P, P, P, P] + [I] * 6 + [P]),
     "mi_stem_pool_bwd": (I, [P, P, P, P] + [I] * 6 + [P]),
     "mi_stem_im2col": (I, [P, P] + [I] * 6 + [P]),

@@ -19,21 +19,20 @@
 //   select    one workgroup per image finds the high cells that hold the ranks floor r and floor r + 1
 //   low       histograms the low bits of the d2 that fall into those two cells
 //   finalize  the two order statistics, the fixed-order sum of the partials, and every output
-#include "mi_common.h"
+#include "edt_common.h"
 
 namespace {
 
 typedef unsigned long long u64;
 
-constexpr int SS_MAX_SIDE = 4096;            // d2 <= 2 * 4095^2 < 2^25; a row of g fits in 16 KiB of LDS
+constexpr int SS_MAX_SIDE = EDT_MAX_SIDE;
 constexpr int SS_MAX_T = MI_SURFACE_MAX_TOL;
-constexpr int SS_D2_BITS = 25;
+constexpr int SS_D2_BITS = EDT_D2_BITS;
 constexpr int SS_LOW_BITS = 12;              // the split of the two-level histogram: 8192 high cells of 4096 values each
 constexpr int SS_LOW = 1 << SS_LOW_BITS;
 constexpr int SS_HIGH = 1 << (SS_D2_BITS - SS_LOW_BITS);
 constexpr long SS_MAX_GRID = 1l << 14;       // workgroups of a launch at most (64 per CU); beyond it a workgroup strides over the rows / columns
-constexpr unsigned SS_NONE = 0xffffu;        // g of a column without a site
-constexpr unsigned SS_D2_MASK = (1u << SS_D2_BITS) - 1u, SS_IS_P = 1u << 30, SS_IS_G = 1u << 31;
+constexpr unsigned SS_D2_MASK = EDT_D2_MASK, SS_IS_P = 1u << 30, SS_IS_G = 1u << 31;
 constexpr int SS_ACC = 24;                   // per image: |P|, |G|, |S(P)|, |S(G)|, the two maxima, [2 * t + direction] tolerance counts from 6
 constexpr int SS_ACC_TOL = 6;
 static_assert(MI_SURFACE_INTS == 11 + 2 * SS_MAX_T && SS_ACC >= SS_ACC_TOL + 2 * SS_MAX_T, "ints row: 11 fields, then 2 T tolerance counts");
@@ -192,69 +191,14 @@ __global__ __launch_bounds__(256) void surface_mark_kernel(const uint8_t* __rest
     }
 }
 
-// g(x, y) of both maps: eight rows are loaded before any is used, the carried state (the last site seen) is two registers.
+// g(x, y) of both maps (edt_sweep_column): bit 0 of a byte of `surf` is a surface pixel of P, bit 1 one of G.
 __global__ __launch_bounds__(256) void surface_cols_kernel(const uint8_t* __restrict__ surf, unsigned* __restrict__ g, int B, int H, int W) {
     const long cols = (long)B * W;
     for (long c = (long)blockIdx.x * 256 + threadIdx.x; c < cols; c += (long)gridDim.x * 256) {
         const int b = (int)(c / W), x = (int)(c % W);
         const uint8_t* s = surf + (long)b * H * W + x;
-        unsigned* o = g + (long)b * H * W + x;
-        int last_p = -1, last_g = -1;
-        for (int y0 = 0; y0 < H; y0 += 8) {                            // down: the nearest site at or above y
-            unsigned v[8];
-#pragma unroll
-            for (int k = 0; k < 8; ++k) v[k] = y0 + k < H ? (unsigned)s[(long)(y0 + k) * W] : 0u;
-#pragma unroll
-            for (int k = 0; k < 8; ++k) {
-                const int y = y0 + k;
-                if (y < H) {
-                    if (v[k] & 1u) last_p = y;
-                    if (v[k] & 2u) last_g = y;
-                    const unsigned dp = last_p < 0 ? SS_NONE : (unsigned)(y - last_p), dg = last_g < 0 ? SS_NONE : (unsigned)(y - last_g);
-                    o[(long)y * W] = dp | (dg << 16);
-                }
-            }
-        }
-        int next_p = -1, next_g = -1;
-        for (int y1 = H - 1; y1 >= 0; y1 -= 8) {                       // up: the nearest site at or below y; reads what this thread wrote
-            unsigned v[8];
-#pragma unroll
-            for (int k = 0; k < 8; ++k) v[k] = y1 - k >= 0 ? o[(long)(y1 - k) * W] : 0xffffffffu;
-#pragma unroll
-            for (int k = 0; k < 8; ++k) {
-                const int y = y1 - k;
-                if (y >= 0) {
-                    unsigned dp = v[k] & 0xffffu, dg = v[k] >> 16;
-                    if (dp == 0u) next_p = y;
-                    if (dg == 0u) next_g = y;
-                    if (next_p >= 0) dp = min(dp, (unsigned)(next_p - y));
-                    if (next_g >= 0) dg = min(dg, (unsigned)(next_g - y));
-                    o[(long)y * W] = dp | (dg << 16);
-                }
-            }
-        }
+        edt_sweep_column([=](int y) { return (unsigned)s[(long)y * W]; }, g + (long)b * H * W + x, H, W);
     }
-}
-
-// d2 of the pixel at column x to the sites of the map whose g sits at `shift` in the row's words.  The sentinel is never squared.  The scan stops
-// at the first dx with dx^2 >= best: every column from there on offers at least dx^2, so it cannot lower the minimum (a tie leaves it as it is).
-__device__ __forceinline__ unsigned ss_query(const unsigned* row, int x, int W, int shift) {
-    unsigned gv = (row[x] >> shift) & 0xffffu;
-    unsigned best = gv == SS_NONE ? 0xffffffffu : gv * gv;
-    const int reach = max(x, W - 1 - x);
-    for (int dx = 1; dx <= reach; ++dx) {
-        const unsigned dx2 = (unsigned)(dx * dx);
-        if (dx2 >= best) break;
-        if (x - dx >= 0) {
-            gv = (row[x - dx] >> shift) & 0xffffu;
-            if (gv != SS_NONE) best = min(best, dx2 + gv * gv);
-        }
-        if (x + dx < W) {
-            gv = (row[x + dx] >> shift) & 0xffffu;
-            if (gv != SS_NONE) best = min(best, dx2 + gv * gv);
-        }
-    }
-    return best & SS_D2_MASK;            // the rows kernel runs only where the other map has a site: best is finite; the mask keeps an index in bounds regardless
 }
 
 __global__ __launch_bounds__(256) void surface_rows_kernel(unsigned* __restrict__ g, int B, int H, int W, SsTol tol, u64* __restrict__ acc,
@@ -284,7 +228,7 @@ __global__ __launch_bounds__(256) void surface_rows_kernel(unsigned* __restrict_
                 const unsigned v = row[x];
                 unsigned word = 0u;
                 if ((v & 0xffffu) == 0u) {                             // a surface pixel of P asks for the nearest surface pixel of G
-                    const unsigned d = ss_query(row, x, W, 16);
+                    const unsigned d = edt_query(row, x, W, 16);
                     s_p += __dsqrt_rn((double)d);
                     m_p = max(m_p, d);
 #pragma unroll
@@ -295,7 +239,7 @@ __global__ __launch_bounds__(256) void surface_rows_kernel(unsigned* __restrict_
                     ++mult;
                 }
                 if ((v >> 16) == 0u) {
-                    const unsigned d = ss_query(row, x, W, 0);
+                    const unsigned d = edt_query(row, x, W, 0);
                     s_g += __dsqrt_rn((double)d);
                     m_g = max(m_g, d);
 #pragma unroll

@@ -487,6 +487,10 @@ __global__ __launch_bounds__(256) void gdl_grad_kernel(const float* __restrict__
 // The launches of mi_upsample_gdl with K = 1:  tvb_reduce_kernel (per-workgroup partial TP / FN / FP / bce) -> tvb_finalize_kernel (one workgroup: the
 // loss and w_t c0, w_t c1, w_b / N in device memory) -> tvb_grad_kernel (d loss / d z gathered along x: tile_stage / tile_gather_x) -> upce_pass2_kernel.
 // exp(-|z|) <= 1 everywhere, so saturated logits stay finite; 1 - p is formed from the same exponential, not by subtraction.
+// SDF (mi_upsample_tversky_bce_sdf) is a mode of the three kernels: the boundary loss of Kervadec et al. on the signed distance map phi [B][H][W] of the
+// label (mi_signed_distance), boundary = 1/N sum p phi, loss += w_bd boundary, d loss / d z += w_bd / N phi q.  One more 4-byte load per pixel in the
+// reduction and the gradient pass, one more partial per workgroup (its own array: the four others stay one float4), one more coefficient.  With SDF
+// false every addition is compiled out: the instantiations mi_upsample_tversky_bce launches are the kernels they were.
 constexpr int TVB_NC = 4;          // TP, FN, FP, the bce sum
 
 // p = sigmoid(z), np = 1 - p, e = exp(-|z|)
@@ -497,14 +501,15 @@ __device__ __forceinline__ void sigmoid_pair(float z, float& p, float& np, float
     np = z >= 0.f ? er : r;
 }
 
-// A row-walk kernel with one channel.  partial: [workgroup][4] floats.
+// A row-walk kernel with one channel.  partial: [workgroup][4] floats; SDF: partial_s [workgroup] floats, the sums of p phi.
+template <bool SDF>
 __global__ __launch_bounds__(256) void tvb_reduce_kernel(const float* __restrict__ low, const float* __restrict__ mask, float* __restrict__ partial, Axis ay,
-                                                         Axis ax, int rows) {
+                                                         Axis ax, int rows, const float* __restrict__ phi, float* __restrict__ partial_s) {
     __shared__ float vrow[GDL_XT + 2];          // source row already interpolated along y
-    __shared__ float red[4][TVB_NC];
+    __shared__ float red[4][TVB_NC + (SDF ? 1 : 0)];
     const int tid = threadIdx.x;
     const RowWalk r = rowwalk_begin(ay, ax, rows, GDL_XT + 2);
-    float tp = 0.f, fn = 0.f, fp = 0.f, bce = 0.f;
+    float tp = 0.f, fn = 0.f, fp = 0.f, bce = 0.f, sb = 0.f;
     for (int y = r.ya; y < r.yb; ++y) {
         rowwalk_stage(r, low, vrow, 1, ay, ax.n_in, y);
         if (r.live) {
@@ -516,6 +521,7 @@ __global__ __launch_bounds__(256) void tvb_reduce_kernel(const float* __restrict
             fn += t * np;
             fp += p * (1.f - t);
             bce += (fmaxf(z, 0.f) - z * t) + log1pf(e);
+            if constexpr (SDF) sb += p * phi[r.pix(ay, ax, y)];
         }
         __syncthreads();          // the next row overwrites vrow
     }
@@ -527,43 +533,66 @@ __global__ __launch_bounds__(256) void tvb_reduce_kernel(const float* __restrict
         red[wv][2] = fp;
         red[wv][3] = bce;
     }
+    if constexpr (SDF) {
+        sb = wave_sum(sb);
+        if (lane == 0) red[wv][TVB_NC] = sb;
+    }
     __syncthreads();
     if (tid < TVB_NC) {
         const long wg = ((long)r.b * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
         partial[wg * TVB_NC + tid] = ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
     }
+    if constexpr (SDF) {
+        if (tid == TVB_NC) {
+            const long wg = ((long)r.b * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
+            partial_s[wg] = ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
+        }
+    }
 }
 
 // One workgroup: the partial rows added in fp64 in a fixed order (thread t takes rows t, t + 256, ...; butterfly per wave; the four waves in order), then
 // loss_out = loss, tversky, bce, 0; coef = w_t c0, w_t c1, w_b / N; sums (nullable) = TP, FN, FP.
+// SDF: loss_out[3] = boundary = S / N with S = sum p phi (0 when w_bd is 0), loss += w_bd boundary, coef[3] = w_bd / N, sums[3] = S.
+template <bool SDF>
 __global__ __launch_bounds__(256) void tvb_finalize_kernel(const float* __restrict__ partial, int n, double npix, float alpha, float eps, float w_t, float w_b,
-                                                           float* __restrict__ loss_out, float* __restrict__ coef, float* __restrict__ sums) {
-    __shared__ double red[4][TVB_NC];
+                                                           float* __restrict__ loss_out, float* __restrict__ coef, float* __restrict__ sums,
+                                                           const float* __restrict__ partial_s, float w_bd) {
+    constexpr int NC = TVB_NC + (SDF ? 1 : 0);
+    __shared__ double red[4][NC];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    double s[TVB_NC] = {0.0, 0.0, 0.0, 0.0};
+    double s[NC] = {};
     for (int i = tid; i < n; i += 256) {
         const float4 v = reinterpret_cast<const float4*>(partial)[i];
         s[0] += (double)v.x;
         s[1] += (double)v.y;
         s[2] += (double)v.z;
         s[3] += (double)v.w;
+        if constexpr (SDF) s[TVB_NC] += (double)partial_s[i];
     }
 #pragma unroll
-    for (int c = 0; c < TVB_NC; ++c) {
+    for (int c = 0; c < NC; ++c) {
         s[c] = wave_sum(s[c]);
         if (lane == 0) red[wv][c] = s[c];
     }
     __syncthreads();
     if (tid == 0) {
-        double tot[TVB_NC];
-        for (int c = 0; c < TVB_NC; ++c) tot[c] = ((red[0][c] + red[1][c]) + red[2][c]) + red[3][c];
+        double tot[NC];
+        for (int c = 0; c < NC; ++c) tot[c] = ((red[0][c] + red[1][c]) + red[2][c]) + red[3][c];
         const double a = (double)alpha, e = (double)eps, tpe = tot[0] + e;
         const double D = tot[0] + a * tot[1] + (1.0 - a) * tot[2] + e;          // >= eps > 0
         const double tversky = 1.0 - tpe / D, bce = tot[3] / npix;
-        loss_out[0] = (float)((double)w_t * tversky + (double)w_b * bce);
+        if constexpr (SDF) {
+            const double boundary = w_bd > 0.f ? tot[TVB_NC] / npix : 0.0;          // w_bd == 0: the term is off, reported as the plain entry reports it
+            loss_out[0] = (float)(((double)w_t * tversky + (double)w_b * bce) + (double)w_bd * boundary);
+            loss_out[3] = (float)boundary;
+            coef[3] = (float)((double)w_bd / npix);
+            if (sums) sums[3] = (float)tot[TVB_NC];
+        } else {
+            loss_out[0] = (float)((double)w_t * tversky + (double)w_b * bce);
+            loss_out[3] = 0.f;
+        }
         loss_out[1] = (float)tversky;
         loss_out[2] = (float)bce;
-        loss_out[3] = 0.f;
         coef[0] = (float)((double)w_t / D);
         coef[1] = (float)((double)w_t * (1.0 - a) * tpe / (D * D));
         coef[2] = (float)((double)w_b / npix);
@@ -575,19 +604,24 @@ __global__ __launch_bounds__(256) void tvb_finalize_kernel(const float* __restri
     }
 }
 
-// An x-tile kernel with one channel: d = d loss / d z from the three coefficients the finalize left in `coef`; every pixel counts.
+// An x-tile kernel with one channel: d = d loss / d z from the three (SDF: four) coefficients the finalize left in `coef`; every pixel counts.
+template <bool SDF>
 __global__ __launch_bounds__(256) void tvb_grad_kernel(const float* __restrict__ low, const float* __restrict__ mask, const float* __restrict__ coef,
-                                                       float* __restrict__ tmp, Axis ay, Axis ax, int npx_max, int jt_cols) {
+                                                       float* __restrict__ tmp, Axis ay, Axis ax, int npx_max, int jt_cols, const float* __restrict__ phi) {
     const XTile t = xtile_begin(grad_lds(npx_max, 1), low, 1, ay, ax, npx_max, jt_cols);
     __syncthreads();
     const float c0 = coef[0], c1 = coef[1], cb = coef[2];
+    const float cd = SDF ? coef[3] : 0.f;
     for (int px = threadIdx.x; px < t.npx; px += 256) {
         const XPixel q = xtile_pixel(t, ax, 1, px);
         const float y = mask[q.pix];
         const float z = (1.f - q.lx) * q.c0[0] + q.lx * q.c1[0];
         float p, np, e;
         sigmoid_pair(z, p, np, e);
-        q.d[0] = (p * np) * (c1 - c0 * y) + cb * (p - y);
+        if constexpr (SDF)
+            q.d[0] = ((p * np) * (c1 - c0 * y) + cb * (p - y)) + (cd * phi[q.pix]) * (p * np);
+        else
+            q.d[0] = (p * np) * (c1 - c0 * y) + cb * (p - y);
     }
     __syncthreads();
     xtile_gather(t, tmp, 1, ax.n_in);
@@ -1020,41 +1054,80 @@ extern "C" int mi_upsample_gdl(const float* low, const int64_t* labels, float* l
     return MI_OK;
 }
 
-extern "C" size_t mi_upsample_tversky_bce_workspace(int B, int h, int w, int H, int W) {
-    if (B <= 0 || h <= 0 || w <= 0 || H <= 0 || W <= 0) return 0;
+// The workspace of both Tversky + BCE entries: the float4 partials, (sdf) the partial sums of p phi, the coefficients, the x pass's output.
+struct TvbWs {
+    size_t partial_s, coef, tmp, total;
+};
+static TvbWs tvb_layout(int B, int w, int H, int W, bool sdf) {
     const GdlPlan p = gdl_plan(B, H, W);
-    return up256(p.nwg * TVB_NC * sizeof(float)) + up256(3 * sizeof(float)) + (size_t)B * H * w * sizeof(float);
+    TvbWs l;
+    l.partial_s = up256(p.nwg * TVB_NC * sizeof(float));
+    l.coef = l.partial_s + (sdf ? up256(p.nwg * sizeof(float)) : 0);
+    l.tmp = l.coef + up256((sdf ? 4 : 3) * sizeof(float));
+    l.total = l.tmp + (size_t)B * H * w * sizeof(float);
+    return l;
 }
 
-extern "C" int mi_upsample_tversky_bce(const float* low, const float* mask, float* loss_out, float* dlow, float* sums, int B, int h, int w, int H, int W,
-                                       float alpha, float eps, float w_tversky, float w_bce, float grad_scale, int align_corners, void* workspace,
-                                       size_t workspace_bytes, void* stream) {
-    MI_REQUIRE(low && mask && loss_out && workspace, "mi_upsample_tversky_bce: null operand");
-    if (int rc = head_check("mi_upsample_tversky_bce", B, h, w, 1, H, W, "")) return rc;
-    MI_REQUIRE(alpha >= 0.f && alpha <= 1.f, "mi_upsample_tversky_bce: alpha outside [0, 1]");          // (a NaN fails both comparisons)
-    MI_REQUIRE(eps > 0.f, "mi_upsample_tversky_bce: eps must be positive");
-    if (workspace_bytes < mi_upsample_tversky_bce_workspace(B, h, w, H, W)) return mi_set_error(MI_ENOMEM, "mi_upsample_tversky_bce: workspace too small");
+extern "C" size_t mi_upsample_tversky_bce_workspace(int B, int h, int w, int H, int W) {
+    if (B <= 0 || h <= 0 || w <= 0 || H <= 0 || W <= 0) return 0;
+    return tvb_layout(B, w, H, W, false).total;
+}
+
+extern "C" size_t mi_upsample_tversky_bce_sdf_workspace(int B, int h, int w, int H, int W) {
+    if (B <= 0 || h <= 0 || w <= 0 || H <= 0 || W <= 0) return 0;
+    return tvb_layout(B, w, H, W, true).total;
+}
+
+// Both entries: phi == nullptr is mi_upsample_tversky_bce (`who`), else the SDF instantiations.
+template <bool SDF>
+static int tvb_launch(const char* who, const float* low, const float* mask, const float* phi, float* loss_out, float* dlow, float* sums, int B, int h, int w,
+                      int H, int W, float alpha, float eps, float w_tversky, float w_bce, float w_boundary, float grad_scale, int align_corners, void* workspace,
+                      size_t workspace_bytes, void* stream) {
+    if (int rc = head_check(who, B, h, w, 1, H, W, "")) return rc;
+    MI_REQUIRE(alpha >= 0.f && alpha <= 1.f, "%s: alpha outside [0, 1]", who);          // (a NaN fails both comparisons)
+    MI_REQUIRE(eps > 0.f, "%s: eps must be positive", who);
+    const TvbWs l = tvb_layout(B, w, H, W, SDF);
+    if (workspace_bytes < l.total) return mi_set_error(MI_ENOMEM, "%s: workspace too small", who);
     const HeadPlan p = head_plan(h, w, H, W, align_corners);
     const GdlPlan pl = gdl_plan(B, H, W);
     hipStream_t st = (hipStream_t)stream;
     float* partial = (float*)workspace;
-    float* coef = (float*)((char*)workspace + up256(pl.nwg * TVB_NC * sizeof(float)));
-    float* tmp = (float*)((char*)coef + up256(3 * sizeof(float)));
+    float* partial_s = (float*)((char*)workspace + l.partial_s);
+    float* coef = (float*)((char*)workspace + l.coef);
+    float* tmp = (float*)((char*)workspace + l.tmp);
     const size_t lds3 = grad_lds(p.npx_max, 1).bytes();          // within the 64 KB every kernel may use: launched without launch_xtile's opt-in
-    MI_REQUIRE(!dlow || lds3 <= 64 * 1024, "mi_upsample_tversky_bce: upsample factor too large for one LDS tile (%zu B)", lds3);
-    hipLaunchKernelGGL(tvb_reduce_kernel, dim3(pl.tiles_x, pl.row_groups, B), dim3(256), 0, st, low, mask, partial, p.ay, p.ax, pl.rows);
+    MI_REQUIRE(!dlow || lds3 <= 64 * 1024, "%s: upsample factor too large for one LDS tile (%zu B)", who, lds3);
+    hipLaunchKernelGGL(tvb_reduce_kernel<SDF>, dim3(pl.tiles_x, pl.row_groups, B), dim3(256), 0, st, low, mask, partial, p.ay, p.ax, pl.rows, phi, partial_s);
     MI_CHECK_LAUNCH("mi_upsample_tversky_bce reduce");
-    hipLaunchKernelGGL(tvb_finalize_kernel, dim3(1), dim3(256), 0, st, (const float*)partial, (int)pl.nwg, (double)B * H * W, alpha, eps, w_tversky, w_bce,
-                       loss_out, coef, sums);
+    hipLaunchKernelGGL(tvb_finalize_kernel<SDF>, dim3(1), dim3(256), 0, st, (const float*)partial, (int)pl.nwg, (double)B * H * W, alpha, eps, w_tversky, w_bce,
+                       loss_out, coef, sums, (const float*)partial_s, w_boundary);
     MI_CHECK_LAUNCH("mi_upsample_tversky_bce finalize");
     if (dlow) {
-        hipLaunchKernelGGL(tvb_grad_kernel, dim3(p.tiles, H, B), dim3(256), lds3, st, low, mask, (const float*)coef, tmp, p.ay, p.ax, p.npx_max, p.jt_cols);
+        hipLaunchKernelGGL(tvb_grad_kernel<SDF>, dim3(p.tiles, H, B), dim3(256), lds3, st, low, mask, (const float*)coef, tmp, p.ay, p.ax, p.npx_max, p.jt_cols,
+                           phi);
         MI_CHECK_LAUNCH("mi_upsample_tversky_bce gradient");
         hipLaunchKernelGGL(upce_pass2_kernel, dim3(nblk((long)B * h * w, 256)), dim3(256), 0, st, (const float*)tmp, (const float*)nullptr, dlow, B, 1, p.ay, w,
                            grad_scale);
         MI_CHECK_LAUNCH("mi_upsample_tversky_bce gradient rows");
     }
     return MI_OK;
+}
+
+extern "C" int mi_upsample_tversky_bce(const float* low, const float* mask, float* loss_out, float* dlow, float* sums, int B, int h, int w, int H, int W,
+                                       float alpha, float eps, float w_tversky, float w_bce, float grad_scale, int align_corners, void* workspace,
+                                       size_t workspace_bytes, void* stream) {
+    MI_REQUIRE(low && mask && loss_out && workspace, "mi_upsample_tversky_bce: null operand");
+    return tvb_launch<false>("mi_upsample_tversky_bce", low, mask, nullptr, loss_out, dlow, sums, B, h, w, H, W, alpha, eps, w_tversky, w_bce, 0.f, grad_scale,
+                             align_corners, workspace, workspace_bytes, stream);
+}
+
+extern "C" int mi_upsample_tversky_bce_sdf(const float* low, const float* mask, const float* phi, float* loss_out, float* dlow, float* sums, int B, int h, int w,
+                                           int H, int W, float alpha, float eps, float w_tversky, float w_bce, float w_boundary, float grad_scale,
+                                           int align_corners, void* workspace, size_t workspace_bytes, void* stream) {
+    MI_REQUIRE(low && mask && phi && loss_out && workspace, "mi_upsample_tversky_bce_sdf: null operand");
+    MI_REQUIRE(w_boundary >= 0.f && std::isfinite(w_boundary), "mi_upsample_tversky_bce_sdf: w_boundary must be finite and not negative");
+    return tvb_launch<true>("mi_upsample_tversky_bce_sdf", low, mask, phi, loss_out, dlow, sums, B, h, w, H, W, alpha, eps, w_tversky, w_bce, w_boundary,
+                            grad_scale, align_corners, workspace, workspace_bytes, stream);
 }
 
 extern "C" size_t mi_upsample_ce_ohem_workspace(int B, int h, int w, int K, int H, int W) {

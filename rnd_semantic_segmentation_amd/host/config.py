@@ -15,7 +15,8 @@ import yaml
 _VALID = (tuple, list, str, int, float, bool, type(None))
 _RANGES = {"TEST.PSEUDO_THRESHOLD": (0.0, 1.0), "TEST.PSEUDO_PORTION": (0.0, 1.0), "SOLVER.TVERSKY_ALPHA": (0.0, 1.0), "SOLVER.LABEL_SMOOTHING": (0.0, 1.0),
            "SOLVER.OHEM_THRESH": (0.0, 1.0), "SOLVER.OHEM_MIN_KEPT": (1, float("inf")), "SOLVER.FOCAL_GAMMA": (0.0, 8.0),
-           "SOLVER.EMA_ALPHA": (0.0, 1.0), "SOLVER.MIX_THRESHOLD": (0.0, 1.0), "SOLVER.LOVASZ_CE": (0.0, float("inf"))}      # closed intervals a merged value has to lie in
+           "SOLVER.EMA_ALPHA": (0.0, 1.0), "SOLVER.MIX_THRESHOLD": (0.0, 1.0), "SOLVER.LOVASZ_CE": (0.0, float("inf")),
+           "SOLVER.BOUNDARY_WEIGHT": (0.0, float("inf"))}      # closed intervals a merged value has to lie in
 _CHOICES = {"SOLVER.LOSS": ("ce", "gdl", "tversky", "ohem", "lovasz"), "SOLVER.GDL_WEIGHT": ("square", "identity", "sqrt")}      # the only values a merged key may take
 
 
@@ -177,6 +178,11 @@ def default_tree():
             # "tversky" = MultiscaleLoss(CompoundLoss([TverskyLoss(TVERSKY_ALPHA), BinaryCrossEntropyLoss()])) (attn/loss.py, as attn_trainer.py combines
             # them) on PraNet's four side outputs (PraNetTrainer only, whose "ce" is its own structure loss)
             "LOSS": "ce", "GDL_WEIGHT": "square", "TVERSKY_ALPHA": 0.7,
+            # not in the reference either: BOUNDARY_WEIGHT (>= 0) times the boundary loss of Kervadec et al. (MIDL 2019), mean(sigmoid(z) * phi) with phi the
+            # signed distance map of (gts >= 0.5) in pixels (mi_signed_distance, once per step on the device), added inside each of the four fused heads of
+            # LOSS "tversky" (PraNetTrainer only; mi_upsample_tversky_bce_sdf).  phi is in pixels, so useful weights are small (0.01); 0 = off, the step
+            # launches what it launched before the key existed.  Under any other LOSS or trainer a weight above 0 is refused (plugin.require_loss).
+            "BOUNDARY_WEIGHT": 0.0,
             # not in the reference either: CLASS_WEIGHTS (empty, or one non-negative factor per class: tools/class_weights.py prints them) and
             # LABEL_SMOOTHING in [0, 1] are CrossEntropyLoss's weight= and label_smoothing= for LOSS "ce" of ASPPTrainer, GALDTrainer and both FADA
             # combos, inside the fused upsample + cross-entropy heads (mi_upsample_ce_w); any other loss or trainer refuses them (plugin.ce_options)

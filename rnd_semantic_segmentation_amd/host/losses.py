@@ -4,8 +4,10 @@
   BinaryCrossEntropyLoss()           loss.py:66-74    F.binary_cross_entropy_with_logits(pred, label.float())
   CompoundLoss(losses, weights)      loss.py:42-64    sum_i w_i loss_i(*inputs), default weights 1 / N
   MultiscaleLoss(loss_fn)            loss.py:29-40    sum over zip(predicts, labels)
+  BoundaryLoss(thresh=0.5)           not in the reference: Kervadec et al. (MIDL 2019), mean(sigmoid(pred) * phi(label)), phi the signed distance map of
+                                     (label >= thresh) from mi_signed_distance; in a CompoundLoss it is the `rest` kind of term, a call of its own
 
-All of them run one autograd Function over mi_upsample_tversky_bce at the identity scale (h == H, w == W: every interpolation weight is 0), whose two
+The first four run one autograd Function over mi_upsample_tversky_bce at the identity scale (h == H, w == W: every interpolation weight is 0), whose two
 weights select the terms; a CompoundLoss of Tversky and BCE terms folds its weights into ONE call.  Inputs: pred [B,1,H,W] or [B,H,W] logits and a label
 of the same shape with values in [0, 1], both on the GPU; CPU tensors and more than one channel are refused (the reference sums dims [0, 2, 3] per channel;
 every user here has one).  PraNetTrainer does not go through these modules: PraNet.losses() runs the fused kernel on the low-resolution maps.
@@ -46,6 +48,44 @@ def tversky_bce(pred, label, alpha=0.7, eps=1.0, weights=(0.5, 0.5), with_terms=
         raise ValueError("%s: alpha in [0, 1] and eps > 0, got %r / %r" % (who, alpha, eps))
     loss, terms = _TverskyBceFn.apply(pred.float(), label.float(), float(alpha), float(eps), float(weights[0]), float(weights[1]))
     return (loss, terms) if with_terms else loss
+
+
+class _BoundaryFn(torch.autograd.Function):
+    """mean(sigmoid(pred) * phi) over every pixel, d / d pred = phi p (1 - p) / N; phi is a constant of the label."""
+
+    @staticmethod
+    def forward(ctx, pred, phi):
+        p = torch.sigmoid(pred)
+        ctx.save_for_backward(p, phi)
+        return (p * phi).mean()
+
+    @staticmethod
+    def backward(ctx, gout):
+        p, phi = ctx.saved_tensors
+        return (phi * p * (1.0 - p)) * (gout / p.numel()), None
+
+
+def boundary(pred, label, thresh=0.5):
+    """The boundary loss on materialised logits: mean(sigmoid(pred) * phi(label)); the gradient flows to pred only and `label` is left as it is."""
+    who = "the boundary loss"
+    if not (pred.is_cuda and label.is_cuda):
+        raise NotImplementedError("%s runs on the MI355X only (got %s / %s tensors): no CPU path exists" % (who, pred.device, label.device))
+    if pred.dim() not in (3, 4) or (pred.dim() == 4 and pred.shape[1] != 1):
+        raise NotImplementedError("%s takes one-channel logits [B,1,H,W] or [B,H,W] (got %s: C > 1 is not implemented)" % (who, tuple(pred.shape)))
+    if tuple(label.shape) != tuple(pred.shape):
+        raise ValueError("%s: label %s does not match pred %s" % (who, tuple(label.shape), tuple(pred.shape)))
+    B, H, W = label.shape[0], label.shape[-2], label.shape[-1]
+    phi = K.signed_distance(label.detach().float().contiguous().view(B, H, W), thresh)
+    return _BoundaryFn.apply(pred.float(), phi.view(pred.shape))
+
+
+class BoundaryLoss(nn.Module):
+    def __init__(self, thresh=0.5):
+        super().__init__()
+        self.thresh = thresh
+
+    def forward(self, pred, label):
+        return boundary(pred, label, self.thresh)
 
 
 class TverskyLoss(nn.Module):

@@ -25,6 +25,15 @@ def require_loss(cfg, who, supported=("ce",)):
     if loss not in supported:
         raise NotImplementedError("{} trains with SOLVER.LOSS {} only (got {!r}); {}".format(
             who, " / ".join(repr(s) for s in supported), loss, _LOSS_HOME.get(loss, "no trainer implements it")))
+    weight = getattr(getattr(cfg, "SOLVER", None), "BOUNDARY_WEIGHT", 0.0)
+    if isinstance(weight, bool) or not isinstance(weight, (int, float)) or not 0.0 <= weight < float("inf"):      # (a merged value was checked there; this one was assigned)
+        raise ValueError("SOLVER.BOUNDARY_WEIGHT {!r} must be a finite number >= 0".format(weight))
+    if weight > 0.0 and "tversky" not in supported:
+        raise NotImplementedError("SOLVER.BOUNDARY_WEIGHT (the boundary loss) is wired into the fused Tversky + BCE heads of PraNetTrainer "
+                                  "(configs/pranet_src_kvasir_boundary.yaml); {} does not know it".format(who))
+    if weight > 0.0 and loss != "tversky":
+        raise ValueError("SOLVER.BOUNDARY_WEIGHT {!r} needs SOLVER.LOSS 'tversky' (got {!r} for {}): the boundary term lives in the fused Tversky + BCE "
+                         "heads".format(weight, loss, who))
     return loss
 
 

@@ -122,12 +122,15 @@ class _PraNetRun(Run):
             acc(gate, dgate, True)
         return self.node(gk.gra_fwd(gate.t, feat.t), back)
 
-    def tversky_head(self, low, mask, alpha, eps, weights):
+    def tversky_head(self, low, mask, alpha, eps, weights, phi=None, w_boundary=0.0):
         """CompoundLoss([TverskyLoss(alpha, eps), BinaryCrossEntropyLoss()], weights)(F.interpolate(low, size=mask.shape[-2:], mode="bilinear"), mask)
         (attn/loss.py on a side output of PraNet_Res2Net.py:127-170) fused, shaped like GALD's gdl_head: mi_upsample_tversky_bce never writes the
-        full-resolution map, and its gradient pass has run by the time the loss exists (the coefficients stay on the device)."""
+        full-resolution map, and its gradient pass has run by the time the loss exists (the coefficients stay on the device).  With phi (the signed
+        distance map of the mask) the head adds w_boundary * mean(sigmoid(z) * phi) in the same launches (mi_upsample_tversky_bce_sdf)."""
         B, h, w, _ = low.t.shape
-        loss_out, dlow, _ = K.upsample_tversky_bce(low.t.reshape(B, h, w), mask, want_grad=self.rec, alpha=alpha, eps=eps, weights=weights, align_corners=False)
+        extra = {} if phi is None else {"phi": phi, "w_boundary": w_boundary}
+        loss_out, dlow, _ = K.upsample_tversky_bce(low.t.reshape(B, h, w), mask, want_grad=self.rec, alpha=alpha, eps=eps, weights=weights, align_corners=False,
+                                                   **extra)
         return self.node(loss_out[0].clone(), lambda g: acc(low, dlow.view(B, h, w, 1) * g, True))
 
 
@@ -347,16 +350,21 @@ class PraNet(Engine):
             return maps                                                              # four scalar losses
         return [run.tap("map%d" % i, m) for i, m in enumerate(maps)]
 
-    def losses(self, x, gts, alpha=0.7, eps=1.0, weights=(0.5, 0.5)):
+    def losses(self, x, gts, alpha=0.7, eps=1.0, weights=(0.5, 0.5), boundary_weight=0.0):
         """(loss5, loss4, loss3, loss2) = CompoundLoss([TverskyLoss(alpha, eps), BinaryCrossEntropyLoss()], weights)(lateral_map_i, gts) (attn/loss.py)
         without materialising the four [B,1,H,W] maps: each head's final upsample, its loss and the gradient are one fused call on the low-resolution
-        map (mi_upsample_tversky_bce).  gts [B,1,H,W] or [B,H,W], values in [0, 1], the size of x."""
+        map (mi_upsample_tversky_bce).  gts [B,1,H,W] or [B,H,W], values in [0, 1], the size of x.
+        boundary_weight > 0 adds that many times the boundary loss mean(sigmoid(z) * phi) to every head: phi, the signed distance map of (gts >= 0.5), is
+        computed once on the device (mi_signed_distance) and shared by the four heads; at 0 neither it nor the heads' phi mode is launched."""
         if not 0.0 <= float(alpha) <= 1.0 or not float(eps) > 0.0 or len(weights) != 2:
             raise ValueError("PraNet.losses: alpha in [0, 1], eps > 0 and weights = (tversky, bce), got %r / %r / %r" % (alpha, eps, weights))
         if gts.dim() not in (3, 4) or (gts.dim() == 4 and gts.shape[1] != 1) or (gts.shape[0], gts.shape[-2], gts.shape[-1]) != (x.shape[0], x.shape[2], x.shape[3]):
             raise ValueError("PraNet.losses: gts must be [B,1,H,W] or [B,H,W] of the images' size %s, got %s" % (tuple(x.shape), tuple(gts.shape)))
+        boundary_weight = _boundary_weight(boundary_weight, "PraNet.losses")
         mask = gts.detach().float().reshape(gts.shape[0], gts.shape[-2], gts.shape[-1]).contiguous()
         self._tversky = (mask, float(alpha), float(eps), (float(weights[0]), float(weights[1])))
+        if boundary_weight > 0.0:
+            self._tversky += (K.signed_distance(mask, 0.5), boundary_weight)
         try:
             return super().forward(x)
         finally:
@@ -364,19 +372,34 @@ class PraNet(Engine):
 
 
 # ------------------------------------------------------------------------------------------------ schedule / trainer / tester
-def step_losses(net, images, gts, criterion="ce", alpha=0.7, literal=False):
+def _boundary_weight(weight, who):
+    if isinstance(weight, bool) or not isinstance(weight, (int, float)) or not 0.0 <= weight < float("inf"):          # (a nan fails both comparisons)
+        raise ValueError("%s: boundary_weight must be a finite number >= 0, got %r" % (who, weight))
+    return float(weight)
+
+
+def step_losses(net, images, gts, criterion="ce", alpha=0.7, literal=False, boundary_weight=0.0):
     """The four losses (lateral 5, 4, 3, 2) of one step.  "ce": the trainer's own structure loss on the four maps (pranet_trainer.py:50-54);
     "tversky": CompoundLoss([TverskyLoss(alpha), BinaryCrossEntropyLoss()]) per side output, the terms MultiscaleLoss adds up (attn/loss.py; every
     head's label is `gts`) - fused with the heads' upsamples (PraNet.losses), or with literal=True (tests and tools/pranet_bench.py only) the
-    composition without the fusion: net(images) materialises the four maps, each goes through the host/losses.py modules."""
+    composition without the fusion: net(images) materialises the four maps, each goes through the host/losses.py modules.
+    boundary_weight > 0 ("tversky" only): plus that many times the boundary loss per side output - inside the fused heads, or with literal=True as a
+    third term BoundaryLoss() of the compound."""
+    boundary_weight = _boundary_weight(boundary_weight, "step_losses")
+    if boundary_weight > 0.0 and criterion == "ce":
+        raise ValueError("step_losses: boundary_weight needs criterion 'tversky' (the structure loss has no boundary term)")
     if criterion == "ce":
         return [structure_loss(o, gts) for o in net(images)]
     if criterion != "tversky":
         raise ValueError("criterion must be 'ce' or 'tversky', got %r" % (criterion,))
     if literal:
-        from .losses import BinaryCrossEntropyLoss, CompoundLoss, TverskyLoss
+        from .losses import BinaryCrossEntropyLoss, BoundaryLoss, CompoundLoss, TverskyLoss
         crit = CompoundLoss([TverskyLoss(alpha=alpha), BinaryCrossEntropyLoss()])
+        if boundary_weight > 0.0:
+            crit = CompoundLoss([TverskyLoss(alpha=alpha), BinaryCrossEntropyLoss(), BoundaryLoss()], weights=[0.5, 0.5, boundary_weight])
         return [crit(o, gts) for o in net(images)]
+    if boundary_weight > 0.0:
+        return list(net.losses(images, gts, alpha=alpha, boundary_weight=boundary_weight))
     return list(net.losses(images, gts, alpha=alpha))
 
 
@@ -385,9 +408,9 @@ class GraphedStep:
     launches - captured once as a HIP graph and replayed: the host cost of a step becomes one graph launch.  Inputs are copied into static
     buffers; the learning rate and Adam's step count live in device memory (FlatAdam.set_device_hyper)."""
 
-    def __init__(self, net, opt, images, gts, warmup=3, criterion="ce", alpha=0.7, literal=False):
+    def __init__(self, net, opt, images, gts, warmup=3, criterion="ce", alpha=0.7, literal=False, boundary_weight=0.0):
         self.net, self.opt = net, opt
-        self.criterion, self.alpha, self.literal = criterion, alpha, literal
+        self.criterion, self.alpha, self.literal, self.boundary_weight = criterion, alpha, literal, boundary_weight
         self.x, self.gt = images.detach().clone(), gts.detach().clone()
         net.ensure_flat()
         side = torch.cuda.Stream()
@@ -407,7 +430,7 @@ class GraphedStep:
 
     def _core(self):
         self.opt.zero_grad()
-        ls = step_losses(self.net, self.x, self.gt, self.criterion, self.alpha, self.literal)
+        ls = step_losses(self.net, self.x, self.gt, self.criterion, self.alpha, self.literal, self.boundary_weight)
         (ls[3] + ls[2] + ls[1] + ls[0]).backward()
         self.opt.step()
         return [l.detach() for l in ls]
@@ -469,7 +492,8 @@ class PraNetTrainer(BaseTrainer):
     """pranet_trainer.py:12-104: Adam(BASE_LR / 8), three passes per batch (the reference's multi-scale loop, whose rescale is a no-op:
     it resizes to trainsize whatever the rate - Appendix B), structure loss on the four side outputs, gradient clamp 0.5, warm-up + cosine
     schedule per epoch, checkpoint {'epoch', 'model', 'optimizer'} as PraNet-<epoch>.pth.  SOLVER.LOSS "ce" (default) is that structure loss;
-    "tversky" replaces it with the Tversky + BCE compound of attn/loss.py on the same four outputs (step_losses), everything else unchanged."""
+    "tversky" replaces it with the Tversky + BCE compound of attn/loss.py on the same four outputs (step_losses), everything else unchanged;
+    SOLVER.BOUNDARY_WEIGHT > 0 adds the boundary loss on the label's signed distance map to each of those four heads."""
 
     LOSSES = ("ce", "tversky")
 
@@ -479,6 +503,7 @@ class PraNetTrainer(BaseTrainer):
     def init_params(self):
         self.loss_name = getattr(self.cfg.SOLVER, "LOSS", "ce")                  # (not in the reference's config: host/config.py)
         self.tversky_alpha = float(getattr(self.cfg.SOLVER, "TVERSKY_ALPHA", 0.7))
+        self.boundary_weight = float(getattr(self.cfg.SOLVER, "BOUNDARY_WEIGHT", 0.0))      # > 0: "tversky" only (plugin.require_loss refused the rest)
         self.trainsize = self.cfg.INPUT.TRAINSIZE
         self.model = PraNet().to(self.device)
         self.model.ensure_flat()
@@ -504,7 +529,8 @@ class PraNetTrainer(BaseTrainer):
             if st["step"] is not None and st["shape"] == (tuple(images.shape), tuple(gts.shape)):
                 return [l.clone() for l in st["step"](images, gts)]
             if st["step"] is None and st["eager"] >= self.GRAPH_WARMUP:
-                st["step"] = GraphedStep(self.model, self.optimizer, images, gts, warmup=0, criterion=self.loss_name, alpha=self.tversky_alpha)
+                st["step"] = GraphedStep(self.model, self.optimizer, images, gts, warmup=0, criterion=self.loss_name, alpha=self.tversky_alpha,
+                                         boundary_weight=self.boundary_weight)
                 st["shape"] = (tuple(images.shape), tuple(gts.shape))
                 return [l.clone() for l in st["step"](images, gts)]
             st["eager"] += 1
@@ -513,7 +539,7 @@ class PraNetTrainer(BaseTrainer):
             outs = self.model(images)
             losses = [self.structure_loss(o, gts) for o in outs]
         else:
-            losses = step_losses(self.model, images, gts, self.loss_name, self.tversky_alpha)
+            losses = step_losses(self.model, images, gts, self.loss_name, self.tversky_alpha, boundary_weight=self.boundary_weight)
         loss = losses[3] + losses[2] + losses[1] + losses[0]
         loss.backward()
         self.optimizer.step()                                       # clip_gradient(optimizer, 0.5) is fused into the update

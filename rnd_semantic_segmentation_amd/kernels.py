@@ -664,21 +664,54 @@ def upsample_lovasz_head(low, labels, crit, want_grad=True, grad_scale=1.0, igno
     return out, dlow
 
 
-def upsample_tversky_bce(low, mask, want_grad=True, grad_scale=1.0, alpha=0.7, eps=1.0, weights=(0.5, 0.5), align_corners=False, want_sums=False):
+def upsample_tversky_bce(low, mask, want_grad=True, grad_scale=1.0, alpha=0.7, eps=1.0, weights=(0.5, 0.5), align_corners=False, want_sums=False,
+                         phi=None, w_boundary=0.0):
     """Fused upsample + CompoundLoss([TverskyLoss(alpha, eps), BinaryCrossEntropyLoss()], weights) (reference attn/loss.py) for one-channel logits:
     low [B,h,w] fp32, mask [B,H,W] fp32 in [0, 1] (H >= h, W >= w; the same size: no upsample).  Returns (loss_out[4] = loss, tversky, bce, 0;
-    dlow [B,h,w] or None; sums[3] = TP, FN, FP or None).  Nothing is read back between its launches."""
+    dlow [B,h,w] or None; sums[3] = TP, FN, FP or None).  Nothing is read back between its launches.
+    phi ([B,H,W] fp32, signed_distance(mask)) adds w_boundary * mean(sigmoid(z) * phi), the boundary loss, through mi_upsample_tversky_bce_sdf:
+    loss_out[3] = that mean, sums[4] = TP, FN, FP, sum p phi.  Without phi the call is mi_upsample_tversky_bce as ever (w_boundary must be 0)."""
     if low.dim() != 3 or mask.dim() != 3 or mask.shape[0] != low.shape[0] or mask.device != low.device:
         raise _lib.MiError("upsample_tversky_bce: low [B,h,w] and mask [B,H,W] on one device, got %s on %s and %s on %s"
                            % (tuple(low.shape), low.device, tuple(mask.shape), mask.device))
     if len(weights) != 2:
         raise ValueError("upsample_tversky_bce: weights = (tversky, bce), got %r" % (weights,))
     L = _lib.lib()
-    dims, ws, out, dlow = _head_buffers(low, mask, L.mi_upsample_tversky_bce_workspace, "uptvb", want_grad, torch.float32, "mask")
-    sums = torch.empty(3, dtype=torch.float32, device=low.device) if want_sums else None
-    check(L.mi_upsample_tversky_bce(_p(low), _p(mask), _p(out), _p(dlow), _p(sums), *dims, float(alpha), float(eps), float(weights[0]),
-                                    float(weights[1]), float(grad_scale), int(bool(align_corners)), _p(ws), ws.numel(), _stream()), "mi_upsample_tversky_bce")
+    if phi is None:
+        if float(w_boundary) != 0.0:
+            raise ValueError("upsample_tversky_bce: w_boundary %r needs phi (signed_distance(mask))" % (w_boundary,))
+        dims, ws, out, dlow = _head_buffers(low, mask, L.mi_upsample_tversky_bce_workspace, "uptvb", want_grad, torch.float32, "mask")
+        sums = torch.empty(3, dtype=torch.float32, device=low.device) if want_sums else None
+        check(L.mi_upsample_tversky_bce(_p(low), _p(mask), _p(out), _p(dlow), _p(sums), *dims, float(alpha), float(eps), float(weights[0]),
+                                        float(weights[1]), float(grad_scale), int(bool(align_corners)), _p(ws), ws.numel(), _stream()), "mi_upsample_tversky_bce")
+        return out, dlow, sums
+    _chk(phi, torch.float32, "phi")
+    if tuple(phi.shape) != tuple(mask.shape) or phi.device != mask.device:
+        raise _lib.MiError("upsample_tversky_bce: phi must be %s on %s like the mask, got %s on %s" % (tuple(mask.shape), mask.device, tuple(phi.shape), phi.device))
+    dims, ws, out, dlow = _head_buffers(low, mask, L.mi_upsample_tversky_bce_sdf_workspace, "uptvb", want_grad, torch.float32, "mask")
+    sums = torch.empty(4, dtype=torch.float32, device=low.device) if want_sums else None
+    check(L.mi_upsample_tversky_bce_sdf(_p(low), _p(mask), _p(phi), _p(out), _p(dlow), _p(sums), *dims, float(alpha), float(eps), float(weights[0]),
+                                        float(weights[1]), float(w_boundary), float(grad_scale), int(bool(align_corners)), _p(ws), ws.numel(), _stream()),
+          "mi_upsample_tversky_bce_sdf")
     return out, dlow, sums
+
+
+def signed_distance(mask, thresh=0.5, want_d2=False, want_counts=False):
+    """Exact signed Euclidean distance map (mi_signed_distance, the definition: include/mi355seg.h): mask [B,H,W] fp32 on the GPU -> phi [B,H,W] fp32,
+    +sqrt(d2) outside G = (mask >= thresh) and -(sqrt(d2) - 1) inside, 0 for an image without a contour.  want_d2 / want_counts (tests and
+    diagnosis) return (phi, d2 int32 [B,H,W] or None, counts int32 [B,2] = foreground, background pixels or None) instead.  Nothing is read back."""
+    _chk(mask, torch.float32, "mask")
+    if mask.dim() != 3:
+        raise _lib.MiError("signed_distance: mask must be [B,H,W], got %s" % (tuple(mask.shape),))
+    B, H, W = mask.shape
+    L = _lib.lib()
+    need = L.mi_signed_distance_workspace(B, H, W)
+    ws = _workspace(need, mask.device, "sdf")
+    phi = torch.empty_like(mask)
+    d2 = torch.empty(mask.shape, dtype=torch.int32, device=mask.device) if want_d2 else None
+    counts = torch.empty((B, 2), dtype=torch.int32, device=mask.device) if want_counts else None
+    check(L.mi_signed_distance(_p(mask), float(thresh), _p(phi), _p(d2), _p(counts), B, H, W, _p(ws), ws.numel() if need else 0, _stream()), "mi_signed_distance")
+    return (phi, d2, counts) if (want_d2 or want_counts) else phi
 
 
 def count_bad_labels(holder, loss_out):
