@@ -606,6 +606,55 @@ int mi_signed_distance(const float* mask /*[B][H][W]*/, float thresh, float* phi
                        int32_t* counts /*[B][2], may be NULL: foreground, background pixels*/, int B, int H, int W, void* workspace,
                        size_t workspace_bytes, void* stream);
 
+/* ---- connected components of a batch of binary masks (not in the reference: scipy.ndimage.label with the cross or the full 3 x 3 structure) ----
+ * mask [B][H][W] uint8; per image the foreground is F = (mask == cls) on the H x W grid.
+ *   Two foreground pixels are neighbours when they differ by one step along x or y (connectivity 4), or by at most one step along each
+ *       (connectivity 8).  A component is a maximal set of foreground pixels joined by chains of neighbours.
+ *   The first pixel of a component is its smallest linear index y * W + x.  Components are numbered 1..n per image in the raster order of their
+ *       first pixels.
+ * Outputs, all written by every call:
+ *   labels [B][H][W] int32 (may be NULL): 0 on background, the component's number elsewhere.
+ *   roots  [B][H][W] int32 (may be NULL): the linear index of the component's first pixel, -1 on background.
+ *   counts [B] int32: n per image.
+ * Bit-reproducible run to run: union-find on row runs whose roots are the smallest index of their component whatever the order of the merges;
+ * integer atomics only, no floating point.  Six launches on `stream`, nothing read back in between (capturable in a HIP graph): rows, merge,
+ * flatten, a scan of the rows' root counts, the numbers, the outputs.  No launch waits on another workgroup.  The workspace
+ * (mi_label_components_workspace bytes, 8-byte aligned, no initialisation needed) holds 8 bytes and one bit per pixel and 4 bytes per row;
+ * mi_label_components_workspace returns 0 for sizes the call refuses.
+ * Refused before any launch (MI_EINVAL unless stated): a NULL mask / counts / workspace, labels and roots both NULL, a non-positive size,
+ * B > 65535, a side above 4096, cls outside 0..255, a connectivity other than 4 or 8, a workspace that is too small (MI_ENOMEM). */
+size_t mi_label_components_workspace(int B, int H, int W);
+int mi_label_components(const uint8_t* mask /*[B][H][W]*/, int B, int H, int W, int cls, int connectivity, int32_t* labels /*[B][H][W], may be NULL*/,
+                        int32_t* roots /*[B][H][W], may be NULL*/, int32_t* counts /*[B]*/, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- lesion-wise detection counts and component filtering of binary masks (TEST.LESION_METRICS, TEST.MASK_MIN_AREA, TEST.MASK_KEEP_LARGEST;
+ * not in the reference) ----
+ * pred [B][H][W] uint8, labels [B][H][W] int64 (any value other than cls is background); per image P = (pred == cls), G = (label == cls), their
+ * components as mi_label_components defines them at `connectivity`.
+ *   Filter: P' = the union of the components of P with at least min_area pixels; with keep_largest only the largest of those stays, a tie goes to
+ *       the component whose first pixel comes first in raster order.  An empty P stays empty.
+ *   True positives: a component p of P' with hit(p) = |p & G| >= 1 and 1000 hit(p) >= overlap_permille |p| (64-bit integers); any other
+ *       component of P' is a false positive.
+ *   Detected lesions: a component g of G with hit'(g) = |g & P'| >= 1 and 1000 hit'(g) >= overlap_permille |g|; any other is missed.
+ *       overlap_permille 0: any shared pixel counts.
+ * Outputs, all written by every call:
+ *   filtered [B][H][W] uint8 (may be NULL): cls on P', and (cls == 0 ? 1 : 0) elsewhere.
+ *   ints [B][MI_LESION_INTS] int64: 0 |P|, 1 |P'|, 2 |G|, 3 components of P, 4 components of P', 5 components of G, 6 true-positive components
+ *        of P', 7 detected components of G, 8 the largest component area of P, 9 of G, 10 |P' & G|, 11 components of P the filter removed
+ *        (counted on its own: equal to field 3 minus field 4).
+ * Bit-reproducible run to run: integer arithmetic with integer atomics, no floating point.  A memset and seven launches on `stream`, nothing
+ * read back in between (capturable in a HIP graph): rows, merge and flatten over P and G as 2 B planes, then selection, hits, counts and the
+ * output row.  No launch waits on another workgroup.  The workspace (mi_lesion_score_workspace bytes, 8-byte aligned, no initialisation needed)
+ * holds 24 bytes and two bits per pixel, 8 bytes per row and 128 bytes per image; mi_lesion_score_workspace returns 0 for sizes the call refuses.
+ * Refused before any launch (MI_EINVAL unless stated): a NULL pred / labels / ints / workspace, a non-positive size, B > 65535, a side above
+ * 4096, cls outside 0..255, a connectivity other than 4 or 8, a negative min_area, keep_largest other than 0 / 1, overlap_permille outside
+ * 0..1000, a workspace that is too small (MI_ENOMEM). */
+#define MI_LESION_INTS 12
+size_t mi_lesion_score_workspace(int B, int H, int W);
+int mi_lesion_score(const uint8_t* pred /*[B][H][W]*/, const int64_t* labels /*[B][H][W]*/, int B, int H, int W, int cls, int connectivity, int min_area,
+                    int keep_largest, int overlap_permille, uint8_t* filtered /*[B][H][W], may be NULL*/, int64_t* ints /*[B][MI_LESION_INTS]*/,
+                    void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- optimiser: torch.optim.SGD(momentum, weight_decay) on flat fp32 buffers (aspp_trainer.py:25-26,94-95)
  * g' = g + wd*p; buf = mu*buf + g'; p -= lr*buf  (buf zero-initialised == torch's first-step buf = g'). */
 int mi_sgd_step(float* p, const float* g, float* buf, size_t n, float lr, float momentum, float weight_decay, void* stream);

@@ -79,6 +79,10 @@ SIGNATURES = {
     "mi_surface_score": (I, [P, P] + [I] * 5 + [P, I, P, P, P, Z, P]),
     "mi_signed_distance_workspace": (Z, [I] * 3),
     "mi_signed_distance": (I, [P, F, P, P, P] + [I] * 3 + [P, Z, P]),
+    "mi_label_components_workspace": (Z, [I] * 3),
+    "mi_label_components": (I, [P] + [I] * 5 + [P, P, P, P, Z, P]),
+    "mi_lesion_score_workspace": (Z, [I] * 3),
+    "mi_lesion_score": (I, [P, P] + [I] * 8 + [P, P, P, Z, P]),
     "mi_stem_pool_fwd": (I, [P, P, P, P, P] + [I] * 6 + [P]),
     "mi_stem_pool_bwd": (I, [P, P, P, P] + [I] * 6 + [P]),
     "mi_stem_im2col": (I, [P, P] + [I] * 6 + [P]),

@@ -224,6 +224,14 @@ def default_tree():
         # symmetric surface distance, and surface Dice at each of SURFACE_TOLERANCES (at most 8 pixel distances >= 0) - measured exactly on the
         # device (mi_surface_score), logged and written to OUTPUT_DIR/pranet_surface_metrics.json; labels other than 1 are background
         # (metrics.surface_settings);
+        # LESION_METRICS True (PranetTester only; the other testers refuse it) = lesion-wise detection rates from the connected components of the
+        # mask and of the label (LESION_CONNECTIVITY 4 or 8), counted on the device (mi_lesion_score): a lesion is detected, and a predicted
+        # component a true positive, when the other mask covers at least the share LESION_OVERLAP in [0, 1] of it (0 = any shared pixel) - lesion
+        # recall, component precision, their F1, false positives per image - logged and written to OUTPUT_DIR/pranet_lesion_metrics.json.
+        # MASK_MIN_AREA > 0 drops the predicted components of fewer pixels, MASK_KEEP_LARGEST True keeps only the largest of the rest, before
+        # the intersection / union lines, the surface metrics and the lesion counts see the mask (the polyp metrics are measured on the soft map
+        # and are not filtered); either filter key works with or without LESION_METRICS; labels other than 1 are background
+        # (metrics.lesion_settings);
         # CRF True (ASPPTester only; the other testers refuse it) = the third part of DeepLabV2 as published, in its locally connected form: the
         # full-resolution probability map is refined by CRF_ITER mean-field iterations over a CRF_WINDOW x CRF_WINDOW window dilated by
         # CRF_DILATION, with a position kernel (weight CRF_POS_W, sigma CRF_POS_XY pixels) and a bilateral kernel (weight CRF_BI_W, sigmas
@@ -257,6 +265,7 @@ def default_tree():
         "TEST": {"BATCH_SIZE": 1, "PRECISION": "fp32", "SCALES": (1.0,), "FLIP": False, "FUSED_SCORE": True, "PSEUDO_THRESHOLD": 0.0,
                  "PSEUDO_CLASSWISE": False, "PSEUDO_PORTION": 0.5, "POLYP_METRICS": False,
                  "SURFACE_METRICS": False, "SURFACE_PERCENTILE": 95, "SURFACE_TOLERANCES": (2.0,),
+                 "LESION_METRICS": False, "LESION_CONNECTIVITY": 8, "LESION_OVERLAP": 0.0, "MASK_MIN_AREA": 0, "MASK_KEEP_LARGEST": False,
                  "CRF": False, "CRF_ITER": 5, "CRF_WINDOW": 7, "CRF_DILATION": 4, "CRF_POS_W": 3.0, "CRF_POS_XY": 3.0, "CRF_BI_W": 10.0,
                  "CRF_BI_XY": 80.0, "CRF_BI_RGB": 13.0,
                  "SLIDE": False, "SLIDE_CROP": (769, 769), "SLIDE_STRIDE": (513, 513),

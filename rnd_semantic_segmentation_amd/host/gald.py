@@ -25,7 +25,8 @@ from .. import gk
 from .. import kernels as K
 from . import arch
 from .metrics import (AverageMeter, adjust_learning_rate, confusion_matrix, dump_json, intersectionAndUnionGPU, require_no_boundary, require_no_crf,
-                      require_no_curves, require_no_polyp_metrics, require_no_slide, require_no_surface, require_plain_argmax, require_single_scale)
+                      require_no_curves, require_no_lesion, require_no_polyp_metrics, require_no_slide, require_no_surface, require_plain_argmax,
+                      require_single_scale)
 from .plugin import BaseTrainer
 from .tape import Engine, FlatAdam, Run, Unit, acc, grad_target, rup32, tile_route
 
@@ -672,6 +673,7 @@ class GALDTester:
         require_plain_argmax(cfg, "GALDTester")
         require_no_polyp_metrics(cfg, "GALDTester")
         require_no_surface(cfg, "GALDTester")
+        require_no_lesion(cfg, "GALDTester")
         require_no_crf(cfg, "GALDTester")
         require_no_slide(cfg, "GALDTester")
         require_no_boundary(cfg, "GALDTester")

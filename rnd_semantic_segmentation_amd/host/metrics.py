@@ -1353,6 +1353,163 @@ class SurfaceMeter(object):
             logger.info("Surface metric, val result: " + ", ".join("{} {:.4f}".format(k, r[k]) for k in self.keys[3:]) + ".")
 
 
+# ----------------------------------------------------------------------------- lesion-wise metrics and mask clean-up (TEST.LESION_METRICS, TEST.MASK_*)
+LESION_INTS = 12                        # MI_LESION_INTS of include/mi355seg.h, where the definition stands
+LESION_FIELDS = ("pred_pixels", "kept_pixels", "lesion_pixels", "pred_components", "kept_components", "lesions", "true_positives", "detected",
+                 "largest_pred", "largest_lesion", "overlap_pixels", "removed_components")
+LESION_DEFAULTS = {"LESION_METRICS": False, "LESION_CONNECTIVITY": 8, "LESION_OVERLAP": 0.0, "MASK_MIN_AREA": 0, "MASK_KEEP_LARGEST": False}
+
+
+def _lesion_check(connectivity, overlap, min_area, keep_largest, names=("connectivity", "overlap", "min_area", "keep_largest")):
+    if isinstance(connectivity, bool) or not isinstance(connectivity, (int, np.integer)) or int(connectivity) not in (4, 8):
+        raise ValueError("%s %r must be 4 or 8" % (names[0], connectivity))
+    if isinstance(overlap, bool) or not isinstance(overlap, (int, float, np.integer, np.floating)) or not 0.0 <= overlap <= 1.0:
+        raise ValueError("%s %r must be a number in [0, 1]" % (names[1], overlap))
+    if isinstance(min_area, bool) or not isinstance(min_area, (int, np.integer)) or min_area < 0:
+        raise ValueError("%s %r must be an integer >= 0" % (names[2], min_area))
+    if not isinstance(keep_largest, bool):
+        raise ValueError("%s %r must be True or False" % (names[3], keep_largest))
+    return int(connectivity), float(overlap), int(min_area), keep_largest
+
+
+def lesion_settings(cfg):
+    """None while TEST.LESION_METRICS is False, TEST.MASK_MIN_AREA 0 and TEST.MASK_KEEP_LARGEST False (none a reference key; absent = these
+    defaults), else (metrics, connectivity, overlap, min_area, keep_largest): LESION_METRICS, LESION_CONNECTIVITY (4 or 8), LESION_OVERLAP (a
+    share in [0, 1]), MASK_MIN_AREA (pixels, >= 0), MASK_KEEP_LARGEST.  Every key is checked whether or not the feature is on."""
+    test = cfg.TEST
+    v = {k: (test[k] if k in test else d) for k, d in LESION_DEFAULTS.items()}
+    if not isinstance(v["LESION_METRICS"], bool):
+        raise ValueError("TEST.LESION_METRICS %r must be True or False" % (v["LESION_METRICS"],))
+    rest = _lesion_check(v["LESION_CONNECTIVITY"], v["LESION_OVERLAP"], v["MASK_MIN_AREA"], v["MASK_KEEP_LARGEST"],
+                         ("TEST.LESION_CONNECTIVITY", "TEST.LESION_OVERLAP", "TEST.MASK_MIN_AREA", "TEST.MASK_KEEP_LARGEST"))
+    if not (v["LESION_METRICS"] or rest[2] > 0 or rest[3]):
+        return None
+    return (v["LESION_METRICS"],) + rest
+
+
+def require_no_lesion(cfg, who):
+    """Components are labelled on PranetTester's binary masks: testers of multi-class models refuse the keys rather than ignore them."""
+    if lesion_settings(cfg) is not None:
+        raise NotImplementedError("%s: TEST.LESION_METRICS / TEST.MASK_MIN_AREA / TEST.MASK_KEEP_LARGEST - lesion-wise metrics and component "
+                                  "filtering exist for PranetTester only; leave them at False / 0 / False" % (who,))
+
+
+def lesion_image_stats(ints):
+    """One image's row of mi_lesion_score's ints [12] (or the same numbers counted elsewhere) as a dict of Python ints under LESION_FIELDS, plus
+    false_positives (kept components that are no true positive) and missed (lesions not detected).  The definitions: include/mi355seg.h."""
+    ints = np.asarray(ints.cpu() if isinstance(ints, torch.Tensor) else ints).astype(np.int64)
+    if ints.shape != (LESION_INTS,):
+        raise ValueError("lesion_image_stats: ints must be [%d], got %s" % (LESION_INTS, ints.shape))
+    s = {k: int(v) for k, v in zip(LESION_FIELDS, ints)}
+    if ((ints < 0).any() or s["removed_components"] != s["pred_components"] - s["kept_components"] or s["true_positives"] > s["kept_components"]
+            or s["detected"] > s["lesions"] or s["kept_pixels"] > s["pred_pixels"] or s["overlap_pixels"] > min(s["kept_pixels"], s["lesion_pixels"])):
+        raise ValueError("lesion_image_stats: the integers %r contradict each other" % (ints.tolist(),))
+    s["false_positives"] = s["kept_components"] - s["true_positives"]
+    s["missed"] = s["lesions"] - s["detected"]
+    return s
+
+
+def _ratio_or_none(num, den):
+    return float(num) / float(den) if den else None
+
+
+class LesionMeter(object):
+    """Dataset aggregation of lesion_image_stats.  Sums over the images, then lesion recall = detected / lesions, component precision = true
+    positives / kept components, their F1, false positives per image; the images with a lesion and none detected, the images without a lesion and
+    a (kept) prediction; what the filter removed.  A ratio whose denominator is 0 is None, not 0 or 1."""
+    SUMS = ("lesions", "detected", "kept_components", "true_positives", "false_positives", "removed_components")
+
+    def __init__(self):
+        self.reset()
+
+    def reset(self):
+        self.sums = {k: 0 for k in self.SUMS}
+        self.removed_pixels = 0
+        self.count = 0
+        self.images_missed = 0
+        self.images_false_alarm = 0
+
+    def update(self, stats):
+        self.count += 1
+        for k in self.SUMS:
+            self.sums[k] += int(stats[k])
+        self.removed_pixels += int(stats["pred_pixels"]) - int(stats["kept_pixels"])
+        self.images_missed += 1 if stats["lesions"] > 0 and stats["detected"] == 0 else 0
+        self.images_false_alarm += 1 if stats["lesions"] == 0 and stats["kept_components"] > 0 else 0
+
+    def as_dict(self):
+        s = self.sums
+        recall, precision = _ratio_or_none(s["detected"], s["lesions"]), _ratio_or_none(s["true_positives"], s["kept_components"])
+        f1 = None if recall is None or precision is None or recall + precision == 0 else 2.0 * recall * precision / (recall + precision)
+        out = {"images": self.count, "lesion_recall": recall, "component_precision": precision, "lesion_f1": f1,
+               "false_positives_per_image": _ratio_or_none(s["false_positives"], self.count), "images_missed": self.images_missed,
+               "images_false_alarm": self.images_false_alarm, "removed_pixels": self.removed_pixels}
+        out.update(s)
+        return out
+
+    def summary(self, logger):
+        r = self.as_dict()
+
+        def f(v):
+            return "n/a" if v is None else "{:.4f}".format(v)
+
+        logger.info("Lesion metric, val result over {} images: recall {} ({}/{} lesions), precision {} ({}/{} components), F1 {}.".format(
+            r["images"], f(r["lesion_recall"]), r["detected"], r["lesions"], f(r["component_precision"]), r["true_positives"], r["kept_components"],
+            f(r["lesion_f1"])))
+        logger.info("Lesion metric, val result: false positives per image {}, images missed {}, false alarms {}, removed components {}.".format(
+            f(r["false_positives_per_image"]), r["images_missed"], r["images_false_alarm"], r["removed_components"]))
+
+
+def literal_lesion_stats(pred, label, cls=1, connectivity=8, min_area=0, keep_largest=False, overlap=0.0, max_rounds=None):
+    """What a user would write without mi_lesion_score, from torch ops on the inputs' device (pred, label [H,W]): every foreground pixel starts
+    with its own linear index, the smallest index of the neighbourhood is propagated by max_pool2d on the negated indices until nothing changes
+    (as many rounds as the longest path inside a component), areas and hits by bincount.  Returns (the 12 integers as a list, filtered uint8
+    [H,W]).  A second derivation for tests and the yardstick of tools/lesion_bench.py; never on a product path.  max_rounds: give up with
+    RuntimeError after that many rounds (the bench's guard against a spiral of a million pixels)."""
+    connectivity, overlap, min_area, keep_largest = _lesion_check(connectivity, overlap, min_area, keep_largest)
+    permille = int(round(1000 * overlap))
+    H, W = pred.shape
+    n = H * W
+    idx = torch.arange(n, dtype=torch.float64, device=pred.device).view(1, 1, H, W)
+    ninf = torch.full_like(idx, float("-inf"))
+    pool = torch.nn.functional.max_pool2d
+
+    def roots(fg):
+        cur = torch.where(fg.view(1, 1, H, W), -idx, ninf)
+        rounds = 0
+        while True:
+            rounds += 1
+            if max_rounds is not None and rounds > max_rounds:
+                raise RuntimeError("literal_lesion_stats: no fixed point after %d rounds" % max_rounds)
+            if connectivity == 8:
+                nxt = pool(cur, 3, 1, 1)
+            else:
+                nxt = torch.maximum(pool(cur, (3, 1), 1, (1, 0)), pool(cur, (1, 3), 1, (0, 1)))
+            nxt = torch.where(fg.view(1, 1, H, W), nxt, ninf)
+            if torch.equal(nxt, cur):
+                return torch.where(fg, (-cur).view(H, W), torch.zeros((), dtype=torch.float64, device=pred.device)).long()
+            cur = nxt
+
+    P, G = pred == cls, label == cls
+    rp, rg = roots(P), roots(G)
+    area_p, area_g = torch.bincount(rp[P], minlength=n), torch.bincount(rg[G], minlength=n)
+    keep = (area_p > 0) & (area_p >= min_area)
+    if keep_largest and bool(keep.any()):
+        top = torch.where(keep, area_p, torch.zeros_like(area_p))
+        first = int((top == top.max()).nonzero()[0])                       # a tie: the smallest root
+        keep = torch.zeros_like(keep)
+        keep[first] = True
+    F = P & keep[rp]
+    hit_p, hit_g = torch.bincount(rp[F & G], minlength=n), torch.bincount(rg[G & F], minlength=n)
+    tp = keep & (hit_p >= 1) & (1000 * hit_p >= permille * area_p)
+    det = (area_g > 0) & (hit_g >= 1) & (1000 * hit_g >= permille * area_g)
+    n_p, n_kept = int((area_p > 0).sum()), int(keep.sum())
+    ints = [int(P.sum()), int(F.sum()), int(G.sum()), n_p, n_kept, int((area_g > 0).sum()), int(tp.sum()), int(det.sum()), int(area_p.max()),
+            int(area_g.max()), int((F & G).sum()), n_p - n_kept]
+    other = torch.full((), 1 if cls == 0 else 0, dtype=torch.uint8, device=pred.device)
+    return ints, torch.where(F, torch.full((), cls, dtype=torch.uint8, device=pred.device), other)
+
+
 # ----------------------------------------------------------------------------- io / logging
 def soft_label_cross_entropy(pred, soft_label, pixel_weights=None):
     """utility.py:172-177 on materialised [N,C,H,W] tensors (API parity: AsppFada uses the fused kernel

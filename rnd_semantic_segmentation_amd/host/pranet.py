@@ -602,11 +602,15 @@ class PranetTester:
     the polyp-segmentation metrics - mean Dice / IoU, F-beta, S-measure, E-measure, MAE - from one fused tail (score) and writes
     OUTPUT_DIR/pranet_polyp_metrics.json; the intersection / union meters are then fed from that tail's mask.  TEST.SURFACE_METRICS True (not
     in the reference either) measures the same mask against the label with kernels.surface_score - Hausdorff distance, its percentile, average
-    symmetric surface distance, surface Dice - and writes OUTPUT_DIR/pranet_surface_metrics.json; the other outputs do not change."""
+    symmetric surface distance, surface Dice - and writes OUTPUT_DIR/pranet_surface_metrics.json; the other outputs do not change.
+    TEST.LESION_METRICS True (not in the reference) counts lesion-wise detections on the connected components of that mask and of the label with
+    kernels.lesion_score and writes OUTPUT_DIR/pranet_lesion_metrics.json.  TEST.MASK_MIN_AREA / TEST.MASK_KEEP_LARGEST filter the mask's
+    components in the same call: the filtered mask then replaces the mask for the intersection / union meters, the surface metrics and the lesion
+    counts.  The polyp metrics are measured on the soft map and are NOT filtered."""
 
     def __init__(self, cfg, device, test_loader, logger):
-        from .metrics import (polyp_settings, require_no_boundary, require_no_crf, require_no_curves, require_no_slide, require_plain_argmax,
-                              require_single_scale, surface_settings)
+        from .metrics import (lesion_settings, polyp_settings, require_no_boundary, require_no_crf, require_no_curves, require_no_slide,
+                              require_plain_argmax, require_single_scale, surface_settings)
         require_single_scale(cfg, "PranetTester")
         require_plain_argmax(cfg, "PranetTester")
         require_no_crf(cfg, "PranetTester")
@@ -616,6 +620,7 @@ class PranetTester:
         self.cfg, self.logger, self.test_loader, self.device = cfg, logger, test_loader, device
         self.polyp_metrics = polyp_settings(cfg)                      # TEST.POLYP_METRICS: test() scores through kernels.polyp_score
         self.surface = surface_settings(cfg)                          # TEST.SURFACE_METRICS: None, or (percentile, tolerances) for kernels.surface_score
+        self.lesion = lesion_settings(cfg)                            # TEST.LESION_METRICS / MASK_*: None, or (metrics, connectivity, overlap, min_area, keep_largest)
         self.model = PraNet()
         self.model.to(device)
         # The reference thresholds an fp32 forward (pranet_tester.py:36-46): TEST.PRECISION 'fp32' (default) evaluates in the reference's precision
@@ -662,12 +667,25 @@ class PranetTester:
         ints, sums = r.ints.cpu().numpy(), r.sums.cpu().numpy()
         return [surface_image_stats(ints[b], sums[b], tolerances, percentile) for b in range(y.shape[0])]
 
+    def lesion_stats(self, mask, y):
+        """TEST.LESION_METRICS / TEST.MASK_MIN_AREA / TEST.MASK_KEEP_LARGEST: one batch's mask (uint8 [B,H,W]) and labels through
+        kernels.lesion_score (foreground = 1, every other label is background); one small copy to the host.  Returns (the filtered mask uint8
+        [B,H,W] on the device, [lesion_image_stats per image])."""
+        from .. import kernels
+        from .metrics import lesion_image_stats
+        _, connectivity, overlap, min_area, keep_largest = self.lesion
+        r = kernels.lesion_score(mask.contiguous(), y.contiguous(), 1, connectivity, min_area, keep_largest, overlap)
+        ints = r.ints.cpu().numpy()
+        return r.filtered, [lesion_image_stats(ints[b]) for b in range(y.shape[0])]
+
     def test(self):
-        from .metrics import AverageMeter, PolypMeter, SurfaceMeter, dump_json, intersectionAndUnionGPU
+        from .metrics import AverageMeter, LesionMeter, PolypMeter, SurfaceMeter, dump_json, intersectionAndUnionGPU
         self.model.eval()
         self.meter = AverageMeter()
         self.polyp_meter = PolypMeter() if self.polyp_metrics else None
         self.surface_meter = SurfaceMeter(*self.surface) if self.surface is not None else None
+        self.lesion_meter = LesionMeter() if self.lesion is not None and self.lesion[0] else None
+        mask_filter = self.lesion is not None and (self.lesion[3] > 0 or self.lesion[4])
         for x, y, names in self.test_loader:
             x = x.to(self.device, non_blocking=True)
             y = y.to(self.device, non_blocking=True)
@@ -679,8 +697,16 @@ class PranetTester:
                     self.polyp_meter.update(s)
             else:
                 pred = self.predict(x, (h, w))
+            mask = self.last_mask if self.polyp_metrics else None    # the uint8 mask the surface and lesion kernels read
+            if self.lesion is not None:
+                filtered, stats = self.lesion_stats(mask if mask is not None else pred.to(torch.uint8), y)
+                if self.lesion_meter is not None:
+                    for s in stats:
+                        self.lesion_meter.update(s)
+                if mask_filter:                                        # from here on the filtered mask is the prediction
+                    mask, pred = filtered, filtered.long()
             if self.surface is not None:
-                for s in self.surface_stats(self.last_mask if self.polyp_metrics else pred.to(torch.uint8), y):
+                for s in self.surface_stats(mask if mask is not None else pred.to(torch.uint8), y):
                     self.surface_meter.update(s)
             inter, union, target, res = intersectionAndUnionGPU(pred, y, self.cfg.MODEL.NUM_CLASSES, self.cfg.INPUT.IGNORE_LABEL)
             self.meter.update(inter.cpu().numpy(), union.cpu().numpy(), target.cpu().numpy(), res.cpu().numpy())
@@ -696,3 +722,13 @@ class PranetTester:
             os.makedirs(self.cfg.OUTPUT_DIR, exist_ok=True)
             dump_json(os.path.join(self.cfg.OUTPUT_DIR, "pranet_surface_metrics.json"),
                       dict(self.surface_meter.as_dict(), percentile=self.surface[0], tolerances=list(self.surface[1])))
+        if mask_filter:
+            self.logger.info("Mask filter: components below {} pixels removed{} (connectivity {}) before the intersection / union{} lines; "
+                             "the polyp metrics are not filtered.".format(self.lesion[3], ", only the largest kept" if self.lesion[4] else "",
+                                                                          self.lesion[1], " and surface" if self.surface is not None else ""))
+        if self.lesion_meter is not None:
+            self.lesion_meter.summary(self.logger)
+            os.makedirs(self.cfg.OUTPUT_DIR, exist_ok=True)
+            dump_json(os.path.join(self.cfg.OUTPUT_DIR, "pranet_lesion_metrics.json"),
+                      dict(self.lesion_meter.as_dict(), connectivity=self.lesion[1], overlap=self.lesion[2], min_area=self.lesion[3],
+                           keep_largest=self.lesion[4]))

@@ -10,8 +10,8 @@ from .metrics import (BOUNDARY_MAPS, BOUNDARY_MAX_WIDTH, CURVE_BINS, PSEUDO_BINS
                       boundary_summary, boundary_width, class_threshold_settings, class_thresholds, classwise_pseudo_labels, classwise_settings,
                       confusion_matrix, crf_channel_scale, crf_refine_output, crf_settings, curves_accumulate, curves_settings, curves_summary,
                       dump_json, inference, intersectionAndUnionGPU, literal_histogram, literal_pseudo, multi_scale_inference, predict_and_score,
-                      require_no_polyp_metrics, require_no_surface, score_settings, slide_inference, slide_plan, slide_settings, strip_prefix_if_present,
-                      threshold_table, tta_settings)
+                      require_no_lesion, require_no_polyp_metrics, require_no_surface, score_settings, slide_inference, slide_plan, slide_settings,
+                      strip_prefix_if_present, threshold_table, tta_settings)
 from .modules import build_classifier, build_feature_extractor
 
 
@@ -30,6 +30,7 @@ class ASPPTester:
         classwise_settings(cfg)                            # a stray TEST.PSEUDO_PORTION is refused before anything is built
         require_no_polyp_metrics(cfg, "ASPPTester")
         require_no_surface(cfg, "ASPPTester")
+        require_no_lesion(cfg, "ASPPTester")
         self.crf = crf_settings(cfg)                       # TEST.CRF: None, or the parameters of kernels.crf_refine (a stray CRF_* key is refused)
         self.crf_scale = crf_channel_scale(cfg) if self.crf is not None else None
         self.slide = slide_settings(cfg)                   # TEST.SLIDE: None, or (crop, stride), each (h, w) (a stray SLIDE_* key is refused)

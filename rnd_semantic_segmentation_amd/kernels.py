@@ -1158,6 +1158,74 @@ def surface_score(pred, labels, cls=1, percentile=95, tolerances=(2.0,)):
     return SurfaceScore(ints, sums)
 
 
+LESION_INTS = 12                            # MI_LESION_INTS
+Components = collections.namedtuple("Components", "labels roots counts")
+LesionScore = collections.namedtuple("LesionScore", "ints filtered")
+
+
+def _chk_components(who, cls, connectivity):
+    if int(cls) != cls or not 0 <= int(cls) <= 255:
+        raise _lib.MiError("%s: cls must be an integer in 0..255, got %r" % (who, cls))
+    if connectivity not in (4, 8):
+        raise _lib.MiError("%s: the connectivity must be 4 or 8, got %r" % (who, connectivity))
+
+
+def label_components(mask, cls=1, connectivity=8, want_labels=True, want_roots=False):
+    """Connected components (mi_label_components, the definition: include/mi355seg.h): mask uint8 [B,H,W] -> Components of device tensors:
+    labels int32 [B,H,W] (0 on background, else 1..n per image in the raster order of each component's first pixel: scipy.ndimage.label with the
+    cross / full 3 x 3 structure), roots int32 [B,H,W] (the linear index of that first pixel, -1 on background) and counts int32 [B].  Foreground
+    is mask == cls.  labels / roots are None when not wanted; at least one must be.  Six launches on the current stream, nothing read back;
+    workspace cached per stream."""
+    _chk(mask, torch.uint8, "mask")
+    if mask.dim() != 3:
+        raise _lib.MiError("label_components: mask must be [B,H,W], got %s" % (tuple(mask.shape),))
+    _chk_components("label_components", cls, connectivity)
+    if not (want_labels or want_roots):
+        raise _lib.MiError("label_components: at least one of want_labels and want_roots")
+    B, H, W = mask.shape
+    dev = mask.device
+    labels = torch.empty((B, H, W), dtype=torch.int32, device=dev) if want_labels else None
+    roots = torch.empty((B, H, W), dtype=torch.int32, device=dev) if want_roots else None
+    counts = torch.empty((B,), dtype=torch.int32, device=dev)
+    ws = _workspace(_lib.lib().mi_label_components_workspace(B, H, W), dev, "components")
+    check(_lib.lib().mi_label_components(_p(mask), B, H, W, int(cls), int(connectivity), _p(labels), _p(roots), _p(counts), _p(ws), ws.numel(), _stream()),
+          "mi_label_components")
+    return Components(labels, roots, counts)
+
+
+def lesion_permille(overlap):
+    """TEST.LESION_OVERLAP as the integer mi_lesion_score compares with."""
+    return int(round(1000 * overlap))
+
+
+def lesion_score(pred, labels, cls=1, connectivity=8, min_area=0, keep_largest=False, overlap=0.0, want_filtered=True):
+    """Lesion-wise tail (mi_lesion_score, the definition: include/mi355seg.h): pred uint8 [B,H,W], labels int64 [B,H,W] on one device ->
+    LesionScore of device tensors: ints int64 [B,12] (|P|, |P'|, |G|, the components of P, P' and G, the true-positive components of P', the
+    detected components of G, the largest component areas of P and G, |P' & G|, the components the filter removed) and filtered uint8 [B,H,W]
+    (cls on P', cls == 0 ? 1 : 0 elsewhere; None when not wanted).  P' keeps the components of P = (pred == cls) of at least min_area pixels,
+    with keep_largest only the largest; `overlap` in [0, 1] is the share of a component the other mask must cover, as per-mille.
+    host/metrics.py lesion_image_stats names the integers.  A memset and seven launches on the current stream, nothing read back; workspace
+    cached per stream."""
+    _chk(pred, torch.uint8, "pred")
+    _chk(labels, torch.int64, "labels")
+    if pred.dim() != 3 or labels.shape != pred.shape or labels.device != pred.device:
+        raise _lib.MiError("lesion_score: pred and labels [B,H,W] on one device, got %s on %s and %s on %s"
+                           % (tuple(pred.shape), pred.device, tuple(labels.shape), labels.device))
+    _chk_components("lesion_score", cls, connectivity)
+    if isinstance(min_area, bool) or int(min_area) != min_area or min_area < 0:
+        raise _lib.MiError("lesion_score: min_area must be an integer >= 0, got %r" % (min_area,))
+    if not (isinstance(overlap, (int, float)) and 0.0 <= float(overlap) <= 1.0):
+        raise _lib.MiError("lesion_score: the overlap must lie in [0, 1], got %r" % (overlap,))
+    B, H, W = pred.shape
+    dev = pred.device
+    ints = torch.empty((B, LESION_INTS), dtype=torch.int64, device=dev)
+    filtered = torch.empty((B, H, W), dtype=torch.uint8, device=dev) if want_filtered else None
+    ws = _workspace(_lib.lib().mi_lesion_score_workspace(B, H, W), dev, "lesion")
+    check(_lib.lib().mi_lesion_score(_p(pred), _p(labels), B, H, W, int(cls), int(connectivity), int(min_area), 1 if keep_largest else 0,
+                                     lesion_permille(overlap), _p(filtered), _p(ints), _p(ws), ws.numel(), _stream()), "mi_lesion_score")
+    return LesionScore(ints, filtered)
+
+
 def stem_pool_fwd(y, scale, shift):
     """y [B,Hc,Wc,C] bf16 (conv1 output) -> (pool [B,Hp,Wp,C] bf16, idx uint8): FrozenBN + ReLU + maxpool 3x3/2/1."""
     _chk(y, torch.bfloat16, "y")
